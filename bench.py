@@ -131,6 +131,47 @@ def pooled_bytes_per_image(masks: torch.Tensor, width: int = 64) -> float:
     return total / m.shape[0]
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, n_rows, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write the arrays one describe() call returned as `directory/<name>.npy` (outside any
+    timed region), for output-for-output comparison of two builds: integer arrays (token
+    ids, lengths) as float64, floating ones as float32.  When the files would exceed
+    `budget` bytes, every array keeps the same fraction of the rows of its leading
+    dimension, a fixed, seeded sample; arrays of one length share their rows, which are
+    written as `rows.npy` (the `n_rows` neurons of the step) or `rows_<length>.npy`.
+    Returns {name: shape} of what was written."""
+    import numpy
+    arrays = {}
+    for name, t in out.items():
+        if not isinstance(t, torch.Tensor):
+            continue
+        dtype = torch.float32 if t.is_floating_point() and t.dtype != torch.float64 \
+            else torch.float64
+        arrays[name] = t.detach().to('cpu', dtype)
+    lengths = sorted({a.shape[0] for a in arrays.values() if a.dim() > 0})
+    data = sum(a.numel() * a.element_size() for a in arrays.values())
+    room = budget - 1024 * (len(arrays) + len(lengths))  # (head room for the .npy headers)
+    if data > room:
+        # kept bytes <= frac x (array bytes + 8 per row for the row lists) <= room
+        scalars = sum(a.element_size() for a in arrays.values() if a.dim() == 0)
+        frac = (room - scalars) / (data - scalars + 8 * sum(lengths))
+        picked = {}
+        for length in lengths:
+            g = torch.Generator().manual_seed(seed)
+            picked[length] = torch.randperm(length, generator=g)[:int(frac * length)].sort().values
+        arrays = {name: a[picked[a.shape[0]]] if a.dim() > 0 else a
+                  for name, a in arrays.items()}
+        for length, rows in picked.items():
+            arrays['rows' if length == n_rows else f'rows_{length}'] = rows.to(torch.float64)
+    path = pathlib.Path(directory)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        numpy.save(path / f'{name}.npy', a.numpy())
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def cpu_baseline(sd, nv, beam, length, temperature, sample, gpu_describe=None,
                  gpu_encode_modes=None, gpu_config1=None):
     """Time the oracle (kind 'port') on the host cores on a bounded sample; with
@@ -575,7 +616,15 @@ def main():
     ap.add_argument('--other-configs', type=int, default=1,
                     help='1: also time SURVEY 8(d) configs 1 and 2 (single-GPU '
                     'runs only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned '
+                    '(tokens, scores, beam tokens / scores, group lengths) as DIR/<name>.npy: '
+                    'float64 for integers, float32 for floats, <= 64 MB in all (a seeded '
+                    'sample of rows beyond that).  Inputs and weights are seeded, so two '
+                    'builds can be compared output for output.  Rank 0 writes its own step')
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.neurons_total <= 0 and args.steps < 1:
+        ap.error('--dump-outputs needs at least one timed step')
 
     # `python bench.py --gpus N` without torchrun: this process becomes the
     # launcher of N ranks (torch.distributed.run on 127.0.0.1, a free port);
@@ -773,6 +822,9 @@ def main():
                   f'images {h(step_data[i][0])} masks {h(step_data[i][1])} '
                   f'tokens {h(o["tokens"])} scores {h(o["scores"])}',
                   file=sys.stderr, flush=True)
+    dumped = None
+    if args.dump_outputs is not None and rank == 0 and outs:
+        dumped = dump_outputs(outs[-1], args.dump_outputs, sizes[n_steps - 1])
 
     # ---- SURVEY 8(d) metric: pinned host uint8 in, tokens + scores on host --
     pcie = None
@@ -946,6 +998,8 @@ def main():
         # status word after the timed steps (milan_status): 0 = no split-f16 value was
         # clamped, no non-finite input pixel
         'status_flags': status_flags,
+        # --dump-outputs: {name: shape} of the arrays written from the last timed step
+        'dumped_outputs': dumped,
         # which collective backend the ranks used (a SCALE record must be auditable)
         'dist_backend': (torch.distributed.get_backend()
                          if sharding.is_distributed() else 'none (single process)'),

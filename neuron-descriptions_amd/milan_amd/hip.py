@@ -19,6 +19,9 @@ import torch
 # MILAN_LIB=<path>: load another build of the library (A/B timing of compiler options)
 LIB_PATH = pathlib.Path(os.environ.get('MILAN_LIB') or
                        pathlib.Path(__file__).resolve().parent / 'lib' / 'libmilan_hip.so')
+# `make EXPERIMENTS=1` (built by __graft_entry__.build() as well): the measured-and-rejected
+# kernels, for the parity tests of those kernels and the tools/bench/ launchers
+EXP_LIB_PATH = pathlib.Path(__file__).resolve().parent / 'lib' / 'libmilan_hip_exp.so'
 
 GREEDY, FORCED, BEAM, RERANK = 0, 1, 2, 3  # MILAN_GREEDY / _FORCED / _BEAM / _RERANK
 PRECISION_F32, PRECISION_SPLIT_F16, PRECISION_F16 = 0, 1, 2
@@ -914,9 +917,11 @@ def conv2d_nhwc(x: torch.Tensor,
                 padding: int = 0,
                 relu: bool = False,
                 residual: Optional[torch.Tensor] = None,
-                precision: str = 'f32') -> torch.Tensor:
-    """Test hook for the implicit-GEMM kernel (milan_conv2d_nhwc)."""
-    lib = load_library()
+                precision: str = 'f32',
+                lib: Optional[ctypes.CDLL] = None) -> torch.Tensor:
+    """Test hook for the implicit-GEMM kernel (milan_conv2d_nhwc); `lib`: another
+    loaded build of the library (load_library(EXP_LIB_PATH)) instead of the default."""
+    lib = lib if lib is not None else load_library()
     device = require_device(x.device)
     n, h, w, cin = x.shape
     cout, cin_w, kh, kw = weight.shape

@@ -3,19 +3,24 @@
 `RunningTopK.state_dict()` must load into the reference's own class
 (src/deps/netdissect/runningstats.py:118-149) and give the same `result()`: upstream
 adds `linear_index` -- row offsets into its flattened candidate buffer, shape
-(units, 1) -- to a (units, k) index tensor.  The reference is imported only when it is
-present (this container); the format itself is checked everywhere.
+(units, 1) -- to a (units, k) index tensor.  What the reference's class returns for these
+states is stored in tests/golden/reference_goldens_topk_state.* (make_golden_topk_state.py);
+the format itself is also checked by spelling out upstream's arithmetic.
 """
-import pathlib
-import sys
+import json
 
 import numpy
 import pytest
 import torch
 
+from conftest import GOLDEN_DIR
 from milan_amd import exemplars
 
-REFERENCE = pathlib.Path('/root/reference')
+
+@pytest.fixture(scope='module')
+def G():
+    return (torch.load(GOLDEN_DIR / 'reference_goldens_topk_state.pt'),
+            json.loads((GOLDEN_DIR / 'reference_goldens_topk_state.json').read_text()))
 
 
 def _filled_topk(units, k, filled, count, seed=0):
@@ -30,7 +35,7 @@ def _filled_topk(units, k, filled, count, seed=0):
 
 
 @pytest.mark.parametrize('units,k,filled', [(7, 5, 5), (4, 4, 4), (6, 15, 9), (1, 3, 2)])
-def test_topk_state_dict_is_netdissect_format(tmp_path, units, k, filled):
+def test_topk_state_dict_is_netdissect_format(G, tmp_path, units, k, filled):
     top = _filled_topk(units, k, filled, count=1000 + units)
     state = top.state_dict()
     width = max(10, 5 * k)
@@ -43,31 +48,13 @@ def test_topk_state_dict_is_netdissect_format(tmp_path, units, k, filled):
     numpy.savez(path, **{k_: v for k_, v in state.items() if v is not None})
     loaded = dict(numpy.load(path, allow_pickle=True))
     want_values, want_index = top.result()
-    if REFERENCE.exists():
-        # (the module's last lines import statsmodels for functions nothing here uses;
-        # absent in this image, stubbed like tests/golden/make_golden_sketch.py does)
-        import types
-        for name in ('statsmodels', 'statsmodels.stats',
-                     'statsmodels.stats.correlation_tools'):
-            if name not in sys.modules:
-                stub = types.ModuleType(name)
-                stub.cov_nearest = stub.corr_nearest = None
-                sys.modules[name] = stub
-        sys.path.insert(0, str(REFERENCE))
-        # (the reference tree is read-only: no __pycache__ directories in it)
-        bytecode, sys.dont_write_bytecode = sys.dont_write_bytecode, True
-        try:
-            from src.deps.netdissect import runningstats
-        finally:
-            sys.dont_write_bytecode = bytecode
-            sys.path.remove(str(REFERENCE))
-        ref = runningstats.RunningTopK(state=loaded)
-        got_values, got_index = ref.result()
-        assert torch.equal(got_values, want_values)
-        assert torch.equal(got_index, want_index)
-        assert ref.size() == top.size()
-    # and the same arithmetic spelled out (what upstream's result() does), so that the
-    # check also runs where the reference is absent
+    # what the reference's RunningTopK(state=...) returns for this file
+    tensors, meta = G
+    name = f'u{units}_k{k}_f{filled}'
+    assert torch.equal(tensors[f'{name}_values'], want_values)
+    assert torch.equal(tensors[f'{name}_index'], want_index)
+    assert meta[name]['size'] == top.size()
+    # and the same arithmetic spelled out (what upstream's result() does) on the file itself
     data = torch.from_numpy(loaded['top_data'])[:, :int(loaded['next'])]
     keep = min(k, int(loaded['next']))
     vals, bti = data.topk(keep, sorted=True)

@@ -384,12 +384,20 @@ def test_bench_gpus_2_without_torchrun_launches_its_own_ranks():
     assert line['scaling'] in ('weak', 'strong')
 
 
-def test_bench_gpus_8_strong_mode_is_the_scale_command(world):
-    """the exact shape of the SCALE command -- `bench.py --gpus 8
-    --neurons-total N` launched WITHOUT torchrun -- as eight gloo ranks sharing this
-    box's one GPU: rc 0, one JSON line, n_gpus 8, and the gathered tokens equal the
-    1-rank run's bit for bit (shards are batch-aligned, kernels are chosen from the layer
-    shape only)."""
+# Ranks of the self-launched SCALE-shape run below.  Every rank holds the GPU, and so do
+# this pytest process, the bench.py launcher and the torchrun agent (both ask
+# torch.cuda.is_available()): 3 + RANKS processes on the one GPU.  Kept at 6 so that the
+# suite runs on GPU hosts that cap the processes holding a device (eight ranks made 11).
+RANKS = 3
+
+
+def test_bench_gpus_3_strong_mode_is_the_scale_command(world):
+    """the exact shape of the SCALE command -- `bench.py --gpus N
+    --neurons-total T` launched WITHOUT torchrun -- as N = 3 gloo ranks sharing this
+    box's one GPU: rc 0, one JSON line, n_gpus 3, and the gathered tokens equal the
+    1-rank run's bit for bit (shards are batch-aligned -- 176 / 176 / 160 neurons, ragged
+    last chunks -- and kernels are chosen from the layer shape only).  World 8's
+    ragged and empty shards are gathered in tests/test_host.py over gloo."""
     env = {k: v for k, v in os.environ.items()
            if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR',
                         'MASTER_PORT', 'MILAN_DIST_BACKEND')}
@@ -400,7 +408,7 @@ def test_bench_gpus_8_strong_mode_is_the_scale_command(world):
               '--from-host-steps', '0', '--other-configs', '0', '--live-traffic', '0',
               '--beam', '16']
     lines = {}
-    for gpus in (8, 1):
+    for gpus in (RANKS, 1):
         out = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus',
                               str(gpus)] + common, capture_output=True, text=True,
                              env=env, cwd=str(REPO), timeout=1500)
@@ -408,10 +416,46 @@ def test_bench_gpus_8_strong_mode_is_the_scale_command(world):
         js = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
         assert len(js) == 1, out.stdout[-2000:]
         lines[gpus] = json.loads(js[0])
-    eight, one = lines[8], lines[1]
-    assert eight['n_gpus'] == 8 and len(eight['per_rank']['neurons']) == 8
-    assert eight['scaling'] == 'strong' and eight['config']['neurons_total'] == 512
-    assert eight['ranks_per_gpu'] == 8 and eight['dist_backend'] == 'gloo'
-    assert eight['status_flags'] == 0 and one['status_flags'] == 0
-    assert (eight['config']['gathered_tokens_sha256'] ==
+    many, one = lines[RANKS], lines[1]
+    assert many['n_gpus'] == RANKS and len(many['per_rank']['neurons']) == RANKS
+    assert many['per_rank']['neurons'] == [176, 176, 160]
+    assert many['scaling'] == 'strong' and many['config']['neurons_total'] == 512
+    assert many['ranks_per_gpu'] == RANKS and many['dist_backend'] == 'gloo'
+    assert many['status_flags'] == 0 and one['status_flags'] == 0
+    assert (many['config']['gathered_tokens_sha256'] ==
             one['config']['gathered_tokens_sha256'])
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` end to end: after two timed steps of 64 neurons, DIR
+    holds what the LAST step returned -- its token hash (MILAN_BENCH_DEBUG's per-step line)
+    matches, the first step's does not -- with one row per neuron of the chunk, token ids
+    as float64, scores as float32, and the result line lists the same shapes."""
+    import hashlib
+    import re
+    hip.release_workspaces()  # the child shares this GPU
+    beam, out_dir = 8, tmp_path / 'dump'
+    env = {k: v for k, v in os.environ.items()
+           if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    env['MILAN_BENCH_DEBUG'] = '1'
+    out = subprocess.run([sys.executable, str(REPO / 'bench.py'), '--gpus', '1',
+                          '--steps', '2', '--warmup', '0', '--chunk', '64', '--beam', str(beam),
+                          '--cpu-sample', '0', '--also-f32-steps', '0', '--no-profile',
+                          '--from-host-steps', '0', '--other-configs', '0', '--fast-steps', '0',
+                          '--live-traffic', '0', '--dump-outputs', str(out_dir)],
+                         capture_output=True, text=True, env=env, cwd=str(REPO), timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
+    assert line['steps'] == 2 and line['ms_per_step'] > 0
+    want = {'tokens': [64, LENGTH], 'scores': [64], 'beam_tokens': [64, beam, LENGTH],
+            'beam_scores': [64, beam], 'out_len': [64 // 16]}
+    assert line['dumped_outputs'] == want
+    assert sorted(p.stem for p in out_dir.iterdir()) == sorted(want)
+    got = {name: numpy.load(out_dir / f'{name}.npy') for name in want}
+    for name, shape in want.items():
+        assert list(got[name].shape) == shape, name
+        assert got[name].dtype == (numpy.float32 if 'scores' in name else numpy.float64), name
+    step_hash = dict(re.findall(r'\[rank 0\] step (\d+) .* tokens (\w+) scores', out.stderr))
+    mine = hashlib.sha256(got['tokens'].astype(numpy.int64).tobytes()).hexdigest()[:12]
+    assert mine == step_hash['1'] != step_hash['0']
+    assert numpy.all((got['out_len'] > 0) & (got['out_len'] <= LENGTH))

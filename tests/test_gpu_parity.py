@@ -481,11 +481,18 @@ STRIP_CASES = [c for c in CONV_CASES
                if c[5] == 3 and c[6] == 1 and c[3] % 32 == 0 and c[4] % 128 == 0]
 
 
+@pytest.fixture(scope='module')
+def exp_lib():
+    """The experiments build of the library (`make EXPERIMENTS=1`, built by build())."""
+    return hip.load_library(hip.EXP_LIB_PATH)
+
+
 @pytest.mark.parametrize('case', STRIP_CASES)
-def test_lds_strip_conv3x3_kernel(dev, case):
+def test_lds_strip_conv3x3_kernel(dev, exp_lib, case):
     """The 3x3 kernel with the input strip resident in LDS (a measured-and-rejected
     experiment; compiled with `make EXPERIMENTS=1`) stays correct: fp32-class error
-    against an fp64 reference, tiles spanning image borders, ragged tiles."""
+    against an fp64 reference, tiles spanning image borders, ragged tiles.  Both precisions
+    run on the experiments build, the only one that has the strip kernel."""
     assert len(STRIP_CASES) >= 5
     n, h, w, cin, cout, k, stride, pad = case
     g = torch.Generator().manual_seed(11 + sum(case))
@@ -496,13 +503,8 @@ def test_lds_strip_conv3x3_kernel(dev, case):
     x_nhwc = x.permute(0, 2, 3, 1).contiguous().to(dev)
     got = {}
     for prec in ('split_f16', 'split_f16_strip'):
-        try:
-            y = hip.conv2d_nhwc(x_nhwc, wt.to(dev), b.to(dev), 1, 1, precision=prec)
-        except ValueError as error:
-            if 'experiments build' in str(error):
-                pytest.skip('the LDS-strip kernel is a rejected experiment: only in '
-                            'a `make EXPERIMENTS=1` build of the library')
-            raise
+        y = hip.conv2d_nhwc(x_nhwc, wt.to(dev), b.to(dev), 1, 1, precision=prec,
+                            lib=exp_lib)
         got[prec] = y.permute(0, 3, 1, 2).cpu().double()
     scale = float(want.abs().max())
     err = {p: float((v - want).abs().max()) for p, v in got.items()}

@@ -545,6 +545,54 @@ def test_bench_and_script_entry_points_parse():
         'cuda' in out.stderr.lower()
 
 
+def test_bench_dump_outputs_types_and_budget(tmp_path):
+    """bench.py --dump-outputs: one .npy per array describe() returned (integers as float64,
+    floats as float32, values unchanged); over the byte budget, a seeded sample of rows --
+    the same rows in every array of one leading length, the same sample on every run --
+    and the budget holds also when an array that is not one row per neuron dominates."""
+    if str(REPO) not in sys.path:
+        sys.path.insert(0, str(REPO))
+    import bench
+    n, beam, length = 40, 6, 5
+    g = torch.Generator().manual_seed(3)
+    out = dict(tokens=torch.randint(0, 5004, (n, length), generator=g),
+               scores=torch.randn(n, generator=g),
+               predictions=None,
+               beam_tokens=torch.randint(0, 5004, (n, beam, length), generator=g),
+               beam_scores=torch.randn(n, beam, generator=g),
+               out_len=torch.full((3,), length, dtype=torch.int32))
+    shapes = bench.dump_outputs(out, tmp_path / 'all', n)
+    assert shapes == {k: list(v.shape) for k, v in out.items() if v is not None}
+    for name, want in out.items():
+        if want is None:
+            continue
+        got = numpy.load(tmp_path / 'all' / f'{name}.npy')
+        assert got.dtype == (numpy.float32 if want.is_floating_point() else numpy.float64)
+        assert numpy.array_equal(got, want.double().numpy())
+    budget = 12000
+    for d in ('a', 'b'):
+        bench.dump_outputs(out, tmp_path / d, n, budget=budget)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= budget
+    rows = numpy.load(tmp_path / 'a' / 'rows.npy')
+    assert numpy.array_equal(rows, numpy.load(tmp_path / 'b' / 'rows.npy'))
+    assert 0 < len(rows) < n and numpy.all(numpy.diff(rows) > 0)
+    idx = torch.from_numpy(rows).long()
+    for name in ('tokens', 'scores', 'beam_tokens', 'beam_scores'):
+        got = numpy.load(tmp_path / 'a' / f'{name}.npy')
+        assert numpy.array_equal(got, out[name][idx].double().numpy()), name
+    idx3 = torch.from_numpy(numpy.load(tmp_path / 'a' / 'rows_3.npy')).long()
+    assert numpy.array_equal(numpy.load(tmp_path / 'a' / 'out_len.npy'),
+                             out['out_len'][idx3].double().numpy())
+    # an array of another leading length that alone exceeds the budget is sampled as well
+    big = dict(out, attentions=torch.randn(7, 4000, generator=g))
+    shapes = bench.dump_outputs(big, tmp_path / 'c', n, budget=5 * budget)
+    assert sum(f.stat().st_size for f in (tmp_path / 'c').iterdir()) <= 5 * budget
+    idx7 = torch.from_numpy(numpy.load(tmp_path / 'c' / 'rows_7.npy')).long()
+    assert 0 < len(idx7) < 7 and shapes['attentions'] == [len(idx7), 4000]
+    assert numpy.array_equal(numpy.load(tmp_path / 'c' / 'attentions.npy'),
+                             big['attentions'][idx7].numpy())
+
+
 def test_shared_gpu_probe_is_quiet_without_a_gpu(recwarn):
     """hip.other_compute_processes(): PIDs with compute queues on a GPU this process
     uses (/sys/class/kfd/kfd/proc/<pid>/queues/*/gpuid).  A process without queues --

@@ -36,7 +36,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MILAN_ABI_VERSION 8
+#define MILAN_ABI_VERSION 9
 
 enum {
   MILAN_OK = 0,
@@ -534,6 +534,46 @@ int milan_conv2d_nhwc(const float* x, int n, int h, int w, int cin,
                       int kh, int kw, int stride, int pad, int relu,
                       const float* residual, float* y, int precision,
                       milan_stream stream);
+
+/* ---- LanguageModel training (src/milan/lms.py:134-265) --------------------
+ * Loss, forward and backward of Embedding -> nn.LSTM(dropout) -> Linear ->
+ * LogSoftmax -> NLLLoss(ignore_index = pad_index) over a padded batch.
+ *   params / grads: HOST arrays of n_params DEVICE fp32 pointers in
+ *     LanguageModel.state_dict() order: embedding.weight, then per layer
+ *     lstm.weight_ih_l, weight_hh_l, bias_ih_l, bias_hh_l, then output.0.weight,
+ *     output.0.bias (n_params = 3 + 4 * lm_layers), raw torch layout.  They are
+ *     read on every call: the ctx only supplies the LM dims (vocab_size,
+ *     pad_index, lm_*) and need not be finalized; its weight arena is not used.
+ *   inputs / targets: (rows, L) int64 (the reference's lossify: inputs with
+ *     <start>, targets with <stop>, both padded).  Ids must lie in
+ *     [0, vocab_size): the caller validates (out-of-range ids are clamped, not
+ *     reported).  Targets equal to pad_index do not count.
+ *   loss_sum_and_count: DEVICE float[2] <- sum of -log p(target) over the
+ *     valid targets and their number; the mean loss is [0] / [1] (NaN when
+ *     [1] == 0, as in torch).
+ *   milan_lm_nll        eval mode (no dropout): the loss only.
+ *   milan_lm_train_step train mode: dropout p on the output of every layer but
+ *     the last, mask a pure function of (seed, layer, row, t, unit):
+ *     keep <=> (mix64(seed ^ mix64(layer<<56 | row<<32 | t<<16 | unit)) >> 40)
+ *     >= (uint32)(p * 2^24), kept values scaled by 1 / (1 - p), mix64 = the
+ *     splitmix64 finaliser.  Then the gradient of the MEAN loss with respect to
+ *     every parameter is written to `grads`: OVERWRITTEN, not accumulated.
+ *     The embedding row of pad_index gets exactly zero.
+ * Precision: exact fp32 MFMA whatever milan_set_precision says (split-f16 is an
+ * inference mode).  Deterministic: no float atomics, fixed reduction orders;
+ * equal inputs and seed give equal bits.  Neither call synchronises.
+ * rows < 2^24, L < 2^16, 1 <= lm_layers <= 8. */
+size_t milan_lm_train_workspace_bytes(const milan_ctx* ctx, int rows, int L);
+int milan_lm_nll(milan_ctx* ctx, const float* const* params, int n_params,
+                 const int64_t* inputs, const int64_t* targets, int rows, int L,
+                 float* loss_sum_and_count, void* workspace,
+                 size_t workspace_bytes, milan_stream stream);
+int milan_lm_train_step(milan_ctx* ctx, const float* const* params,
+                        float* const* grads, int n_params,
+                        const int64_t* inputs, const int64_t* targets, int rows,
+                        int L, float dropout, uint64_t seed,
+                        float* loss_sum_and_count, void* workspace,
+                        size_t workspace_bytes, milan_stream stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -78,7 +78,7 @@ class Dims(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 8  # MILAN_ABI_VERSION this binding was written against
+ABI_VERSION = 9  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
 TRUNK_BOTTLENECK, TRUNK_BASIC, TRUNK_ALEXNET, TRUNK_NONE = 0, 1, 2, 3
@@ -165,6 +165,11 @@ SIGNATURES = {
     'milan_exemplar_render':
         (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P,
               ctypes.POINTER(_F), ctypes.POINTER(_F), _I, _I, _P, _P, _P, _P]),
+    'milan_lm_train_workspace_bytes': (_SZ, [_P, _I, _I]),
+    'milan_lm_nll': (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _SZ, _P]),
+    'milan_lm_train_step':
+        (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _F, ctypes.c_uint64, _P, _P,
+              _SZ, _P]),
     'milan_conv2d_nhwc':
         (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I,
               _P]),
@@ -310,7 +315,9 @@ class Context:
     """Owns one `milan_ctx` (packed weights on one GPU) plus a workspace."""
 
     def __init__(self, dims: Dims, state_dict: Dict[str, torch.Tensor],
-                 device: torch.device):
+                 device: torch.device, finalize: bool = True):
+        """`finalize=False`: a context that only carries `dims` (no weights,
+        no packed arena) -- what the LM training calls need."""
         self.lib = load_library()
         self.device = require_device(device)
         self.dims = dims
@@ -329,9 +336,10 @@ class Context:
                 _check(
                     self.lib.milan_set_weight(self._h, name.encode(),
                                               t.data_ptr(), shape, t.dim()))
-            _check(
-                self.lib.milan_finalize_weights(self._h,
-                                                _stream(self.device)))
+            if finalize:
+                _check(
+                    self.lib.milan_finalize_weights(self._h,
+                                                    _stream(self.device)))
             del keep
         self._ws: Optional[torch.Tensor] = None
         # what a saturated split-f16 value does (see `_guarded`): 'raise' (default),
@@ -812,6 +820,81 @@ class Context:
                                            ws.data_ptr(), ws.numel(),
                                            _stream(self.device)))
         return out
+
+    # -- LanguageModel training (include/milan_hip.h, milan_lm_train_step) --
+    def _lm_train_call(self, params, inputs, targets):
+        rows, length = inputs.shape
+        if targets.shape != inputs.shape:
+            raise ValueError(f'targets {tuple(targets.shape)} != inputs '
+                             f'{tuple(inputs.shape)}')
+        v = self.dims.vocab_size
+        for name, ids in (('inputs', inputs), ('targets', targets)):
+            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= v):
+                raise ValueError(f'{name} hold ids outside [0, {v})')
+        if len(params) != 3 + 4 * self.dims.lm_layers:
+            raise ValueError(f'{len(params)} parameters, expected '
+                             f'{3 + 4 * self.dims.lm_layers}')
+        for p in params:
+            if (p.device != self.device or p.dtype != torch.float32
+                    or not p.is_contiguous()):
+                raise ValueError('LM parameters must be contiguous float32 on '
+                                 f'{self.device}')
+        inputs = _dev(inputs, self.device, torch.long)
+        targets = _dev(targets, self.device, torch.long)
+        need = int(self.lib.milan_lm_train_workspace_bytes(self._h, rows,
+                                                           length))
+        if need == 0:
+            _check(ERR_SHAPE)
+        ws = getattr(self, '_train_ws', None)
+        if ws is None or ws.numel() < need:
+            self._train_ws = None
+            ws = self._train_ws = torch.empty(need, dtype=torch.uint8,
+                                              device=self.device)
+        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
+        loss = torch.empty(2, device=self.device)
+        return inputs, targets, ptrs, ws, loss
+
+    def lm_nll(self, params, inputs: torch.Tensor,
+               targets: torch.Tensor) -> torch.Tensor:
+        """NLLLoss(ignore_index=pad) of the LM in eval mode: device tensor
+        [sum of -log p over the non-pad targets, their count].  `params`:
+        LanguageModel.state_dict() values in order.  Does not synchronise."""
+        inputs, targets, ptrs, ws, loss = self._lm_train_call(
+            params, inputs, targets)
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_lm_nll(self._h, ptrs, len(params),
+                                      inputs.data_ptr(), targets.data_ptr(),
+                                      inputs.shape[0], inputs.shape[1],
+                                      loss.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _stream(self.device)))
+        return loss
+
+    def lm_train_step(self, params, grads, inputs: torch.Tensor,
+                      targets: torch.Tensor, dropout: float = 0.,
+                      seed: int = 0) -> torch.Tensor:
+        """Train-mode loss (as `lm_nll`) and the gradient of the mean loss
+        with respect to every parameter, OVERWRITTEN into `grads` (same order
+        and shapes as `params`).  Does not synchronise."""
+        inputs, targets, ptrs, ws, loss = self._lm_train_call(
+            params, inputs, targets)
+        for p, g in zip(params, grads):
+            if (g.shape != p.shape or g.device != self.device
+                    or g.dtype != torch.float32 or not g.is_contiguous()):
+                raise ValueError('gradients must be contiguous float32 '
+                                 'tensors shaped like the parameters')
+        if len(grads) != len(params):
+            raise ValueError(f'{len(grads)} gradients for {len(params)} '
+                             'parameters')
+        gptrs = (_P * len(grads))(*[g.data_ptr() for g in grads])
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_lm_train_step(
+                    self._h, ptrs, gptrs, len(params), inputs.data_ptr(),
+                    targets.data_ptr(), inputs.shape[0], inputs.shape[1],
+                    float(dropout), int(seed) & (2**64 - 1), loss.data_ptr(),
+                    ws.data_ptr(), ws.numel(), _stream(self.device)))
+        return loss
 
     def describe(self,
                  images: torch.Tensor,

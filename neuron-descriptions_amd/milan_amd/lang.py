@@ -3,7 +3,8 @@
 Mirrors the inference-relevant half of the reference's `src/utils/lang.py`:
 `Vocab` (:94-172), `Indexer` special ids (:231-260), `unindex` (:573-612) and
 `reconstruct` (:678-730), plus `Indexer.index` / `__call__` (:331-514) for
-`Decoder.score`.  The tokenizer itself (spaCy) is not in this image: `__call__`
+`Decoder.score`, and `vocab` / `indexer` (:181-216, :750-778) for training a
+`LanguageModel` on new annotations.  The tokenizer itself (spaCy) is not in this image: `__call__`
 takes any callable (or pre-tokenized captions) and the serialized tokenizer
 payload is carried opaquely so checkpoints round-trip.
 
@@ -12,8 +13,10 @@ payload is carried opaquely so checkpoints round-trip.
 are mapped through a pre-built table and identical sequences are cached, and
 `LazyCaptions` defers the per-beam strings until somebody reads them.
 """
+import collections
 import dataclasses
-from typing import Any, Dict, Mapping, Optional, Sequence, Tuple, Union
+from typing import (Any, Dict, Iterable, Mapping, Optional, Sequence, Tuple,
+                    Union)
 
 START_TOKEN = '<start>'
 STOP_TOKEN = '<stop>'
@@ -125,12 +128,7 @@ class Indexer:
     def __call__(self, texts, **kwargs):
         """Tokenize then index.  `tokenize` is the spaCy-backed `Tokenizer` in
         the reference; any callable str|[str] -> tokens|[tokens] works here."""
-        if not callable(self.tokenize):
-            raise NotImplementedError(
-                'text -> ids indexing needs a tokenizer: the checkpoint\'s spaCy '
-                'tokenizer is not available in this build; set '
-                '`indexer.tokenize` to a callable or pass pre-tokenized '
-                'sequences to `Indexer.index`')
+        _require_tokenizer(self.tokenize)
         return self.index(self.tokenize(texts), **kwargs)
 
     def index(self,
@@ -281,6 +279,52 @@ class LazyCaptions(Sequence):
 
     def __repr__(self):
         return f'LazyCaptions({len(self)} x {self._tokens.shape[1]})'
+
+
+def _require_tokenizer(tokenize) -> None:
+    if not callable(tokenize):
+        raise NotImplementedError(
+            'text -> ids indexing needs a tokenizer: the checkpoint\'s spaCy '
+            'tokenizer is not available in this build; set '
+            '`indexer.tokenize` to a callable or pass pre-tokenized '
+            'sequences to `Indexer.index`')
+
+
+def vocab(texts: Sequence[str],
+          tokenize: Any = None,
+          ignore_rarer_than: Optional[int] = None,
+          ignore_in: Optional[Iterable[str]] = None) -> Vocab:
+    """Vocabulary of `texts` (reference lang.py:181-216): tokens in
+    `Counter.most_common()` order, without those seen `ignore_rarer_than` times
+    or fewer and those in `ignore_in`.  `tokenize`: any callable
+    [str] -> [tokens] (the reference defaults to its spaCy tokenizer, which is
+    not in this build: None raises NotImplementedError)."""
+    _require_tokenizer(tokenize)
+    ignore_in = frozenset(ignore_in) if ignore_in is not None else None
+
+    def ignore(token: str, count: int) -> bool:
+        yn = ignore_rarer_than is not None and count <= ignore_rarer_than
+        yn |= ignore_in is not None and token in ignore_in
+        return yn
+
+    counts = collections.Counter(
+        tok for toks in tokenize(texts) for tok in toks)
+    return Vocab(tuple(token for token, count in counts.most_common()
+                       if not ignore(token, count)))
+
+
+def indexer(texts: Sequence[str],
+            tokenize: Any = None,
+            ignore_rarer_than: Optional[int] = None,
+            ignore_in: Optional[Iterable[str]] = None,
+            **kwargs: Any) -> Indexer:
+    """An `Indexer` over `vocab(texts, ...)` (reference lang.py:750-778);
+    keyword arguments go to the `Indexer` constructor."""
+    vocabulary = vocab(texts,
+                       tokenize=tokenize,
+                       ignore_rarer_than=ignore_rarer_than,
+                       ignore_in=ignore_in)
+    return Indexer(vocabulary, tokenize, **kwargs)
 
 
 def join(texts: Any, delimiter: str = ' ') -> str:

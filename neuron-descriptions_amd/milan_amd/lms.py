@@ -1,19 +1,79 @@
-"""The LSTM language model used for PMI decoding / reranking.
+"""The LSTM language model used for PMI decoding / reranking, and its training.
 
-Mirror of the reference's `src/milan/lms.py:17-101` (inference surface):
-Embedding(V,E,padding_idx) -> 2-layer LSTM -> Linear(V) + LogSoftmax, and
-`forward(inputs, reduce=True)` = masked sequence log-probability with the
-reference's stop-mask off-by-one (lms.py:93-96).  Works attached to a Decoder
-(sharing its HIP context) or standalone, like the reference's module.
-Training (`fit`) and text scoring (`logp`, needs the spaCy tokenizer) are out
-of scope.
+Mirror of the reference's `src/milan/lms.py`: Embedding(V,E,padding_idx) ->
+LSTM(layers, dropout) -> Linear(V) + LogSoftmax.
+  * `forward(inputs, reduce=True)` = masked sequence log-probability with the
+    reference's stop-mask off-by-one (lms.py:93-96); `logp(texts)` indexes
+    text with start/stop/pad/unk first (lms.py:103-132).  Works attached to a
+    Decoder (sharing its HIP context) or standalone.
+  * `fit(dataset, ...)` (lms.py:134-265): NLLLoss(ignore_index=pad) training
+    with the reference's split, shuffling, optimizer and early stopping.  The
+    loss and every gradient come from libmilan_hip (`milan_lm_train_step`:
+    exact fp32 MFMA, deterministic; include/milan_hip.h); the torch optimizer
+    then steps the parameters.
+  * `lm(dataset, ...)` (lms.py:283-322) builds the indexer from the dataset's
+    annotations and a model initialised as the reference's would be (same
+    draws from torch's global generator).
+Text needs a tokenizer: the reference's is spaCy, which is not in this build,
+so `indexer.tokenize` (or `indexer_kwargs['tokenize']`) is any callable
+str | [str] -> tokens | [tokens]; without one, NotImplementedError.
 """
-from typing import Any, Mapping, Optional
+from typing import (Any, List, Mapping, Optional, Sequence, Sized, Type,
+                    Union, cast)
 
+import numpy as np
 import torch
-from torch import nn
+from torch import nn, optim
+from torch.utils import data
 
-from milan_amd import hip, lang, params
+from milan_amd import hip, lang, params, training
+
+
+def dropout_mask(seed: int, layer: int, rows: int, length: int, units: int,
+                 p: float) -> torch.Tensor:
+    """Host restatement of the training kernels' dropout mask on the output of
+    LSTM layer `layer`: (rows, length, units) bool, True = kept (kept values
+    are scaled by 1 / (1 - p)).  A pure function of (seed, layer, row, t,
+    unit); see milan_lm_train_step in include/milan_hip.h."""
+    m64 = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+    def mix64(z):
+        with np.errstate(over='ignore'):
+            z = (z + np.uint64(0x9E3779B97F4A7C15)) & m64
+            z = ((z ^ (z >> np.uint64(30))) *
+                 np.uint64(0xBF58476D1CE4E5B9)) & m64
+            z = ((z ^ (z >> np.uint64(27))) *
+                 np.uint64(0x94D049BB133111EB)) & m64
+            return z ^ (z >> np.uint64(31))
+
+    b = np.arange(rows, dtype=np.uint64)[:, None, None]
+    t = np.arange(length, dtype=np.uint64)[None, :, None]
+    j = np.arange(units, dtype=np.uint64)[None, None, :]
+    key = ((np.uint64(layer) << np.uint64(56)) | (b << np.uint64(32)) |
+           (t << np.uint64(16)) | j)
+    z = mix64(np.uint64(seed & 0xFFFFFFFFFFFFFFFF) ^ mix64(key))
+    threshold = int(float(np.float32(p)) * 16777216.0)
+    return torch.from_numpy((z >> np.uint64(40)) >= np.uint64(threshold))
+
+
+class _SequenceDataset(data.Dataset):
+    """The annotations of a dataset, one sample per sequence (a sample's
+    annotation may be a str or a list of str; reference lms.py:176-200)."""
+
+    def __init__(self, dataset: data.Dataset, annotation_index: int = 4):
+        self.sequences: List[str] = []
+        for index in range(len(cast(Sized, dataset))):
+            annotation = dataset[index][annotation_index]
+            if isinstance(annotation, str):
+                self.sequences.append(annotation)
+            else:
+                self.sequences += annotation
+
+    def __getitem__(self, index: int) -> str:
+        return self.sequences[index]
+
+    def __len__(self) -> int:
+        return len(self.sequences)
 
 
 class LanguageModel(nn.Module):
@@ -86,6 +146,169 @@ class LanguageModel(nn.Module):
         picked = lps[:, :-1].gather(2, targets.unsqueeze(-1)).squeeze(-1)
         return picked.mul(masks.to(lps.device)).sum(dim=-1)
 
+    def reset_parameters(self) -> None:
+        """Initialise the parameters as the reference's torch modules do
+        (the constructor leaves them zero): nn.Embedding, nn.LSTM and
+        nn.Linear are built in the reference's order, so the draws from
+        torch's global generator are the same."""
+        v, e, h = len(self.indexer), self.embedding_size, self.hidden_size
+        embedding = nn.Embedding(v, e, padding_idx=self.indexer.pad_index)
+        lstm = nn.LSTM(input_size=e,
+                       hidden_size=h,
+                       num_layers=self.layers,
+                       dropout=self.dropout,
+                       batch_first=True)
+        output = nn.Linear(h, v)
+        state = {'embedding.weight': embedding.weight}
+        state.update({f'lstm.{k}': t for k, t in lstm.state_dict().items()})
+        state.update({'output.0.weight': output.weight,
+                      'output.0.bias': output.bias})
+        with torch.no_grad():
+            self.load_state_dict(state)
+
+    def logp(self,
+             sequences: Sequence[str],
+             device: Optional[Any] = None) -> torch.Tensor:
+        """Log probability of each text (reference lms.py:103-132): indexed
+        with start / stop / pad / unk, then `forward(reduce=True)`."""
+        if device is not None:
+            self.to(device)
+        self.eval()
+        inputs = torch.tensor(self.indexer(sequences,
+                                           start=True,
+                                           stop=True,
+                                           pad=True,
+                                           unk=True))
+        with torch.no_grad():
+            return self(inputs, reduce=True)
+
+    # -- training (reference lms.py:134-265) -----------------------------------
+    def _param_names(self) -> List[str]:
+        names = ['embedding.weight']
+        for layer in range(self.layers):
+            names += [f'lstm.{kind}_l{layer}' for kind in
+                      ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
+        return names + ['output.0.weight', 'output.0.bias']
+
+    def fit(self,
+            dataset: data.Dataset,
+            annotation_index: int = 4,
+            batch_size: int = 128,
+            max_epochs: int = 100,
+            patience: int = 4,
+            hold_out: Union[float, Sequence[int]] = .1,
+            optimizer_t: Type[optim.Optimizer] = optim.AdamW,
+            optimizer_kwargs: Optional[Mapping[str, Any]] = None,
+            device: Optional[Any] = None,
+            display_progress_as: Optional[str] = 'train lm') -> None:
+        """Train on the annotations of `dataset` (reference lms.py:134-265).
+
+        Same loop as the reference: hold-out split (`random_split` on torch's
+        global generator, or `fixed_split(hold_out)`), shuffled training
+        batches, `optimizer_t(self.parameters(), **optimizer_kwargs)`,
+        NLLLoss(ignore_index=pad), early stopping on the validation loss.
+        The loss and gradients of a batch come from `milan_lm_train_step`
+        (train mode, dropout masks seeded from the device's torch generator)
+        and are written into `p.grad`; the torch optimizer then steps.
+        Validation uses `milan_lm_nll` (eval mode).  As in the reference,
+        the "best" state kept for the restore on stop is `state_dict()`,
+        whose tensors share storage with the parameters: the model ends with
+        the parameters of the last epoch run.
+        """
+        if optimizer_kwargs is None:
+            optimizer_kwargs = {}
+        if device is not None:
+            self.to(device)
+        device = hip.require_device(self.embedding.weight.device)
+
+        sequences = _SequenceDataset(dataset,
+                                     annotation_index=annotation_index)
+        if isinstance(hold_out, float):
+            train, val = training.random_split(sequences, hold_out=hold_out)
+        else:
+            train, val = training.fixed_split(sequences, hold_out)
+        train_loader = data.DataLoader(train,
+                                       batch_size=batch_size,
+                                       shuffle=True)
+        val_loader = data.DataLoader(val, batch_size=batch_size)
+
+        optimizer = optimizer_t(self.parameters(), **optimizer_kwargs)
+        stopper = training.EarlyStopping(patience=patience)
+
+        # an LM-dims context that is never finalized: the training calls read
+        # the live parameters, so optimizer steps never rebuild it
+        sd = {f'lm.{k}': v for k, v in self.state_dict().items()}
+        ctx = hip.Context(hip.make_dims(sd, len(self.indexer.vocab)), {},
+                          device, finalize=False)
+        named = dict(self.named_parameters())
+        weights = [named[name] for name in self._param_names()]
+        grads = [torch.empty_like(p) for p in weights]
+        cuda_generator = torch.cuda.default_generators[device.index]
+
+        def batch(texts):
+            inputs = torch.tensor(self.indexer(texts,
+                                               start=True,
+                                               stop=False,
+                                               pad=True,
+                                               unk=True))
+            targets = torch.tensor(self.indexer(texts,
+                                                start=False,
+                                                stop=True,
+                                                pad=True,
+                                                unk=True))
+            return inputs, targets
+
+        def mean(loss: torch.Tensor) -> float:
+            return (loss[0] / loss[1]).item()
+
+        progress = range(max_epochs)
+        if display_progress_as is not None:
+            try:
+                from tqdm.auto import tqdm
+                progress = tqdm(progress, desc=display_progress_as)
+            except ImportError:
+                pass
+
+        best = self.state_dict()
+        for _ in progress:
+            self.train()
+            train_loss = 0.
+            for texts in train_loader:
+                inputs, targets = batch(texts)
+                seed = 0
+                if self.training and self.dropout > 0:
+                    seed = int(torch.randint(2**62, (), device=device,
+                                             generator=cuda_generator))
+                dropout = self.dropout if self.training else 0.
+                loss = ctx.lm_train_step(weights, grads, inputs, targets,
+                                         dropout, seed)
+                for p, g in zip(weights, grads):
+                    p.grad = g
+                optimizer.step()
+                optimizer.zero_grad()
+                train_loss += mean(loss)
+            train_loss /= len(train_loader)
+
+            self.eval()
+            val_loss = 0.
+            for texts in val_loader:
+                inputs, targets = batch(texts)
+                val_loss += mean(ctx.lm_nll(weights, inputs, targets))
+            val_loss /= len(val_loader)
+
+            if not isinstance(progress, range):
+                progress.set_description(f'{display_progress_as} '
+                                         f'[train_loss={train_loss:.3f}, '
+                                         f'val_loss={val_loss:.3f}]')
+
+            if stopper(val_loss):
+                self.load_state_dict(best)
+                break
+
+            if stopper.improved:
+                best = self.state_dict()
+        ctx.close()
+
     def properties(self) -> Mapping[str, Any]:
         return {
             'indexer': self.indexer,
@@ -94,3 +317,27 @@ class LanguageModel(nn.Module):
             'layers': self.layers,
             'dropout': self.dropout,
         }
+
+
+def lm(dataset: data.Dataset,
+       annotation_index: int = 4,
+       indexer_kwargs: Optional[Mapping[str, Any]] = None,
+       **kwargs: Any) -> LanguageModel:
+    """A LanguageModel for the annotations of `dataset` (reference
+    lms.py:283-322): each sample's annotations are joined with `lang.join`,
+    the indexer is built from them (`start`, `stop`, `pad`, `unk` default to
+    True; `tokenize` must be given, see the module docstring) and **kwargs go
+    to the constructor.  The parameters are initialised as the reference's
+    torch modules initialise theirs, with the same draws from torch's global
+    generator."""
+    indexer_kwargs = dict(indexer_kwargs or {})
+    annotations = [
+        lang.join(dataset[index][annotation_index])
+        for index in range(len(cast(Sized, dataset)))
+    ]
+    for key in ('start', 'stop', 'pad', 'unk'):
+        indexer_kwargs.setdefault(key, True)
+    indexer = lang.indexer(annotations, **indexer_kwargs)
+    model = LanguageModel(indexer, **kwargs)
+    model.reset_parameters()
+    return model

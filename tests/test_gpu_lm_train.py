@@ -1,0 +1,320 @@
+"""LanguageModel training on the GPU (csrc/lm_train.hip, milan_lm_train_step).
+
+  * Loss and every parameter gradient of one batch against torch autograd on
+    the CPU in float64 (same weights, same batch; with dropout the host
+    regenerates the kernels' mask and applies it in the torch model).
+  * Determinism, overwrite semantics, the padding row.
+  * `LanguageModel.fit` against the reference's own training run
+    (tests/golden/make_golden_lm_fit.py): per-batch and per-epoch losses,
+    final parameters, the early-stopping epoch.
+  * After `fit`, inference (`forward`, `logp`, an attached Decoder's rerank)
+    uses the new weights.
+"""
+import json
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import GOLDEN_DIR
+from milan_amd import decoders, encoders, hip, lang, lms, synthetic
+from oracle import milan_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+META = json.loads((GOLDEN_DIR / 'reference_goldens_lm_fit.json').read_text())
+
+
+@pytest.fixture(scope='module')
+def dev():
+    hip.load_library()
+    return hip.require_device('cuda')
+
+
+def tokenize(texts):
+    if isinstance(texts, str):
+        return tuple(texts.lower().split())
+    return tuple(tuple(t.lower().split()) for t in texts)
+
+
+def names(layers):
+    out = ['embedding.weight']
+    for l in range(layers):
+        out += [f'lstm.{k}_l{l}' for k in ('weight_ih', 'weight_hh', 'bias_ih',
+                                            'bias_hh')]
+    return out + ['output.0.weight', 'output.0.bias']
+
+
+def random_state(v, e, h, layers, seed):
+    g = torch.Generator().manual_seed(seed)
+    sd = {'embedding.weight': torch.randn(v, e, generator=g)}
+    k = h**-0.5
+    for l in range(layers):
+        cin = e if l == 0 else h
+        for name, shape in (('weight_ih', (4 * h, cin)), ('weight_hh', (4 * h, h)),
+                            ('bias_ih', (4 * h,)), ('bias_hh', (4 * h,))):
+            sd[f'lstm.{name}_l{l}'] = (torch.rand(shape, generator=g) * 2 - 1) * k
+    sd['output.0.weight'] = (torch.rand(v, h, generator=g) * 2 - 1) * k
+    sd['output.0.bias'] = (torch.rand(v, generator=g) * 2 - 1) * k
+    return {n: sd[n] for n in names(layers)}
+
+
+def random_batch(v, rows, length, seed):
+    """inputs / targets as lossify builds them: <start> + ids / ids + <stop>,
+    ragged pads, one all-pad row, repeated tokens, <unk>."""
+    nv = v - 4
+    start, stop, pad, unk = nv, nv + 1, nv + 2, nv + 3
+    g = torch.Generator().manual_seed(seed)
+    inputs = torch.full((rows, length), pad, dtype=torch.long)
+    targets = torch.full((rows, length), pad, dtype=torch.long)
+    for r in range(rows):
+        n = 0 if r == 1 else int(torch.randint(1, length, (), generator=g))
+        toks = torch.randint(0, nv, (n,), generator=g)
+        if n > 3:
+            toks[1] = toks[2]  # repeated token
+            toks[-1] = unk
+        if r == 1:  # all pad: not a single valid target
+            continue
+        inputs[r, 0] = start
+        inputs[r, 1:n + 1] = toks
+        targets[r, :n] = toks
+        targets[r, n] = stop
+    return inputs, targets
+
+
+def torch_loss(sd, inputs, targets, pad, layers, masks=None, p=0.):
+    """float64 autograd restatement: Embedding(padding_idx) -> LSTM (dropout
+    on the output of every layer but the last, explicit masks) -> Linear ->
+    log_softmax -> sum of NLL over non-pad targets.  Returns (sum, count,
+    grads)."""
+    w = {k: t.double().clone().requires_grad_(True) for k, t in sd.items()}
+    x = F.embedding(inputs, w['embedding.weight'], padding_idx=pad)
+    rows, length = inputs.shape
+    for l in range(layers):
+        h4 = w[f'lstm.weight_hh_l{l}'].shape[0]
+        hsz = h4 // 4
+        pre = x @ w[f'lstm.weight_ih_l{l}'].t() + w[f'lstm.bias_ih_l{l}'] + \
+            w[f'lstm.bias_hh_l{l}']
+        h = x.new_zeros(rows, hsz)
+        c = x.new_zeros(rows, hsz)
+        outs = []
+        for t in range(length):
+            gates = pre[:, t] + h @ w[f'lstm.weight_hh_l{l}'].t()
+            i, f, gg, o = gates.split(hsz, dim=1)
+            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
+            h = torch.sigmoid(o) * torch.tanh(c)
+            outs.append(h)
+        x = torch.stack(outs, 1)
+        if masks is not None and l < layers - 1:
+            x = x * masks[l].double() / (1 - p)
+    logits = x @ w['output.0.weight'].t() + w['output.0.bias']
+    lp = F.log_softmax(logits, -1)
+    total = F.nll_loss(lp.reshape(-1, lp.shape[-1]), targets.reshape(-1),
+                       ignore_index=pad, reduction='sum')
+    count = int((targets != pad).sum())
+    (total / count).backward()
+    return float(total), count, {k: t.grad for k, t in w.items()}
+
+
+def train_ctx(sd, v, dev):
+    dims = hip.make_dims({f'lm.{k}': t for k, t in sd.items()}, v - 4)
+    return hip.Context(dims, {}, dev, finalize=False)
+
+
+def run_step(ctx, sd, inputs, targets, dev, p=0., seed=0, grads=None):
+    params = [t.to(dev).contiguous() for t in sd.values()]
+    if grads is None:
+        grads = [torch.full_like(t, float('nan')) for t in params]
+    loss = ctx.lm_train_step(params, grads, inputs, targets, p, seed)
+    torch.cuda.synchronize()
+    return loss.cpu(), [g.cpu() for g in grads]
+
+
+def check_grads(sd, loss, grads, want_sum, want_count, want_grads):
+    assert int(loss[1]) == want_count
+    assert abs(float(loss[0]) - want_sum) <= 1e-5 * abs(want_sum), \
+        (float(loss[0]), want_sum)
+    worst = 0.
+    for (name, _), got in zip(sd.items(), grads):
+        want = want_grads[name]
+        scale = float(want.abs().max())
+        err = float((got.double() - want).abs().max())
+        worst = max(worst, err / max(scale, 1e-30))
+        assert err <= 1e-4 * scale + 1e-12, (name, err, scale)
+    print(f'loss {float(loss[0]):.6f} ({want_sum:.6f}), worst grad err / max|grad| '
+          f'{worst:.2e}')
+
+
+@pytest.mark.parametrize('v,e,h,layers,rows,length', [
+    (61, 16, 32, 1, 9, 7),
+    (64, 16, 32, 2, 16, 12),
+    (61, 32, 32, 3, 5, 9),
+    (64, 128, 512, 2, 6, 8),
+    (5004, 128, 512, 2, 8, 12),
+    (5004, 16, 32, 3, 3, 5),
+])
+def test_gradients_match_autograd_float64(dev, v, e, h, layers, rows, length):
+    sd = random_state(v, e, h, layers, seed=v + h + layers)
+    inputs, targets = random_batch(v, rows, length, seed=rows * length)
+    ctx = train_ctx(sd, v, dev)
+    loss, grads = run_step(ctx, sd, inputs, targets, dev)
+    check_grads(sd, loss, grads, *torch_loss(sd, inputs, targets, v - 2, layers))
+    # eval-mode loss is the same forward
+    nll = ctx.lm_nll([t.to(dev) for t in sd.values()], inputs, targets).cpu()
+    assert torch.equal(nll, loss)
+    ctx.close()
+
+
+@pytest.mark.parametrize('v,e,h,layers,p', [(61, 16, 32, 2, 0.5),
+                                            (64, 32, 512, 3, 0.2)])
+def test_dropout_gradients_match_with_host_mask(dev, v, e, h, layers, p):
+    sd = random_state(v, e, h, layers, seed=5)
+    inputs, targets = random_batch(v, 7, 10, seed=8)
+    ctx = train_ctx(sd, v, dev)
+    seed = 0x1234_5678_9abc_def0
+    loss, grads = run_step(ctx, sd, inputs, targets, dev, p, seed)
+    masks = [lms.dropout_mask(seed, l, 7, 10, h, p) for l in range(layers - 1)]
+    check_grads(sd, loss, grads,
+                *torch_loss(sd, inputs, targets, v - 2, layers, masks, p))
+    ctx.close()
+
+
+def test_deterministic_overwritten_and_padding_row_zero(dev):
+    v, e, h, layers = 5004, 64, 256, 2
+    sd = random_state(v, e, h, layers, seed=2)
+    inputs, targets = random_batch(v, 64, 16, seed=4)
+    ctx = train_ctx(sd, v, dev)
+    params = [t.to(dev) for t in sd.values()]
+    grads = [torch.full_like(t, 7.) for t in params]  # garbage: overwritten
+    loss1, g1 = run_step(ctx, sd, inputs, targets, dev, 0.5, 99, grads=grads)
+    loss2, g2 = run_step(ctx, sd, inputs, targets, dev, 0.5, 99)
+    assert torch.equal(loss1, loss2)
+    for a, b in zip(g1, g2):
+        assert torch.equal(a, b)
+    assert not g1[0][v - 2].any()  # padding_idx row exactly zero
+    loss3, g3 = run_step(ctx, sd, inputs, targets, dev, 0.5, 100)
+    assert not torch.equal(loss1, loss3) and not torch.equal(g1[1], g3[1])
+    ctx.close()
+
+
+# ---- fit against the reference's run ---------------------------------------------
+@pytest.fixture(scope='module')
+def golden():
+    return torch.load(GOLDEN_DIR / 'reference_goldens_lm_fit.pt')
+
+
+def dataset():
+    return [(i, None, None, None, ann) for i, ann in enumerate(META['corpus'])]
+
+
+# max |parameter - reference| after the run.  Measured on the MI355X: 3.9e-7
+# (fit_split), 3.1e-7 (fit_fixed), both at lr 1e-3, and 7.7e-5 for fit_stop at
+# lr 0.05 (Adam's normalised steps amplify fp32 reordering); bounds ~13-25x that.
+PARAM_ATOL = {'fit_split': 1e-5, 'fit_fixed': 1e-5, 'fit_stop': 1e-3}
+
+
+@pytest.mark.parametrize('case', ['fit_split', 'fit_fixed', 'fit_stop'])
+def test_fit_reproduces_reference_run(dev, golden, monkeypatch, case):
+    torch.manual_seed(7)
+    model = lms.lm(dataset(), indexer_kwargs=dict(tokenize=tokenize), **META['dims'])
+    for name, t in model.state_dict().items():
+        assert torch.equal(t, golden[f'{case}_init'][name])
+    model.to(dev)
+    seen = {'train': [], 'val': []}
+    train_step, nll = hip.Context.lm_train_step, hip.Context.lm_nll
+
+    def spy(kind, fn):
+        def call(self, *a, **k):
+            loss = fn(self, *a, **k)
+            seen[kind].append(loss)
+            return loss
+        return call
+
+    monkeypatch.setattr(hip.Context, 'lm_train_step', spy('train', train_step))
+    monkeypatch.setattr(hip.Context, 'lm_nll', spy('val', nll))
+    torch.set_rng_state(golden[f'{case}_rng'])
+    model.fit(dataset(), batch_size=16, display_progress_as=None,
+              **META[case]['kwargs'])
+    want = META[case]
+    got = {k: [float(l[0] / l[1]) for l in v] for k, v in seen.items()}
+    assert len(got['train']) == want['epochs'] * want['train_batches']
+    assert len(got['val']) == want['epochs'] * want['val_batches']
+    for kind in ('train', 'val'):
+        g = torch.tensor(got[kind], dtype=torch.float64)
+        w = torch.tensor(want[f'batch_{kind}_loss'], dtype=torch.float64)
+        rel = float(((g - w).abs() / w.abs()).max())
+        print(f'{case} {kind}: max relative loss gap {rel:.2e}')
+        assert rel <= 1e-4, (kind, rel)
+    n = want['train_batches']
+    epochs = [sum(got['train'][i * n:(i + 1) * n]) / n for i in range(want['epochs'])]
+    assert epochs == pytest.approx(want['train_loss'], rel=1e-4)
+    worst = 0.
+    final = golden[f'{case}_final']
+    for name, t in model.state_dict().items():
+        gap = float((t.cpu() - final[name]).abs().max())
+        worst = max(worst, gap)
+    print(f'{case}: max |param - reference| {worst:.2e} after {want["epochs"]} epochs')
+    assert worst <= PARAM_ATOL[case], worst
+
+
+# ---- inference after fit --------------------------------------------------------
+NV = 40
+
+
+def vocab_corpus(n=120, seed=3):
+    tokens = synthetic.vocab_tokens(NV)
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for i in range(n):
+        k = int(torch.randint(2, 8, (), generator=g))
+        ids = torch.randint(0, NV, (k,), generator=g).tolist()
+        out.append((i, None, None, None, ' '.join(tokens[j] for j in ids)))
+    return out
+
+
+def test_inference_uses_fitted_weights(dev):
+    idx = lang.Indexer(lang.Vocab(synthetic.vocab_tokens(NV)), tokenize, True, True,
+                       True, True)
+    enc = encoders.PyramidConvEncoder('resnet50', width=16, pretrained=False)
+    lm = lms.LanguageModel(idx, 16, 32, layers=2, dropout=0.)
+    dec = decoders.Decoder(idx, enc, lm, embedding_size=16, hidden_size=32,
+                           length=8, beam_size=4)
+    sd = synthetic.milan_state_dict(NV + 4, 'resnet50', seed=11, width=16,
+                                    hidden_size=32, embedding_size=16,
+                                    lm_hidden_size=32, lm_embedding_size=16)
+    dec.load_state_dict(sd, strict=True)
+    dec.to(dev)
+    feats = torch.randn(3, 5, dec.encoder.feature_shape[0],
+                        generator=torch.Generator().manual_seed(1)).abs()
+    texts = [c[4] for c in vocab_corpus(6, seed=9)]
+    seqs = torch.tensor(idx(texts, start=True, stop=True, pad=True, unk=True))
+    before_score = lm(seqs, reduce=True).cpu()
+    before_rerank = dec(feats.to(dev), encode=False, strategy='rerank').scores.cpu()
+
+    torch.manual_seed(0)
+    lm.fit(vocab_corpus(), batch_size=16, max_epochs=2, display_progress_as=None,
+           optimizer_kwargs=dict(lr=1e-2))
+    fitted = {k: t.detach().cpu() for k, t in dec.state_dict().items()}
+    assert not torch.equal(fitted['lm.output.0.weight'], sd['lm.output.0.weight'])
+    lm_sd = {k[3:]: t for k, t in fitted.items() if k.startswith('lm.')}
+
+    with torch.no_grad():
+        want_score = O.lm_score(seqs, fitted, idx.stop_index)
+    for got in (lm(seqs, reduce=True).cpu(), lm.logp(texts).cpu()):
+        scale = float(want_score.abs().max())
+        assert float((got - want_score).abs().max()) <= 2e-5 * scale + 2e-5
+        assert not torch.allclose(got, before_score)
+    # a standalone copy of the fitted LM (its own context) agrees too
+    solo = lms.LanguageModel(idx, 16, 32, layers=2, dropout=0.)
+    solo.load_state_dict(lm_sd)
+    assert torch.allclose(solo.to(dev)(seqs, reduce=True).cpu(), want_score,
+                          rtol=2e-5, atol=2e-5)
+
+    out = dec(feats.to(dev), encode=False, strategy='rerank')
+    with torch.no_grad():
+        want = O.forward(feats, fitted, NV, 'rerank', length=8, beam_size=4)
+    # rerank score = beam score - temperature * LM score of the chosen beam
+    torch.testing.assert_close(out.beam_scores.cpu(), want['beam_scores'],
+                               rtol=1e-4, atol=2e-3)
+    torch.testing.assert_close(out.scores.cpu(), want['scores'], rtol=1e-4, atol=2e-3)
+    assert not torch.allclose(out.scores.cpu(), before_rerank)

@@ -36,7 +36,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MILAN_ABI_VERSION 9
+#define MILAN_ABI_VERSION 10
 
 enum {
   MILAN_OK = 0,
@@ -574,6 +574,61 @@ int milan_lm_train_step(milan_ctx* ctx, const float* const* params,
                         int L, float dropout, uint64_t seed,
                         float* loss_sum_and_count, void* workspace,
                         size_t workspace_bytes, milan_stream stream);
+
+/* ---- Decoder training (src/milan/decoders.py:873-1070) -----------------------
+ * Loss, forward and backward of the teacher-forced attention LSTM,
+ * Decoder.forward(features, strategy=targets, mi=False) in training mode, with
+ * NLLLoss(ignore_index = pad_index) and the double-stochasticity regulariser.
+ *   params / grads: HOST arrays of 19 DEVICE fp32 pointers, the decoder's own
+ *     state dict in the reference's order: init_h.0.weight, init_h.0.bias,
+ *     init_c.0.weight, init_c.0.bias, embedding.weight,
+ *     attend.query_to_hidden.weight, .bias, attend.key_to_hidden.weight, .bias,
+ *     attend.output.0.weight, .bias, feature_gate.0.weight, .bias,
+ *     lstm.weight_ih, lstm.weight_hh, lstm.bias_ih, lstm.bias_hh,
+ *     output.1.weight, output.1.bias; raw torch layout.  They are read on every
+ *     call: the ctx only supplies the decoder dims (feature, hidden, embedding,
+ *     attention and vocab sizes, start_index, pad_index) and need not be
+ *     finalized; its weight arena is not used.
+ *   features: (rows, k, feature_size) fp32 DEVICE, the frozen encoder's output
+ *     (no gradient flows into it).
+ *   targets: (rows, L) int64 DEVICE, the indexed captions without <start>
+ *     (with <stop>, padded).  The input of step 0 is <start>, of step t
+ *     targets[:, t-1].  Ids must lie in [0, vocab_size): the caller validates
+ *     (out-of-range ids are clamped, not reported).  Targets equal to pad_index
+ *     do not count in the NLL.
+ *   loss_terms: DEVICE float[3] <- the sum of -log p(target) over the valid
+ *     targets, their number, and sum over (row, feature) of
+ *     (1 - sum_t alpha_t)^2 over all L steps (pad steps included).  The mean
+ *     NLL is [0] / [1] (NaN when [1] == 0, as in torch); the training loss is
+ *     [0] / [1] + regularization_weight * [2] / (rows * k).
+ *   milan_decoder_nll        eval mode (no dropout).  The reference's validation
+ *     loss is the NLL alone, [0] / [1].
+ *   milan_decoder_train_step train mode: dropout p on h before the output
+ *     Linear, mask a pure function of (seed, row, t, unit):
+ *     keep <=> (mix64(seed ^ mix64(0xDC<<56 | row<<32 | t<<16 | unit)) >> 40)
+ *     >= (uint32)(p * 2^24), kept values scaled by 1 / (1 - p), mix64 = the
+ *     splitmix64 finaliser (the LM's hash with its own tag 0xDC in place of the
+ *     layer).  Then the gradient of the training loss with respect to every
+ *     parameter is written to `grads`: OVERWRITTEN, not accumulated.  The
+ *     embedding has no padding row: pad inputs get their gradient too.
+ * Precision: exact fp32 MFMA whatever milan_set_precision says.  Deterministic:
+ * no float atomics, fixed reduction orders; equal inputs and seed give equal
+ * bits.  Neither call synchronises.
+ * 0 < rows < 2^24, 0 < L < 2^16, 0 < k <= 64, rows * L * k < 2^30,
+ * hidden_size < 2^14. */
+size_t milan_decoder_train_workspace_bytes(const milan_ctx* ctx, int rows,
+                                           int k, int L);
+int milan_decoder_nll(milan_ctx* ctx, const float* const* params, int n_params,
+                      const float* features, const int64_t* targets, int rows,
+                      int k, int L, float* loss_terms, void* workspace,
+                      size_t workspace_bytes, milan_stream stream);
+int milan_decoder_train_step(milan_ctx* ctx, const float* const* params,
+                             float* const* grads, int n_params,
+                             const float* features, const int64_t* targets,
+                             int rows, int k, int L, float dropout,
+                             uint64_t seed, float regularization_weight,
+                             float* loss_terms, void* workspace,
+                             size_t workspace_bytes, milan_stream stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -1,0 +1,618 @@
+// Decoder training (src/milan/decoders.py:873-1070): the loss, forward and backward of the
+// teacher-forced attention LSTM, Decoder.forward(features, strategy=targets, mi=False) in
+// training mode (decoders.py:431-463, 576-634), over a padded (rows, L) batch of targets
+// with k visual features per row.
+//
+//   h_0 = tanh(W_h mean_k f + b_h),  c_0 = tanh(W_c mean_k f + b_c)
+//   per step t (input x_t = <start> at t = 0, targets[:, t-1] after):
+//     q = W_q h_t + b_q;  u_k = tanh(q + W_k f_k + b_k);  s_k = w_o . u_k + b_o
+//     alpha = softmax_k(s);  ctx = sum_k alpha_k f_k;  z = ctx * sigmoid(W_g h_t + b_g)
+//     (h_{t+1}, c_{t+1}) = LSTMCell([emb(x_t) ; z], (h_t, c_t))
+//     log p_t = log_softmax(W_out dropout(h_{t+1}) + b_out)
+//   loss = NLL(ignore pad) mean + w * mean_{row, k} (1 - sum_t alpha_{t,k})^2
+//
+// As in lm_train.hip: exact fp32 MFMA whatever milan_set_precision says, raw torch-layout
+// parameters read on every call through the strided GEMM of train_common.h, fixed
+// reduction orders and no float atomics (equal inputs and seed give equal bits).
+//
+// Layout.  Hoisted before the time loop: the feature mean and the
+// init_h / init_c GEMMs, the attention keys W_k f + b_k of all rows * k features, and the
+// embedding columns of W_ih for all rows * L inputs (teacher forcing knows every input up
+// front).  Per step: the query and gate GEMMs, one attention kernel (scores, softmax,
+// context, gate), the context columns of W_ih and W_hh accumulated into the step's gates,
+// the cell.  After the loop: one vocabulary GEMM, the NLL rows and the regulariser.
+// Backward per step, in reverse time: cell, dz = dG . W_ih[:, E:], one attention-backward
+// kernel (gate, context, softmax and tanh backward into dq and the per-feature dK, which is
+// accumulated in fixed t order), dh_t = dq . W_q + dgate . W_g + dG . W_hh.  The weight
+// gradients are grouped GEMMs over all steps after the loop.
+#include "train_common.h"
+
+namespace milan {
+namespace dect {
+
+using lmt::colsum;
+using lmt::gemm;
+using lmt::Scratch;
+using lmt::split_scratch_floats;
+using lmt::View;
+using lmt::view;
+
+constexpr int kMaxK = 64;  // features per row (the attention kernels keep k scores in LDS)
+// the decoder's dropout mask tag: the top byte of the hashed key, above every LM layer
+constexpr uint64_t kDropoutTag = 0xDC;
+
+// keep <=> (mix64(seed ^ mix64(0xDC << 56 | row << 32 | t << 16 | unit)) >> 40) >= thr
+__device__ __forceinline__ bool keep(uint64_t seed, int row, int t, int unit, uint32_t thr) {
+  const uint64_t key = kDropoutTag << 56 | (uint64_t)row << 32 | (uint64_t)t << 16 |
+                       (uint64_t)unit;
+  return (uint32_t)(lmt::mix64(seed ^ lmt::mix64(key)) >> 40) >= thr;
+}
+
+__device__ __forceinline__ int clamp_id(int64_t id, int V) {
+  return id < 0 ? 0 : (id >= V ? V - 1 : (int)id);
+}
+__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
+
+__device__ __forceinline__ float wave_sum(float v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+static unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
+
+// Teacher-forced inputs: in[b][0] = start, in[b][t] = targets[b][t - 1].
+__global__ void inputs_kernel(const int64_t* __restrict__ tgt, int64_t* __restrict__ in, int rows,
+                              int L, int start) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * L) return;
+  const int t = (int)(i % L);
+  in[i] = t ? tgt[i - 1] : (int64_t)start;
+}
+
+// X[n][e] = embedding[in[n]][e] for e < E (row stride E + F: the context columns follow)
+__global__ void embed_kernel(const int64_t* __restrict__ ids, const float* __restrict__ emb,
+                             float* __restrict__ X, int N, int E, int F, int V) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)N * E) return;
+  const int n = (int)(i / E), e = (int)(i % E);
+  X[(long)n * (E + F) + e] = emb[(long)clamp_id(ids[n], V) * E + e];
+}
+
+// pooled[b][f] = (sum over k of feat[b][k][f], in k order) / k
+__global__ void pool_kernel(const float* __restrict__ feat, float* __restrict__ pooled, int rows,
+                            int k, int F) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * F) return;
+  const int b = (int)(i / F), f = (int)(i % F);
+  float s = 0.f;
+  for (int j = 0; j < k; ++j) s += feat[((long)b * k + j) * F + f];
+  pooled[i] = s / (float)k;
+}
+
+// slot 0 of Hs and C: tanh of the init_h / init_c pre-activations written there
+__global__ void init_fwd_kernel(float* __restrict__ Hs, float* __restrict__ C, int rows, int L,
+                                int H) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * H) return;
+  const long o = (i / H) * (L + 1) * H + i % H;
+  Hs[o] = tanhf(Hs[o]);
+  C[o] = tanhf(C[o]);
+}
+
+// Attention of step t, one workgroup per row b.  Q: queries [rows * L][A]; Kh: keys
+// [rows * k][A]; GT: gate pre-activations in, sigmoid out [rows * L][F].  Writes U (the tanh
+// hidden, [rows * L * k][A]), ALPHA [rows * L][k], CTX [rows * L][F] and z = ctx * gate into
+// the context columns of X.
+__global__ __launch_bounds__(256) void attend_fwd_kernel(
+    const float* __restrict__ Q, const float* __restrict__ Kh, const float* __restrict__ feat,
+    const float* __restrict__ w_o, const float* __restrict__ b_o, float* __restrict__ GT,
+    float* __restrict__ CTX, float* __restrict__ X, float* __restrict__ ALPHA,
+    float* __restrict__ U, int L, int k, int A, int F, int E, int t) {
+  __shared__ float sc[kMaxK];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long n = (long)b * L + t;
+  const float* q = Q + n * A;
+  for (int j = w; j < k; j += 4) {
+    const float* kh = Kh + ((long)b * k + j) * A;
+    float* u = U + (n * k + j) * A;
+    float s = 0.f;
+    for (int a = lane; a < A; a += 64) {
+      const float v = tanhf(q[a] + kh[a]);
+      u[a] = v;
+      s += v * w_o[a];
+    }
+    s = wave_sum(s);
+    if (lane == 0) sc[j] = s + b_o[0];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float m = -INFINITY;
+    for (int j = 0; j < k; ++j) m = fmaxf(m, sc[j]);
+    float sum = 0.f;
+    for (int j = 0; j < k; ++j) {
+      sc[j] = expf(sc[j] - m);
+      sum += sc[j];
+    }
+    for (int j = 0; j < k; ++j) {
+      sc[j] = sc[j] / sum;
+      ALPHA[n * k + j] = sc[j];
+    }
+  }
+  __syncthreads();
+  const float* fb = feat + (long)b * k * F;
+  for (int f = tid; f < F; f += blockDim.x) {
+    float c = 0.f;
+    for (int j = 0; j < k; ++j) c += sc[j] * fb[(long)j * F + f];
+    const float g = sigm(GT[n * F + f]);
+    GT[n * F + f] = g;
+    CTX[n * F + f] = c;
+    X[n * (E + F) + E + f] = c * g;
+  }
+}
+
+// One LSTM cell step t (torch gate order i, f, g, o).  G: pre-activations of step t in,
+// activated gates out [rows * L][4H]; C, Hs: [rows][L + 1][H], slot t in, slot t + 1 out.
+__global__ void cell_fwd_kernel(float* __restrict__ G, float* __restrict__ C,
+                                float* __restrict__ Hs, int rows, int L, int H, int t) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * H) return;
+  const int b = (int)(i / H), j = (int)(i % H);
+  float* g = G + ((long)b * L + t) * 4 * H;
+  const float ig = sigm(g[j]), fg = sigm(g[H + j]), gg = tanhf(g[2 * H + j]),
+              og = sigm(g[3 * H + j]);
+  const long o = ((long)b * (L + 1) + t) * H + j;
+  const float c = fg * C[o] + ig * gg;
+  g[j] = ig;
+  g[H + j] = fg;
+  g[2 * H + j] = gg;
+  g[3 * H + j] = og;
+  C[o + H] = c;
+  Hs[o + H] = og * tanhf(c);
+}
+
+// HD[b][t][j] = dropout(h_{t+1})  (mask * scale)
+__global__ void dropout_fwd_kernel(const float* __restrict__ Hs, float* __restrict__ HD, int rows,
+                                   int L, int H, uint64_t seed, uint32_t thr, float scale) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * L * H) return;
+  const int j = (int)(i % H);
+  const long bt = i / H;
+  const int t = (int)(bt % L), b = (int)(bt / L);
+  const float h = Hs[((long)b * (L + 1) + t + 1) * H + j];
+  HD[i] = keep(seed, b, t, j, thr) ? h * scale : 0.f;
+}
+
+// dY[b][t][j] *= mask * scale (the same mask as dropout_fwd_kernel)
+__global__ void dropout_bwd_kernel(float* __restrict__ dY, int rows, int L, int H, uint64_t seed,
+                                   uint32_t thr, float scale) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * L * H) return;
+  const int j = (int)(i % H);
+  const long bt = i / H;
+  const int t = (int)(bt % L), b = (int)(bt / L);
+  dY[i] = keep(seed, b, t, j, thr) ? dY[i] * scale : 0.f;
+}
+
+// S[b][j] = sum over t (in order) of alpha[b][t][j]
+__global__ void attn_sum_kernel(const float* __restrict__ ALPHA, float* __restrict__ S, int rows,
+                                int L, int k) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * k) return;
+  const int b = (int)(i / k), j = (int)(i % k);
+  float s = 0.f;
+  for (int t = 0; t < L; ++t) s += ALPHA[((long)b * L + t) * k + j];
+  S[i] = s;
+}
+
+// out[0] = sum over rows * k of (1 - S)^2 (one workgroup, fixed order)
+__global__ __launch_bounds__(256) void reg_reduce_kernel(const float* __restrict__ S, long n,
+                                                         float* __restrict__ out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (long i = threadIdx.x; i < n; i += blockDim.x) {
+    const float d = 1.f - S[i];
+    s += d * d;
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Backward of cell step t.  dY: dL/dh_{t+1} from the output layer [rows * L][H]; dhrec:
+// dL/dh_{t+1} through step t + 1 (absent at t = L - 1); dc: dL/dc_{t+1} in (absent at
+// t = L - 1), dL/dc_t out.  G: activated gates in, d(pre-activation) out.
+__global__ void cell_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dhrec,
+                                float* __restrict__ G, const float* __restrict__ C,
+                                float* __restrict__ dc, int rows, int L, int H, int t) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * H) return;
+  const int b = (int)(i / H), j = (int)(i % H);
+  const bool last = t == L - 1;
+  float* g = G + ((long)b * L + t) * 4 * H;
+  const float ig = g[j], fg = g[H + j], gg = g[2 * H + j], og = g[3 * H + j];
+  const long o = ((long)b * (L + 1) + t) * H + j;
+  const float cp = C[o], c = C[o + H];
+  const float d_h = dY[((long)b * L + t) * H + j] + (last ? 0.f : dhrec[i]);
+  const float tc = tanhf(c);
+  const float dcur = d_h * og * (1.f - tc * tc) + (last ? 0.f : dc[i]);
+  dc[i] = dcur * fg;
+  g[j] = dcur * gg * ig * (1.f - ig);
+  g[H + j] = dcur * cp * fg * (1.f - fg);
+  g[2 * H + j] = dcur * ig * (1.f - gg * gg);
+  g[3 * H + j] = d_h * tc * og * (1.f - og);
+}
+
+// Attention backward of step t, one workgroup per row b.  dZ: dL/dz of the step [rows][F].
+// Writes DGP (d gate pre-activation, [rows * L][F]), DS (d score, [rows * L][k]), DQ (d query,
+// [rows * L][A]) and accumulates dKh [rows * k][A] (overwritten at t = L - 1, then added to
+// in decreasing t).  reg = 2 w / (rows * k): the regulariser adds -reg (1 - S) to d alpha.
+__global__ __launch_bounds__(256) void attend_bwd_kernel(
+    const float* __restrict__ dZ, const float* __restrict__ GT, const float* __restrict__ CTX,
+    const float* __restrict__ feat, const float* __restrict__ ALPHA, const float* __restrict__ U,
+    const float* __restrict__ S, const float* __restrict__ w_o, float reg,
+    float* __restrict__ DGP, float* __restrict__ DS, float* __restrict__ DQ,
+    float* __restrict__ dKh, int L, int k, int A, int F, int t) {
+  __shared__ float da[kMaxK];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long n = (long)b * L + t;
+  const float* dz = dZ + (long)b * F;
+  const float* gt = GT + n * F;
+  const float* fb = feat + (long)b * k * F;
+  for (int f = tid; f < F; f += blockDim.x) {
+    const float g = gt[f];
+    DGP[n * F + f] = dz[f] * CTX[n * F + f] * g * (1.f - g);
+  }
+  // d alpha_j = (dz * gate) . f_j - reg (1 - S_j)
+  for (int j = w; j < k; j += 4) {
+    const float* fj = fb + (long)j * F;
+    float s = 0.f;
+    for (int f = lane; f < F; f += 64) s += dz[f] * gt[f] * fj[f];
+    s = wave_sum(s);
+    if (lane == 0) da[j] = s - reg * (1.f - S[(long)b * k + j]);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float dot = 0.f;
+    for (int j = 0; j < k; ++j) dot += ALPHA[n * k + j] * da[j];
+    for (int j = 0; j < k; ++j) {
+      da[j] = ALPHA[n * k + j] * (da[j] - dot);
+      DS[n * k + j] = da[j];
+    }
+  }
+  __syncthreads();
+  for (int a = tid; a < A; a += blockDim.x) {
+    const float wa = w_o[a];
+    float dq = 0.f;
+    for (int j = 0; j < k; ++j) {
+      const float u = U[(n * k + j) * A + a];
+      const float du = da[j] * wa * (1.f - u * u);
+      dq += du;
+      const long o = ((long)b * k + j) * A + a;
+      dKh[o] = t == L - 1 ? du : dKh[o] + du;
+    }
+    DQ[n * A + a] = dq;
+  }
+}
+
+// d pre-activations of init_h / init_c from dh_0 (dhrec) and dc_0 (dc)
+__global__ void init_bwd_kernel(const float* __restrict__ Hs, const float* __restrict__ C,
+                                const float* __restrict__ dhrec, const float* __restrict__ dc,
+                                float* __restrict__ dph, float* __restrict__ dpc, int rows, int L,
+                                int H) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * H) return;
+  const long o = (i / H) * (L + 1) * H + i % H;
+  const float h = Hs[o], c = C[o];
+  dph[i] = dhrec[i] * (1.f - h * h);
+  dpc[i] = dc[i] * (1.f - c * c);
+}
+
+// ---- workspace layout -------------------------------------------------------------------
+struct Plan {
+  int V, E, H, A, F, pad, start, rows, k, L, N;
+  size_t ids, pooled, kh, x, g, cst, hs, hd, q, gt, ctx, alpha, u, s, logits, lse, term, valid;
+  size_t dy, dhrec, dc, dz, dgp, ds, dq, dkh, dxe, dph, dpc, scratch, scratch_floats, total;
+};
+
+static int make_plan(const milan_ctx* c, int rows, int k, int L, Plan* p) {
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "decoder train: null ctx");
+  const milan_dims& d = c->d;
+  MILAN_REQUIRE(rows > 0 && L > 0 && rows < (1 << 24) && L < (1 << 16), MILAN_ERR_SHAPE,
+                "decoder train: need 0 < rows < 2^24 and 0 < L < 2^16 (rows %d, L %d)", rows, L);
+  MILAN_REQUIRE(k > 0 && k <= kMaxK, MILAN_ERR_SHAPE,
+                "decoder train: need 0 < k <= %d features per row, got %d", kMaxK, k);
+  MILAN_REQUIRE((long)rows * L * k < (1L << 30), MILAN_ERR_SHAPE, "decoder train: batch too large");
+  MILAN_REQUIRE(d.hidden_size > 0 && d.hidden_size < (1 << 14) && d.embedding_size > 0 &&
+                    d.attention_size > 0 && d.feature_size > 0 && d.vocab_size > 0,
+                MILAN_ERR_SHAPE, "decoder train: the context has no decoder dims");
+  p->V = d.vocab_size;
+  p->E = d.embedding_size;
+  p->H = d.hidden_size;
+  p->A = d.attention_size;
+  p->F = d.feature_size;
+  p->pad = d.pad_index;
+  p->start = d.start_index;
+  p->rows = rows;
+  p->k = k;
+  p->L = L;
+  const int N = p->N = rows * L, H = p->H, E = p->E, V = p->V, A = p->A, F = p->F;
+  const long BK = (long)rows * k;
+  size_t off = 0;
+  auto take = [&](size_t floats) {
+    const size_t at = off;
+    off += (floats + 63) / 64 * 64;
+    return at;
+  };
+  p->ids = take((size_t)N * 2);  // int64
+  p->pooled = take((size_t)rows * F);
+  p->kh = take((size_t)BK * A);
+  p->x = take((size_t)N * (E + F));
+  p->g = take((size_t)N * 4 * H);
+  p->cst = take((size_t)rows * (L + 1) * H);
+  p->hs = take((size_t)rows * (L + 1) * H);
+  p->hd = take((size_t)N * H);
+  p->q = take((size_t)N * A);
+  p->gt = take((size_t)N * F);
+  p->ctx = take((size_t)N * F);
+  p->alpha = take((size_t)N * k);
+  p->u = take((size_t)N * k * A);
+  p->s = take((size_t)BK);
+  p->logits = take((size_t)N * V);
+  p->lse = take(N);
+  p->term = take(N);
+  p->valid = take(N);
+  p->dy = take((size_t)N * H);
+  p->dhrec = take((size_t)rows * H);
+  p->dc = take((size_t)rows * H);
+  p->dz = take((size_t)rows * F);
+  p->dgp = take((size_t)N * F);
+  p->ds = take((size_t)N * k);
+  p->dq = take((size_t)N * A);
+  p->dkh = take((size_t)BK * A);
+  p->dxe = take((size_t)N * E);
+  p->dph = take((size_t)rows * H);
+  p->dpc = take((size_t)rows * H);
+  size_t sc = 0;
+  auto need = [&](size_t f) { sc = f > sc ? f : sc; };
+  auto cs = [&](long R, long cols) { need((size_t)lmt::colsum_chunks((int)R) * cols); };
+  cs(N, V);
+  cs(N, 4 * H);
+  cs(N, A);
+  cs(N, F);
+  cs(BK, A);
+  cs((long)N * k, 1);
+  cs(rows, H);
+  const int KK = (int)((long)N * k);
+  const int shapes[][3] = {
+      {rows, H, F},  {(int)BK, A, F}, {N, 4 * H, E},  {rows, A, H},     {rows, F, H},
+      {rows, 4 * H, F}, {rows, 4 * H, H}, {N, V, H},  {V, H, N},        {N, H, V},
+      {rows, F, 4 * H}, {rows, H, A}, {rows, H, 4 * H}, {4 * H, E + F, N}, {4 * H, H, N}, {A, H, N},
+      {F, H, N},     {A, F, (int)BK}, {1, A, KK},     {N, E, 4 * H},    {H, F, rows}};
+  for (const auto& s : shapes) need(split_scratch_floats(s[0], s[1], s[2]));
+  p->scratch = take(sc);
+  p->scratch_floats = sc;
+  p->total = off * sizeof(float);
+  return 0;
+}
+
+// the 19 tensors of the decoder's own state dict, in the reference's order
+enum {
+  P_INIT_H_W, P_INIT_H_B, P_INIT_C_W, P_INIT_C_B, P_EMB, P_Q_W, P_Q_B, P_K_W, P_K_B, P_O_W,
+  P_O_B, P_GATE_W, P_GATE_B, P_W_IH, P_W_HH, P_B_IH, P_B_HH, P_OUT_W, P_OUT_B, N_PARAMS
+};
+
+static int check_params(const void* const* params, int n, const char* what) {
+  MILAN_REQUIRE(params, MILAN_ERR_ARG, "decoder train: null %s list", what);
+  MILAN_REQUIRE(n == N_PARAMS, MILAN_ERR_ARG,
+                "decoder train: %d %s pointers given, the decoder's state dict has %d", n, what,
+                (int)N_PARAMS);
+  for (int i = 0; i < n; ++i)
+    MILAN_REQUIRE(params[i], MILAN_ERR_ARG, "decoder train: %s %d is null", what, i);
+  return 0;
+}
+
+static uint32_t drop_threshold(float p) { return (uint32_t)((double)p * 16777216.0); }
+
+// Forward, loss terms [nll sum, valid count, sum (1 - S)^2].  thr > 0: dropout on h.
+static int forward(const Plan& p, const float* const* w, float* ws, const float* feat,
+                   const int64_t* targets, uint32_t thr, float scale, uint64_t seed, float* loss,
+                   hipStream_t s) {
+  const int N = p.N, H = p.H, E = p.E, V = p.V, A = p.A, F = p.F, rows = p.rows, k = p.k,
+            L = p.L;
+  const int BK = rows * k;
+  const Scratch sc{ws + p.scratch, p.scratch_floats};
+  const View none = view(nullptr, 0);
+  int64_t* ids = (int64_t*)(ws + p.ids);
+  float *X = ws + p.x, *G = ws + p.g, *C = ws + p.cst, *Hs = ws + p.hs, *Q = ws + p.q,
+        *GT = ws + p.gt, *Kh = ws + p.kh;
+  hipLaunchKernelGGL(inputs_kernel, dim3(blocks_for(N)), dim3(256), 0, s, targets, ids, rows, L,
+                     p.start);
+  hipLaunchKernelGGL(embed_kernel, dim3(blocks_for((long)N * E)), dim3(256), 0, s, ids,
+                     w[P_EMB], X, N, E, F, V);
+  hipLaunchKernelGGL(pool_kernel, dim3(blocks_for((long)rows * F)), dim3(256), 0, s, feat,
+                     ws + p.pooled, rows, k, F);
+  MILAN_CHECK_HIP(hipGetLastError());
+  // h_0, c_0 into slot 0 of Hs / C
+  const View slot0h = view(Hs, (long)(L + 1) * H), slot0c = view(C, (long)(L + 1) * H);
+  MILAN_TRY(gemm(view(ws + p.pooled, F), 0, view(w[P_INIT_H_W], F), 1, slot0h, none,
+                 w[P_INIT_H_B], nullptr, rows, H, F, sc, s));
+  MILAN_TRY(gemm(view(ws + p.pooled, F), 0, view(w[P_INIT_C_W], F), 1, slot0c, none,
+                 w[P_INIT_C_B], nullptr, rows, H, F, sc, s));
+  hipLaunchKernelGGL(init_fwd_kernel, dim3(blocks_for((long)rows * H)), dim3(256), 0, s, Hs, C,
+                     rows, L, H);
+  // attention keys of every feature, embedding part of every step's gates
+  MILAN_TRY(gemm(view(feat, F), 0, view(w[P_K_W], F), 1, view(Kh, A), none, w[P_K_B], nullptr,
+                 BK, A, F, sc, s));
+  MILAN_TRY(gemm(view(X, E + F), 0, view(w[P_W_IH], E + F), 1, view(G, 4 * H), none, w[P_B_IH],
+                 w[P_B_HH], N, 4 * H, E, sc, s));
+  for (int t = 0; t < L; ++t) {
+    const View ht = view(Hs + (size_t)t * H, (long)(L + 1) * H);
+    MILAN_TRY(gemm(ht, 0, view(w[P_Q_W], H), 1, view(Q + (size_t)t * A, (long)L * A), none,
+                   w[P_Q_B], nullptr, rows, A, H, sc, s));
+    MILAN_TRY(gemm(ht, 0, view(w[P_GATE_W], H), 1, view(GT + (size_t)t * F, (long)L * F), none,
+                   w[P_GATE_B], nullptr, rows, F, H, sc, s));
+    hipLaunchKernelGGL(attend_fwd_kernel, dim3(rows), dim3(256), 0, s, Q, Kh, feat, w[P_O_W],
+                       w[P_O_B], GT, ws + p.ctx, X, ws + p.alpha, ws + p.u, L, k, A, F, E, t);
+    MILAN_CHECK_HIP(hipGetLastError());
+    const View gt = view(G + (size_t)t * 4 * H, (long)L * 4 * H);
+    MILAN_TRY(gemm(view(X + (size_t)t * (E + F) + E, (long)L * (E + F)), 0,
+                   view(w[P_W_IH] + E, E + F), 1, gt, gt, nullptr, nullptr, rows, 4 * H, F, sc,
+                   s));
+    MILAN_TRY(gemm(ht, 0, view(w[P_W_HH], H), 1, gt, gt, nullptr, nullptr, rows, 4 * H, H, sc, s));
+    hipLaunchKernelGGL(cell_fwd_kernel, dim3(blocks_for((long)rows * H)), dim3(256), 0, s, G, C,
+                       Hs, rows, L, H, t);
+  }
+  // logits of every position from (dropped-out) h_{t+1}
+  View hout = view(Hs + H, H, L, (long)(L + 1) * H);
+  if (thr) {
+    hipLaunchKernelGGL(dropout_fwd_kernel, dim3(blocks_for((long)N * H)), dim3(256), 0, s, Hs,
+                       ws + p.hd, rows, L, H, seed, thr, scale);
+    hout = view(ws + p.hd, H);
+  }
+  MILAN_TRY(gemm(hout, 0, view(w[P_OUT_W], H), 1, view(ws + p.logits, V), none, w[P_OUT_B],
+                 nullptr, N, V, H, sc, s));
+  lmt::launch_nll_rows(ws + p.logits, targets, N, V, p.pad, ws + p.lse, ws + p.term,
+                       ws + p.valid, s);
+  lmt::launch_loss_reduce(ws + p.term, ws + p.valid, N, loss, s);
+  hipLaunchKernelGGL(attn_sum_kernel, dim3(blocks_for(BK)), dim3(256), 0, s, ws + p.alpha,
+                     ws + p.s, rows, L, k);
+  hipLaunchKernelGGL(reg_reduce_kernel, dim3(1), dim3(256), 0, s, ws + p.s, (long)BK, loss + 2);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+static int backward(const Plan& p, const float* const* w, float* const* gr, float* ws,
+                    const float* feat, const int64_t* targets, uint32_t thr, float scale,
+                    uint64_t seed, float reg_weight, const float* loss, hipStream_t s) {
+  const int N = p.N, H = p.H, E = p.E, V = p.V, A = p.A, F = p.F, rows = p.rows, k = p.k,
+            L = p.L;
+  const int BK = rows * k;
+  const Scratch sc{ws + p.scratch, p.scratch_floats};
+  const View none = view(nullptr, 0);
+  const int64_t* ids = (const int64_t*)(ws + p.ids);
+  float *X = ws + p.x, *G = ws + p.g, *Hs = ws + p.hs, *dY = ws + p.dy, *dh = ws + p.dhrec,
+        *dc = ws + p.dc, *dZ = ws + p.dz, *DGP = ws + p.dgp, *DQ = ws + p.dq, *DS = ws + p.ds,
+        *dKh = ws + p.dkh;
+  float* dlog = ws + p.logits;
+  lmt::launch_dlogits(dlog, targets, ws + p.lse, ws + p.valid, loss, N, V, s);
+  const View hout = thr ? view(ws + p.hd, H) : view(Hs + H, H, L, (long)(L + 1) * H);
+  // output layer: dW_out = dlogits^T . h_out, db_out = sum dlogits, dY = dlogits . W_out
+  MILAN_TRY(gemm(view(dlog, V), 1, hout, 0, view(gr[P_OUT_W], H), none, nullptr, nullptr, V, H,
+                 N, sc, s));
+  MILAN_TRY(colsum(dlog, N, V, gr[P_OUT_B], nullptr, sc, s));
+  MILAN_TRY(gemm(view(dlog, V), 0, view(w[P_OUT_W], H), 0, view(dY, H), none, nullptr, nullptr,
+                 N, H, V, sc, s));
+  if (thr)
+    hipLaunchKernelGGL(dropout_bwd_kernel, dim3(blocks_for((long)N * H)), dim3(256), 0, s, dY,
+                       rows, L, H, seed, thr, scale);
+  const float reg = 2.f * reg_weight / (float)BK;
+  for (int t = L - 1; t >= 0; --t) {
+    hipLaunchKernelGGL(cell_bwd_kernel, dim3(blocks_for((long)rows * H)), dim3(256), 0, s, dY, dh,
+                       G, ws + p.cst, dc, rows, L, H, t);
+    const View dgt = view(G + (size_t)t * 4 * H, (long)L * 4 * H);
+    // dz = dG_t . W_ih[:, E:]
+    MILAN_TRY(gemm(dgt, 0, view(w[P_W_IH] + E, E + F), 0, view(dZ, F), none, nullptr, nullptr,
+                   rows, F, 4 * H, sc, s));
+    hipLaunchKernelGGL(attend_bwd_kernel, dim3(rows), dim3(256), 0, s, dZ, ws + p.gt, ws + p.ctx,
+                       feat, ws + p.alpha, ws + p.u, ws + p.s, w[P_O_W], reg, DGP, DS, DQ, dKh, L,
+                       k, A, F, t);
+    MILAN_CHECK_HIP(hipGetLastError());
+    // dL/dh_t through step t = dq . W_q + dgate . W_g + dG . W_hh
+    const View dhv = view(dh, H);
+    MILAN_TRY(gemm(view(DQ + (size_t)t * A, (long)L * A), 0, view(w[P_Q_W], H), 0, dhv, none,
+                   nullptr, nullptr, rows, H, A, sc, s));
+    MILAN_TRY(gemm(view(DGP + (size_t)t * F, (long)L * F), 0, view(w[P_GATE_W], H), 0, dhv, dhv,
+                   nullptr, nullptr, rows, H, F, sc, s));
+    MILAN_TRY(gemm(dgt, 0, view(w[P_W_HH], H), 0, dhv, dhv, nullptr, nullptr, rows, H, 4 * H, sc,
+                   s));
+  }
+  // weight gradients, grouped over all steps (h_t = slot t of Hs)
+  const View hprev = view(Hs, H, L, (long)(L + 1) * H);
+  MILAN_TRY(gemm(view(G, 4 * H), 1, view(X, E + F), 0, view(gr[P_W_IH], E + F), none, nullptr,
+                 nullptr, 4 * H, E + F, N, sc, s));
+  MILAN_TRY(gemm(view(G, 4 * H), 1, hprev, 0, view(gr[P_W_HH], H), none, nullptr, nullptr, 4 * H,
+                 H, N, sc, s));
+  MILAN_TRY(colsum(G, N, 4 * H, gr[P_B_IH], gr[P_B_HH], sc, s));
+  MILAN_TRY(gemm(view(DQ, A), 1, hprev, 0, view(gr[P_Q_W], H), none, nullptr, nullptr, A, H, N,
+                 sc, s));
+  MILAN_TRY(colsum(DQ, N, A, gr[P_Q_B], nullptr, sc, s));
+  MILAN_TRY(gemm(view(DGP, F), 1, hprev, 0, view(gr[P_GATE_W], H), none, nullptr, nullptr, F, H,
+                 N, sc, s));
+  MILAN_TRY(colsum(DGP, N, F, gr[P_GATE_B], nullptr, sc, s));
+  MILAN_TRY(gemm(view(dKh, A), 1, view(feat, F), 0, view(gr[P_K_W], F), none, nullptr, nullptr,
+                 A, F, BK, sc, s));
+  MILAN_TRY(colsum(dKh, BK, A, gr[P_K_B], nullptr, sc, s));
+  const int NK = N * k;
+  MILAN_TRY(gemm(view(DS, 1), 1, view(ws + p.u, A), 0, view(gr[P_O_W], A), none, nullptr,
+                 nullptr, 1, A, NK, sc, s));
+  MILAN_TRY(colsum(DS, NK, 1, gr[P_O_B], nullptr, sc, s));
+  // embedding: dX_emb = dG . W_ih[:, :E], summed by token id (no padding row)
+  MILAN_TRY(gemm(view(G, 4 * H), 0, view(w[P_W_IH], E + F), 0, view(ws + p.dxe, E), none,
+                 nullptr, nullptr, N, E, 4 * H, sc, s));
+  lmt::launch_embed_grad(ids, ws + p.dxe, N, E, V, -1, gr[P_EMB], s);
+  // init_h / init_c from dh_0 / dc_0
+  hipLaunchKernelGGL(init_bwd_kernel, dim3(blocks_for((long)rows * H)), dim3(256), 0, s, Hs,
+                     ws + p.cst, dh, dc, ws + p.dph, ws + p.dpc, rows, L, H);
+  MILAN_TRY(gemm(view(ws + p.dph, H), 1, view(ws + p.pooled, F), 0, view(gr[P_INIT_H_W], F),
+                 none, nullptr, nullptr, H, F, rows, sc, s));
+  MILAN_TRY(colsum(ws + p.dph, rows, H, gr[P_INIT_H_B], nullptr, sc, s));
+  MILAN_TRY(gemm(view(ws + p.dpc, H), 1, view(ws + p.pooled, F), 0, view(gr[P_INIT_C_W], F),
+                 none, nullptr, nullptr, H, F, rows, sc, s));
+  MILAN_TRY(colsum(ws + p.dpc, rows, H, gr[P_INIT_C_B], nullptr, sc, s));
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace dect
+}  // namespace milan
+
+using namespace milan;
+using namespace milan::dect;
+
+extern "C" {
+
+size_t milan_decoder_train_workspace_bytes(const milan_ctx* c, int rows, int k, int L) {
+  Plan p;
+  if (make_plan(c, rows, k, L, &p) != 0) return 0;
+  return p.total;
+}
+
+int milan_decoder_nll(milan_ctx* c, const float* const* params, int n_params,
+                      const float* features, const int64_t* targets, int rows, int k, int L,
+                      float* loss_terms, void* ws, size_t ws_bytes, milan_stream stream) {
+  MILAN_REQUIRE(features && targets && loss_terms && ws, MILAN_ERR_ARG,
+                "milan_decoder_nll: null argument");
+  Plan p;
+  MILAN_TRY(make_plan(c, rows, k, L, &p));
+  MILAN_REQUIRE(ws_bytes >= p.total, MILAN_ERR_WORKSPACE,
+                "milan_decoder_nll: workspace %zu < %zu bytes", ws_bytes, p.total);
+  MILAN_TRY(check_params((const void* const*)params, n_params, "parameter"));
+  return forward(p, params, (float*)ws, features, targets, 0, 1.f, 0, loss_terms,
+                 (hipStream_t)stream);
+}
+
+int milan_decoder_train_step(milan_ctx* c, const float* const* params, float* const* grads,
+                             int n_params, const float* features, const int64_t* targets,
+                             int rows, int k, int L, float dropout, uint64_t seed,
+                             float regularization_weight, float* loss_terms, void* ws,
+                             size_t ws_bytes, milan_stream stream) {
+  MILAN_REQUIRE(features && targets && loss_terms && ws, MILAN_ERR_ARG,
+                "milan_decoder_train_step: null argument");
+  MILAN_REQUIRE(dropout >= 0.f && dropout < 1.f, MILAN_ERR_ARG,
+                "milan_decoder_train_step: dropout %g not in [0, 1)", (double)dropout);
+  Plan p;
+  MILAN_TRY(make_plan(c, rows, k, L, &p));
+  MILAN_REQUIRE(ws_bytes >= p.total, MILAN_ERR_WORKSPACE,
+                "milan_decoder_train_step: workspace %zu < %zu bytes", ws_bytes, p.total);
+  MILAN_TRY(check_params((const void* const*)params, n_params, "parameter"));
+  MILAN_TRY(check_params((const void* const*)grads, n_params, "gradient"));
+  const uint32_t thr = drop_threshold(dropout);
+  const float scale = dropout > 0.f ? 1.f / (1.f - dropout) : 1.f;
+  const hipStream_t s = (hipStream_t)stream;
+  MILAN_TRY(forward(p, params, (float*)ws, features, targets, thr, scale, seed, loss_terms, s));
+  return backward(p, params, grads, (float*)ws, features, targets, thr, scale, seed,
+                  regularization_weight, loss_terms, s);
+}
+
+}  // extern "C"

@@ -19,27 +19,12 @@
 // column sums (bias gradients) and the embedding gradient are ordered loops; the loss
 // reduction is one workgroup.  No float atomics: two calls with the same inputs and seed
 // give identical bits.
-#include "common.h"
+#include "train_common.h"
 
 namespace milan {
 namespace lmt {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Element (r, c) of a 2-D view is p[off(r) + c], off(r) = (r / grp) * gs + (r % grp) * rs
-// (grp == 0: r * rs).  The grouped form addresses a (rows, L) slice of a (rows, L + 1)
-// buffer as one row range (the h_{t-1} operand of dW_hh).
-struct View {
-  const float* p;
-  long rs;
-  int grp;
-  long gs;
-};
-static View view(const float* p, long rs, int grp = 0, long gs = 0) { return {p, rs, grp, gs}; }
-
-__device__ __forceinline__ long voff(const View& v, int r) {
-  return v.grp ? (long)(r / v.grp) * v.gs + (long)(r % v.grp) * v.rs : (long)r * v.rs;
-}
 
 // C(m, n) = sum_k A(m, k) B(k, n) [+ D(m, n)] [+ bias1[n]] [+ bias2[n]]
 //   ta = 0: A(m, k) = a(m, k);  ta = 1: A(m, k) = a(k, m)
@@ -176,18 +161,13 @@ static int plan_splits(int M, int N, int K, int* kchunk) {
   return (K + kc - 1) / kc > 0 ? (K + kc - 1) / kc : 1;
 }
 
-static size_t split_scratch_floats(int M, int N, int K) {
+size_t split_scratch_floats(int M, int N, int K) {
   int kc;
   const int s = plan_splits(M, N, K, &kc);
   return s > 1 ? (size_t)s * M * N : 0;
 }
 
-struct Scratch {
-  float* p;
-  size_t floats;
-};
-
-static int gemm(View a, int ta, View b, int tb, View c, View d, const float* bias1,
+int gemm(View a, int ta, View b, int tb, View c, View d, const float* bias1,
                 const float* bias2, int M, int N, int K, Scratch sc, hipStream_t s) {
   if (M <= 0 || N <= 0) return 0;
   GemmArgs g{a, b, c, d, ta, tb, M, N, K, 0, nullptr, bias1, bias2};
@@ -214,12 +194,6 @@ static int gemm(View a, int ta, View b, int tb, View c, View d, const float* bia
 // keep  <=>  (mix64(seed ^ mix64(key)) >> 40) >= thr,   thr = (uint32)(p * 2^24),
 // key = layer << 56 | row << 32 | t << 16 | unit  (splitmix64 finaliser; restated on the
 // host by milan_amd.lms.dropout_mask).
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __device__ __forceinline__ bool keep(uint64_t seed, int layer, int row, int t, int unit,
                                      uint32_t thr) {
   const uint64_t key = (uint64_t)layer << 56 | (uint64_t)row << 32 | (uint64_t)t << 16 |
@@ -382,12 +356,12 @@ __global__ void colsum_final_kernel(const float* __restrict__ part, int chunks, 
   if (out2) out2[n] = s;
 }
 
-static int colsum_chunks(int R) {
+int colsum_chunks(int R) {
   const int c = (R + 63) / 64;
   return c < 1 ? 1 : (c > 64 ? 64 : c);
 }
 
-static int colsum(const float* X, int R, int N, float* out1, float* out2, Scratch sc,
+int colsum(const float* X, int R, int N, float* out1, float* out2, Scratch sc,
                   hipStream_t s) {
   const int chunks = colsum_chunks(R), rchunk = (R + chunks - 1) / chunks;
   MILAN_REQUIRE((size_t)chunks * N <= sc.floats, MILAN_ERR_WORKSPACE,
@@ -653,6 +627,24 @@ static int backward(const Plan& p, const Params& w, const Grads& gr, float* ws,
                      gr.emb);
   MILAN_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+// host launchers of the kernels above, for decoder_train.hip (train_common.h)
+void launch_nll_rows(const float* logits, const int64_t* tgt, int N, int V, int pad, float* lse,
+                     float* term, float* valid, hipStream_t s) {
+  hipLaunchKernelGGL(nll_rows_kernel, dim3(N), dim3(256), 0, s, logits, tgt, V, pad, lse, term,
+                     valid);
+}
+void launch_loss_reduce(const float* term, const float* valid, int N, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s, term, valid, N, out);
+}
+void launch_dlogits(float* logits, const int64_t* tgt, const float* lse, const float* valid,
+                    const float* loss, int N, int V, hipStream_t s) {
+  hipLaunchKernelGGL(dlogits_kernel, dim3(N), dim3(256), 0, s, logits, tgt, lse, valid, loss, V);
+}
+void launch_embed_grad(const int64_t* ids, const float* dX, int N, int E, int V, int pad,
+                       float* dEmb, hipStream_t s) {
+  hipLaunchKernelGGL(embed_grad_kernel, dim3(V), dim3(256), 0, s, ids, dX, N, E, V, pad, dEmb);
 }
 
 }  // namespace lmt

@@ -17,19 +17,27 @@ What differs by design:
     neurons, so captions / rerank choices equal the reference's batch-16 run;
   * `score` and `strategy='sample'` are built on the same kernels (the
     tokenizer of `score` is any callable: spaCy is not in this image);
-  * out of scope: training (`fit`), `bleu` / `rouge` /
-    `bert_score` (need sacrebleu / rouge / bert_score), `DecoderWithCLIP`.
+  * `fit` (:873-1070) trains the decoder with the reference's loop; the loss
+    and gradients of a batch come from `milan_decoder_train_step` (exact fp32,
+    deterministic; include/milan_hip.h), the torch optimizer steps.
+    `decoder()` (:1214-1259) builds a seeded, reference-initialised model;
+    `bleu` scores with `metrics.bleu`, a pure-Python restatement of
+    sacrebleu 1.5.1's corpus BLEU;
+  * out of scope (SURVEY.md section 2.1): a training-mode `forward` (raises;
+    `fit` does not need it), `rouge` / `bert_score` (need rouge /
+    bert_score), `DecoderWithCLIP`.
 """
 import os
 import weakref
-from typing import (Any, Dict, Mapping, NamedTuple, Optional, Sequence, Tuple,
-                    Union)
+from typing import (Any, Dict, Mapping, NamedTuple, Optional, Sequence, Sized,
+                    Tuple, Type, Union, cast)
 
 import torch
-from torch import nn
+from torch import nn, optim
 from torch.utils import data
 
-from milan_amd import encoders, hip, lang, lms, params, serialize
+from milan_amd import (encoders, hip, lang, lms, metrics, params, serialize,
+                       training)
 
 Strategy = Union[torch.Tensor, str]
 
@@ -38,6 +46,16 @@ STRATEGY_SAMPLE = 'sample'
 STRATEGY_BEAM = 'beam'
 STRATEGY_RERANK = 'rerank'
 STRATEGIES = (STRATEGY_GREEDY, STRATEGY_SAMPLE, STRATEGY_BEAM, STRATEGY_RERANK)
+# the decoder's own state dict in the reference's order: what Decoder.fit
+# trains (milan_decoder_train_step's parameter list)
+TRAIN_PARAMS = (
+    'init_h.0.weight', 'init_h.0.bias', 'init_c.0.weight', 'init_c.0.bias',
+    'embedding.weight', 'attend.query_to_hidden.weight',
+    'attend.query_to_hidden.bias', 'attend.key_to_hidden.weight',
+    'attend.key_to_hidden.bias', 'attend.output.0.weight',
+    'attend.output.0.bias', 'feature_gate.0.weight', 'feature_gate.0.bias',
+    'lstm.weight_ih', 'lstm.weight_hh', 'lstm.bias_ih', 'lstm.bias_hh',
+    'output.1.weight', 'output.1.bias')
 _HIP_STRATEGY = {
     STRATEGY_GREEDY: hip.GREEDY,
     STRATEGY_BEAM: hip.BEAM,
@@ -598,6 +616,227 @@ class Decoder(nn.Module):
             captions += list(output.captions)
         return tuple(captions)
 
+    def bleu(self,
+             dataset: data.Dataset,
+             annotation_index: int = 4,
+             predictions: Optional[Sequence[str]] = None,
+             **kwargs: Any) -> metrics.BLEUScore:
+        """Corpus BLEU of this model's captions on `dataset` (reference
+        :713-738): `predict(dataset, **kwargs)` unless `predictions` are
+        given, then `metrics.bleu`."""
+        if predictions is None:
+            predictions = self.predict(dataset, **kwargs)
+        return metrics.bleu(dataset,
+                            predictions,
+                            annotation_index=annotation_index)
+
+    # -- training (reference :873-1070) ----------------------------------------------
+    def reset_parameters(self) -> None:
+        """Initialise the decoder's own parameters as the reference's torch
+        modules do (the constructor leaves them zero): init_h, init_c,
+        embedding, attention (query, key, output), feature_gate, LSTMCell and
+        output are built in the reference's order, so the draws from torch's
+        global generator are the same."""
+        fs, hs, es, v = (self.feature_size, self.hidden_size,
+                         self.embedding_size, self.vocab_size)
+        a = self.attend.hidden_size
+        init_h, init_c = nn.Linear(fs, hs), nn.Linear(fs, hs)
+        embedding = nn.Embedding(v, es)
+        query, key, score = nn.Linear(hs, a), nn.Linear(fs, a), nn.Linear(a, 1)
+        gate = nn.Linear(hs, fs)
+        lstm = nn.LSTMCell(es + fs, hs)
+        output = nn.Linear(hs, v)
+        state = {'embedding.weight': embedding.weight}
+        for name, module in (('init_h.0', init_h), ('init_c.0', init_c),
+                             ('attend.query_to_hidden', query),
+                             ('attend.key_to_hidden', key),
+                             ('attend.output.0', score),
+                             ('feature_gate.0', gate), ('output.1', output)):
+            state[f'{name}.weight'] = module.weight
+            state[f'{name}.bias'] = module.bias
+        state.update({f'lstm.{k}': t for k, t in lstm.state_dict().items()})
+        with torch.no_grad():
+            for name, param in self.named_parameters():
+                if name in state:
+                    param.copy_(state[name])
+
+    def _train_params(self) -> Tuple[torch.nn.Parameter, ...]:
+        """The 19 tensors milan_decoder_train_step reads, in its order."""
+        named = dict(self.named_parameters())
+        return tuple(named[name] for name in TRAIN_PARAMS)
+
+    def fit(self,
+            dataset: data.Dataset,
+            mask: bool = True,
+            image_index: int = 2,
+            mask_index: int = 3,
+            annotation_index: int = 4,
+            batch_size: int = 64,
+            max_epochs: int = 100,
+            patience: int = 4,
+            hold_out: Union[float, Sequence[int]] = .1,
+            stop_on_bleu: bool = True,
+            regularization_weight: float = 1.,
+            optimizer_t: Type[optim.Optimizer] = optim.AdamW,
+            optimizer_kwargs: Optional[Mapping[str, Any]] = None,
+            features: Optional[data.TensorDataset] = None,
+            num_workers: int = 0,
+            device: Optional[Union[str, torch.device]] = None,
+            display_progress_as: Optional[str] = 'train decoder') -> None:
+        """Train the decoder on `dataset` (reference :873-1070).
+
+        Same loop as the reference: the hold-out split is by neuron
+        (`random_split` on torch's global generator, or `fixed_split`), the
+        batches are one sample per annotation, shuffled by a DataLoader;
+        `optimizer_t(self.parameters(), **optimizer_kwargs)`; the training
+        loss is NLLLoss(ignore_index=pad) plus `regularization_weight` times
+        the double-stochasticity regulariser; each epoch ends with the
+        validation NLL and a greedy, likelihood-only `bleu` of the validation
+        neurons; `EarlyStopping` tracks BLEU (`stop_on_bleu`) or the
+        validation loss.
+
+        A batch's loss and the gradients of the decoder's 19 own tensors come
+        from `milan_decoder_train_step` (train mode, dropout seeded from the
+        device's torch generator when `dropout > 0`); the encoder and LM keep
+        `grad=None`, so the optimizer leaves them alone.  Features come from
+        `features` or, without it, from `self.encode` under no_grad.  As in the
+        reference, the "best" state kept for the restore on stop is
+        `state_dict()`, whose tensors share storage with the parameters: the
+        model ends with the parameters of the last epoch run.  It is left in
+        eval mode.
+        """
+        if device is not None:
+            self.to(device)
+        if optimizer_kwargs is None:
+            optimizer_kwargs = {}
+        device = hip.require_device(self.device)
+
+        class WrapperDataset(data.Dataset):
+            """Split by neuron, iterate by annotation (reference :957-987)."""
+
+            def __init__(self, subset: data.Subset):
+                self.samples = []
+                for index in subset.indices:
+                    if features is None:
+                        images = dataset[index][image_index]
+                        masks = dataset[index][mask_index] if mask else None
+                        images_or_features = (images, masks)
+                    else:
+                        images_or_features = features[index]
+                    annotations = dataset[index][annotation_index]
+                    if isinstance(annotations, str):
+                        annotations = [annotations]
+                    for annotation in annotations:
+                        self.samples.append((images_or_features, annotation))
+
+            def __getitem__(self, index: int):
+                return self.samples[index]
+
+            def __len__(self) -> int:
+                return len(self.samples)
+
+        if isinstance(hold_out, float):
+            train, val = training.random_split(dataset, hold_out=hold_out)
+        else:
+            train, val = training.fixed_split(dataset, hold_out)
+        train_loader = data.DataLoader(WrapperDataset(train),
+                                       num_workers=num_workers,
+                                       batch_size=batch_size,
+                                       shuffle=True)
+        val_loader = data.DataLoader(WrapperDataset(val),
+                                     num_workers=num_workers,
+                                     batch_size=batch_size)
+
+        optimizer = optimizer_t(self.parameters(), **optimizer_kwargs)
+        stopper = training.EarlyStopping(patience=patience,
+                                         decreasing=not stop_on_bleu)
+
+        # a context that only carries the decoder's dims, never finalized: the
+        # training calls read the live parameters, so optimizer steps never
+        # rebuild it (inference after fit rebuilds `_context()`, which keys on
+        # the parameters' versions)
+        sd = {k: v for k, v in self.state_dict().items()
+              if not k.startswith(('encoder.', 'lm.'))}
+        ctx = hip.Context(hip.make_dims(sd, len(self.indexer.vocab)), {},
+                          device, finalize=False)
+        weights = self._train_params()
+        grads = [torch.empty_like(p) for p in weights]
+        cuda_generator = torch.cuda.default_generators[device.index]
+
+        def prepare(batch):
+            images_or_features, captions = batch
+            if features is None:
+                images, masks = images_or_features
+                with torch.no_grad():
+                    inputs = self.encode(
+                        images.to(device),
+                        masks=masks.to(device) if masks is not None else None)
+            else:
+                inputs, = images_or_features
+            targets = torch.tensor(self.indexer(captions))[:, 1:]
+            return inputs.to(device, torch.float32), targets
+
+        progress = range(max_epochs)
+        if display_progress_as is not None:
+            try:
+                from tqdm.auto import tqdm
+                progress = tqdm(progress, desc=display_progress_as)
+            except ImportError:
+                pass
+
+        best = self.state_dict()
+        for _ in progress:
+            self.train()
+            self.encoder.eval()
+            train_loss = 0.
+            for batch in train_loader:
+                inputs, targets = prepare(batch)
+                seed = 0
+                if self.dropout > 0:
+                    seed = int(torch.randint(2**62, (), device=device,
+                                             generator=cuda_generator))
+                terms = ctx.decoder_train_step(weights, grads, inputs, targets,
+                                               self.dropout, seed,
+                                               regularization_weight)
+                for p, g in zip(weights, grads):
+                    p.grad = g
+                optimizer.step()
+                optimizer.zero_grad()
+                regularizer = terms[2] / (inputs.shape[0] * inputs.shape[1])
+                loss = terms[0] / terms[1] + regularization_weight * regularizer
+                train_loss += loss.item()
+            train_loss /= len(train_loader)
+
+            self.eval()
+            val_loss = 0.
+            for batch in val_loader:
+                inputs, targets = prepare(batch)
+                terms = ctx.decoder_nll(weights, inputs, targets)
+                val_loss += (terms[0] / terms[1]).item()
+            val_loss /= len(val_loader)
+            val_bleu = self.bleu(val,
+                                 strategy=STRATEGY_GREEDY,
+                                 mi=False,
+                                 device=device,
+                                 display_progress_as=None).score
+
+            if not isinstance(progress, range):
+                progress.set_description(f'{display_progress_as} '
+                                         f'[train_loss={train_loss:.3f}, '
+                                         f'val_loss={val_loss:.3f}, '
+                                         f'val_bleu={val_bleu:.1f}]')
+
+            stop = stop_on_bleu and stopper(val_bleu)
+            stop |= not stop_on_bleu and stopper(val_loss)
+            if stop:
+                self.load_state_dict(best)
+                break
+
+            if stopper.improved:
+                best = self.state_dict()
+        self.eval()
+        ctx.close()
+
     # -- serialisation (reference serialize.py:175-269, decoders.py:1072-1109) ---------
     def properties(self) -> Mapping[str, Any]:
         return {
@@ -668,3 +907,32 @@ class Decoder(nn.Module):
         """Load a reference-format checkpoint (serialize.py:255-269).
         Keyword arguments are forwarded to `torch.load`."""
         return cls.deserialize(serialize.load_payload(file, **kwargs))
+
+
+def decoder(dataset: data.Dataset,
+            encoder: encoders.Encoder,
+            rerank_with_clip: bool = False,
+            annotation_index: int = 4,
+            indexer_kwargs: Optional[Mapping[str, Any]] = None,
+            **kwargs: Any) -> Decoder:
+    """A new Decoder for the annotations of `dataset` (reference
+    decoders.py:1214-1259): each sample's annotations are joined with
+    `lang.join`, the indexer is built from them (`start`, `stop`, `pad`, `unk`
+    default to True; `tokenize` must be given, as for `lms.lm`) and **kwargs go
+    to the constructor.  The parameters are initialised as the reference's
+    torch modules initialise theirs, with the same draws from torch's global
+    generator.  `rerank_with_clip=True` (DecoderWithCLIP) is not built."""
+    if rerank_with_clip:
+        raise NotImplementedError('DecoderWithCLIP (CLIP reranking) is not '
+                                  'part of this build')
+    indexer_kwargs = dict(indexer_kwargs or {})
+    annotations = [
+        lang.join(dataset[index][annotation_index])
+        for index in range(len(cast(Sized, dataset)))
+    ]
+    for key in ('start', 'stop', 'pad', 'unk'):
+        indexer_kwargs.setdefault(key, True)
+    indexer = lang.indexer(annotations, **indexer_kwargs)
+    model = Decoder(indexer, encoder, **kwargs)
+    model.reset_parameters()
+    return model

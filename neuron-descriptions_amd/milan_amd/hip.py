@@ -78,7 +78,7 @@ class Dims(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 9  # MILAN_ABI_VERSION this binding was written against
+ABI_VERSION = 10  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
 TRUNK_BOTTLENECK, TRUNK_BASIC, TRUNK_ALEXNET, TRUNK_NONE = 0, 1, 2, 3
@@ -170,6 +170,12 @@ SIGNATURES = {
     'milan_lm_train_step':
         (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _F, ctypes.c_uint64, _P, _P,
               _SZ, _P]),
+    'milan_decoder_train_workspace_bytes': (_SZ, [_P, _I, _I, _I]),
+    'milan_decoder_nll':
+        (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    'milan_decoder_train_step':
+        (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, _F, _P,
+              _P, _SZ, _P]),
     'milan_conv2d_nhwc':
         (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I,
               _P]),
@@ -893,6 +899,95 @@ class Context:
                     self._h, ptrs, gptrs, len(params), inputs.data_ptr(),
                     targets.data_ptr(), inputs.shape[0], inputs.shape[1],
                     float(dropout), int(seed) & (2**64 - 1), loss.data_ptr(),
+                    ws.data_ptr(), ws.numel(), _stream(self.device)))
+        return loss
+
+    # -- Decoder training (include/milan_hip.h, milan_decoder_train_step) --
+    DECODER_TRAIN_PARAMS = 19
+
+    def _decoder_train_call(self, params, features, targets):
+        if features.dim() != 3:
+            raise ValueError('features must be (rows, k, feature_size), got '
+                             f'{tuple(features.shape)}')
+        if targets.dim() != 2 or len(targets) != len(features):
+            raise ValueError(f'targets {tuple(targets.shape)} must be (rows, L) '
+                             f'for features {tuple(features.shape)}')
+        rows, k, f = features.shape
+        length = targets.shape[1]
+        if f != self.dims.feature_size:
+            raise ValueError(f'feature size {f} != the decoder\'s '
+                             f'{self.dims.feature_size}')
+        v = self.dims.vocab_size
+        if targets.numel() and (int(targets.min()) < 0 or
+                                int(targets.max()) >= v):
+            raise ValueError(f'targets hold ids outside [0, {v})')
+        if len(params) != self.DECODER_TRAIN_PARAMS:
+            raise ValueError(f'{len(params)} parameters, expected '
+                             f'{self.DECODER_TRAIN_PARAMS}')
+        for p in params:
+            if (p.device != self.device or p.dtype != torch.float32
+                    or not p.is_contiguous()):
+                raise ValueError('decoder parameters must be contiguous '
+                                 f'float32 on {self.device}')
+        features = _dev(features, self.device, torch.float32)
+        targets = _dev(targets, self.device, torch.long)
+        need = int(self.lib.milan_decoder_train_workspace_bytes(
+            self._h, rows, k, length))
+        if need == 0:
+            _check(ERR_SHAPE)
+        ws = getattr(self, '_train_ws', None)
+        if ws is None or ws.numel() < need:
+            self._train_ws = None
+            ws = self._train_ws = torch.empty(need, dtype=torch.uint8,
+                                              device=self.device)
+        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
+        loss = torch.empty(3, device=self.device)
+        return features, targets, ptrs, ws, loss
+
+    def decoder_nll(self, params, features: torch.Tensor,
+                    targets: torch.Tensor) -> torch.Tensor:
+        """Teacher-forced decoder in eval mode: device tensor [sum of -log p
+        over the non-pad targets, their count, sum of (1 - sum_t alpha)^2].
+        `params`: the decoder's 19 own state-dict tensors in the reference's
+        order; `features` (rows, k, F); `targets` (rows, L) without <start>.
+        Does not synchronise."""
+        features, targets, ptrs, ws, loss = self._decoder_train_call(
+            params, features, targets)
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_decoder_nll(
+                    self._h, ptrs, len(params), features.data_ptr(),
+                    targets.data_ptr(), features.shape[0], features.shape[1],
+                    targets.shape[1], loss.data_ptr(), ws.data_ptr(),
+                    ws.numel(), _stream(self.device)))
+        return loss
+
+    def decoder_train_step(self, params, grads, features: torch.Tensor,
+                           targets: torch.Tensor, dropout: float = 0.,
+                           seed: int = 0,
+                           regularization_weight: float = 1.) -> torch.Tensor:
+        """Train-mode loss terms (as `decoder_nll`) and the gradient of
+        [0] / [1] + regularization_weight * [2] / (rows * k) with respect to
+        every parameter, OVERWRITTEN into `grads` (same order and shapes as
+        `params`).  Does not synchronise."""
+        features, targets, ptrs, ws, loss = self._decoder_train_call(
+            params, features, targets)
+        if len(grads) != len(params):
+            raise ValueError(f'{len(grads)} gradients for {len(params)} '
+                             'parameters')
+        for p, g in zip(params, grads):
+            if (g.shape != p.shape or g.device != self.device
+                    or g.dtype != torch.float32 or not g.is_contiguous()):
+                raise ValueError('gradients must be contiguous float32 '
+                                 'tensors shaped like the parameters')
+        gptrs = (_P * len(grads))(*[g.data_ptr() for g in grads])
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_decoder_train_step(
+                    self._h, ptrs, gptrs, len(params), features.data_ptr(),
+                    targets.data_ptr(), features.shape[0], features.shape[1],
+                    targets.shape[1], float(dropout), int(seed) & (2**64 - 1),
+                    float(regularization_weight), loss.data_ptr(),
                     ws.data_ptr(), ws.numel(), _stream(self.device)))
         return loss
 

@@ -56,6 +56,18 @@ def dropout_mask(seed: int, layer: int, rows: int, length: int, units: int,
     return torch.from_numpy((z >> np.uint64(40)) >= np.uint64(threshold))
 
 
+
+DECODER_DROPOUT_TAG = 0xDC  # the decoder's mask, never one of the LM's layers
+
+
+def decoder_dropout_mask(seed: int, rows: int, length: int, units: int,
+                         p: float) -> torch.Tensor:
+    """Host restatement of the decoder training kernel's dropout mask on h
+    before the output Linear: (rows, length, units) bool, True = kept.  The
+    LM's hash with the tag 0xDC in place of the layer; see
+    milan_decoder_train_step in include/milan_hip.h."""
+    return dropout_mask(seed, DECODER_DROPOUT_TAG, rows, length, units, p)
+
 class _SequenceDataset(data.Dataset):
     """The annotations of a dataset, one sample per sequence (a sample's
     annotation may be a str or a list of str; reference lms.py:176-200)."""

@@ -10,22 +10,33 @@ neurons; the default 16 steps x 256 neurons = the 4096-neuron workload.
 
 What is timed:
   * `value`: K steps over uint8 exemplars ALREADY RESIDENT IN HBM (the bench
-    contract), barrier + synchronize on both sides, max over ranks.
+    contract), barrier + synchronize on both sides, max over ranks.  A plain run
+    does only this: set up, warm up, time the K steps (with the HIP-event
+    `roofline` of those same steps), write `--dump-outputs`, print the line.
+`--full` adds every other leg (each also has a flag of its own that switches it on
+or off in either kind of run):
   * `pcie_inclusive` (same number of steps, in the same run): SURVEY 8(d)'s
     definition of the metric -- exemplars start as uint8 in PINNED HOST memory,
     travel H2D double-buffered on a side stream (milan_amd/ingest.py), and the
     top-1 token ids + scores are copied back to pinned host memory inside the
     timed region.
   * `f32_mode`: the same steps in the exact-fp32 MFMA mode (8 steps).
+  * `fast_mode`: the same steps with layer3 / layer4 on plain f16, and its
+    caption-flip rate against f32 (8 steps).
   * `other_configs`: SURVEY 8(d) config 1 (256 neurons, greedy, mi=False) and
     config 2 (1152 neurons, beam 16 + rerank) on the same GPU.
+  * `cpu_baseline`: the torch-CPU oracle timed on a sample, with parity and
+    precision checks of the HIP path against it.
+  * `roofline.traffic` measured live by two child runs under rocprofv3 --pmc
+    (a plain run quotes the committed summary under profiles/).
 Rank r of N describes its own neurons (no data-path collective; weights are
 broadcast from rank 0 over RCCL, results gathered at the end).  Default: every
 rank runs `--steps` chunks ("scaling": "weak").  `--neurons-total T` fixes the
 WHOLE-JOB size instead (rank r takes `partition(T, N, r, align=16)`; "scaling":
 "strong"): `--gpus 8 --neurons-total 4096` is BASELINE's metric as quoted.
 
-    python bench.py                      # 1 GPU
+    python bench.py                      # 1 GPU, the headline only
+    python bench.py --full               # 1 GPU, every leg
     python bench.py --gpus 8             # launches its own 8 ranks (torch.distributed.run)
     python bench.py --gpus 8 --neurons-total 4096   # the SCALE line: BASELINE's metric as quoted
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
@@ -430,12 +441,11 @@ def measure_traffic_live(args):
     with tempfile.TemporaryDirectory(dir='/tmp') as tmp:
         for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
             out = os.path.join(tmp, counter)
+            # (a plain run: without --full the child times its one step and nothing else)
             cmd = [rocprof, '--kernel-trace', '--pmc', counter, '-d', out, '-o', 'p',
                    '--', sys.executable, str(REPO / 'bench.py'), '--steps', '1',
                    '--warmup', '0', '--chunk', str(args.chunk), '--precision',
-                   args.precision, '--also-f32-steps', '0', '--cpu-sample', '0',
-                   '--no-profile', '--from-host-steps', '0', '--other-configs', '0',
-                   '--fast-steps', '0', '--live-traffic', '0']
+                   args.precision, '--no-profile']
             env = dict(os.environ, TMPDIR='/tmp')
             try:
                 r = subprocess.run(cmd, cwd='/tmp', env=env, capture_output=True,
@@ -562,6 +572,11 @@ def stage_report(stages, n_steps, n_images_per_step, neurons_per_step, beam,
     return out
 
 
+# what --full turns on: flag -> its default there (a plain run defaults every one to 0)
+FULL_DEFAULTS = {'cpu_sample': 32, 'from_host_steps': -1, 'fast_steps': 8,
+                 'also_f32_steps': 8, 'live_traffic': 1, 'other_configs': 1}
+
+
 def rccl_version():
     try:
         return '.'.join(str(v) for v in torch.cuda.nccl.version())
@@ -569,7 +584,7 @@ def rccl_version():
         return None
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=16)
@@ -588,44 +603,59 @@ def main():
                     help='vocabulary tokens (V = vocab + 4 specials)')
     ap.add_argument('--strategy', default='rerank',
                     choices=['greedy', 'beam', 'rerank'])
-    ap.add_argument('--cpu-sample', type=int, default=32,
-                    help='neurons for the CPU baseline leg (0 = skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beyond the headline (PCIe-inclusive, f32 and '
+                    'fast modes, other configs, CPU baseline, live PMC traffic): the '
+                    'defaults of the flags below marked "--full: N"; without --full they '
+                    'default to 0 and a run only sets up, warms up, times --steps and '
+                    'prints its line')
+    ap.add_argument('--cpu-sample', type=int, default=None,
+                    help='neurons for the CPU baseline leg (0 = skip; --full: 32)')
     ap.add_argument('--no-profile', action='store_true',
                     help='do not bracket GEMM launches / stages with HIP events')
-    ap.add_argument('--from-host-steps', type=int, default=-1,
+    ap.add_argument('--from-host-steps', type=int, default=None,
                     help='steps of the PCIe-inclusive leg (pinned host uint8 -> '
                     'double-buffered H2D -> describe -> D2H of tokens + scores); '
-                    '-1 = as many as the main run, 0 = skip')
-    ap.add_argument('--fast-steps', type=int, default=8,
+                    '-1 = as many as the main run, 0 = skip (--full: -1)')
+    ap.add_argument('--fast-steps', type=int, default=None,
                     help='extra timed steps in the FAST mode (layer3 / layer4 on plain f16: '
                     'narrower than the reference, a reported extra, never `value`), with its '
-                    'caption-flip rate against f32 on --fast-agreement neurons; 0 = skip')
+                    'caption-flip rate against f32 on --fast-agreement neurons; 0 = skip '
+                    '(--full: 8)')
     ap.add_argument('--fast-agreement', type=int, default=1024)
     ap.add_argument('--precision', default='split_f16',
                     choices=['split_f16', 'f32'],
                     help='split_f16: operands as (hi,lo) f16 pairs, 3 f16 '
                     'MFMAs per product, fp32 accumulate (fp32-GEMM-class error, '
                     'same parity suite); f32: exact fp32-in MFMA')
-    ap.add_argument('--also-f32-steps', type=int, default=8,
+    ap.add_argument('--also-f32-steps', type=int, default=None,
                     help='extra timed steps in f32 mode, reported under '
-                    '"f32_mode" (0 = skip)')
-    ap.add_argument('--live-traffic', type=int, default=1,
+                    '"f32_mode" (0 = skip; --full: 8)')
+    ap.add_argument('--live-traffic', type=int, default=None,
                     help='1: measure roofline.traffic in this run (two extra child '
                     'passes under rocprofv3 --pmc, ~1 min each, single-GPU runs '
-                    'only); 0: quote the committed offline summary')
-    ap.add_argument('--other-configs', type=int, default=1,
+                    'only); 0: quote the committed offline summary (--full: 1)')
+    ap.add_argument('--other-configs', type=int, default=None,
                     help='1: also time SURVEY 8(d) configs 1 and 2 (single-GPU '
-                    'runs only)')
+                    'runs only; --full: 1)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step returned '
                     '(tokens, scores, beam tokens / scores, group lengths) as DIR/<name>.npy: '
                     'float64 for integers, float32 for floats, <= 64 MB in all (a seeded '
                     'sample of rows beyond that).  Inputs and weights are seeded, so two '
                     'builds can be compared output for output.  Rank 0 writes its own step')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    # the extra legs: on by default with --full, off in a plain run; a flag given wins
+    for name, full in FULL_DEFAULTS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else 0)
     if args.dump_outputs is not None and args.neurons_total <= 0 and args.steps < 1:
         ap.error('--dump-outputs needs at least one timed step')
+    return args
 
+
+def main():
+    args = parse_args()
     # `python bench.py --gpus N` without torchrun: this process becomes the
     # launcher of N ranks (torch.distributed.run on 127.0.0.1, a free port);
     # rank 0 of that job prints the JSON line.  Under torchrun (the driver's
@@ -1000,6 +1030,8 @@ def main():
         'status_flags': status_flags,
         # --dump-outputs: {name: shape} of the arrays written from the last timed step
         'dumped_outputs': dumped,
+        # --full: the legs beyond the headline were run by default
+        'full': args.full,
         # which collective backend the ranks used (a SCALE record must be auditable)
         'dist_backend': (torch.distributed.get_backend()
                          if sharding.is_distributed() else 'none (single process)'),
@@ -1017,8 +1049,9 @@ def main():
     result['per_rank']['value_min'] = min(result['per_rank']['value'])
     result['per_rank']['value_max'] = max(result['per_rank']['value'])
     # HBM bytes per launch of the dominant kernel: PMC counters need their own
-    # rocprofv3 passes (tools/pmc_traffic.sh), so the figure is read from the
-    # committed summary of those passes, not collected live.
+    # rocprofv3 passes, collected live only with --live-traffic (on under --full);
+    # otherwise the figure is read from the committed summary of such passes
+    # (tools/pmc_traffic.sh).
     traffic_bytes, traffic_note = None, 'not collected (PMC needs separate rocprofv3 passes)'
     live_reason = None
     dom_family = max(kernels, key=lambda k: kernels[k]['ms']) if kernels else None
@@ -1032,7 +1065,7 @@ def main():
         else:
             live_reason, traffic_note = f'no PMC rows for the family {dom_family}', None
     for name in ([] if traffic_bytes is not None else
-                 ['r5_hbm_traffic.json', 'r4_hbm_traffic.json', 'r3_hbm_traffic.json', 'r2_hbm_traffic.json', 'r1_hbm_traffic.json']):
+                 ['r6_hbm_traffic.json', 'r5_hbm_traffic.json', 'r4_hbm_traffic.json', 'r3_hbm_traffic.json', 'r2_hbm_traffic.json', 'r1_hbm_traffic.json']):
         tpath = REPO / 'profiles' / name
         if args.precision != 'f32' and tpath.exists():
             with open(tpath) as f:

@@ -341,8 +341,8 @@ def test_two_rank_bench_equals_one_rank(world):
 
 def test_two_rank_bench_weak_mode_all_legs(world):
     """The driver's multi-GPU command line (weak scaling: --steps per rank)
-    with every leg on: resident run, PCIe-inclusive leg, f32 leg, gather."""
-    args = ['--steps', '2', '--chunk', '32', '--warmup', '1', '--cpu-sample',
+    with every leg on (--full): resident run, PCIe-inclusive leg, f32 leg, gather."""
+    args = ['--full', '--steps', '2', '--chunk', '32', '--warmup', '1', '--cpu-sample',
             '0', '--also-f32-steps', '1', '--beam', '8']
     out = _bench(args, 2, 29950 + os.getpid() % 40)
     assert out['n_gpus'] == 2 and out['scaling'] == 'weak'

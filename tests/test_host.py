@@ -593,6 +593,28 @@ def test_bench_dump_outputs_types_and_budget(tmp_path):
                              big['attentions'][idx7].numpy())
 
 
+def test_bench_plain_run_is_lean_and_full_runs_every_leg():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs no leg beyond the headline
+    (PCIe-inclusive, f32 / fast modes, other configs, CPU baseline, live PMC traffic);
+    `--full` turns every one on at its former default, and a flag given explicitly wins
+    either way."""
+    if str(REPO) not in sys.path:
+        sys.path.insert(0, str(REPO))
+    import bench
+    legs = ('cpu_sample', 'from_host_steps', 'fast_steps', 'also_f32_steps',
+            'live_traffic', 'other_configs')
+    plain = bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert not plain.full and all(getattr(plain, k) == 0 for k in legs)
+    assert (plain.steps, plain.warmup, plain.chunk, plain.precision) == (20, 5, 640, 'split_f16')
+    full = bench.parse_args(['--full'])
+    assert full.full
+    assert {k: getattr(full, k) for k in legs} == {
+        'cpu_sample': 32, 'from_host_steps': -1, 'fast_steps': 8, 'also_f32_steps': 8,
+        'live_traffic': 1, 'other_configs': 1}
+    assert bench.parse_args(['--full', '--cpu-sample', '0']).cpu_sample == 0
+    assert bench.parse_args(['--also-f32-steps', '2']).also_f32_steps == 2
+
+
 def test_shared_gpu_probe_is_quiet_without_a_gpu(recwarn):
     """hip.other_compute_processes(): PIDs with compute queues on a GPU this process
     uses (/sys/class/kfd/kfd/proc/<pid>/queues/*/gpuid).  A process without queues --

@@ -36,7 +36,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define MILAN_ABI_VERSION 10
+#define MILAN_ABI_VERSION 11
 
 enum {
   MILAN_OK = 0,
@@ -590,7 +590,8 @@ int milan_lm_train_step(milan_ctx* ctx, const float* const* params,
  *     attention and vocab sizes, start_index, pad_index) and need not be
  *     finalized; its weight arena is not used.
  *   features: (rows, k, feature_size) fp32 DEVICE, the frozen encoder's output
- *     (no gradient flows into it).
+ *     (no gradient flows into it here; milan_decoder_backward below computes
+ *     one).
  *   targets: (rows, L) int64 DEVICE, the indexed captions without <start>
  *     (with <stop>, padded).  The input of step 0 is <start>, of step t
  *     targets[:, t-1].  Ids must lie in [0, vocab_size): the caller validates
@@ -629,6 +630,45 @@ int milan_decoder_train_step(milan_ctx* ctx, const float* const* params,
                              uint64_t seed, float regularization_weight,
                              float* loss_terms, void* workspace,
                              size_t workspace_bytes, milan_stream stream);
+
+/* Teacher-forced forward and backward for autograd (Decoder.forward in training
+ * mode with a tensor strategy): the forward of milan_decoder_train_step with its
+ * outputs returned instead of a loss, and a backward driven by arbitrary
+ * upstream gradients.  Parameter list, ctx, dims, dropout mask, precision and
+ * determinism as above; neither call synchronises.
+ *   milan_decoder_grad_workspace_bytes: the workspace both calls need (the
+ *     train-step workspace plus dctx, the pooled-feature gradient and the
+ *     feature-gradient GEMM scratch); 0 on bad dims.
+ *   milan_decoder_forward_train: logprobs_out (rows, L, vocab) fp32 DEVICE <-
+ *     log_softmax of every position; attentions_out (rows, L, k) fp32 DEVICE
+ *     <- the attention weights.  Pad targets are ordinary inputs (no loss).
+ *     The workspace keeps the activations for one milan_decoder_backward.
+ *   milan_decoder_backward: consumes a workspace filled by
+ *     milan_decoder_forward_train with the same params, features, targets,
+ *     dims, dropout and seed.  dlogprobs (rows, L, vocab) and dattentions
+ *     (rows, L, k) fp32 DEVICE are the upstream gradients (NULL: zero).
+ *     `grads` are OVERWRITTEN with the gradient of sum(dlogprobs * logprobs)
+ *     + sum(dattentions * attentions) with respect to the 19 parameters;
+ *     dfeatures (rows, k, feature_size) fp32 DEVICE <- its gradient with
+ *     respect to the features (NULL: not computed), summed in the fixed order
+ *     (keys + context over increasing t) + mean pool.  The backward overwrites
+ *     activations in place: one forward supports exactly one backward. */
+size_t milan_decoder_grad_workspace_bytes(const milan_ctx* ctx, int rows, int k,
+                                          int L);
+int milan_decoder_forward_train(milan_ctx* ctx, const float* const* params,
+                                int n_params, const float* features,
+                                const int64_t* targets, int rows, int k, int L,
+                                float dropout, uint64_t seed,
+                                float* logprobs_out, float* attentions_out,
+                                void* workspace, size_t workspace_bytes,
+                                milan_stream stream);
+int milan_decoder_backward(milan_ctx* ctx, const float* const* params,
+                           float* const* grads, int n_params,
+                           const float* features, const int64_t* targets,
+                           int rows, int k, int L, float dropout, uint64_t seed,
+                           const float* dlogprobs, const float* dattentions,
+                           float* dfeatures, void* workspace,
+                           size_t workspace_bytes, milan_stream stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

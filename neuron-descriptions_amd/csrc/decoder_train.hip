@@ -295,6 +295,110 @@ __global__ __launch_bounds__(256) void attend_bwd_kernel(
   }
 }
 
+// attend_bwd_kernel driven by an upstream gradient instead of the regulariser (the autograd
+// backward, milan_decoder_backward): d alpha_j = (dz * gate) . f_j + dA[n][j] (dA null: zero),
+// and DCTX [rows * L][F] (null: not stored) receives dctx = dz * gate, the context's share of
+// the feature gradient.  A kernel of its own, so that attend_bwd_kernel, which
+// milan_decoder_train_step runs, keeps its instruction stream.
+__global__ __launch_bounds__(256) void attend_bwd_up_kernel(
+    const float* __restrict__ dZ, const float* __restrict__ GT, const float* __restrict__ CTX,
+    const float* __restrict__ feat, const float* __restrict__ ALPHA, const float* __restrict__ U,
+    const float* __restrict__ dA, const float* __restrict__ w_o, float* __restrict__ DCTX,
+    float* __restrict__ DGP, float* __restrict__ DS, float* __restrict__ DQ,
+    float* __restrict__ dKh, int L, int k, int A, int F, int t) {
+  __shared__ float da[kMaxK];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long n = (long)b * L + t;
+  const float* dz = dZ + (long)b * F;
+  const float* gt = GT + n * F;
+  const float* fb = feat + (long)b * k * F;
+  for (int f = tid; f < F; f += blockDim.x) {
+    const float g = gt[f];
+    DGP[n * F + f] = dz[f] * CTX[n * F + f] * g * (1.f - g);
+    if (DCTX) DCTX[n * F + f] = dz[f] * g;
+  }
+  for (int j = w; j < k; j += 4) {
+    const float* fj = fb + (long)j * F;
+    float s = 0.f;
+    for (int f = lane; f < F; f += 64) s += dz[f] * gt[f] * fj[f];
+    s = wave_sum(s);
+    if (lane == 0) da[j] = dA ? s + dA[n * k + j] : s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float dot = 0.f;
+    for (int j = 0; j < k; ++j) dot += ALPHA[n * k + j] * da[j];
+    for (int j = 0; j < k; ++j) {
+      da[j] = ALPHA[n * k + j] * (da[j] - dot);
+      DS[n * k + j] = da[j];
+    }
+  }
+  __syncthreads();
+  for (int a = tid; a < A; a += blockDim.x) {
+    const float wa = w_o[a];
+    float dq = 0.f;
+    for (int j = 0; j < k; ++j) {
+      const float u = U[(n * k + j) * A + a];
+      const float du = da[j] * wa * (1.f - u * u);
+      dq += du;
+      const long o = ((long)b * k + j) * A + a;
+      dKh[o] = t == L - 1 ? du : dKh[o] + du;
+    }
+    DQ[n * A + a] = dq;
+  }
+}
+
+// out[n][v] = logits[n][v] - lse[n]: the log-probabilities of every position
+__global__ void log_softmax_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                                   float* __restrict__ out, int N, int V) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)N * V) return;
+  out[i] = logits[i] - lse[i / V];
+}
+
+// Log-softmax backward from an upstream gradient G [N][V] (null: zero), one workgroup per
+// row: logits[n][v] <- G[n][v] - exp(logits[n][v] - lse[n]) * sum_v G[n][v], in place.  The
+// row sum is taken in a fixed order (per-thread strided sums, lanes by xor butterfly, the 4
+// waves in order).
+__global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float* __restrict__ G,
+                                                              float* __restrict__ logits,
+                                                              const float* __restrict__ lse,
+                                                              int V) {
+  __shared__ float red[4];
+  const int n = blockIdx.x;
+  float* x = logits + (long)n * V;
+  const float* g = G ? G + (long)n * V : nullptr;
+  float s = 0.f;
+  if (g)
+    for (int v = threadIdx.x; v < V; v += blockDim.x) s += g[v];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const float sum = red[0] + red[1] + red[2] + red[3];
+  const float l = lse[n];
+  for (int v = threadIdx.x; v < V; v += blockDim.x)
+    x[v] = g ? g[v] - expf(x[v] - l) * sum : 0.f;
+}
+
+// The context and mean-pool shares of the feature gradient, added to the key share that dF
+// [rows][k][F] holds: dF[b][j][f] = (dF[b][j][f] + sum over t (increasing) of
+// alpha[b][t][j] * dctx[b][t][f]) + dpool[b][f] / k.
+__global__ void dfeat_kernel(const float* __restrict__ ALPHA, const float* __restrict__ DCTX,
+                             const float* __restrict__ dpool, float* __restrict__ dF, int rows,
+                             int L, int k, int F) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)rows * k * F) return;
+  const int f = (int)(i % F);
+  const long bj = i / F;
+  const int j = (int)(bj % k), b = (int)(bj / k);
+  float s = 0.f;
+  for (int t = 0; t < L; ++t) {
+    const long n = (long)b * L + t;
+    s += ALPHA[n * k + j] * DCTX[n * F + f];
+  }
+  dF[i] = (dF[i] + s) + dpool[(long)b * F + f] / (float)k;
+}
+
 // d pre-activations of init_h / init_c from dh_0 (dhrec) and dc_0 (dc)
 __global__ void init_bwd_kernel(const float* __restrict__ Hs, const float* __restrict__ C,
                                 const float* __restrict__ dhrec, const float* __restrict__ dc,
@@ -313,6 +417,10 @@ struct Plan {
   int V, E, H, A, F, pad, start, rows, k, L, N;
   size_t ids, pooled, kh, x, g, cst, hs, hd, q, gt, ctx, alpha, u, s, logits, lse, term, valid;
   size_t dy, dhrec, dc, dz, dgp, ds, dq, dkh, dxe, dph, dpc, scratch, scratch_floats, total;
+  // after `total`, what the autograd pair (milan_decoder_forward_train / _backward) adds:
+  // the loss terms the forward still computes, dctx_t = dz_t * gate_t of every step, the
+  // pooled features' gradient and the scratch of the feature-gradient GEMMs
+  size_t terms, dctx, dpool, gscratch, gscratch_floats, grad_total;
 };
 
 static int make_plan(const milan_ctx* c, int rows, int k, int L, Plan* p) {
@@ -393,6 +501,14 @@ static int make_plan(const milan_ctx* c, int rows, int k, int L, Plan* p) {
   p->scratch = take(sc);
   p->scratch_floats = sc;
   p->total = off * sizeof(float);
+  p->terms = take(4);
+  p->dctx = take((size_t)N * F);
+  p->dpool = take((size_t)rows * F);
+  const size_t gk = split_scratch_floats((int)BK, F, A), gp = split_scratch_floats(rows, F, H);
+  const size_t gsc = gk > gp ? gk : gp;  // dKh . W_k, then dph . W_init_h + dpc . W_init_c
+  p->gscratch = take(gsc);
+  p->gscratch_floats = gsc;
+  p->grad_total = off * sizeof(float);
   return 0;
 }
 
@@ -482,9 +598,20 @@ static int forward(const Plan& p, const float* const* w, float* ws, const float*
   return 0;
 }
 
+// Upstream gradients of the autograd backward (milan_decoder_backward): the logits buffer
+// already holds dlogits; dattn [rows * L][k] is dL/d alpha (null: zero); dctx [rows * L][F]
+// receives dz * gate per step (null: not stored).
+struct Upstream {
+  const float* dattn;
+  float* dctx;
+};
+
+// Backward of the training loss (up == nullptr: dlogits from the loss terms `loss`, the
+// regulariser with `reg_weight`) or of upstream gradients (up != nullptr).
 static int backward(const Plan& p, const float* const* w, float* const* gr, float* ws,
                     const float* feat, const int64_t* targets, uint32_t thr, float scale,
-                    uint64_t seed, float reg_weight, const float* loss, hipStream_t s) {
+                    uint64_t seed, float reg_weight, const float* loss, const Upstream* up,
+                    hipStream_t s) {
   const int N = p.N, H = p.H, E = p.E, V = p.V, A = p.A, F = p.F, rows = p.rows, k = p.k,
             L = p.L;
   const int BK = rows * k;
@@ -495,7 +622,7 @@ static int backward(const Plan& p, const float* const* w, float* const* gr, floa
         *dc = ws + p.dc, *dZ = ws + p.dz, *DGP = ws + p.dgp, *DQ = ws + p.dq, *DS = ws + p.ds,
         *dKh = ws + p.dkh;
   float* dlog = ws + p.logits;
-  lmt::launch_dlogits(dlog, targets, ws + p.lse, ws + p.valid, loss, N, V, s);
+  if (!up) lmt::launch_dlogits(dlog, targets, ws + p.lse, ws + p.valid, loss, N, V, s);
   const View hout = thr ? view(ws + p.hd, H) : view(Hs + H, H, L, (long)(L + 1) * H);
   // output layer: dW_out = dlogits^T . h_out, db_out = sum dlogits, dY = dlogits . W_out
   MILAN_TRY(gemm(view(dlog, V), 1, hout, 0, view(gr[P_OUT_W], H), none, nullptr, nullptr, V, H,
@@ -514,9 +641,14 @@ static int backward(const Plan& p, const float* const* w, float* const* gr, floa
     // dz = dG_t . W_ih[:, E:]
     MILAN_TRY(gemm(dgt, 0, view(w[P_W_IH] + E, E + F), 0, view(dZ, F), none, nullptr, nullptr,
                    rows, F, 4 * H, sc, s));
-    hipLaunchKernelGGL(attend_bwd_kernel, dim3(rows), dim3(256), 0, s, dZ, ws + p.gt, ws + p.ctx,
-                       feat, ws + p.alpha, ws + p.u, ws + p.s, w[P_O_W], reg, DGP, DS, DQ, dKh, L,
-                       k, A, F, t);
+    if (up)
+      hipLaunchKernelGGL(attend_bwd_up_kernel, dim3(rows), dim3(256), 0, s, dZ, ws + p.gt,
+                         ws + p.ctx, feat, ws + p.alpha, ws + p.u, up->dattn, w[P_O_W], up->dctx,
+                         DGP, DS, DQ, dKh, L, k, A, F, t);
+    else
+      hipLaunchKernelGGL(attend_bwd_kernel, dim3(rows), dim3(256), 0, s, dZ, ws + p.gt,
+                         ws + p.ctx, feat, ws + p.alpha, ws + p.u, ws + p.s, w[P_O_W], reg, DGP,
+                         DS, DQ, dKh, L, k, A, F, t);
     MILAN_CHECK_HIP(hipGetLastError());
     // dL/dh_t through step t = dq . W_q + dgate . W_g + dG . W_hh
     const View dhv = view(dh, H);
@@ -612,7 +744,81 @@ int milan_decoder_train_step(milan_ctx* c, const float* const* params, float* co
   const hipStream_t s = (hipStream_t)stream;
   MILAN_TRY(forward(p, params, (float*)ws, features, targets, thr, scale, seed, loss_terms, s));
   return backward(p, params, grads, (float*)ws, features, targets, thr, scale, seed,
-                  regularization_weight, loss_terms, s);
+                  regularization_weight, loss_terms, nullptr, s);
+}
+
+size_t milan_decoder_grad_workspace_bytes(const milan_ctx* c, int rows, int k, int L) {
+  Plan p;
+  if (make_plan(c, rows, k, L, &p) != 0) return 0;
+  return p.grad_total;
+}
+
+int milan_decoder_forward_train(milan_ctx* c, const float* const* params, int n_params,
+                                const float* features, const int64_t* targets, int rows, int k,
+                                int L, float dropout, uint64_t seed, float* logprobs_out,
+                                float* attentions_out, void* ws, size_t ws_bytes,
+                                milan_stream stream) {
+  MILAN_REQUIRE(features && targets && logprobs_out && attentions_out && ws, MILAN_ERR_ARG,
+                "milan_decoder_forward_train: null argument");
+  MILAN_REQUIRE(dropout >= 0.f && dropout < 1.f, MILAN_ERR_ARG,
+                "milan_decoder_forward_train: dropout %g not in [0, 1)", (double)dropout);
+  Plan p;
+  MILAN_TRY(make_plan(c, rows, k, L, &p));
+  MILAN_REQUIRE(ws_bytes >= p.grad_total, MILAN_ERR_WORKSPACE,
+                "milan_decoder_forward_train: workspace %zu < %zu bytes", ws_bytes, p.grad_total);
+  MILAN_TRY(check_params((const void* const*)params, n_params, "parameter"));
+  const uint32_t thr = drop_threshold(dropout);
+  const float scale = dropout > 0.f ? 1.f / (1.f - dropout) : 1.f;
+  const hipStream_t s = (hipStream_t)stream;
+  float* w = (float*)ws;
+  MILAN_TRY(forward(p, params, w, features, targets, thr, scale, seed, w + p.terms, s));
+  hipLaunchKernelGGL(log_softmax_kernel, dim3(blocks_for((long)p.N * p.V)), dim3(256), 0, s,
+                     w + p.logits, w + p.lse, logprobs_out, p.N, p.V);
+  MILAN_CHECK_HIP(hipGetLastError());
+  MILAN_CHECK_HIP(hipMemcpyAsync(attentions_out, w + p.alpha, (size_t)p.N * k * sizeof(float),
+                                 hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int milan_decoder_backward(milan_ctx* c, const float* const* params, float* const* grads,
+                           int n_params, const float* features, const int64_t* targets, int rows,
+                           int k, int L, float dropout, uint64_t seed, const float* dlogprobs,
+                           const float* dattentions, float* dfeatures, void* ws, size_t ws_bytes,
+                           milan_stream stream) {
+  MILAN_REQUIRE(features && targets && ws, MILAN_ERR_ARG, "milan_decoder_backward: null argument");
+  MILAN_REQUIRE(dropout >= 0.f && dropout < 1.f, MILAN_ERR_ARG,
+                "milan_decoder_backward: dropout %g not in [0, 1)", (double)dropout);
+  Plan p;
+  MILAN_TRY(make_plan(c, rows, k, L, &p));
+  MILAN_REQUIRE(ws_bytes >= p.grad_total, MILAN_ERR_WORKSPACE,
+                "milan_decoder_backward: workspace %zu < %zu bytes", ws_bytes, p.grad_total);
+  MILAN_TRY(check_params((const void* const*)params, n_params, "parameter"));
+  MILAN_TRY(check_params((const void* const*)grads, n_params, "gradient"));
+  const uint32_t thr = drop_threshold(dropout);
+  const float scale = dropout > 0.f ? 1.f / (1.f - dropout) : 1.f;
+  const hipStream_t s = (hipStream_t)stream;
+  float* w = (float*)ws;
+  // dlogits into the logits buffer, where backward() expects them
+  hipLaunchKernelGGL(log_softmax_bwd_kernel, dim3(p.N), dim3(256), 0, s, dlogprobs, w + p.logits,
+                     w + p.lse, p.V);
+  MILAN_CHECK_HIP(hipGetLastError());
+  const Upstream up{dattentions, dfeatures ? w + p.dctx : nullptr};
+  MILAN_TRY(backward(p, params, grads, w, features, targets, thr, scale, seed, 0.f, nullptr, &up,
+                     s));
+  if (!dfeatures) return 0;
+  // dF = (dKh . W_k + sum_t alpha_t dctx_t) + (dph . W_init_h + dpc . W_init_c) / k
+  const Scratch gsc{w + p.gscratch, p.gscratch_floats};
+  const View none = view(nullptr, 0), dpool = view(w + p.dpool, p.F);
+  MILAN_TRY(gemm(view(w + p.dkh, p.A), 0, view(params[P_K_W], p.F), 0, view(dfeatures, p.F), none,
+                 nullptr, nullptr, rows * k, p.F, p.A, gsc, s));
+  MILAN_TRY(gemm(view(w + p.dph, p.H), 0, view(params[P_INIT_H_W], p.F), 0, dpool, none, nullptr,
+                 nullptr, rows, p.F, p.H, gsc, s));
+  MILAN_TRY(gemm(view(w + p.dpc, p.H), 0, view(params[P_INIT_C_W], p.F), 0, dpool, dpool, nullptr,
+                 nullptr, rows, p.F, p.H, gsc, s));
+  hipLaunchKernelGGL(dfeat_kernel, dim3(blocks_for((long)rows * k * p.F)), dim3(256), 0, s,
+                     w + p.alpha, w + p.dctx, w + p.dpool, dfeatures, rows, L, k, p.F);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // extern "C"

@@ -23,9 +23,15 @@ What differs by design:
     `decoder()` (:1214-1259) builds a seeded, reference-initialised model;
     `bleu` scores with `metrics.bleu`, a pure-Python restatement of
     sacrebleu 1.5.1's corpus BLEU;
-  * out of scope (SURVEY.md section 2.1): a training-mode `forward` (raises;
-    `fit` does not need it), `rouge` / `bert_score` (need rouge /
-    bert_score), `DecoderWithCLIP`.
+  * `forward` in training mode with a tensor strategy (teacher forcing) is
+    differentiable: `TeacherForced` runs `milan_decoder_forward_train` and,
+    on `backward()`, `milan_decoder_backward`, so
+    predictions, attentions and scores carry `grad_fn` and a user's own loss,
+    optimizer loop or torch `Encoder` trains through it.  The decoder's 19
+    own tensors require grad, as the reference's modules do;
+  * out of scope: training-mode greedy / sample /
+    beam decoding (raises NotImplementedError), `rouge` / `bert_score` (need
+    rouge / bert_score), `DecoderWithCLIP`.
 """
 import os
 import weakref
@@ -34,6 +40,7 @@ from typing import (Any, Dict, Mapping, NamedTuple, Optional, Sequence, Sized,
 
 import torch
 from torch import nn, optim
+from torch.autograd.function import once_differentiable
 from torch.utils import data
 
 from milan_amd import (encoders, hip, lang, lms, metrics, params, serialize,
@@ -116,6 +123,47 @@ class Attention(params.ParamTree):
             root=self)
 
 
+class TeacherForced(torch.autograd.Function):
+    """Teacher-forced decoder with dropout as one autograd node:
+    `milan_decoder_forward_train` / `milan_decoder_backward`
+    (include/milan_hip.h).  Inputs: the dims-only hip.Context, targets (rows,
+    L), dropout, seed, features (rows, k, F) and the 19 TRAIN_PARAMS tensors;
+    outputs: log-probs (rows, L, V) and attentions (rows, L, k).  The
+    forward's workspace holds every activation and the backward overwrites
+    them in place, so the graph supports one backward."""
+
+    @staticmethod
+    def forward(ctx, hctx, targets, dropout, seed, features, *params):
+        logprobs, attentions, ws = hctx.decoder_forward_train(
+            params, features, targets, dropout, seed)
+        ctx.hctx, ctx.dropout, ctx.seed, ctx.ws = hctx, dropout, seed, ws
+        ctx.save_for_backward(targets, features, *params)
+        ctx.set_materialize_grads(False)
+        return logprobs, attentions
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dlogprobs, dattentions):
+        ws, ctx.ws = ctx.ws, None
+        if ws is None:
+            raise RuntimeError(
+                'the teacher-forced decoder graph was already backpropagated '
+                'once: its activations are consumed by the first backward; run '
+                'the forward again')
+        targets, features, *params = ctx.saved_tensors
+        dfeatures = (torch.empty_like(features)
+                     if ctx.needs_input_grad[4] else None)
+        grads = [torch.empty_like(p) for p in params]
+        contig = [None if g is None else g.contiguous()
+                  for g in (dlogprobs, dattentions)]
+        ctx.hctx.decoder_backward(params, grads, features, targets,
+                                  ctx.dropout, ctx.seed, *contig, dfeatures, ws)
+        # (the kernels compute all 19; torch accumulates the ones asked for)
+        pgrads = [g if need else None
+                  for g, need in zip(grads, ctx.needs_input_grad[5:])]
+        return (None, None, None, None, dfeatures, *pgrads)
+
+
 class Decoder(nn.Module):
     """Neuron caption decoder (reference decoders.py:224)."""
 
@@ -193,10 +241,17 @@ class Decoder(nn.Module):
         self.attend = Attention(hidden_size,
                                 fs,
                                 hidden_size=attention_hidden_size)
+        # the decoder's own tensors are trainable, as the reference's torch
+        # modules are (the training-mode forward differentiates them; every
+        # other path computes in HIP without autograd)
+        for p in self._train_params():
+            p.requires_grad_(True)
         if lm is not None:
             lm._owner = weakref.ref(self)
         self._ctx: Optional[hip.Context] = None
         self._ctx_key = None
+        self._train_ctx: Optional[hip.Context] = None  # training-mode forward
+        self._train_ctx_key = None
         self.eval()  # hubs.py:130 hands out models in eval mode
 
     # -- reference properties -------------------------------------------------
@@ -314,9 +369,13 @@ class Decoder(nn.Module):
                                      int(strategy.max()) >= self.vocab_size):
                 raise IndexError('index out of range in self')  # nn.Embedding
         if self.training:
-            raise NotImplementedError(
-                'training-mode forward (dropout active) is not built; call '
-                '.eval() -- milan.pretrained() returns eval-mode models')
+            if not isinstance(strategy, torch.Tensor):
+                raise NotImplementedError(
+                    'training-mode forward (dropout active) is built for '
+                    'teacher forcing (a tensor strategy) only; call .eval() '
+                    'to decode -- milan.pretrained() returns eval-mode models')
+            return self._forward_train(images_or_features, masks, encode,
+                                       strategy)
 
         if isinstance(strategy, str) and strategy == STRATEGY_SAMPLE:
             return self._sample(images_or_features, masks, encode, length, mi,
@@ -369,6 +428,56 @@ class Decoder(nn.Module):
             beam_scores=beam_scores,
             beam_tokens=beam_tokens,
         )
+
+    def _train_context(self) -> hip.Context:
+        """A context that only carries the decoder's dims, never finalized,
+        cached on the decoder: the training calls read the live parameters, so
+        optimizer steps do not rebuild it."""
+        device = hip.require_device(self.device)
+        key = (device, tuple(p.shape for p in self._train_params()))
+        if self._train_ctx is None or self._train_ctx_key != key:
+            sd = {k: v for k, v in self.state_dict().items()
+                  if not k.startswith(('encoder.', 'lm.'))}
+            # (the old one closes when the last graph that holds it goes)
+            self._train_ctx = hip.Context(
+                hip.make_dims(sd, len(self.indexer.vocab)), {}, device,
+                finalize=False)
+            self._train_ctx_key = key
+        return self._train_ctx
+
+    def _forward_train(self, images_or_features, masks, encode,
+                       targets: torch.Tensor) -> DecoderOutput:
+        """Training-mode teacher forcing (reference :431-463 with dropout on):
+        predictions and attentions carry `grad_fn` through `TeacherForced`, and
+        so does `scores`.  Features from the native encoder come under no_grad
+        (its trunk has no backward); a foreign torch Encoder runs with
+        autograd and receives the feature gradient."""
+        device = hip.require_device(self.device)
+        if encode:
+            if self._has_hip_encoder():
+                with torch.no_grad():
+                    features = self.encode(images_or_features, masks=masks)
+            else:
+                features = self.encode(images_or_features, masks=masks)
+        else:
+            features = images_or_features
+        features = features.to(device, torch.float32).contiguous()
+        targets = targets.to(device, torch.long).contiguous()
+        seed = 0
+        if self.dropout > 0:  # as Decoder.fit draws it
+            seed = int(torch.randint(
+                2**62, (), device=device,
+                generator=torch.cuda.default_generators[device.index]))
+        predictions, attentions = TeacherForced.apply(
+            self._train_context(), targets, float(self.dropout), seed,
+            features, *self._train_params())
+        # scores[:] += predictions[idx_b, currents] per step (reference :460-463)
+        scores = predictions.gather(2, targets.unsqueeze(-1)).squeeze(-1).sum(1)
+        return DecoderOutput(
+            captions=self.indexer.reconstruct(targets.tolist()),
+            scores=scores, tokens=targets, predictions=predictions,
+            attentions=attentions, beam_captions=None, beam_scores=None,
+            beam_tokens=None)
 
     def _sample(self, images_or_features, masks, encode, length, mi,
                 temperature) -> DecoderOutput:

@@ -78,7 +78,7 @@ class Dims(ctypes.Structure):
     ]
 
 
-ABI_VERSION = 10  # MILAN_ABI_VERSION this binding was written against
+ABI_VERSION = 11  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
 TRUNK_BOTTLENECK, TRUNK_BASIC, TRUNK_ALEXNET, TRUNK_NONE = 0, 1, 2, 3
@@ -176,6 +176,13 @@ SIGNATURES = {
     'milan_decoder_train_step':
         (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, _F, _P,
               _P, _SZ, _P]),
+    'milan_decoder_grad_workspace_bytes': (_SZ, [_P, _I, _I, _I]),
+    'milan_decoder_forward_train':
+        (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, _P, _P, _P,
+              _SZ, _P]),
+    'milan_decoder_backward':
+        (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, _P, _P,
+              _P, _P, _SZ, _P]),
     'milan_conv2d_nhwc':
         (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I,
               _P]),
@@ -905,7 +912,7 @@ class Context:
     # -- Decoder training (include/milan_hip.h, milan_decoder_train_step) --
     DECODER_TRAIN_PARAMS = 19
 
-    def _decoder_train_call(self, params, features, targets):
+    def _decoder_args(self, params, features, targets):
         if features.dim() != 3:
             raise ValueError('features must be (rows, k, feature_size), got '
                              f'{tuple(features.shape)}')
@@ -931,8 +938,26 @@ class Context:
                                  f'float32 on {self.device}')
         features = _dev(features, self.device, torch.float32)
         targets = _dev(targets, self.device, torch.long)
+        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
+        return features, targets, ptrs
+
+    def _decoder_grads(self, params, grads):
+        if len(grads) != len(params):
+            raise ValueError(f'{len(grads)} gradients for {len(params)} '
+                             'parameters')
+        for p, g in zip(params, grads):
+            if (g.shape != p.shape or g.device != self.device
+                    or g.dtype != torch.float32 or not g.is_contiguous()):
+                raise ValueError('gradients must be contiguous float32 '
+                                 'tensors shaped like the parameters')
+        return (_P * len(grads))(*[g.data_ptr() for g in grads])
+
+    def _decoder_train_call(self, params, features, targets):
+        features, targets, ptrs = self._decoder_args(params, features,
+                                                     targets)
+        rows, k, _ = features.shape
         need = int(self.lib.milan_decoder_train_workspace_bytes(
-            self._h, rows, k, length))
+            self._h, rows, k, targets.shape[1]))
         if need == 0:
             _check(ERR_SHAPE)
         ws = getattr(self, '_train_ws', None)
@@ -940,7 +965,6 @@ class Context:
             self._train_ws = None
             ws = self._train_ws = torch.empty(need, dtype=torch.uint8,
                                               device=self.device)
-        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
         loss = torch.empty(3, device=self.device)
         return features, targets, ptrs, ws, loss
 
@@ -972,15 +996,7 @@ class Context:
         `params`).  Does not synchronise."""
         features, targets, ptrs, ws, loss = self._decoder_train_call(
             params, features, targets)
-        if len(grads) != len(params):
-            raise ValueError(f'{len(grads)} gradients for {len(params)} '
-                             'parameters')
-        for p, g in zip(params, grads):
-            if (g.shape != p.shape or g.device != self.device
-                    or g.dtype != torch.float32 or not g.is_contiguous()):
-                raise ValueError('gradients must be contiguous float32 '
-                                 'tensors shaped like the parameters')
-        gptrs = (_P * len(grads))(*[g.data_ptr() for g in grads])
+        gptrs = self._decoder_grads(params, grads)
         with torch.cuda.device(self.device):
             _check(
                 self.lib.milan_decoder_train_step(
@@ -990,6 +1006,78 @@ class Context:
                     float(regularization_weight), loss.data_ptr(),
                     ws.data_ptr(), ws.numel(), _stream(self.device)))
         return loss
+
+    def decoder_forward_train(self, params, features: torch.Tensor,
+                              targets: torch.Tensor, dropout: float = 0.,
+                              seed: int = 0):
+        """Teacher-forced decoder in train mode (milan_decoder_forward_train):
+        returns (log-probs (rows, L, V), attentions (rows, L, k), workspace).
+        The workspace is a fresh uint8 device tensor holding the activations
+        that ONE `decoder_backward` consumes; it is not `_train_ws`, so other
+        calls on this context leave it alone.  Does not synchronise."""
+        features, targets, ptrs = self._decoder_args(params, features, targets)
+        rows, k, _ = features.shape
+        length = targets.shape[1]
+        need = int(self.lib.milan_decoder_grad_workspace_bytes(
+            self._h, rows, k, length))
+        if need == 0:
+            _check(ERR_SHAPE)
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        logprobs = torch.empty(rows, length, self.dims.vocab_size,
+                               device=self.device)
+        attentions = torch.empty(rows, length, k, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_decoder_forward_train(
+                    self._h, ptrs, len(params), features.data_ptr(),
+                    targets.data_ptr(), rows, k, length, float(dropout),
+                    int(seed) & (2**64 - 1), logprobs.data_ptr(),
+                    attentions.data_ptr(), ws.data_ptr(), ws.numel(),
+                    _stream(self.device)))
+        return logprobs, attentions, ws
+
+    def decoder_backward(self, params, grads, features: torch.Tensor,
+                         targets: torch.Tensor, dropout: float, seed: int,
+                         dlogprobs: Optional[torch.Tensor],
+                         dattentions: Optional[torch.Tensor],
+                         dfeatures: Optional[torch.Tensor],
+                         ws: torch.Tensor) -> None:
+        """Backward of `decoder_forward_train` (milan_decoder_backward) from
+        upstream gradients of its log-probs and attentions (None: zero), with
+        the forward's params, features, targets, dropout and seed.  The
+        gradients of the 19 parameters are OVERWRITTEN into `grads`, the
+        feature gradient into `dfeatures` (None: not computed).  Consumes
+        `ws`: a second backward from the same workspace is wrong.  Does not
+        synchronise."""
+        if len(params) != self.DECODER_TRAIN_PARAMS:
+            raise ValueError(f'{len(params)} parameters, expected '
+                             f'{self.DECODER_TRAIN_PARAMS}')
+        rows, k, f = features.shape
+        length = targets.shape[1]
+        shapes = ((dlogprobs, (rows, length, self.dims.vocab_size)),
+                  (dattentions, (rows, length, k)), (dfeatures, (rows, k, f)))
+        for t, shape in shapes:
+            if t is not None and (tuple(t.shape) != shape
+                                  or t.device != self.device
+                                  or t.dtype != torch.float32
+                                  or not t.is_contiguous()):
+                raise ValueError(f'gradient {tuple(t.shape)} must be a '
+                                 f'contiguous float32 {shape} on {self.device}')
+        need = int(self.lib.milan_decoder_grad_workspace_bytes(
+            self._h, rows, k, length))
+        if need == 0 or ws.numel() < need:
+            raise ValueError('workspace does not come from decoder_forward_train '
+                             'at these dims')
+        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
+        gptrs = self._decoder_grads(params, grads)
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_decoder_backward(
+                    self._h, ptrs, gptrs, len(params), features.data_ptr(),
+                    targets.data_ptr(), rows, k, length, float(dropout),
+                    int(seed) & (2**64 - 1), _ptr(dlogprobs), _ptr(dattentions),
+                    _ptr(dfeatures), ws.data_ptr(), ws.numel(),
+                    _stream(self.device)))
 
     def describe(self,
                  images: torch.Tensor,

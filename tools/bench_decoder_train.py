@@ -12,7 +12,11 @@ and, like the batches, sit on the device before the timed window; a step is
 forward + loss + backward + optimizer step; the window ends with a device
 synchronise.
 
-    python tools/bench_decoder_train.py --steps 30 --warmup 5 [--only hip|torch] [--out f.json]
+The `autograd` leg is a user's own loop on the differentiable training-mode
+`Decoder.forward` (milan_decoder_forward_train / milan_decoder_backward): the
+reference's loss in torch on its outputs, loss.backward(), AdamW.
+
+    python tools/bench_decoder_train.py --steps 30 --warmup 5 [--only hip|autograd|torch] [--out f.json]
 
 Needs an MI355X; prints one JSON line.
 """
@@ -91,6 +95,34 @@ def bench_hip(indexer, data, dev, warmup, steps):
     return seconds
 
 
+def bench_autograd(indexer, data, dev, warmup, steps):
+    """A user's own loop on the differentiable training-mode forward: the
+    forward (milan_decoder_forward_train), the reference's loss in torch on its
+    outputs, loss.backward() (milan_decoder_backward) and AdamW."""
+    model = decoders.Decoder(indexer, _Features(), embedding_size=E, hidden_size=H,
+                             dropout=DROPOUT)
+    torch.manual_seed(0)
+    model.reset_parameters()
+    model.to(dev).train()
+    opt = torch.optim.AdamW(model.parameters())
+    crit = nn.NLLLoss(ignore_index=indexer.pad_index)
+    data = [(f.to(dev), t.to(dev)) for f, t in data]
+
+    def step(feats, targets):
+        out = model(feats, length=targets.shape[1], strategy=targets, mi=False)
+        loss = crit(out.predictions.permute(0, 2, 1), targets)
+        loss = loss + REG * ((1 - out.attentions.sum(dim=1))**2).mean()
+        loss.backward()
+        opt.step()
+        opt.zero_grad()
+
+    seconds = timed(step, data, warmup, steps)
+    ctx = model._train_context()
+    ws = int(ctx.lib.milan_decoder_grad_workspace_bytes(ctx._h, BATCH, K, L))
+    step_ws = int(ctx.lib.milan_decoder_train_workspace_bytes(ctx._h, BATCH, K, L))
+    return seconds, dict(workspace_bytes=ws, train_step_workspace_bytes=step_ws)
+
+
 class TorchDecoder(nn.Module):
     """The reference's decoder modules and teacher-forced training loss."""
 
@@ -146,7 +178,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--only', choices=('hip', 'torch'))
+    ap.add_argument('--only', choices=('hip', 'autograd', 'torch'))
     ap.add_argument('--out')
     args = ap.parse_args()
     dev = hip.require_device('cuda')
@@ -159,15 +191,22 @@ def main():
                              L=int(data[0][1].shape[1]), dropout=DROPOUT,
                              regularization_weight=REG),
                   steps=args.steps, warmup=args.warmup, tokens_per_step=per_step)
-    for name, fn in (('hip', bench_hip), ('torch', bench_torch)):
+    for name, fn in (('hip', bench_hip), ('autograd', bench_autograd),
+                     ('torch', bench_torch)):
         if args.only and args.only != name:
             continue
         seconds = fn(indexer, data, dev, args.warmup, args.steps)
+        extra = {}
+        if isinstance(seconds, tuple):
+            seconds, extra = seconds
         result[name] = dict(ms_per_step=1e3 * seconds / args.steps,
-                            tokens_per_s=per_step * args.steps / seconds)
+                            tokens_per_s=per_step * args.steps / seconds, **extra)
     if 'hip' in result and 'torch' in result:
         result['hip_over_torch_time'] = (result['hip']['ms_per_step'] /
                                          result['torch']['ms_per_step'])
+    if 'hip' in result and 'autograd' in result:
+        result['autograd_over_hip_time'] = (result['autograd']['ms_per_step'] /
+                                            result['hip']['ms_per_step'])
     line = json.dumps(result)
     print(line)
     if args.out:

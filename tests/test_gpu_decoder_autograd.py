@@ -19,9 +19,9 @@ import sys
 
 import pytest
 import torch
-import torch.nn.functional as F
 from torch import nn
 
+import trainref
 from conftest import REPO
 from milan_amd import decoders, encoders, hip, lms, training
 from test_gpu_decoder_train import (META, NOISE_ONLY, corpus_dataset,
@@ -43,39 +43,6 @@ def golden():
     out = torch.load(GOLDEN_DIR / 'reference_goldens_decoder_fit.pt')
     out['features'] = golden_features()
     return out
-
-
-def torch_forward(w, feats, targets, start, mask=None, p=0.):
-    """The reference's teacher-forced forward (:431-463 over step :576-634) in
-    the dtype of `w` and `feats`: (log-probs (rows, L, V), attentions
-    (rows, L, k)).  `mask`: the kernel's dropout mask on h, (rows, L, H)."""
-    rows, k, _ = feats.shape
-    length = targets.shape[1]
-    pooled = feats.mean(dim=1)
-    h = torch.tanh(pooled @ w['init_h.0.weight'].t() + w['init_h.0.bias'])
-    c = torch.tanh(pooled @ w['init_c.0.weight'].t() + w['init_c.0.bias'])
-    keys = feats @ w['attend.key_to_hidden.weight'].t() + w['attend.key_to_hidden.bias']
-    inputs = torch.cat([torch.full((rows, 1), start, dtype=torch.long,
-                                   device=targets.device), targets[:, :-1]], 1)
-    hsz = h.shape[1]
-    logps, atts = [], []
-    for t in range(length):
-        q = h @ w['attend.query_to_hidden.weight'].t() + w['attend.query_to_hidden.bias']
-        u = torch.tanh(q[:, None] + keys)
-        s = (u @ w['attend.output.0.weight'].t()).squeeze(-1) + w['attend.output.0.bias']
-        a = torch.softmax(s, dim=1)
-        ctx = (a[..., None] * feats).sum(dim=1)
-        gate = torch.sigmoid(h @ w['feature_gate.0.weight'].t() + w['feature_gate.0.bias'])
-        x = torch.cat([w['embedding.weight'][inputs[:, t]], ctx * gate], dim=1)
-        gates = (x @ w['lstm.weight_ih'].t() + w['lstm.bias_ih'] +
-                 h @ w['lstm.weight_hh'].t() + w['lstm.bias_hh'])
-        i, f, gg, o = gates.split(hsz, dim=1)
-        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h = torch.sigmoid(o) * torch.tanh(c)
-        hd = h if mask is None else h * mask[:, t].to(h.dtype) / (1 - p)
-        logps.append(F.log_softmax(hd @ w['output.1.weight'].t() + w['output.1.bias'], -1))
-        atts.append(a)
-    return torch.stack(logps, 1), torch.stack(atts, 1)
 
 
 def peek_seed(dev):
@@ -170,7 +137,7 @@ def test_gradients_match_autograd_float64(dev, case, p, upstream):
     w = {n: t.detach().double().requires_grad_()
          for n, t in zip(decoders.TRAIN_PARAMS, params_of(dec))}
     x64 = feats.to(dev).double().requires_grad_()
-    lp, att = torch_forward(w, x64, targets.to(dev), v - 4, mask, p)
+    lp, att = trainref.decoder_forward(w, x64, targets.to(dev), v - 4, mask, p)
     want_loss = 0.
     if use_lp:
         want_loss = want_loss + (lp * glp.to(dev).double()).sum()
@@ -344,7 +311,7 @@ def test_foreign_encoder_receives_feature_gradient(dev):
     w = {n: t.detach().double() for n, t in zip(decoders.TRAIN_PARAMS, params_of(dec))}
     scale = dec.encoder.scale.detach().double().requires_grad_()
     mask = lms.decoder_dropout_mask(seed, rows, length, hsz, .5).to(dev)
-    lp, att = torch_forward(w, feats.to(dev).double() * scale, targets.to(dev), v - 4,
+    lp, att = trainref.decoder_forward(w, feats.to(dev).double() * scale, targets.to(dev), v - 4,
                             mask, .5)
     ((lp * glp.double()).sum() + (att * gatt.double()).sum()).backward()
     rel = float((got.double() - scale.grad).abs().max() / scale.grad.abs().max())

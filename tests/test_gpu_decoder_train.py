@@ -16,8 +16,8 @@ import json
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+import trainref
 from conftest import GOLDEN_DIR
 from milan_amd import decoders, encoders, hip, lang, lms, synthetic
 
@@ -73,11 +73,12 @@ class IdentityEncoder(encoders.Encoder):
         return {'feature_size': self.feature_shape[0]}
 
 
-def make_decoder(nvocab, fs, hidden, emb, seed):
+def make_decoder(nvocab, fs, hidden, emb, seed, attention_hidden_size=None):
     idx = lang.Indexer(lang.Vocab(synthetic.vocab_tokens(nvocab)), tokenize, True,
                        True, True, True)
     dec = decoders.Decoder(idx, IdentityEncoder(fs), embedding_size=emb,
-                           hidden_size=hidden, dropout=0.)
+                           hidden_size=hidden, attention_hidden_size=attention_hidden_size,
+                           dropout=0.)
     torch.manual_seed(seed)
     dec.reset_parameters()
     return dec
@@ -97,48 +98,6 @@ def random_batch(v, rows, k, fs, length, seed, all_pad_rows=()):
     for r in all_pad_rows:
         targets[r] = pad
     return feats, targets
-
-
-def torch_loss(w, feats, targets, start, pad, mask=None, p=0., reg_weight=1.):
-    """float64 autograd of the reference's training loss (Decoder.fit :1017-1022
-    over forward :431-463 / step :576-634).  Returns (nll sum, count,
-    regulariser sum of squares, grads)."""
-    w = {k: t.detach().double().requires_grad_() for k, t in w.items()}
-    feats = feats.double()
-    rows, k, _ = feats.shape
-    length = targets.shape[1]
-    pooled = feats.mean(dim=1)
-    h = torch.tanh(pooled @ w['init_h.0.weight'].t() + w['init_h.0.bias'])
-    c = torch.tanh(pooled @ w['init_c.0.weight'].t() + w['init_c.0.bias'])
-    keys = feats @ w['attend.key_to_hidden.weight'].t() + w['attend.key_to_hidden.bias']
-    inputs = torch.cat([torch.full((rows, 1), start, dtype=torch.long,
-                                   device=targets.device), targets[:, :-1]], 1)
-    hsz = h.shape[1]
-    logps, atts = [], []
-    for t in range(length):
-        q = h @ w['attend.query_to_hidden.weight'].t() + w['attend.query_to_hidden.bias']
-        u = torch.tanh(q[:, None] + keys)
-        s = (u @ w['attend.output.0.weight'].t()).squeeze(-1) + w['attend.output.0.bias']
-        a = torch.softmax(s, dim=1)
-        ctx = (a[..., None] * feats).sum(dim=1)
-        gate = torch.sigmoid(h @ w['feature_gate.0.weight'].t() + w['feature_gate.0.bias'])
-        x = torch.cat([w['embedding.weight'][inputs[:, t]], ctx * gate], dim=1)
-        gates = (x @ w['lstm.weight_ih'].t() + w['lstm.bias_ih'] +
-                 h @ w['lstm.weight_hh'].t() + w['lstm.bias_hh'])
-        i, f, gg, o = gates.split(hsz, dim=1)
-        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-        h = torch.sigmoid(o) * torch.tanh(c)
-        hd = h if mask is None else h * mask[:, t].double() / (1 - p)
-        logps.append(F.log_softmax(hd @ w['output.1.weight'].t() + w['output.1.bias'], -1))
-        atts.append(a)
-    lp = torch.stack(logps, 1)
-    total = F.nll_loss(lp.reshape(-1, lp.shape[-1]), targets.reshape(-1),
-                       ignore_index=pad, reduction='sum')
-    count = int((targets != pad).sum())
-    regsum = ((1 - torch.stack(atts, 1).sum(dim=1))**2).sum()
-    (total / count + reg_weight * regsum / (rows * k)).backward()
-    return (float(total), count, float(regsum.detach()),
-            {n: t.grad for n, t in w.items()})
 
 
 def train_ctx(dec, dev):
@@ -207,9 +166,8 @@ def test_gradients_match_autograd_float64(dev, case, p, reg):
     seed = 0x0123_4567_89ab_cdef
     loss, grads = run_step(ctx, params, feats, targets, dev, p, seed, reg)
     mask = lms.decoder_dropout_mask(seed, rows, length, hsz, p) if p else None
-    want = torch_loss({n: t.to(dev) for n, t in zip(decoders.TRAIN_PARAMS, params)},
-                      feats.to(dev), targets.to(dev), v - 4, v - 2,
-                      None if mask is None else mask.to(dev), p, reg)
+    want = trainref.decoder_loss(dict(zip(decoders.TRAIN_PARAMS, params)), feats, targets,
+                                 v - 4, v - 2, mask, p, reg, device=dev)
     check(loss, grads, *want, tag=f'{case} p={p} reg={reg}')
     if not p:  # eval-mode terms are the same forward
         nll = ctx.decoder_nll([t.to(dev) for t in params], feats, targets).cpu()
@@ -227,8 +185,8 @@ def test_pad_inputs_and_all_pad_rows(dev):
     assert (targets[:, :-1] == v - 2).any()  # pad is an input somewhere
     ctx = train_ctx(dec, dev)
     loss, grads = run_step(ctx, params, feats, targets, dev)
-    want = torch_loss({n: t.to(dev) for n, t in zip(decoders.TRAIN_PARAMS, params)},
-                      feats.to(dev), targets.to(dev), v - 4, v - 2)
+    want = trainref.decoder_loss(dict(zip(decoders.TRAIN_PARAMS, params)), feats, targets,
+                                 v - 4, v - 2, device=dev)
     check(loss, grads, *want, tag='pad rows')
     emb_grad = grads[decoders.TRAIN_PARAMS.index('embedding.weight')]
     assert emb_grad[v - 2].abs().max() > 0  # no padding_idx: the pad row learns

@@ -14,8 +14,8 @@ import json
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+import trainref
 from conftest import GOLDEN_DIR
 from milan_amd import decoders, encoders, hip, lang, lms, synthetic
 from oracle import milan_oracle as O
@@ -82,40 +82,6 @@ def random_batch(v, rows, length, seed):
     return inputs, targets
 
 
-def torch_loss(sd, inputs, targets, pad, layers, masks=None, p=0.):
-    """float64 autograd restatement: Embedding(padding_idx) -> LSTM (dropout
-    on the output of every layer but the last, explicit masks) -> Linear ->
-    log_softmax -> sum of NLL over non-pad targets.  Returns (sum, count,
-    grads)."""
-    w = {k: t.double().clone().requires_grad_(True) for k, t in sd.items()}
-    x = F.embedding(inputs, w['embedding.weight'], padding_idx=pad)
-    rows, length = inputs.shape
-    for l in range(layers):
-        h4 = w[f'lstm.weight_hh_l{l}'].shape[0]
-        hsz = h4 // 4
-        pre = x @ w[f'lstm.weight_ih_l{l}'].t() + w[f'lstm.bias_ih_l{l}'] + \
-            w[f'lstm.bias_hh_l{l}']
-        h = x.new_zeros(rows, hsz)
-        c = x.new_zeros(rows, hsz)
-        outs = []
-        for t in range(length):
-            gates = pre[:, t] + h @ w[f'lstm.weight_hh_l{l}'].t()
-            i, f, gg, o = gates.split(hsz, dim=1)
-            c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
-            h = torch.sigmoid(o) * torch.tanh(c)
-            outs.append(h)
-        x = torch.stack(outs, 1)
-        if masks is not None and l < layers - 1:
-            x = x * masks[l].double() / (1 - p)
-    logits = x @ w['output.0.weight'].t() + w['output.0.bias']
-    lp = F.log_softmax(logits, -1)
-    total = F.nll_loss(lp.reshape(-1, lp.shape[-1]), targets.reshape(-1),
-                       ignore_index=pad, reduction='sum')
-    count = int((targets != pad).sum())
-    (total / count).backward()
-    return float(total), count, {k: t.grad for k, t in w.items()}
-
-
 def train_ctx(sd, v, dev):
     dims = hip.make_dims({f'lm.{k}': t for k, t in sd.items()}, v - 4)
     return hip.Context(dims, {}, dev, finalize=False)
@@ -158,7 +124,7 @@ def test_gradients_match_autograd_float64(dev, v, e, h, layers, rows, length):
     inputs, targets = random_batch(v, rows, length, seed=rows * length)
     ctx = train_ctx(sd, v, dev)
     loss, grads = run_step(ctx, sd, inputs, targets, dev)
-    check_grads(sd, loss, grads, *torch_loss(sd, inputs, targets, v - 2, layers))
+    check_grads(sd, loss, grads, *trainref.lm_loss(sd, inputs, targets, v - 2, layers))
     # eval-mode loss is the same forward
     nll = ctx.lm_nll([t.to(dev) for t in sd.values()], inputs, targets).cpu()
     assert torch.equal(nll, loss)
@@ -175,7 +141,7 @@ def test_dropout_gradients_match_with_host_mask(dev, v, e, h, layers, p):
     loss, grads = run_step(ctx, sd, inputs, targets, dev, p, seed)
     masks = [lms.dropout_mask(seed, l, 7, 10, h, p) for l in range(layers - 1)]
     check_grads(sd, loss, grads,
-                *torch_loss(sd, inputs, targets, v - 2, layers, masks, p))
+                *trainref.lm_loss(sd, inputs, targets, v - 2, layers, masks, p))
     ctx.close()
 
 

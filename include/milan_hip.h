@@ -670,6 +670,96 @@ int milan_decoder_backward(milan_ctx* ctx, const float* const* params,
                            float* dfeatures, void* workspace,
                            size_t workspace_bytes, milan_stream stream);
 
+/* ---- CLIP reranker (src/milan/rerankers.py, DecoderWithCLIP) ------------------
+ * A context of its own: the dims of a ViT CLIP and one arena holding its weights
+ * in the state-dict layout of OpenAI's `clip` (visual.conv1.weight, ...,
+ * transformer.resblocks.N.*, text_projection), row-major fp32 as torch stores
+ * them.  milan_clip_set_weight records caller-owned DEVICE pointers by name;
+ * milan_clip_finalize_weights checks that every tensor the dims need is there
+ * with the right element count, copies them into the arena and synchronises
+ * (the only call here that does).  Unknown names are ignored.
+ *
+ * Precision: exact fp32 MFMA, whatever any milan_ctx's precision is.
+ * Deterministic: fixed reduction orders, no float atomics.
+ * Attention runs one workgroup per (sequence, head) with Q, K, V of the head in
+ * LDS: 4 * (3 * tokens * (head + 1) + 4 * tokens) bytes must fit 64 KiB, for
+ * tokens = (resolution / patch)^2 + 1 and tokens = context_length;
+ * milan_clip_create refuses other dims with MILAN_ERR_SHAPE and says so. */
+typedef struct milan_clip_ctx milan_clip_ctx;
+typedef struct milan_clip_dims {
+  int32_t resolution;     /* input pixels per side (224)          */
+  int32_t patch;          /* conv1 kernel = stride (32)           */
+  int32_t vision_width;   /* 768 */
+  int32_t vision_layers;  /* 12; at most 64 can be mask layers    */
+  int32_t vision_heads;   /* 12  */
+  int32_t embed_dim;      /* 512 */
+  int32_t context_length; /* 77  */
+  int32_t vocab_size;     /* 49408 */
+  int32_t text_width;     /* 512 */
+  int32_t text_layers;    /* 12  */
+  int32_t text_heads;     /* 8   */
+} milan_clip_dims;
+
+int milan_clip_create(milan_clip_ctx** out, int device,
+                      const milan_clip_dims* dims);
+void milan_clip_destroy(milan_clip_ctx* ctx);
+int milan_clip_set_weight(milan_clip_ctx* ctx, const char* name,
+                          const float* data, const int64_t* shape, int ndim);
+int milan_clip_finalize_weights(milan_clip_ctx* ctx, milan_stream stream);
+
+/* Image embeddings (CLIPWithMasks.forward, image side).
+ *   images: (n, 3, resolution, resolution) fp32 DEVICE.  `resolution` must be the
+ *     model's (MILAN_ERR_SHAPE otherwise: the reference's default path fails
+ *     there too, it never uses its resized tensor).
+ *   renorm_mul_add: HOST float[6] = mul[3], add[3]: every pixel of channel c
+ *     becomes x * mul[c] + add[c] before the patch embedding (the reference's
+ *     Renormalizer); NULL: no renormalisation.
+ *   masks: (n, 1, resolution, resolution) fp32 DEVICE or NULL.  They are resized
+ *     to the patch grid (bilinear, align_corners = false, no antialiasing); in
+ *     every layer l with bit l of mask_layers set, after the softmax, the CLS
+ *     query's weights on the patch keys are multiplied by them, the same for
+ *     every head; the row is not renormalised.
+ *   both = 0: out (n, embed_dim) <- L2-normalised embeddings, masked if masks.
+ *   both = 1 (needs masks): out (2, n, embed_dim) <- [0] masked, [1] unmasked;
+ *     the 2 n sequences go through every layer as one batch.
+ * Does not synchronise. */
+size_t milan_clip_image_workspace_bytes(const milan_clip_ctx* ctx, int n,
+                                        int both);
+int milan_clip_encode_images(milan_clip_ctx* ctx, const float* images, int n,
+                             int resolution, const float* masks,
+                             uint64_t mask_layers, int both,
+                             const float* renorm_mul_add, float* out,
+                             void* workspace, size_t workspace_bytes,
+                             milan_stream stream);
+
+/* Text embeddings (encode_text + L2 normalisation).
+ *   tokens: (rows, context_length) int64 DEVICE.  The embedding of a row is read
+ *     at the first position of its largest id (the end-of-text token).
+ *   positions: the tower runs over the first `positions` <= context_length
+ *     positions only.  It is causal, so any positions > every row's
+ *     end-of-text position gives what context_length gives, up to the rounding
+ *     of GEMM tiles; the caller passes max(eot) + 1.  (A row whose end-of-text
+ *     lies beyond is read at positions - 1.)
+ *   out: (rows, embed_dim) fp32 DEVICE.  Does not synchronise. */
+size_t milan_clip_text_workspace_bytes(const milan_clip_ctx* ctx, int rows,
+                                       int positions);
+int milan_clip_encode_texts(milan_clip_ctx* ctx, const int64_t* tokens,
+                            int rows, int positions, float* out,
+                            void* workspace, size_t workspace_bytes,
+                            milan_stream stream);
+
+/* Rerank scores (CLIPWithMasksReranker.forward before the sort):
+ *   out[c] = (1 - lam) * sum_i <masked[n][i], texts[c]>
+ *            +     lam * sum_i <unmasked[n][i], texts[c]>,   i < k in order,
+ * for text row c of neuron n = neuron_of[c] (int32 DEVICE, `rows` entries), or
+ * n = c / candidates when neuron_of is NULL.  masked / unmasked: (neurons, k,
+ * embed) fp32 DEVICE, texts (rows, embed), out (rows).  Does not synchronise. */
+int milan_clip_rerank_scores(const float* masked, const float* unmasked,
+                             const float* texts, const int32_t* neuron_of,
+                             int neurons, int k, int rows, int candidates,
+                             int embed, float lam, float* out,
+                             milan_stream stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

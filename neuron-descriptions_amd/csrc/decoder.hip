@@ -2058,7 +2058,7 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
   MILAN_REQUIRE(!forced || predictions, MILAN_ERR_ARG,
                 "teacher forcing needs the predictions output");
   MILAN_REQUIRE(beam >= 1 && beam <= V, MILAN_ERR_ARG,
-                "beam_size %d must be in 1..vocab_size", beam);
+                "beam_size=%d must be in 1..vocab_size (%d)", beam, c->d.vocab_size);
   MILAN_REQUIRE(greedy || (beam_tokens && beam_scores), MILAN_ERR_ARG,
                 "beam search needs beam_tokens and beam_scores outputs");
   MILAN_REQUIRE(tokens && scores, MILAN_ERR_ARG, "tokens/scores outputs required");
@@ -2122,7 +2122,9 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
   // ---- beam search (allennlp 2.10 semantics, fixed `length` steps) ----------
   const size_t merge_lds = sizeof(float) * ((size_t)beam * beam + 2 * beam + 16 + 528);
   MILAN_REQUIRE(merge_lds <= 64 * 1024, MILAN_ERR_ARG,
-                "beam_size %d too large for the merge kernel", beam);
+                "beam_size=%d too large for the merge kernel: beam^2 + 2 beam + 544 floats must "
+                "fit 64 KiB of LDS (beam_size <= 125); pass a smaller beam_size=",
+                beam);
   int beam_prev = 1, rows = n, lpcur = 0;
   std::optional<StageScope> search_scope;
   search_scope.emplace(MILAN_STAGE_DEC_SEARCH, s);

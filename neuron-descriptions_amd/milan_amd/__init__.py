@@ -8,13 +8,17 @@
 from milan_amd.decoders import (STRATEGIES, STRATEGY_BEAM, STRATEGY_GREEDY,
                                 STRATEGY_RERANK, STRATEGY_SAMPLE, Decoder,
                                 DecoderOutput, DecoderState, DecoderStep,
-                                decoder)
+                                DecoderWithCLIP, decoder)
 from milan_amd.encoders import Encoder, PyramidConvEncoder, encoder
 from milan_amd.lms import LanguageModel
 from milan_amd.loaders import pretrained, pretrained_sharded
+from milan_amd.rerankers import (CLIPWithMasks, CLIPWithMasksReranker,
+                                 RerankerOutput, reranker)
 
 __all__ = [
-    'Decoder', 'DecoderOutput', 'DecoderState', 'DecoderStep', 'Encoder',
+    'Decoder', 'DecoderOutput', 'DecoderState', 'DecoderStep',
+    'DecoderWithCLIP', 'CLIPWithMasks', 'CLIPWithMasksReranker',
+    'RerankerOutput', 'reranker', 'Encoder',
     'PyramidConvEncoder', 'LanguageModel', 'decoder', 'encoder', 'pretrained',
     'pretrained_sharded',
     'STRATEGIES', 'STRATEGY_BEAM', 'STRATEGY_GREEDY', 'STRATEGY_RERANK',

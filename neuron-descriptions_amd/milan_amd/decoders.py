@@ -31,7 +31,9 @@ What differs by design:
     own tensors require grad, as the reference's modules do;
   * out of scope: training-mode greedy / sample /
     beam decoding (raises NotImplementedError), `rouge` / `bert_score` (need
-    rouge / bert_score), `DecoderWithCLIP`.
+    rouge / bert_score);
+  * `DecoderWithCLIP` reranks the beam with CLIP (milan_amd.rerankers: both
+    towers in HIP).
 """
 import os
 import weakref
@@ -43,8 +45,8 @@ from torch import nn, optim
 from torch.autograd.function import once_differentiable
 from torch.utils import data
 
-from milan_amd import (encoders, hip, lang, lms, metrics, params, serialize,
-                       training)
+from milan_amd import (encoders, hip, lang, lms, metrics, params, rerankers,
+                       serialize, training)
 
 Strategy = Union[torch.Tensor, str]
 
@@ -985,6 +987,11 @@ class Decoder(nn.Module):
                     strict: bool = False,
                     load_state_dict: bool = True) -> 'Decoder':
         payload = dict(payload)
+        if (not issubclass(cls, DecoderWithCLIP)
+                and 'reranker_kwargs' in serialize.props(payload)):
+            # a checkpoint of a DecoderWithCLIP (the reference's included)
+            return DecoderWithCLIP.deserialize(payload, strict=strict,
+                                               load_state_dict=load_state_dict)
         state_dict = payload.pop('state_dict', None)
         p = dict(serialize.props(payload))
         children = payload.get('children') or {}
@@ -1018,6 +1025,127 @@ class Decoder(nn.Module):
         return cls.deserialize(serialize.load_payload(file, **kwargs))
 
 
+class DecoderWithCLIP(Decoder):
+    """Decoder that uses CLIP to rerank the final beam (reference
+    decoders.py:1115-1211).  The CLIP towers run in HIP on the decoder's GPU,
+    in exact fp32 whatever `precision` says (milan_amd.rerankers)."""
+
+    def __init__(self,
+                 *args: Any,
+                 reranker_kwargs: Optional[Mapping[str, Any]] = None,
+                 **kwargs: Any):
+        kwargs.setdefault('strategy', STRATEGY_BEAM)
+        kwargs.setdefault('beam_size', 1000)
+        kwargs.setdefault('temperature', .5)
+        super().__init__(*args, **kwargs)
+        self.reranker_kwargs = dict(reranker_kwargs) if reranker_kwargs else {}
+        self.reranker_kwargs.setdefault('name', 'ViT-B/32')
+        self.reranker_kwargs.setdefault('jit', False)
+        self.reranker_kwargs.setdefault('device', 'cpu')
+        self.reranker = rerankers.reranker(**self.reranker_kwargs)
+
+    def forward(  # type: ignore[override]
+        self,
+        images_or_features: torch.Tensor,
+        masks: Optional[torch.Tensor] = None,
+        lam: Optional[float] = None,
+        **kwargs: Any,
+    ) -> DecoderOutput:
+        """Beam-decode, then rerank the beam with CLIP.  `images_or_features`
+        must be the images (CLIP needs them intact) and `masks` must be given.
+        captions / scores / tokens are those of the top-ranked beam; the other
+        fields are the beam search's."""
+        if masks is None:
+            raise ValueError('must specify masks in DecoderWithCLIP')
+        if 'strategy' in kwargs:
+            raise ValueError('cannot set "strategy" in DecoderWithCLIP')
+        images = images_or_features
+        outputs = super().forward(images, masks=masks, strategy=STRATEGY_BEAM,
+                                  **kwargs)
+        beam_captions, beam_scores, beam_tokens = (outputs.beam_captions,
+                                                   outputs.beam_scores,
+                                                   outputs.beam_tokens)
+        assert beam_captions is not None and beam_scores is not None
+        assert beam_tokens is not None
+        clip_images, clip_masks = images, masks
+        if clip_images.dim() == 4:  # (B, 3, H, W): one exemplar per sample
+            clip_images, clip_masks = images.unsqueeze(1), masks.unsqueeze(1)
+        # (uint8 images stand for x * float32(1 / 255), the floats the reference's
+        # dataset hands to both the encoder and CLIP; the reranker converts them chunk
+        # by chunk)
+        device = self.device
+        clip_images, clip_masks = clip_images.to(device), clip_masks.to(device)
+        texts = [list(captions) for captions in beam_captions]
+        rerankeds = self.reranker(clip_images, clip_masks, texts, lam=lam)
+        captions = tuple(reranked[0] for reranked in rerankeds.texts)
+        best = torch.tensor([order[0] for order in rerankeds.orders],
+                            device=beam_scores.device)
+        rows = torch.arange(len(best), device=beam_scores.device)
+        return DecoderOutput(captions, beam_scores[rows, best],
+                             beam_tokens[rows, best], *outputs[3:])
+
+    def properties(self) -> Mapping[str, Any]:
+        # (the CLIP tensors travel in the state dict and the tokenizer is code:
+        # neither is a property)
+        kwargs = {
+            key: value for key, value in self.reranker_kwargs.items()
+            if key not in ('weights', 'tokenize')
+        }
+        # heads that `clip` would infer itself (width // 64) are not written, so that the
+        # reference can load the checkpoint (its clip.load rejects unknown keywords)
+        dims = self.reranker.clip_with_masks.dims
+        for side in ('vision', 'text'):
+            if kwargs.get(f'{side}_heads') == dims[f'{side}_width'] // 64:
+                del kwargs[f'{side}_heads']
+        return {**super().properties(), 'reranker_kwargs': kwargs}
+
+    def serialize(self, state_dict: bool = True) -> Dict[str, Any]:
+        """As Decoder.serialize; the state dict also holds CLIP's tensors under
+        the names a reference DecoderWithCLIP gives them."""
+        out = super().serialize(state_dict=state_dict)
+        if state_dict:
+            out['state_dict'].update(rerankers.to_reference_keys(
+                self.reranker.clip_with_masks.weights))
+        return out
+
+    @classmethod
+    def deserialize(cls,
+                    payload: Mapping[str, Any],
+                    strict: bool = False,
+                    load_state_dict: bool = True,
+                    reranker_kwargs: Optional[Mapping[str, Any]] = None
+                    ) -> 'DecoderWithCLIP':
+        """`reranker_kwargs` (e.g. `weights=`, `tokenize=`) override the
+        serialized ones.  CLIP's tensors are taken from the payload's state
+        dict when it has them (a checkpoint of a DecoderWithCLIP, the
+        reference's included)."""
+        payload = dict(payload)
+        props = dict(serialize.props(payload))
+        kwargs = dict(props.get('reranker_kwargs') or {})
+        kwargs.update(reranker_kwargs or {})
+        state = payload.get('state_dict')
+        if state is not None:
+            clip_state = rerankers.from_reference_keys(state)
+            if clip_state and 'weights' not in kwargs:
+                kwargs['weights'] = clip_state
+            payload['state_dict'] = type(state)(
+                (key, value) for key, value in state.items()
+                if not key.startswith(rerankers.REFERENCE_PREFIX))
+        props['reranker_kwargs'] = kwargs
+        payload['properties'] = props
+        return super().deserialize(payload, strict=strict,
+                                   load_state_dict=load_state_dict)
+
+    @classmethod
+    def from_decoder(cls,
+                     decoder: Decoder,
+                     reranker_kwargs: Optional[Mapping[str, Any]] = None
+                     ) -> 'DecoderWithCLIP':
+        """Convert a base Decoder to a DecoderWithCLIP."""
+        return cls.deserialize(decoder.serialize(),
+                               reranker_kwargs=reranker_kwargs)
+
+
 def decoder(dataset: data.Dataset,
             encoder: encoders.Encoder,
             rerank_with_clip: bool = False,
@@ -1030,10 +1158,8 @@ def decoder(dataset: data.Dataset,
     default to True; `tokenize` must be given, as for `lms.lm`) and **kwargs go
     to the constructor.  The parameters are initialised as the reference's
     torch modules initialise theirs, with the same draws from torch's global
-    generator.  `rerank_with_clip=True` (DecoderWithCLIP) is not built."""
-    if rerank_with_clip:
-        raise NotImplementedError('DecoderWithCLIP (CLIP reranking) is not '
-                                  'part of this build')
+    generator.  `rerank_with_clip=True` gives a DecoderWithCLIP; its
+    `reranker_kwargs` (`weights=`, `tokenize=`) go in **kwargs."""
     indexer_kwargs = dict(indexer_kwargs or {})
     annotations = [
         lang.join(dataset[index][annotation_index])
@@ -1042,6 +1168,14 @@ def decoder(dataset: data.Dataset,
     for key in ('start', 'stop', 'pad', 'unk'):
         indexer_kwargs.setdefault(key, True)
     indexer = lang.indexer(annotations, **indexer_kwargs)
-    model = Decoder(indexer, encoder, **kwargs)
+    if rerank_with_clip:
+        try:
+            model: Decoder = DecoderWithCLIP(indexer, encoder, **kwargs)
+        except ImportError as error:
+            # what this factory raised before the reranker was built, and still does
+            # when neither the `clip` package nor reranker_kwargs['weights'] is there
+            raise NotImplementedError(str(error)) from error
+    else:
+        model = Decoder(indexer, encoder, **kwargs)
     model.reset_parameters()
     return model

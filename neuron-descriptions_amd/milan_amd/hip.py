@@ -78,6 +78,14 @@ class Dims(ctypes.Structure):
     ]
 
 
+class ClipDims(ctypes.Structure):
+    """struct milan_clip_dims."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'resolution', 'patch', 'vision_width', 'vision_layers', 'vision_heads',
+        'embed_dim', 'context_length', 'vocab_size', 'text_width',
+        'text_layers', 'text_heads')]
+
+
 ABI_VERSION = 11  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
@@ -183,6 +191,21 @@ SIGNATURES = {
     'milan_decoder_backward':
         (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, ctypes.c_uint64, _P, _P,
               _P, _P, _SZ, _P]),
+    'milan_clip_create': (_I, [ctypes.POINTER(_P), _I,
+                               ctypes.POINTER(ClipDims)]),
+    'milan_clip_destroy': (None, [_P]),
+    'milan_clip_set_weight':
+        (_I, [_P, ctypes.c_char_p, _P,
+              ctypes.POINTER(ctypes.c_int64), _I]),
+    'milan_clip_finalize_weights': (_I, [_P, _P]),
+    'milan_clip_image_workspace_bytes': (_SZ, [_P, _I, _I]),
+    'milan_clip_encode_images':
+        (_I, [_P, _P, _I, _I, _P, ctypes.c_uint64, _I,
+              ctypes.POINTER(_F), _P, _P, _SZ, _P]),
+    'milan_clip_text_workspace_bytes': (_SZ, [_P, _I, _I]),
+    'milan_clip_encode_texts': (_I, [_P, _P, _I, _I, _P, _P, _SZ, _P]),
+    'milan_clip_rerank_scores':
+        (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
     'milan_conv2d_nhwc':
         (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I,
               _P]),
@@ -1135,6 +1158,124 @@ class Context:
             return out
 
         return self._guarded('describe', run, check)
+
+
+class ClipContext:
+    """Owns one `milan_clip_ctx`: the weights of a ViT CLIP on one GPU and a
+    workspace.  Every call computes in exact fp32 on torch's current stream and
+    does not synchronise."""
+
+    def __init__(self, dims: ClipDims, state_dict: Dict[str, torch.Tensor],
+                 device: torch.device):
+        self.lib = load_library()
+        self.device = require_device(device)
+        self.dims = dims
+        self._h = _P()
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_clip_create(ctypes.byref(self._h),
+                                              self.device.index,
+                                              ctypes.byref(dims)))
+            keep = []
+            for name, tensor in state_dict.items():
+                if not tensor.dtype.is_floating_point:
+                    continue
+                t = _dev(tensor.detach(), self.device, torch.float32)
+                keep.append(t)
+                shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
+                _check(self.lib.milan_clip_set_weight(self._h, name.encode(),
+                                                      t.data_ptr(), shape,
+                                                      t.dim()))
+            _check(self.lib.milan_clip_finalize_weights(self._h,
+                                                        _stream(self.device)))
+            del keep
+        self._ws: Optional[torch.Tensor] = None
+
+    def close(self) -> None:
+        if getattr(self, '_h', None):
+            self.lib.milan_clip_destroy(self._h)
+            self._h = None
+        self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _workspace(self, need: int) -> torch.Tensor:
+        if need == 0:
+            _check(ERR_ARG)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def encode_images(self, images: torch.Tensor,
+                      masks: Optional[torch.Tensor] = None,
+                      mask_layers: int = 0, both: bool = False,
+                      mul_add: Optional[Sequence[float]] = None) -> torch.Tensor:
+        """(n, 3, R, R) [+ (n, 1, R, R) masks] -> L2-normalised (n, embed), or
+        (2, n, embed) = (masked, unmasked) when `both`."""
+        images = _dev(images, self.device, torch.float32)
+        n, res = images.shape[0], images.shape[-1]
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != res:
+            raise ValueError(f'images must be (n, 3, R, R), got {tuple(images.shape)}')
+        if masks is not None:
+            masks = _dev(masks, self.device, torch.float32)
+            if masks.numel() != n * res * res:
+                raise ValueError(f'masks {tuple(masks.shape)} do not match '
+                                 f'images {tuple(images.shape)}')
+        e = self.dims.embed_dim
+        out = torch.empty((2, n, e) if both else (n, e), device=self.device)
+        if n == 0:
+            return out
+        ma = None if mul_add is None else (_F * 6)(*mul_add)
+        with torch.cuda.device(self.device):
+            ws = self._workspace(int(self.lib.milan_clip_image_workspace_bytes(
+                self._h, n, int(both))))
+            _check(self.lib.milan_clip_encode_images(
+                self._h, images.data_ptr(), n, res, _ptr(masks), mask_layers,
+                int(both), ma, out.data_ptr(), ws.data_ptr(), ws.numel(),
+                _stream(self.device)))
+        return out
+
+    def encode_texts(self, tokens: torch.Tensor, positions: int) -> torch.Tensor:
+        """(rows, context) token ids -> L2-normalised (rows, embed), the towers
+        run over the first `positions` positions."""
+        tokens = _dev(tokens, self.device, torch.long)
+        if tokens.dim() != 2 or tokens.shape[1] != self.dims.context_length:
+            raise ValueError(f'tokens must be (rows, {self.dims.context_length}), '
+                             f'got {tuple(tokens.shape)}')
+        rows = tokens.shape[0]
+        out = torch.empty((rows, self.dims.embed_dim), device=self.device)
+        if rows == 0:
+            return out
+        with torch.cuda.device(self.device):
+            ws = self._workspace(int(self.lib.milan_clip_text_workspace_bytes(
+                self._h, rows, positions)))
+            _check(self.lib.milan_clip_encode_texts(
+                self._h, tokens.data_ptr(), rows, positions, out.data_ptr(),
+                ws.data_ptr(), ws.numel(), _stream(self.device)))
+        return out
+
+    def rerank_scores(self, masked: torch.Tensor, unmasked: torch.Tensor,
+                      texts: torch.Tensor, neuron_of: Optional[torch.Tensor],
+                      candidates: int, lam: float) -> torch.Tensor:
+        """masked / unmasked (neurons, k, embed), texts (rows, embed) -> (rows,)."""
+        neurons, k, e = masked.shape
+        rows = texts.shape[0]
+        masked = _dev(masked, self.device, torch.float32)
+        unmasked = _dev(unmasked, self.device, torch.float32)
+        texts = _dev(texts, self.device, torch.float32)
+        if neuron_of is not None:
+            neuron_of = _dev(neuron_of, self.device, torch.int32)
+        out = torch.empty(rows, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_clip_rerank_scores(
+                masked.data_ptr(), unmasked.data_ptr(), texts.data_ptr(),
+                _ptr(neuron_of), neurons, k, rows, candidates, e, float(lam),
+                out.data_ptr(), _stream(self.device)))
+        return out
 
 
 def profile_enable(enable: bool) -> None:

@@ -760,6 +760,81 @@ int milan_clip_rerank_scores(const float* masked, const float* unmasked,
                              int embed, float lam, float* out,
                              milan_stream stream);
 
+/* ---- BERTScore (src/utils/metrics.py:94-150, Decoder.bert_score) ----------------
+ * A context of its own: the dims of a BERT-family (post-LN) encoder and one arena
+ * holding its weights under their HuggingFace state-dict names without the
+ * model prefix (embeddings.word_embeddings.weight, ...,
+ * encoder.layer.N.attention.self.query.weight, ...), row-major fp32 as torch
+ * stores them, nothing packed.  set_weight / finalize_weights behave as their
+ * milan_clip_* namesakes; only layers 0 .. layers - 1 are asked for.  No pooler.
+ *
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them
+ * (dlsym / hasattr(lib, "milan_bert_create")).
+ *
+ * Precision: exact fp32 MFMA.  Deterministic: fixed reduction orders, no float
+ * atomics, and the GEMMs' split count depends on K alone, so the embeddings of
+ * a sentence do not depend on which other sentences share its call.
+ * Attention runs one workgroup per (sentence, head) with Q, K, V of the head in
+ * LDS: 4 * (3 * tokens * (head + 1) + 4 * tokens) bytes at tokens =
+ * MILAN_BERT_MAX_TOKENS must fit 64 KiB (head size <= 83); milan_bert_create
+ * refuses other dims with MILAN_ERR_SHAPE and names them. */
+#define MILAN_BERT_MAX_TOKENS 64 /* longest supported sentence, specials included */
+typedef struct milan_bert_ctx milan_bert_ctx;
+typedef struct milan_bert_dims {
+  int32_t vocab_size;      /* 50265 (roberta-large)                           */
+  int32_t width;           /* 1024 */
+  int32_t layers;          /* encoder layers TO RUN (17 of roberta-large's 24) */
+  int32_t heads;           /* 16   */
+  int32_t intermediate;    /* 4096 */
+  int32_t max_positions;   /* rows of the position table (514)                */
+  int32_t type_vocab;      /* rows of the token-type table; row 0 is used     */
+  int32_t position_offset; /* position id of a sentence's first token:
+                              pad_id + 1 for RoBERTa (2), 0 for BERT          */
+  float eps;               /* layer_norm_eps (1e-5 RoBERTa, 1e-12 BERT)       */
+} milan_bert_dims;
+
+int milan_bert_create(milan_bert_ctx** out, int device,
+                      const milan_bert_dims* dims);
+void milan_bert_destroy(milan_bert_ctx* ctx);
+int milan_bert_set_weight(milan_bert_ctx* ctx, const char* name,
+                          const float* data, const int64_t* shape, int ndim);
+int milan_bert_finalize_weights(milan_bert_ctx* ctx, milan_stream stream);
+
+/* Token embeddings of n ragged sentences: the last hidden state of the cut model.
+ *   ids: (total) int64 DEVICE, the sentences' token ids (specials included)
+ *     one after the other; offsets: (n + 1) int32 DEVICE, ascending, offsets[0]
+ *     = 0, offsets[n] = total: sentence s owns rows offsets[s] .. offsets[s + 1].
+ *   max_len: the longest sentence, computed by the caller on the host.  More
+ *     than MILAN_BERT_MAX_TOKENS, or than max_positions - position_offset, is
+ *     MILAN_ERR_SHAPE.  (The kernels clamp a length beyond max_len for memory
+ *     safety only.)
+ *   Position ids are position_offset + index in the sentence; token type 0.
+ *   Every GEMM runs over the `total` real rows; there is no padding.
+ *   normalize = 1: every row is divided by its L2 norm (what score_pairs takes).
+ *   out: (total, width) fp32 DEVICE.  Does not synchronise. */
+size_t milan_bert_encode_workspace_bytes(const milan_bert_ctx* ctx, int n,
+                                         int total);
+int milan_bert_encode(milan_bert_ctx* ctx, const int64_t* ids,
+                      const int32_t* offsets, int n, int total, int max_len,
+                      int normalize, float* out, void* workspace,
+                      size_t workspace_bytes, milan_stream stream);
+
+/* BERTScore's greedy matching for `pairs` (candidate, reference) pairs.
+ *   emb: (rows, width) L2-normalised token embeddings of n_sent sentences,
+ *     offsets (n_sent + 1) int32 as above (several encode calls may have filled
+ *     the table); weights: (rows) idf weight of every token, not normalised;
+ *     cand / ref: (pairs) int32 sentence numbers.  All DEVICE.
+ *   Per pair: sim = C R^T (float64 accumulation), p_i = max_j sim_ij and r_j =
+ *     max_i sim_ij over the other sentence's real tokens, weights normalised to
+ *     sum 1 per sentence, P = sum_i w_i p_i, R = sum_j v_j r_j in token order,
+ *     F = 2 P R / (P + R), NaN -> 0.  A sentence of at most 2 tokens ([cls, sep])
+ *     gives P = R = F = 0.
+ *   out: (pairs, 3) fp32 = P, R, F.  Does not synchronise. */
+int milan_bert_score_pairs(const float* emb, const int32_t* offsets,
+                           const float* weights, const int32_t* cand,
+                           const int32_t* ref, int pairs, int n_sent, int width,
+                           float* out, milan_stream stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

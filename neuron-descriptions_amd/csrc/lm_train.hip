@@ -167,11 +167,47 @@ size_t split_scratch_floats(int M, int N, int K) {
   return s > 1 ? (size_t)s * M * N : 0;
 }
 
+// Splits of K as a function of K alone (at least 256 of K per split, at most 8 splits): the
+// bits of an output row then depend on that row of A and on B, not on how many rows the
+// call has.
+static int plan_splits_rows(int K, int* kchunk) {
+  int s = 1;
+  while (s < 8 && K / (2 * s) >= 256) s *= 2;
+  int kc = (K + s - 1) / s;
+  kc = (kc + BK - 1) / BK * BK;
+  if (kc == 0) kc = BK;
+  *kchunk = kc;
+  return (K + kc - 1) / kc > 0 ? (K + kc - 1) / kc : 1;
+}
+
+size_t rows_scratch_floats(int M, int N, int K) {
+  int kc;
+  const int s = plan_splits_rows(K, &kc);
+  return s > 1 ? (size_t)s * M * N : 0;
+}
+
+static int gemm_planned(View a, int ta, View b, int tb, View c, View d, const float* bias1,
+                        const float* bias2, int M, int N, int K, bool by_rows, Scratch sc,
+                        hipStream_t s);
+
 int gemm(View a, int ta, View b, int tb, View c, View d, const float* bias1,
                 const float* bias2, int M, int N, int K, Scratch sc, hipStream_t s) {
+  return gemm_planned(a, ta, b, tb, c, d, bias1, bias2, M, N, K, false, sc, s);
+}
+
+int gemm_rows(View a, int ta, View b, int tb, View c, View d, const float* bias1,
+              const float* bias2, int M, int N, int K, Scratch sc, hipStream_t s) {
+  return gemm_planned(a, ta, b, tb, c, d, bias1, bias2, M, N, K, true, sc, s);
+}
+
+static int gemm_planned(View a, int ta, View b, int tb, View c, View d, const float* bias1,
+                        const float* bias2, int M, int N, int K, bool by_rows, Scratch sc,
+                        hipStream_t s) {
   if (M <= 0 || N <= 0) return 0;
   GemmArgs g{a, b, c, d, ta, tb, M, N, K, 0, nullptr, bias1, bias2};
-  const int splits = K > 0 ? plan_splits(M, N, K, &g.kchunk) : 1;
+  const int splits = K <= 0 ? 1
+                            : (by_rows ? plan_splits_rows(K, &g.kchunk)
+                                       : plan_splits(M, N, K, &g.kchunk));
   if (K <= 0) g.kchunk = BK;
   if (splits > 1) {
     MILAN_REQUIRE((size_t)splits * M * N <= sc.floats, MILAN_ERR_WORKSPACE,

@@ -48,6 +48,13 @@ int gemm(View a, int ta, View b, int tb, View c, View d, const float* bias1, con
 // scratch floats gemm() needs for an (M, N, K) problem
 size_t split_scratch_floats(int M, int N, int K);
 
+// The same GEMM with the split count a function of K alone, so that the bits of an output
+// row do not depend on M (the BERTScore tower: a sentence's embeddings must not depend on the
+// batch it is encoded in).  Scratch: rows_scratch_floats.
+int gemm_rows(View a, int ta, View b, int tb, View c, View d, const float* bias1,
+              const float* bias2, int M, int N, int K, Scratch sc, hipStream_t s);
+size_t rows_scratch_floats(int M, int N, int K);
+
 // out1[n] (= out2[n] when given) = sum over the R rows of X [R][N], in a fixed order;
 // needs colsum_chunks(R) * N scratch floats
 int colsum_chunks(int R);

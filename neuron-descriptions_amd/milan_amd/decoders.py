@@ -30,8 +30,9 @@ What differs by design:
     optimizer loop or torch `Encoder` trains through it.  The decoder's 19
     own tensors require grad, as the reference's modules do;
   * out of scope: training-mode greedy / sample /
-    beam decoding (raises NotImplementedError), `rouge` / `bert_score` (need
-    rouge / bert_score);
+    beam decoding (raises NotImplementedError), `rouge` (needs rouge);
+  * `bert_score` scores with `metrics.bert_score`: the encoder and the token
+    matching run in HIP (milan_amd.bertscore, DESIGN.md 4.15);
   * `DecoderWithCLIP` reranks the beam with CLIP (milan_amd.rerankers: both
     towers in HIP).
 """
@@ -740,6 +741,27 @@ class Decoder(nn.Module):
         return metrics.bleu(dataset,
                             predictions,
                             annotation_index=annotation_index)
+
+    def bert_score(self,
+                   dataset: data.Dataset,
+                   annotation_index: int = 4,
+                   bert_scorer_batch_size: int = 16,
+                   predictions: Optional[Sequence[str]] = None,
+                   device: Optional[Union[str, torch.device]] = None,
+                   bert_scorer: Optional[Any] = None,
+                   **kwargs: Any) -> Mapping[str, float]:
+        """Average BERTScore P/R/F ('p', 'r', 'f') of this model's captions on
+        `dataset` (reference :771-807): `predict(dataset, **kwargs)` unless
+        `predictions` are given, then `metrics.bert_score`.  `bert_scorer`: a
+        `milan_amd.bertscore.BERTScorer`; by default `bertscore.load()`."""
+        if predictions is None:
+            predictions = self.predict(dataset, **kwargs)
+        return metrics.bert_score(dataset,
+                                  predictions,
+                                  annotation_index=annotation_index,
+                                  batch_size=bert_scorer_batch_size,
+                                  device=device,
+                                  bert_scorer=bert_scorer)
 
     # -- training (reference :873-1070) ----------------------------------------------
     def reset_parameters(self) -> None:

@@ -86,6 +86,15 @@ class ClipDims(ctypes.Structure):
         'text_layers', 'text_heads')]
 
 
+class BertDims(ctypes.Structure):
+    """struct milan_bert_dims."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'vocab_size', 'width', 'layers', 'heads', 'intermediate',
+        'max_positions', 'type_vocab', 'position_offset')] + [('eps', ctypes.c_float)]
+
+
+BERT_MAX_TOKENS = 64  # MILAN_BERT_MAX_TOKENS
+
 ABI_VERSION = 11  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
@@ -206,6 +215,16 @@ SIGNATURES = {
     'milan_clip_encode_texts': (_I, [_P, _P, _I, _I, _P, _P, _SZ, _P]),
     'milan_clip_rerank_scores':
         (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
+    'milan_bert_create': (_I, [ctypes.POINTER(_P), _I,
+                               ctypes.POINTER(BertDims)]),
+    'milan_bert_destroy': (None, [_P]),
+    'milan_bert_set_weight':
+        (_I, [_P, ctypes.c_char_p, _P,
+              ctypes.POINTER(ctypes.c_int64), _I]),
+    'milan_bert_finalize_weights': (_I, [_P, _P]),
+    'milan_bert_encode_workspace_bytes': (_SZ, [_P, _I, _I]),
+    'milan_bert_encode': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    'milan_bert_score_pairs': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     'milan_conv2d_nhwc':
         (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I,
               _P]),
@@ -1275,6 +1294,108 @@ class ClipContext:
                 masked.data_ptr(), unmasked.data_ptr(), texts.data_ptr(),
                 _ptr(neuron_of), neurons, k, rows, candidates, e, float(lam),
                 out.data_ptr(), _stream(self.device)))
+        return out
+
+
+class BertContext:
+    """Owns one `milan_bert_ctx`: the weights of a BERT-family encoder on one
+    GPU and a workspace.  Every call computes in exact fp32 on torch's current
+    stream and does not synchronise."""
+
+    def __init__(self, dims: BertDims, state_dict: Dict[str, torch.Tensor],
+                 device: torch.device):
+        self.lib = load_library()
+        self.device = require_device(device)
+        self.dims = dims
+        self._h = _P()
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_bert_create(ctypes.byref(self._h),
+                                              self.device.index,
+                                              ctypes.byref(dims)))
+            keep = []
+            for name, tensor in state_dict.items():
+                if not tensor.dtype.is_floating_point:
+                    continue
+                t = _dev(tensor.detach(), self.device, torch.float32)
+                keep.append(t)
+                shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
+                _check(self.lib.milan_bert_set_weight(self._h, name.encode(),
+                                                      t.data_ptr(), shape,
+                                                      t.dim()))
+            _check(self.lib.milan_bert_finalize_weights(self._h,
+                                                        _stream(self.device)))
+            del keep
+        self._ws: Optional[torch.Tensor] = None
+
+    def close(self) -> None:
+        if getattr(self, '_h', None):
+            self.lib.milan_bert_destroy(self._h)
+            self._h = None
+        self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _workspace(self, need: int) -> torch.Tensor:
+        if need == 0:
+            _check(ERR_ARG)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def encode(self, ids: torch.Tensor, offsets: torch.Tensor, max_len: int,
+               normalize: bool = True,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ids (total,) int64 and offsets (n + 1,) int32 of n ragged sentences
+        (DEVICE tensors; `max_len` = the longest, known to the host) -> (total,
+        width) token embeddings, L2-normalised when `normalize`; written to
+        `out` when given."""
+        total, n = ids.numel(), offsets.numel() - 1
+        if (ids.dtype != torch.long or offsets.dtype != torch.int32 or
+                ids.device != self.device or offsets.device != self.device or
+                not ids.is_contiguous() or not offsets.is_contiguous()):
+            raise ValueError('ids must be int64 and offsets int32, contiguous, '
+                             f'on {self.device}')
+        if out is None:
+            out = torch.empty((total, self.dims.width), device=self.device)
+        if (out.shape != (total, self.dims.width) or out.dtype != torch.float32
+                or out.device != self.device or not out.is_contiguous()):
+            raise ValueError(f'out must be float32 ({total}, {self.dims.width})')
+        if n <= 0 or total == 0:
+            return out
+        with torch.cuda.device(self.device):
+            ws = self._workspace(int(self.lib.milan_bert_encode_workspace_bytes(
+                self._h, n, total)))
+            _check(self.lib.milan_bert_encode(
+                self._h, ids.data_ptr(), offsets.data_ptr(), n, total,
+                int(max_len), int(normalize), out.data_ptr(), ws.data_ptr(),
+                ws.numel(), _stream(self.device)))
+        return out
+
+    def score_pairs(self, emb: torch.Tensor, offsets: torch.Tensor,
+                    weights: torch.Tensor, cand: torch.Tensor,
+                    ref: torch.Tensor) -> torch.Tensor:
+        """emb (rows, width) normalised, offsets (n + 1,) int32, weights (rows,),
+        cand / ref (pairs,) int32 sentence numbers -> (pairs, 3) = P, R, F."""
+        emb = _dev(emb, self.device, torch.float32)
+        offsets = _dev(offsets, self.device, torch.int32)
+        weights = _dev(weights, self.device, torch.float32)
+        cand = _dev(cand, self.device, torch.int32)
+        ref = _dev(ref, self.device, torch.int32)
+        if (weights.numel() != emb.shape[0] or cand.numel() != ref.numel() or
+                emb.shape[1] != self.dims.width):
+            raise ValueError('score_pairs: emb / weights / cand / ref disagree')
+        pairs = cand.numel()
+        out = torch.empty((pairs, 3), device=self.device)
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_bert_score_pairs(
+                emb.data_ptr(), offsets.data_ptr(), weights.data_ptr(),
+                cand.data_ptr(), ref.data_ptr(), pairs, offsets.numel() - 1,
+                emb.shape[1], out.data_ptr(), _stream(self.device)))
         return out
 
 

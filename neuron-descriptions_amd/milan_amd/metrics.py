@@ -1,4 +1,4 @@
-"""Corpus BLEU (reference `src/utils/metrics.py:16-43`).
+"""Corpus BLEU and BERTScore (reference `src/utils/metrics.py:16-43, 94-150`).
 
 The reference scores with `sacrebleu.corpus_bleu` (sacrebleu 1.5.1, its
 defaults: 13a tokenizer, 'exp' smoothing, no lowercasing, 4-grams).  sacrebleu
@@ -6,12 +6,14 @@ is not part of this build, so `corpus_bleu` below restates that computation in
 pure Python.  It was written from knowledge of sacrebleu 1.5.1's algorithm, not
 read from its source, and there is no oracle for it here: it is pinned by
 hand-worked cases (tests/test_decoder_train_host.py) rather than checked
-against sacrebleu itself.  `rouge` and `bert_score` are not built.
+against sacrebleu itself.  `bert_score` keeps the reference's preprocessing and
+hands the scoring to `milan_amd.bertscore` (HIP).  `rouge` alone is not built.
 """
 import collections
 import math
 import re
-from typing import List, NamedTuple, Sequence
+import warnings
+from typing import Any, List, Mapping, NamedTuple, Optional, Sequence
 
 from torch.utils import data
 
@@ -137,3 +139,41 @@ def bleu(dataset: data.Dataset,
             annotations = [annotations]
         references.append([anno.lower().strip('. ') for anno in annotations])
     return corpus_bleu(predictions, list(zip(*references)))
+
+
+def bert_score(dataset: data.Dataset,
+               predictions: Sequence[str],
+               annotation_index: int = 4,
+               batch_size: int = 16,
+               device: Optional[Any] = None,
+               bert_scorer: Optional[Any] = None) -> Mapping[str, float]:
+    """Average BERTScore P/R/F of `predictions` against the annotations of
+    `dataset` (reference metrics.py:94-150), under the keys 'p', 'r', 'f'.
+    Predictions and annotations are lowercased and stripped of '. '; with an
+    idf scorer the idf is computed over all annotations, flattened.
+    `bert_scorer` defaults to `bertscore.load(device=device)`: roberta-large
+    cut to 17 layers, idf, rescaled with the baseline, read from
+    `MILAN_MODELS_DIR`."""
+    if bert_scorer is None:
+        from milan_amd import bertscore
+        bert_scorer = bertscore.load(idf=True, rescale_with_baseline=True,
+                                     device=device)
+
+    predictions = [pred.lower().strip('. ') for pred in predictions]
+
+    references = []
+    for index in range(len(predictions)):
+        annotations = dataset[index][annotation_index]
+        if isinstance(annotations, str):
+            annotations = [annotations]
+        references.append([anno.lower().strip('. ') for anno in annotations])
+
+    if bert_scorer.idf:
+        with warnings.catch_warnings():
+            warnings.filterwarnings('ignore', message=r'.*Overwriting.*')
+            bert_scorer.compute_idf([r for rs in references for r in rs])
+
+    prf = bert_scorer.score(predictions, references, batch_size=batch_size)
+    return {
+        key: scores.mean().item() for key, scores in zip(('p', 'r', 'f'), prf)
+    }

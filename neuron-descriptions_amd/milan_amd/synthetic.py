@@ -300,6 +300,33 @@ def exemplars(n_neurons: int,
     return images, masks.view(n_neurons, k, 1, size, size)
 
 
+def annotated_samples(n_neurons: int,
+                      words: Sequence[str],
+                      annotations: int = 3,
+                      k: int = 2,
+                      size: int = 64,
+                      seed: int = 1,
+                      longest: int = 8) -> list:
+    """A small annotated dataset in the sample layout of the reference's
+    AnnotatedTopImagesDataset: (layer, unit, images, masks, annotations) with
+    float images in [0, 1], float masks and `annotations` captions per neuron
+    drawn from `words` (some capitalised and ending in '.', as human
+    annotations do)."""
+    images, masks = exemplars(n_neurons, k=k, size=size, seed=seed, zero_every=0)
+    g = _gen(seed + 2)
+    samples = []
+    for n in range(n_neurons):
+        captions = []
+        for _ in range(annotations):
+            count = int(torch.randint(1, longest + 1, (1,), generator=g))
+            picks = torch.randint(0, len(words), (count,), generator=g).tolist()
+            caption = ' '.join(words[i] for i in picks)
+            captions.append(caption.capitalize() + '.' if len(captions) % 2 else caption)
+        samples.append(('layer', n, images[n].float() / 255., masks[n].float(),
+                        tuple(captions)))
+    return samples
+
+
 def describe(sd: Dict[str, torch.Tensor]) -> Sequence[str]:
     """Human-readable `name shape` lines (used by docs/tests)."""
     return [f'{k} {tuple(v.shape)}' for k, v in sd.items()]

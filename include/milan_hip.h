@@ -575,6 +575,50 @@ int milan_lm_train_step(milan_ctx* ctx, const float* const* params,
                         float* loss_sum_and_count, void* workspace,
                         size_t workspace_bytes, milan_stream stream);
 
+/* Forward and backward for autograd (LanguageModel.forward in training mode with
+ * trainable parameters): the forward of milan_lm_train_step with its log-probs
+ * returned instead of a loss, and a backward driven by arbitrary upstream
+ * gradients.  Parameter list, ctx, dims, dropout mask, precision and
+ * determinism as above; neither call synchronises.
+ *
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them
+ * (dlsym / hasattr(lib, "milan_lm_forward_train")).
+ *   milan_lm_grad_workspace_bytes: the workspace both calls need (the
+ *     train-step workspace plus the forward's unused loss terms); 0 on bad dims.
+ *   milan_lm_forward_train: logprobs_out (rows, L, vocab) fp32 DEVICE <-
+ *     log_softmax of every position (NULL: not written); picked_out (rows, L)
+ *     fp32 DEVICE <- logprobs[r, t, targets[r, t]] (NULL: not written).
+ *     targets: (rows, L) int64 DEVICE, given if and only if picked_out is; ids
+ *     in [0, vocab_size), the caller validates (clamped, not reported).  With
+ *     picked_out alone the (rows, L, vocab) log-probs are never written.  Pad
+ *     ids are ordinary inputs (their embedding row is whatever the parameter
+ *     holds) and ordinary targets.  The workspace keeps the activations for one
+ *     milan_lm_backward.
+ *   milan_lm_backward: consumes a workspace filled by milan_lm_forward_train
+ *     with the same params, inputs, dims, dropout and seed.  dlogprobs (rows, L,
+ *     vocab) and dpicked (rows, L) fp32 DEVICE are the upstream gradients (NULL:
+ *     zero; both NULL: MILAN_ERR_ARG); targets as in the forward, required with
+ *     dpicked.  Per position g_v = dlogprobs[v] + (v == target ? dpicked : 0)
+ *     and dlogit_v = g_v - exp(logit_v - lse) * sum_v g_v, the row sum in a
+ *     fixed order.  `grads` are OVERWRITTEN with the gradient of
+ *     sum(dlogprobs * logprobs) + sum(dpicked * picked) with respect to every
+ *     parameter; the embedding row of pad_index gets exactly zero.  The backward
+ *     overwrites activations in place: one forward supports exactly one
+ *     backward. */
+size_t milan_lm_grad_workspace_bytes(const milan_ctx* ctx, int rows, int L);
+int milan_lm_forward_train(milan_ctx* ctx, const float* const* params,
+                           int n_params, const int64_t* inputs, int rows, int L,
+                           float dropout, uint64_t seed, float* logprobs_out,
+                           float* picked_out, const int64_t* targets,
+                           void* workspace, size_t workspace_bytes,
+                           milan_stream stream);
+int milan_lm_backward(milan_ctx* ctx, const float* const* params,
+                      float* const* grads, int n_params, const int64_t* inputs,
+                      int rows, int L, float dropout, uint64_t seed,
+                      const float* dlogprobs, const float* dpicked,
+                      const int64_t* targets, void* workspace,
+                      size_t workspace_bytes, milan_stream stream);
+
 /* ---- Decoder training (src/milan/decoders.py:873-1070) -----------------------
  * Loss, forward and backward of the teacher-forced attention LSTM,
  * Decoder.forward(features, strategy=targets, mi=False) in training mode, with

@@ -371,6 +371,60 @@ __global__ __launch_bounds__(256) void dlogits_kernel(float* __restrict__ logits
     x[v] = ok ? (expf(x[v] - l) - (v == t ? 1.f : 0.f)) * inv : 0.f;
 }
 
+// ---- the autograd pair (milan_lm_forward_train / milan_lm_backward) ------------------------
+// out[n][v] = logits[n][v] - lse[n]
+__global__ void lm_logprobs_kernel(const float* __restrict__ logits,
+                                   const float* __restrict__ lse, float* __restrict__ out, int N,
+                                   int V) {
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i >= (long)N * V) return;
+  out[i] = logits[i] - lse[i / V];
+}
+
+// picked[n] = logits[n][tgt[n]] - lse[n]: the log-prob of one token per position, without
+// the [N][V] log-probs ever being written
+__global__ void lm_picked_kernel(const float* __restrict__ logits,
+                                 const int64_t* __restrict__ tgt, const float* __restrict__ lse,
+                                 float* __restrict__ picked, int N, int V) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  picked[n] = logits[(long)n * V + clamp_id(tgt[n], V)] - lse[n];
+}
+
+// Log-softmax backward from upstream gradients of the log-probs, G [N][V], and of the picked
+// log-probs, gp [N] (either null: zero), one workgroup per position:
+//   g_v = G[n][v] + (v == tgt[n] ? gp[n] : 0)
+//   logits[n][v] <- g_v - exp(logits[n][v] - lse[n]) * sum_v g_v
+// in place, where backward() expects dlogits.  The row sum has one order whatever V is:
+// thread i adds its elements v = i, i + 256, ... in increasing v, the 64 lanes of a wave by
+// xor butterfly, the 4 waves in order.
+__global__ __launch_bounds__(256) void lm_log_softmax_bwd_kernel(
+    const float* __restrict__ G, const float* __restrict__ gp, const int64_t* __restrict__ tgt,
+    float* __restrict__ logits, const float* __restrict__ lse, int V) {
+  __shared__ float red[4];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  float* x = logits + (long)n * V;
+  const float* g = G ? G + (long)n * V : nullptr;
+  const int t = gp ? clamp_id(tgt[n], V) : -1;
+  const float dp = gp ? gp[n] : 0.f;
+  float s = 0.f;
+  if (g) {
+    for (int v = tid; v < V; v += 256) s += v == t ? g[v] + dp : g[v];
+  } else if (t >= 0 && (t & 255) == tid) {
+    s = dp;
+  }
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((tid & 63) == 0) red[tid >> 6] = s;
+  __syncthreads();
+  const float sum = ((red[0] + red[1]) + red[2]) + red[3];
+  const float l = lse[n];
+  for (int v = tid; v < V; v += 256) {
+    float gv = g ? g[v] : 0.f;
+    if (v == t) gv += dp;
+    x[v] = gv - expf(x[v] - l) * sum;
+  }
+}
+
 // Column sums of X [R][N], stage 1: part[c][n] = sum over the rows of chunk c, in order.
 __global__ void colsum_part_kernel(const float* __restrict__ X, int R, int N, int rchunk,
                                    float* __restrict__ part) {
@@ -474,6 +528,7 @@ struct Plan {
   int V, E, H, NL, pad, rows, L, N;
   size_t x0, xin[8], gates[8], cst[8], hs[8];  // per-layer float offsets
   size_t logits, lse, term, valid, dy, dhrec, dc, scratch, scratch_floats, total;
+  size_t terms, grad_total;  // after `total`: what the autograd pair adds
 };
 
 static int make_plan(const milan_ctx* c, int rows, int L, Plan* p) {
@@ -532,6 +587,11 @@ static int make_plan(const milan_ctx* c, int rows, int L, Plan* p) {
   p->scratch = take(sc);
   p->scratch_floats = sc;
   p->total = off * sizeof(float);
+  // after `total`, what the autograd pair (milan_lm_forward_train / _backward) adds: the
+  // forward's loss terms, which nobody reads (the backward overwrites activations in place
+  // and needs no buffer of its own)
+  p->terms = take(2);
+  p->grad_total = off * sizeof(float);
   return 0;
 }
 
@@ -610,6 +670,21 @@ struct Grads {
   float *emb, *w_ih[8], *w_hh[8], *b_ih[8], *b_hh[8], *w_out, *b_out;
 };
 
+static int unpack_grads(const Plan& p, float* const* grads, int n, Grads* g) {
+  Params gp;
+  MILAN_TRY(unpack(p, (const float* const*)grads, n, &gp));
+  g->emb = const_cast<float*>(gp.emb);
+  for (int l = 0; l < p.NL; ++l) {
+    g->w_ih[l] = const_cast<float*>(gp.w_ih[l]);
+    g->w_hh[l] = const_cast<float*>(gp.w_hh[l]);
+    g->b_ih[l] = const_cast<float*>(gp.b_ih[l]);
+    g->b_hh[l] = const_cast<float*>(gp.b_hh[l]);
+  }
+  g->w_out = const_cast<float*>(gp.w_out);
+  g->b_out = const_cast<float*>(gp.b_out);
+  return 0;
+}
+
 static int backward(const Plan& p, const Params& w, const Grads& gr, float* ws,
                     const int64_t* inputs, const int64_t* targets, float p_drop, uint64_t seed,
                     const float* loss, hipStream_t s) {
@@ -619,8 +694,9 @@ static int backward(const Plan& p, const Params& w, const Grads& gr, float* ws,
   const uint32_t thr = drop_threshold(p_drop);
   const float scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   float* dlog = ws + p.logits;
-  hipLaunchKernelGGL(dlogits_kernel, dim3(N), dim3(256), 0, s, dlog, targets, ws + p.lse,
-                     ws + p.valid, loss, V);
+  if (loss)  // (null: the logits buffer already holds dlogits, milan_lm_backward)
+    hipLaunchKernelGGL(dlogits_kernel, dim3(N), dim3(256), 0, s, dlog, targets, ws + p.lse,
+                       ws + p.valid, loss, V);
   const View htop = view(ws + p.hs[p.NL - 1] + H, H, L, (long)(L + 1) * H);
   // dW_out = dlogits^T . H,  db_out = sum dlogits,  dH = dlogits . W_out
   MILAN_TRY(gemm(view(dlog, V), 1, htop, 0, view(gr.w_out, H), none, nullptr, nullptr, V, H, N,
@@ -726,21 +802,75 @@ int milan_lm_train_step(milan_ctx* c, const float* const* params, float* const* 
                 "milan_lm_train_step: workspace %zu < %zu bytes", ws_bytes, p.total);
   Params w;
   MILAN_TRY(unpack(p, params, n_params, &w));
-  Params gp;
-  MILAN_TRY(unpack(p, (const float* const*)grads, n_params, &gp));
   Grads g;
-  g.emb = const_cast<float*>(gp.emb);
-  for (int l = 0; l < p.NL; ++l) {
-    g.w_ih[l] = const_cast<float*>(gp.w_ih[l]);
-    g.w_hh[l] = const_cast<float*>(gp.w_hh[l]);
-    g.b_ih[l] = const_cast<float*>(gp.b_ih[l]);
-    g.b_hh[l] = const_cast<float*>(gp.b_hh[l]);
-  }
-  g.w_out = const_cast<float*>(gp.w_out);
-  g.b_out = const_cast<float*>(gp.b_out);
+  MILAN_TRY(unpack_grads(p, grads, n_params, &g));
   const hipStream_t s = (hipStream_t)stream;
   MILAN_TRY(forward(p, w, (float*)ws, inputs, targets, dropout, seed, loss_sum_and_count, s));
   return backward(p, w, g, (float*)ws, inputs, targets, dropout, seed, loss_sum_and_count, s);
+}
+
+size_t milan_lm_grad_workspace_bytes(const milan_ctx* c, int rows, int L) {
+  Plan p;
+  if (make_plan(c, rows, L, &p) != 0) return 0;
+  return p.grad_total;
+}
+
+int milan_lm_forward_train(milan_ctx* c, const float* const* params, int n_params,
+                           const int64_t* inputs, int rows, int L, float dropout, uint64_t seed,
+                           float* logprobs_out, float* picked_out, const int64_t* targets,
+                           void* ws, size_t ws_bytes, milan_stream stream) {
+  MILAN_REQUIRE(inputs && ws, MILAN_ERR_ARG, "milan_lm_forward_train: null argument");
+  MILAN_REQUIRE((picked_out != nullptr) == (targets != nullptr), MILAN_ERR_ARG,
+                "milan_lm_forward_train: targets go with picked_out, and only with it");
+  MILAN_REQUIRE(dropout >= 0.f && dropout < 1.f, MILAN_ERR_ARG,
+                "milan_lm_forward_train: dropout %g not in [0, 1)", (double)dropout);
+  Plan p;
+  MILAN_TRY(make_plan(c, rows, L, &p));
+  MILAN_REQUIRE(ws_bytes >= p.grad_total, MILAN_ERR_WORKSPACE,
+                "milan_lm_forward_train: workspace %zu < %zu bytes", ws_bytes, p.grad_total);
+  Params w;
+  MILAN_TRY(unpack(p, params, n_params, &w));
+  const hipStream_t s = (hipStream_t)stream;
+  float* f = (float*)ws;
+  // the forward of the train step; its loss terms (of `targets`, or of the inputs read as
+  // targets when there are none: any ids do) land behind the plan and are not used
+  MILAN_TRY(forward(p, w, f, inputs, targets ? targets : inputs, dropout, seed, f + p.terms, s));
+  if (logprobs_out)
+    hipLaunchKernelGGL(lm_logprobs_kernel, dim3(blocks_for((long)p.N * p.V)), dim3(256), 0, s,
+                       f + p.logits, f + p.lse, logprobs_out, p.N, p.V);
+  if (picked_out)
+    hipLaunchKernelGGL(lm_picked_kernel, dim3(blocks_for(p.N)), dim3(256), 0, s, f + p.logits,
+                       targets, f + p.lse, picked_out, p.N, p.V);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int milan_lm_backward(milan_ctx* c, const float* const* params, float* const* grads,
+                      int n_params, const int64_t* inputs, int rows, int L, float dropout,
+                      uint64_t seed, const float* dlogprobs, const float* dpicked,
+                      const int64_t* targets, void* ws, size_t ws_bytes, milan_stream stream) {
+  MILAN_REQUIRE(grads && inputs && ws, MILAN_ERR_ARG, "milan_lm_backward: null argument");
+  MILAN_REQUIRE(dlogprobs || dpicked, MILAN_ERR_ARG,
+                "milan_lm_backward: neither dlogprobs nor dpicked given");
+  MILAN_REQUIRE(!dpicked || targets, MILAN_ERR_ARG,
+                "milan_lm_backward: dpicked needs the targets of the forward");
+  MILAN_REQUIRE(dropout >= 0.f && dropout < 1.f, MILAN_ERR_ARG,
+                "milan_lm_backward: dropout %g not in [0, 1)", (double)dropout);
+  Plan p;
+  MILAN_TRY(make_plan(c, rows, L, &p));
+  MILAN_REQUIRE(ws_bytes >= p.grad_total, MILAN_ERR_WORKSPACE,
+                "milan_lm_backward: workspace %zu < %zu bytes", ws_bytes, p.grad_total);
+  Params w;
+  MILAN_TRY(unpack(p, params, n_params, &w));
+  Grads g;
+  MILAN_TRY(unpack_grads(p, grads, n_params, &g));
+  const hipStream_t s = (hipStream_t)stream;
+  float* f = (float*)ws;
+  // dlogits into the logits buffer, where backward() expects them
+  hipLaunchKernelGGL(lm_log_softmax_bwd_kernel, dim3(p.N), dim3(256), 0, s, dlogprobs, dpicked,
+                     targets, f + p.logits, f + p.lse, p.V);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return backward(p, w, g, f, inputs, nullptr, dropout, seed, nullptr, s);
 }
 
 }  // extern "C"

@@ -187,6 +187,13 @@ SIGNATURES = {
     'milan_lm_train_step':
         (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _F, ctypes.c_uint64, _P, _P,
               _SZ, _P]),
+    'milan_lm_grad_workspace_bytes': (_SZ, [_P, _I, _I]),
+    'milan_lm_forward_train':
+        (_I, [_P, _P, _I, _P, _I, _I, _F, ctypes.c_uint64, _P, _P, _P, _P, _SZ,
+              _P]),
+    'milan_lm_backward':
+        (_I, [_P, _P, _P, _I, _P, _I, _I, _F, ctypes.c_uint64, _P, _P, _P, _P,
+              _SZ, _P]),
     'milan_decoder_train_workspace_bytes': (_SZ, [_P, _I, _I, _I]),
     'milan_decoder_nll':
         (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
@@ -230,6 +237,11 @@ SIGNATURES = {
               _P]),
 }
 
+# entry points added without a new ABI version: a library built before them
+# (an older MILAN_LIB) still loads, and the calls that need them say so
+PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
+          'milan_lm_backward')
+
 _lib = None
 
 
@@ -249,6 +261,8 @@ def load_library(path: Optional[os.PathLike] = None) -> ctypes.CDLL:
     except OSError as error:
         raise HipUnavailableError(f'cannot load {p}: {error}') from error
     for name, (restype, argtypes) in SIGNATURES.items():
+        if name in PROBED and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the export is missing
         fn.restype = restype
         fn.argtypes = argtypes
@@ -950,6 +964,115 @@ class Context:
                     float(dropout), int(seed) & (2**64 - 1), loss.data_ptr(),
                     ws.data_ptr(), ws.numel(), _stream(self.device)))
         return loss
+
+    # -- LanguageModel.forward in training mode (milan_lm_forward_train) --
+    def _lm_grad_args(self, params, inputs, targets, check_ids=True):
+        for name in PROBED:
+            if not hasattr(self.lib, name):
+                raise HipUnavailableError(
+                    f'the loaded libmilan_hip has no {name}: it was built '
+                    'before the differentiable LanguageModel.forward; rebuild '
+                    'it (or unset MILAN_LIB)')
+        if inputs.dim() != 2:
+            raise ValueError('inputs must be (rows, L), got '
+                             f'{tuple(inputs.shape)}')
+        if targets is not None and targets.shape != inputs.shape:
+            raise ValueError(f'targets {tuple(targets.shape)} != inputs '
+                             f'{tuple(inputs.shape)}')
+        v = self.dims.vocab_size
+        for name, ids in (('inputs', inputs), ('targets', targets)):
+            if not check_ids or ids is None or not ids.numel():
+                continue  # (the backward takes what its forward checked)
+            if int(ids.min()) < 0 or int(ids.max()) >= v:
+                raise ValueError(f'{name} hold ids outside [0, {v})')
+        if len(params) != 3 + 4 * self.dims.lm_layers:
+            raise ValueError(f'{len(params)} parameters, expected '
+                             f'{3 + 4 * self.dims.lm_layers}')
+        for p in params:
+            if (p.device != self.device or p.dtype != torch.float32
+                    or not p.is_contiguous()):
+                raise ValueError('LM parameters must be contiguous float32 on '
+                                 f'{self.device}')
+        inputs = _dev(inputs, self.device, torch.long)
+        if targets is not None:
+            targets = _dev(targets, self.device, torch.long)
+        need = int(self.lib.milan_lm_grad_workspace_bytes(
+            self._h, inputs.shape[0], inputs.shape[1]))
+        if need == 0:
+            _check(ERR_SHAPE)
+        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
+        return inputs, targets, ptrs, need
+
+    def lm_forward_train(self, params, inputs: torch.Tensor,
+                         dropout: float = 0., seed: int = 0,
+                         targets: Optional[torch.Tensor] = None,
+                         want_logprobs: bool = True):
+        """The LM in train mode (milan_lm_forward_train): returns (log-probs
+        (rows, L, V) or None, picked (rows, L) or None, workspace).  `targets`
+        (rows, L): picked[r, t] = logprobs[r, t, targets[r, t]]; with
+        `want_logprobs=False` the (rows, L, V) tensor is never written.  The
+        workspace is a fresh uint8 device tensor holding the activations that
+        ONE `lm_backward` consumes; it is not `_train_ws`, so other calls on
+        this context leave it alone.  Does not synchronise."""
+        if targets is None and not want_logprobs:
+            raise ValueError('nothing to compute: no targets and no log-probs')
+        inputs, targets, ptrs, need = self._lm_grad_args(params, inputs,
+                                                         targets)
+        rows, length = inputs.shape
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        logprobs = picked = None
+        if want_logprobs:
+            logprobs = torch.empty(rows, length, self.dims.vocab_size,
+                                   device=self.device)
+        if targets is not None:
+            picked = torch.empty(rows, length, device=self.device)
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_lm_forward_train(
+                    self._h, ptrs, len(params), inputs.data_ptr(), rows,
+                    length, float(dropout), int(seed) & (2**64 - 1),
+                    _ptr(logprobs), _ptr(picked), _ptr(targets),
+                    ws.data_ptr(), ws.numel(), _stream(self.device)))
+        return logprobs, picked, ws
+
+    def lm_backward(self, params, grads, inputs: torch.Tensor, dropout: float,
+                    seed: int, dlogprobs: Optional[torch.Tensor],
+                    dpicked: Optional[torch.Tensor],
+                    targets: Optional[torch.Tensor], ws: torch.Tensor) -> None:
+        """Backward of `lm_forward_train` (milan_lm_backward) from upstream
+        gradients of its log-probs and picked log-probs (None: zero; not both),
+        with the forward's params, inputs, targets, dropout and seed.  The
+        gradients of every parameter are OVERWRITTEN into `grads`.  Consumes
+        `ws`: a second backward from the same workspace is wrong.  Does not
+        synchronise."""
+        if dlogprobs is None and dpicked is None:
+            raise ValueError('neither dlogprobs nor dpicked given')
+        if dpicked is not None and targets is None:
+            raise ValueError('dpicked needs the targets of the forward')
+        inputs, targets, ptrs, need = self._lm_grad_args(params, inputs,
+                                                         targets, False)
+        rows, length = inputs.shape
+        shapes = ((dlogprobs, (rows, length, self.dims.vocab_size)),
+                  (dpicked, (rows, length)))
+        for t, shape in shapes:
+            if t is not None and (tuple(t.shape) != shape
+                                  or t.device != self.device
+                                  or t.dtype != torch.float32
+                                  or not t.is_contiguous()):
+                raise ValueError(f'gradient {tuple(t.shape)} must be a '
+                                 f'contiguous float32 {shape} on {self.device}')
+        if ws.numel() < need:
+            raise ValueError('workspace does not come from lm_forward_train '
+                             'at these dims')
+        gptrs = self._decoder_grads(params, grads)
+        with torch.cuda.device(self.device):
+            _check(
+                self.lib.milan_lm_backward(
+                    self._h, ptrs, gptrs, len(params), inputs.data_ptr(), rows,
+                    length, float(dropout), int(seed) & (2**64 - 1),
+                    _ptr(dlogprobs), _ptr(dpicked),
+                    _ptr(targets) if dpicked is not None else None,
+                    ws.data_ptr(), ws.numel(), _stream(self.device)))
 
     # -- Decoder training (include/milan_hip.h, milan_decoder_train_step) --
     DECODER_TRAIN_PARAMS = 19

@@ -11,6 +11,16 @@ LSTM(layers, dropout) -> Linear(V) + LogSoftmax.
     loss and every gradient come from libmilan_hip (`milan_lm_train_step`:
     exact fp32 MFMA, deterministic; include/milan_hip.h); the torch optimizer
     then steps the parameters.
+  * `forward` in training mode is differentiable once the parameters ask
+    for it: after `lm.requires_grad_(True); lm.train()` the call runs
+    `TrainingForward` (`milan_lm_forward_train` and, on `backward()`,
+    `milan_lm_backward`) with inter-layer dropout on, so the
+    log-probs (`reduce=False`) and the sequence scores (`reduce=True`) carry
+    `grad_fn` and a user's own loss or optimizer loop trains the LM.  The one
+    difference from the reference, whose parameters are trainable by
+    default: the parameters here are created with `requires_grad=False`, and
+    while none of them requires grad every call runs the inference kernels
+    (no dropout, no graph), in training mode too.
   * `lm(dataset, ...)` (lms.py:283-322) builds the indexer from the dataset's
     annotations and a model initialised as the reference's would be (same
     draws from torch's global generator).
@@ -23,7 +33,9 @@ from typing import (Any, List, Mapping, Optional, Sequence, Sized, Type,
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn, optim
+from torch.autograd.function import once_differentiable
 from torch.utils import data
 
 from milan_amd import hip, lang, params, training
@@ -88,6 +100,52 @@ class _SequenceDataset(data.Dataset):
         return len(self.sequences)
 
 
+class TrainingForward(torch.autograd.Function):
+    """The LM with inter-layer dropout as one autograd node:
+    `milan_lm_forward_train` / `milan_lm_backward` (include/milan_hip.h).
+    Inputs: the dims-only hip.Context, inputs (rows, L), targets (rows, L) or
+    None, dropout, seed and the 4 * layers + 3 parameters in state-dict order.
+    Output: without targets the log-probs (rows, L, V); with targets only
+    picked[r, t] = logprobs[r, t, targets[r, t]], (rows, L) -- no (rows, L, V)
+    tensor then exists in either direction.  The forward's workspace holds
+    every activation and the backward overwrites them in place, so the graph
+    supports one backward."""
+
+    @staticmethod
+    def forward(ctx, hctx, inputs, targets, dropout, seed, *params):
+        logprobs, picked, ws = hctx.lm_forward_train(
+            params, inputs, dropout, seed, targets=targets,
+            want_logprobs=targets is None)
+        ctx.hctx, ctx.dropout, ctx.seed, ctx.ws = hctx, dropout, seed, ws
+        ctx.inputs, ctx.targets = inputs, targets
+        ctx.save_for_backward(*params)
+        ctx.set_materialize_grads(False)
+        return logprobs if targets is None else picked
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, upstream):
+        if upstream is None:
+            return (None,) * (5 + len(ctx.saved_tensors))
+        ws, ctx.ws = ctx.ws, None
+        if ws is None:
+            raise RuntimeError(
+                'the training-mode LM graph was already backpropagated once: '
+                'its activations are consumed by the first backward; run the '
+                'forward again')
+        params = ctx.saved_tensors
+        grads = [torch.empty_like(p) for p in params]
+        upstream = upstream.contiguous()
+        picked = ctx.targets is not None
+        ctx.hctx.lm_backward(params, grads, ctx.inputs, ctx.dropout, ctx.seed,
+                             None if picked else upstream,
+                             upstream if picked else None, ctx.targets, ws)
+        # (the kernels compute them all; torch accumulates the ones asked for)
+        pgrads = [g if need else None
+                  for g, need in zip(grads, ctx.needs_input_grad[5:])]
+        return (None, None, None, None, None, *pgrads)
+
+
 class LanguageModel(nn.Module):
     """Parameter owner + HIP entry point for the LM."""
 
@@ -120,6 +178,8 @@ class LanguageModel(nn.Module):
         self._owner = None
         self._ctx: Optional[hip.Context] = None
         self._ctx_key = None
+        self._train_ctx: Optional[hip.Context] = None  # training-mode forward
+        self._train_ctx_key = None
 
     def _context(self) -> hip.Context:
         if self._owner is not None and self._owner() is not None:
@@ -147,7 +207,13 @@ class LanguageModel(nn.Module):
         default everything after the first stop token is dropped -- with the
         reference's off-by-one: the term predicting the token AFTER the stop
         still counts (lms.py:93-95).
+
+        In training mode with at least one parameter requiring grad (they do
+        not by default: `lm.requires_grad_(True)`) the result carries
+        `grad_fn` and inter-layer dropout is on; see `_forward_train`.
         """
+        if self.training and any(p.requires_grad for p in self.parameters()):
+            return self._forward_train(inputs, reduce, masks)
         ctx = self._context()
         if reduce and masks is None:
             return ctx.lm_score(inputs)  # fused: never materialises (B,L,V)
@@ -157,6 +223,60 @@ class LanguageModel(nn.Module):
         targets = inputs[:, 1:].to(lps.device)
         picked = lps[:, :-1].gather(2, targets.unsqueeze(-1)).squeeze(-1)
         return picked.mul(masks.to(lps.device)).sum(dim=-1)
+
+    def _train_context(self, device: torch.device) -> hip.Context:
+        """A context that only carries the LM's dims, never finalized, cached
+        on the LM (attached to a Decoder or not): the training calls read the
+        live parameters, so optimizer steps do not rebuild it."""
+        key = (device, tuple(p.shape for p in self.parameters()))
+        if self._train_ctx is None or self._train_ctx_key != key:
+            sd = {f'lm.{k}': v for k, v in self.state_dict().items()}
+            # (the old one closes when the last graph that holds it goes)
+            self._train_ctx = hip.Context(
+                hip.make_dims(sd, len(self.indexer.vocab)), {}, device,
+                finalize=False)
+            self._train_ctx_key = key
+        return self._train_ctx
+
+    def _forward_train(self, inputs: torch.Tensor, reduce: bool,
+                       masks: Optional[torch.Tensor]) -> torch.Tensor:
+        """`forward` through `TrainingForward` (reference lms.py:85-101 with
+        nn.LSTM's dropout on): dropout `self.dropout` on the output of every
+        layer but the last, its seed drawn from the device's generator when
+        there is a mask to draw (dropout > 0 and more than one layer).
+        `reduce=True` asks the kernels for the log-probs of the next tokens
+        alone; the mask and the sum over positions are torch's, and `masks` is
+        a constant.  Under `torch.no_grad()` this is still the training
+        forward, and nothing is kept."""
+        if masks is not None and masks.requires_grad:
+            raise ValueError('masks is a constant of the training-mode forward: '
+                             'no gradient flows into it (detach it)')
+        if inputs.dim() != 2:
+            raise ValueError(f'inputs must be 2D, got {inputs.dim()}')
+        device = hip.require_device(self.embedding.weight.device)
+        named = dict(self.named_parameters())
+        weights = [named[name] for name in self._param_names()]
+        seed = 0
+        if self.dropout > 0 and self.layers > 1:  # as fit draws it
+            seed = int(torch.randint(
+                2**62, (), device=device,
+                generator=torch.cuda.default_generators[device.index]))
+        hctx = self._train_context(device)
+        inputs = inputs.to(device, torch.long).contiguous()
+        if not reduce:
+            return TrainingForward.apply(hctx, inputs, None,
+                                         float(self.dropout), seed, *weights)
+        # position t predicts inputs[:, t + 1]; the last one predicts nothing
+        # (any id does there: its term is cut off below)
+        targets = F.pad(inputs[:, 1:], (0, 1))
+        picked = TrainingForward.apply(hctx, inputs, targets,
+                                       float(self.dropout), seed, *weights)
+        if masks is None:
+            # ones up to AND INCLUDING the term after the first stop token
+            stopped = inputs.eq(self.indexer.stop_index).cumsum(dim=1).gt(0)
+            masks = torch.ones_like(picked[:, :-1])
+            masks[:, 1:] = (~stopped[:, :-2]).to(masks.dtype)
+        return picked[:, :-1].mul(masks.to(device)).sum(dim=-1)
 
     def reset_parameters(self) -> None:
         """Initialise the parameters as the reference's torch modules do

@@ -12,6 +12,12 @@ tokens/s counts the non-pad targets.
 
     python tools/bench_lm_train.py --steps 50 --warmup 10 [--only hip|torch] [--out f.json]
 
+`--autograd` times, in the same process and on the same batches, the fused step
+and a user's loop on the differentiable training-mode `LanguageModel.forward`
+(DESIGN.md 4.16): forward + `F.nll_loss(ignore_index=pad)` + `backward()` +
+AdamW, and `forward(reduce=True)` with a sum loss.  There is no threshold: the
+fused step of the same run is the yardstick.
+
 Needs an MI355X; prints one JSON line.
 """
 import argparse
@@ -24,6 +30,7 @@ ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / 'neuron-descriptions_amd'))
 
 import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
 from torch import nn  # noqa: E402
 
 from milan_amd import hip, lang, lms  # noqa: E402
@@ -84,6 +91,33 @@ def bench_hip(indexer, data, dev, warmup, steps):
     return seconds
 
 
+def bench_autograd(indexer, data, dev, warmup, steps, reduce=False):
+    """A user's loop on the training-mode forward: log-probs + nll_loss, or
+    (reduce) the sequence scores with a sum loss; backward; AdamW."""
+    torch.manual_seed(0)
+    model = lms.LanguageModel(indexer, E, H, LAYERS, DROPOUT)
+    model.reset_parameters()
+    model.to(dev)
+    model.requires_grad_(True)
+    model.train()
+    opt = torch.optim.AdamW(model.parameters())
+    pad = indexer.pad_index
+    data = [(i.to(dev), t.to(dev)) for i, t in data]
+
+    def step(inputs, targets):
+        if reduce:
+            loss = -model(inputs, reduce=True).sum()
+        else:
+            lp = model(inputs)
+            loss = F.nll_loss(lp.reshape(-1, lp.shape[-1]), targets.reshape(-1),
+                              ignore_index=pad)
+        loss.backward()
+        opt.step()
+        opt.zero_grad()
+
+    return timed(step, data, warmup, steps)
+
+
 def bench_torch(indexer, data, dev, warmup, steps):
     torch.manual_seed(0)
     v = len(indexer)
@@ -111,6 +145,8 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--only', choices=('hip', 'torch'))
+    ap.add_argument('--autograd', action='store_true',
+                    help='the fused step against the differentiable forward')
     ap.add_argument('--out')
     args = ap.parse_args()
     dev = hip.require_device('cuda')
@@ -122,7 +158,21 @@ def main():
     result = dict(model=dict(V=len(indexer), E=E, H=H, layers=LAYERS, batch=BATCH,
                              L=int(data[0][0].shape[1]), dropout=DROPOUT),
                   steps=args.steps, warmup=args.warmup, tokens_per_step=per_step)
-    for name, fn in (('hip', bench_hip), ('torch', bench_torch)):
+    legs = [('hip', bench_hip), ('torch', bench_torch)]
+    if args.autograd:
+        ctx = hip.Context(hip.make_dims(
+            {f'lm.{k}': v for k, v in
+             lms.LanguageModel(indexer, E, H, LAYERS, DROPOUT).state_dict().items()},
+            len(indexer.vocab)), {}, dev, finalize=False)
+        rows, length = data[0][0].shape
+        result['workspace_bytes'] = dict(
+            train_step=int(ctx.lib.milan_lm_train_workspace_bytes(ctx._h, rows, length)),
+            autograd=int(ctx.lib.milan_lm_grad_workspace_bytes(ctx._h, rows, length)))
+        ctx.close()
+        legs = [('hip', bench_hip), ('autograd', bench_autograd),
+                ('autograd_reduce',
+                 lambda *a: bench_autograd(*a, reduce=True))]
+    for name, fn in legs:
         if args.only and args.only != name:
             continue
         seconds = fn(indexer, data, dev, args.warmup, args.steps)
@@ -131,6 +181,10 @@ def main():
     if 'hip' in result and 'torch' in result:
         result['hip_over_torch_time'] = (result['hip']['ms_per_step'] /
                                          result['torch']['ms_per_step'])
+    for name in ('autograd', 'autograd_reduce'):
+        if name in result and 'hip' in result:
+            result[f'{name}_over_hip_time'] = (result[name]['ms_per_step'] /
+                                               result['hip']['ms_per_step'])
     line = json.dumps(result)
     print(line)
     if args.out:

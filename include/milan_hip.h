@@ -290,6 +290,35 @@ int milan_set_fusion(milan_ctx* ctx, int flags);
 int milan_set_precision(milan_ctx* ctx, int precision);
 int milan_get_precision(const milan_ctx* ctx);
 
+/* Image sharing (opt-in, default off; csrc/share.hip).  The reference runs the
+ * trunk on the unmasked image and the masks enter at the pooling only (src/milan/encoders.py:
+ * 295-318): the features of an exemplar slot are pool(trunk(image), mask).  With sharing
+ * enabled, slots of ONE ENCODER PASS that hold byte-identical uint8 images go through the
+ * trunk once and every slot pools its own mask from that result; the features are bit for
+ * bit those of the unshared pass.  Identity is decided by comparing bytes (a 64-bit hash only
+ * selects the candidates), so two different images are never merged.
+ *   Scope: one encoder pass = MILAN_ENC_SUB images (default 9600: one 640-neuron chunk of 15
+ *     exemplars).  Duplicates in different passes, chunks or calls are NOT shared.
+ *   Applies to: the pooled encode (milan_encode, the encode half of milan_describe) of a
+ *     ResNet trunk over uint8 images, outside calibration; `masks` may be NULL.
+ *   Accepted and ignored for: float images (they may carry NaN pixels and take the full
+ *     pass), milan_encode_spatial and the AlexNet pyramid: such a pass runs exactly as
+ *     without the flag and counts slots == trunk_images.
+ *   milan_image_sharing_stats: cumulative over the encoder passes run WHILE SHARING WAS
+ *     ENABLED since creation / the last clear: exemplar slots seen, and images that actually
+ *     went through the trunk.  The counters live on the device and are added to by a kernel of
+ *     the pass: milan_encode / milan_describe read nothing back, stay free of synchronisation
+ *     and capturable into a hipGraph.  This call synchronises `stream` (like milan_status).
+ *   MILAN_SHARE_HASH_BITS=<0..64> (read at milan_create, default 64) keeps only that many low
+ *     bits of the hash: a test knob (0: every pair of slots is compared byte for byte).
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them
+ * (dlsym / hasattr(lib, "milan_set_image_sharing")). */
+int milan_set_image_sharing(milan_ctx* ctx, int enable);   /* default 0 */
+int milan_get_image_sharing(const milan_ctx* ctx);
+int milan_image_sharing_stats(milan_ctx* ctx, long long* slots,
+                              long long* trunk_images, int clear,
+                              milan_stream stream);
+
 /* Split-f16 mode fails LOUDLY (round 5).  The reference computes in plain fp32
  * (src/milan/encoders.py:295-320) and never saturates; the (hi, lo) f16 storage clamps
  * |x * 2^act_scale_log2| at 65504.  Every kernel that writes split format keeps the running

@@ -144,6 +144,20 @@ int milan_create(milan_ctx** out, int device, const milan_dims* dims) {
       if (e != hipSuccess) r = (int)e;
     }
   }
+  if (r == 0) {
+    // image sharing: the two device-side counters of milan_image_sharing_stats
+    r = dev_alloc(c, (void**)&c->share_stats, 256);
+    if (r == 0) {
+      hipError_t e = hipMemset(c->share_stats, 0, 256);
+      if (e != hipSuccess) r = (int)e;
+    }
+  }
+  if (const char* e = getenv("MILAN_SHARE_HASH_BITS")) {
+    // test knob: only that many low bits of the image hash select candidates (0: every pair
+    // of slots goes through the byte comparison)
+    const int k = atoi(e);
+    c->share_hash_bits = k < 0 ? 0 : (k > 64 ? 64 : k);
+  }
   if (r != 0) { milan_destroy(c); return r; }
   *out = c;
   return 0;
@@ -497,6 +511,28 @@ int milan_set_fusion(milan_ctx* c, int flags) {
                            MILAN_FUSE_SKIP_EMPTY | MILAN_FUSE_BNECK | MILAN_FUSE_SPARSE_TAIL)) == 0, MILAN_ERR_ARG,
                 "unknown fusion flags %d", flags);
   c->fusion = flags;
+  return 0;
+}
+
+int milan_set_image_sharing(milan_ctx* c, int enable) {
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
+  c->share_images = enable != 0;
+  return 0;
+}
+
+int milan_get_image_sharing(const milan_ctx* c) { return c ? c->share_images : -1; }
+
+int milan_image_sharing_stats(milan_ctx* c, long long* slots, long long* trunk_images, int clear,
+                              milan_stream stream) {
+  MILAN_REQUIRE(c && slots && trunk_images, MILAN_ERR_ARG,
+                "milan_image_sharing_stats: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  long long host[2] = {0, 0};
+  MILAN_CHECK_HIP(hipMemcpyAsync(host, c->share_stats, sizeof(host), hipMemcpyDeviceToHost, s));
+  if (clear) MILAN_TRY(launch_zero_fill(c->share_stats, sizeof(host), s));
+  MILAN_CHECK_HIP(hipStreamSynchronize(s));
+  *slots = host[0];
+  *trunk_images = host[1];
   return 0;
 }
 

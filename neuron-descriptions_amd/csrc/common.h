@@ -162,6 +162,27 @@ int device_cus8(int* out);
 void* gemm_profile_begin(double flops, double bytes, hipStream_t s);
 void gemm_profile_end(void* rec, hipStream_t s);
 
+// ---- image sharing (share.hip; milan_set_image_sharing) ---------------------------------
+// Classes of byte-identical uint8 images among the n slots of one encoder pass, all on the
+// device: order[c] = root image of live class c (ascending), *count = live classes,
+// class_of[i] = trunk slot of exemplar slot i (-1: nothing to pool), bbox_c[c] = union of the
+// members' level-0 bounding boxes.
+struct ShareArgs {
+  const unsigned char* images;  // [n][bytes]
+  long bytes;                   // 3 * H * W
+  int n;
+  int hash_bits;                // low bits of the hash that select candidates (MILAN_SHARE_HASH_BITS)
+  int skip_empty;               // 0: every class is live
+  const int* list_n;            // [n][5] (mask_pyramid_kernel)
+  const int* bbox;              // [n][4]
+  void* hash;                   // [n] 8 bytes each
+  int *rep, *flag;              // [n] scratch
+  int *order, *bbox_c, *count, *class_of;
+};
+int launch_image_classes(const ShareArgs& a, hipStream_t s);
+// stats[0] += n, stats[1] += *live (n when live == nullptr); one thread, nothing read back
+int launch_share_count(long long* stats, int n, const int* live, hipStream_t s);
+
 // ---- fused expand -> reduce chain (chain.hip) --------------------------------
 // One launch = a bottleneck's 1x1 expand conv c3 (+ residual + ReLU) AND the next
 // bottleneck's 1x1 reduce conv c1 (+ ReLU): X = relu(T2 W3^T + b3 + R),
@@ -512,6 +533,10 @@ struct milan_ctx {
   // a value hit the +-65504 clamp and by the input conversion when a pixel was not finite
   unsigned* status = nullptr;
   unsigned* calib = nullptr;   // != nullptr only inside milan_encoder_absmax
+  // image sharing (milan_set_image_sharing; share.hip): off by default
+  int share_images = 0;
+  int share_hash_bits = 64;            // MILAN_SHARE_HASH_BITS at milan_create (a test knob)
+  long long* share_stats = nullptr;    // device: exemplar slots seen, images through the trunk
   std::vector<milan::Bottleneck> blocks[4];
   float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
   // decoder

@@ -813,27 +813,40 @@ __global__ __launch_bounds__(1024) void compact_images_kernel(
 
 // features[img][col_off + c] = sum_p w[p] * tap[img][p][c]   (encoders.py:317)
 // grid (n_images, ceil(C/64)); 4 waves split the pixel list, lane = channel.
-template <int SPLIT_IN>   // 0: fp32 tap, 1: split format, 2: plain f16 (fast mode)
+// SHARED (image sharing, share.hip): the grid runs over EXEMPLAR slots, slot i pools the tap
+// of trunk slot class_of[i]; slots with class -1 or a class outside [img0, img0 + ncls) do
+// nothing (their rows were zero-filled); lists / weights / poison / feature row stay slot i's.
+template <int SPLIT_IN, bool SHARED = false>   // 0: fp32 tap, 1: split format, 2: plain f16 (fast mode)
 __global__ __launch_bounds__(256) void masked_pool_kernel(
     const float* __restrict__ tap, int P, int C, int level, Levels lv,
     const int* __restrict__ list_idx, const float* __restrict__ list_w,
     const int* __restrict__ list_n, float* __restrict__ features, int fstride,
     int col_off, int img0, float inv_scale, const int* __restrict__ poison = nullptr,
-    const int* __restrict__ order = nullptr, const int* __restrict__ live = nullptr) {
+    const int* __restrict__ order = nullptr, const int* __restrict__ live = nullptr,
+    const int* __restrict__ class_of = nullptr, int ncls = 0) {
   __shared__ float part[4][64];
-  // (image count on the device: slots beyond it hold no image -- their feature rows were
-  // zero-filled -- and order[] is only defined below it)
-  if (live != nullptr && (int)blockIdx.x + img0 >= *live) return;
-  // `tap` points at slot img0 of the batch; lists / features are indexed by the image
-  // number (`order`: the batch holds only the images with a non-empty mask, in this order)
-  const int img = order ? order[blockIdx.x + img0] : blockIdx.x + img0;
+  int img, trow;   // image number (lists / features) and row of `tap`
+  if constexpr (SHARED) {
+    img = blockIdx.x;
+    const int cls = class_of[img];
+    if (cls < img0 || cls >= img0 + ncls) return;
+    trow = cls - img0;
+  } else {
+    // (image count on the device: slots beyond it hold no image -- their feature rows were
+    // zero-filled -- and order[] is only defined below it)
+    if (live != nullptr && (int)blockIdx.x + img0 >= *live) return;
+    // `tap` points at slot img0 of the batch; lists / features are indexed by the image
+    // number (`order`: the batch holds only the images with a non-empty mask, in this order)
+    img = order ? order[blockIdx.x + img0] : blockIdx.x + img0;
+    trow = blockIdx.x;
+  }
   const int c = blockIdx.y * 64 + (threadIdx.x & 63);
   const int phase = threadIdx.x >> 6;
   const long base = (long)img * lv.per_image + lv.off[level];
   const int cnt = list_n[img * 5 + level];
   // split format: channel c lives in group c/8 = 32 B [hi x8 | lo x8]
   const long coff = SPLIT_IN == 1 ? (long)(c >> 3) * 8 : c;
-  const float* t = tap + (SPLIT_IN == 2 ? (long)blockIdx.x * P * (C / 2) : (long)blockIdx.x * P * C + coff);
+  const float* t = tap + (SPLIT_IN == 2 ? (long)trow * P * (C / 2) : (long)trow * P * C + coff);
   auto fetch = [&](int p) -> float {
     if constexpr (SPLIT_IN == 2) {
       return (float)reinterpret_cast<const _Float16*>(t + (long)p * (C / 2))[c];
@@ -874,16 +887,27 @@ __global__ __launch_bounds__(256) void masked_pool_kernel(
 // waves walk the list interleaved.  grid (n_images, ceil(C / 512)); partial sums are added in a
 // fixed order (slot ascending), so results do not depend on timing (not the bits of
 // masked_pool_kernel<1>: another association of the same fp32 sum).
+template <bool SHARED = false>   // (see masked_pool_kernel)
 __global__ __launch_bounds__(256) void masked_pool_split8_kernel(
     const float* __restrict__ tap, int P, int C, int level, Levels lv,
     const int* __restrict__ list_idx, const float* __restrict__ list_w,
     const int* __restrict__ list_n, float* __restrict__ features, int fstride,
     int col_off, int img0, float inv_scale, const int* __restrict__ poison,
-    const int* __restrict__ order, int lpp, const int* __restrict__ live = nullptr) {
+    const int* __restrict__ order, int lpp, const int* __restrict__ live = nullptr,
+    const int* __restrict__ class_of = nullptr, int ncls = 0) {
   __shared__ float part[4 * 64 * 8];
-  const int slot_img = blockIdx.x + img0;
-  if (live != nullptr && slot_img >= *live) return;   // (see masked_pool_kernel)
-  const int img = order ? order[slot_img] : slot_img;
+  int img, trow;
+  if constexpr (SHARED) {
+    img = blockIdx.x;
+    const int cls = class_of[img];
+    if (cls < img0 || cls >= img0 + ncls) return;
+    trow = cls - img0;
+  } else {
+    const int slot_img = blockIdx.x + img0;
+    if (live != nullptr && slot_img >= *live) return;   // (see masked_pool_kernel)
+    img = order ? order[slot_img] : slot_img;
+    trow = blockIdx.x;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int G = C / 8, pw = 64 / lpp;
   const int gl = lane % lpp, sub = lane / lpp;
@@ -891,7 +915,7 @@ __global__ __launch_bounds__(256) void masked_pool_split8_kernel(
   const int slot = wave * pw + sub, nslots = 4 * pw;
   const long base = (long)img * lv.per_image + lv.off[level];
   const int cnt = list_n[img * 5 + level];
-  const float* t = tap + (long)blockIdx.x * P * C + (long)g * 8;
+  const float* t = tap + (long)trow * P * C + (long)g * 8;
   float a0[8], a1[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) { a0[e] = 0.f; a1[e] = 0.f; }
@@ -970,11 +994,27 @@ __global__ void act_absmax_kernel(const float* __restrict__ x, long n,
 // (tests/test_gpu_sparse_tail.py) -- and the row counts stay on the device (GemmArgs::m_live).
 constexpr int kTailMaxP = 1024;   // pixels of the last stage per image (7 x 7 = 49 at 224 x 224)
 
+// Image sharing: set 0 of trunk slot c is the UNION of its members' level-4 lists, gathered
+// here as a byte map s0[c][p] (zero-filled; every writer stores the same 1).  Dilation
+// distributes over union, so sets 1 and 2 of tail_sets_kernel are then exactly the pixels
+// some member's pooling depends on.
+__global__ __launch_bounds__(64) void tail_union_kernel(
+    const int* __restrict__ list_idx, const int* __restrict__ list_n, Levels lv,
+    const int* __restrict__ class_of, int P, unsigned char* __restrict__ s0) {
+  const int i = blockIdx.x, c = class_of[i];
+  if (c < 0) return;
+  const long base = (long)i * lv.per_image + lv.off[4];
+  const int cnt = list_n[i * 5 + 4];
+  for (int e = threadIdx.x; e < cnt; e += 64) s0[(long)c * P + list_idx[base + e]] = 1;
+}
+
 // sets k = 0 (listed pixels), 1 (dilated once), 2 (dilated twice) of batch slot j, ascending
+// (s0 != nullptr: set 0 is given as a byte map, see tail_union_kernel)
 __global__ __launch_bounds__(64) void tail_sets_kernel(
     const int* __restrict__ list_idx, const int* __restrict__ list_n, Levels lv,
     const int* __restrict__ order, const int* __restrict__ live, int n,
-    int* __restrict__ loc, int* __restrict__ cnt) {
+    int* __restrict__ loc, int* __restrict__ cnt,
+    const unsigned char* __restrict__ s0 = nullptr) {
   __shared__ unsigned char s[3][kTailMaxP];
   const int j = blockIdx.x, lane = threadIdx.x;
   const int h = lv.h[4], w = lv.w[4], P = h * w;
@@ -983,11 +1023,15 @@ __global__ __launch_bounds__(64) void tail_sets_kernel(
     return;
   }
   const int img = order ? order[j] : j;
-  for (int p = lane; p < P; p += 64) s[0][p] = 0;
-  __syncthreads();
-  const long base = (long)img * lv.per_image + lv.off[4];
-  const int c = list_n[img * 5 + 4];
-  for (int i = lane; i < c; i += 64) s[0][list_idx[base + i]] = 1;
+  if (s0 != nullptr) {
+    for (int p = lane; p < P; p += 64) s[0][p] = s0[(long)j * P + p];
+  } else {
+    for (int p = lane; p < P; p += 64) s[0][p] = 0;
+    __syncthreads();
+    const long base = (long)img * lv.per_image + lv.off[4];
+    const int c = list_n[img * 5 + 4];
+    for (int i = lane; i < c; i += 64) s[0][list_idx[base + i]] = 1;
+  }
   __syncthreads();
   for (int k = 1; k < 3; ++k) {
     for (int p = lane; p < P; p += 64) {
@@ -1102,6 +1146,11 @@ struct EncPlan {
   // mask-aware tail of the last stage: per-slot pixel sets [3][n][P4], their counts / offsets
   // [3][n], the global row lists [3][n * P4] and row counts [3] (device)
   int *tail_loc, *tail_cnt, *tail_off, *tail_rows, *tail_U;
+  // image sharing (share.hip): per-slot hash / rep / flag / class_of, and the union of the
+  // members' level-4 lists per trunk slot as a byte map [n][P4]
+  void* sh_hash;
+  int *sh_rep, *sh_flag, *class_of;
+  unsigned char* tail_s0;
 };
 
 static int conv_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
@@ -1157,6 +1206,11 @@ static int plan(const milan_ctx* c, int n, int H, int W, Arena& a, EncPlan* pl) 
     pl->tail_cnt = a.get<int>(3 * (size_t)n);
     pl->tail_off = a.get<int>(3 * (size_t)n);
     pl->tail_U = a.get<int>(4);
+    pl->sh_hash = a.get<unsigned long long>((size_t)n);
+    pl->sh_rep = a.get<int>((size_t)n);
+    pl->sh_flag = a.get<int>((size_t)n);
+    pl->class_of = a.get<int>((size_t)n);
+    pl->tail_s0 = a.get<unsigned char>(((size_t)n * P4 + 3) & ~(size_t)3);
   }
   return 0;
 }
@@ -1300,9 +1354,13 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
                 "encoder weights were not uploaded");
   MILAN_REQUIRE(n > 0 && H >= 1 && W >= 1, MILAN_ERR_SHAPE,
                 "encode: need n>0 and H,W>=1 (got n=%d H=%d W=%d)", n, H, W);
-  if (c->d.trunk_kind == MILAN_TRUNK_ALEXNET)
+  if (c->d.trunk_kind == MILAN_TRUNK_ALEXNET) {
+    // (image sharing covers the ResNet trunks: accepted and ignored here, slots == images)
+    if (c->share_images && c->share_stats != nullptr)
+      MILAN_TRY(launch_share_count(c->share_stats, n, nullptr, s));
     return alexnet_run_batch(c, images, image_dtype, masks, mask_dtype, n, H, W,
                              features, ws, s);
+  }
   EncPlan pl;
   plan(c, n, H, W, ws, &pl);
   MILAN_REQUIRE(ws.off <= ws.size, MILAN_ERR_WORKSPACE,
@@ -1347,7 +1405,26 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
   const int n_all = n;
   const int* order = nullptr;
   const int* live = nullptr;
-  if (!spatial && masks != nullptr && image_dtype == MILAN_DTYPE_U8 && c->calib == nullptr &&
+  // 1c. image sharing (milan_set_image_sharing; share.hip): slots of this pass that show the
+  // same uint8 image share one trunk slot.  The same mechanism, generalised: slot j of the
+  // trunk batch holds the root image of the j-th live class (order[j]), bbox_c[j] is the
+  // union of the members' boxes and the pooling of exemplar slot i reads trunk slot
+  // class_of[i].  masks may be NULL (every list is full: one class per distinct image).
+  const int* class_of = nullptr;
+  if (!spatial && image_dtype == MILAN_DTYPE_U8 && c->calib == nullptr && c->share_images) {
+    ShareArgs sa{};
+    sa.images = (const unsigned char*)images; sa.bytes = (long)3 * H * W; sa.n = n_all;
+    sa.hash_bits = c->share_hash_bits;
+    sa.skip_empty = (c->fusion & MILAN_FUSE_SKIP_EMPTY) != 0;
+    sa.list_n = pl.list_n; sa.bbox = pl.bbox; sa.hash = pl.sh_hash; sa.rep = pl.sh_rep;
+    sa.flag = pl.sh_flag; sa.order = pl.order; sa.bbox_c = pl.bbox_c; sa.count = pl.count;
+    sa.class_of = pl.class_of;
+    MILAN_TRY(launch_image_classes(sa, s));
+    MILAN_TRY(launch_zero_fill(features, sizeof(float) * (size_t)n_all * c->d.feature_size, s));
+    order = pl.order;
+    live = pl.count;
+    class_of = pl.class_of;
+  } else if (!spatial && masks != nullptr && image_dtype == MILAN_DTYPE_U8 && c->calib == nullptr &&
       (c->fusion & MILAN_FUSE_SKIP_EMPTY)) {
     hipLaunchKernelGGL(compact_images_kernel, dim3(1), dim3(1024), 0, s, pl.list_n, n_all,
                        pl.bbox, pl.order, pl.bbox_c, pl.count);
@@ -1357,6 +1434,10 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
     order = pl.order;
     live = pl.count;
   }
+  // the device-side counters of milan_image_sharing_stats (only while sharing is enabled: the
+  // default pass launches what it always did); a pass that does not share counts slots == images
+  if (c->share_images && c->share_stats != nullptr)
+    MILAN_TRY(launch_share_count(c->share_stats, n_all, class_of ? live : nullptr, s));
   const int* const bbox = order ? pl.bbox_c : pl.bbox;
   // every trunk launch carries the device-side image count (rows per image = Ho x Wo)
   auto launch_live = [&](GemmArgs g) -> int {
@@ -1436,6 +1517,31 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
     if (cnt == 0) return 0;
     StageScope scope(MILAN_STAGE_ENC_POOL, s);
     const int P = pl.lv.h[level] * pl.lv.w[level];
+    if (class_of != nullptr) {
+      // image sharing: the grid runs over all exemplar slots, `cnt` trunk slots from img0 on
+      if (fast && level >= 3)
+        hipLaunchKernelGGL((masked_pool_kernel<2, true>), dim3(n, (C + 63) / 64), dim3(256), 0, s,
+                           tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
+                           col_off, img0, 1.f / c->act_scale, poison, order, live, class_of, cnt);
+      else if (split && level > 0) {
+        static const bool vec = !(getenv("MILAN_POOL_VEC") && atoi(getenv("MILAN_POOL_VEC")) == 0);
+        const int G = C / 8;
+        if (vec && C % 8 == 0 && (G % 64 == 0 || (G < 64 && 64 % G == 0)) && (col_off % 4) == 0)
+          hipLaunchKernelGGL(masked_pool_split8_kernel<true>, dim3(n, (G + 63) / 64), dim3(256), 0,
+                             s, tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features,
+                             F, col_off, img0, 1.f / c->act_scale, poison, order, G < 64 ? G : 64,
+                             live, class_of, cnt);
+        else
+          hipLaunchKernelGGL((masked_pool_kernel<1, true>), dim3(n, (C + 63) / 64), dim3(256), 0, s,
+                             tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
+                             col_off, img0, 1.f / c->act_scale, poison, order, live, class_of, cnt);
+      } else
+        hipLaunchKernelGGL((masked_pool_kernel<0, true>), dim3(n, (C + 63) / 64), dim3(256), 0, s,
+                           tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
+                           col_off, img0, 1.f, poison, order, live, class_of, cnt);
+      MILAN_CHECK_HIP(hipGetLastError());
+      return 0;
+    }
     if (fast && level >= 3)
       hipLaunchKernelGGL(masked_pool_kernel<2>, dim3(cnt, (C + 63) / 64),
                          dim3(256), 0, s, tap, P, C, level, pl.lv, pl.list_idx,
@@ -1446,7 +1552,7 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
       static const bool vec = !(getenv("MILAN_POOL_VEC") && atoi(getenv("MILAN_POOL_VEC")) == 0);
       const int G = C / 8;
       if (vec && C % 8 == 0 && (G % 64 == 0 || (G < 64 && 64 % G == 0)) && (col_off % 4) == 0)
-        hipLaunchKernelGGL(masked_pool_split8_kernel, dim3(cnt, (G + 63) / 64), dim3(256), 0, s, tap,
+        hipLaunchKernelGGL(masked_pool_split8_kernel<false>, dim3(cnt, (G + 63) / 64), dim3(256), 0, s, tap,
                            P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
                            col_off, img0, 1.f / c->act_scale, poison, order, G < 64 ? G : 64, live);
       else
@@ -1547,8 +1653,15 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
     tail = need <= (size_t)pl.h1 * pl.w1 * wd;
   }
   if (tail) {
+    const unsigned char* s0 = nullptr;
+    if (class_of != nullptr) {
+      MILAN_TRY(launch_zero_fill(pl.tail_s0, ((size_t)n * P4 + 3) & ~(size_t)3, s));
+      hipLaunchKernelGGL(tail_union_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
+                         class_of, P4, pl.tail_s0);
+      s0 = pl.tail_s0;
+    }
     hipLaunchKernelGGL(tail_sets_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
-                       order, live, n, pl.tail_loc, pl.tail_cnt);
+                       order, live, n, pl.tail_loc, pl.tail_cnt, s0);
     hipLaunchKernelGGL(tail_scan_kernel, dim3(3), dim3(256), 0, s, pl.tail_cnt, n, pl.tail_off,
                        pl.tail_U);
     hipLaunchKernelGGL(tail_fill_kernel, dim3(n, 3), dim3(64), 0, s, pl.tail_loc, pl.tail_cnt,

@@ -181,7 +181,8 @@ class Decoder(nn.Module):
                  length: int = 15,
                  strategy: Optional[str] = None,
                  temperature: float = .2,
-                 beam_size: int = 50):
+                 beam_size: int = 50,
+                 share_images: bool = False):
         super().__init__()
         if lm is not None:
             mine, theirs = indexer.vocab.unique, lm.indexer.vocab.unique
@@ -220,6 +221,11 @@ class Decoder(nn.Module):
         # replay each distinct decode pass from a captured hipGraph (helps
         # only launch-bound small batches; see hip.Context.enable_graphs)
         self.use_graphs = os.environ.get('MILAN_GRAPHS', '0') == '1'
+        # exemplar slots of one encoder pass that hold the same uint8 image share one
+        # trunk pass (hip.Context.set_image_sharing; same bits, opt-in: how often real
+        # exemplar sets repeat an image inside a chunk is not measured).  Not a
+        # property of the model: `properties()` and checkpoints do not carry it.
+        self.share_images = bool(share_images)
 
         f = torch.float32
         fs, hs, es, v = (self.feature_size, hidden_size, embedding_size,
@@ -302,7 +308,17 @@ class Decoder(nn.Module):
             'MILAN_ON_SATURATION', 'f32' if self.precision == 'auto' else 'raise')
         if bool(getattr(self._ctx, '_graphs', False)) != bool(self.use_graphs):
             self._ctx.enable_graphs(self.use_graphs)
+        self._apply_share_images(self._ctx)
         return self._ctx
+
+    def _apply_share_images(self, ctx) -> None:
+        """`self.share_images` -> the context's flag (MILAN_SHARE_IMAGES, read when the
+        context was created, stays on when the attribute is left at its default)."""
+        import os
+        want = bool(self.share_images) or bool(
+            int(os.environ.get('MILAN_SHARE_IMAGES') or 0))
+        if bool(ctx.image_sharing) != want:
+            ctx.set_image_sharing(want)
 
     def calibrate(self, images: torch.Tensor, headroom: float = 8.0) -> int:
         """Choose the split-f16 trunk's activation scale from a sample of exemplar
@@ -623,13 +639,27 @@ class Decoder(nn.Module):
                 num_workers: int = 0,
                 device: Optional[Union[str, torch.device]] = None,
                 display_progress_as: Optional[str] = 'predict captions',
+                share_images: Optional[bool] = None,
                 **kwargs: Any) -> Tuple[str, ...]:
         """Feed an entire dataset through the decoder (reference :809-871).
 
         Same arguments and return value.  `batch_size` keeps its meaning for
         the result (allennlp's early exit is evaluated per `batch_size`
         neurons) but the GPU is fed `self.chunk_size` neurons at a time.
+        `share_images` overrides `self.share_images` for this call (identical
+        images inside one chunk go through the trunk once; same captions).
         """
+        if share_images is not None:
+            saved, self.share_images = self.share_images, bool(share_images)
+            try:
+                return self.predict(dataset, mask=mask, image_index=image_index,
+                                    mask_index=mask_index, batch_size=batch_size,
+                                    features=features, num_workers=num_workers,
+                                    device=device,
+                                    display_progress_as=display_progress_as,
+                                    **kwargs)
+            finally:
+                self.share_images = saved
         if device is not None:
             self.to(device)
         chunk = max(batch_size, (self.chunk_size // batch_size) * batch_size)

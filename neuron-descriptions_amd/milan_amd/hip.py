@@ -12,7 +12,7 @@ import ctypes
 import os
 import pathlib
 import weakref
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -143,6 +143,12 @@ SIGNATURES = {
         ctypes.POINTER(ctypes.c_longlong)
     ]),
     'milan_set_fusion': (_I, [_P, _I]),
+    'milan_set_image_sharing': (_I, [_P, _I]),
+    'milan_get_image_sharing': (_I, [_P]),
+    'milan_image_sharing_stats': (_I, [
+        _P, ctypes.POINTER(ctypes.c_longlong),
+        ctypes.POINTER(ctypes.c_longlong), _I, _P
+    ]),
     'milan_set_precision': (_I, [_P, _I]),
     'milan_get_precision': (_I, [_P]),
     'milan_profile_enable': (_I, [_I]),
@@ -423,6 +429,8 @@ class Context:
             self.set_fusion(chain=bool(bits & 1), wide=bool(bits & 2), stem=bool(bits & 4),
                             conv3=bool(bits & 8), skip_empty=bool(bits & 16),
                             bneck=bool(bits & 32), sparse_tail=bool(bits & 64))
+        if os.environ.get('MILAN_SHARE_IMAGES'):  # opt-in image sharing (set_image_sharing)
+            self.set_image_sharing(bool(int(os.environ['MILAN_SHARE_IMAGES'])))
         default = os.environ.get('MILAN_PRECISION')
         if default == 'auto':
             self.set_precision('split_f16')
@@ -483,6 +491,27 @@ class Context:
             (FUSE_STEM if stem else 0) | (FUSE_CONV3 if conv3 else 0) |
             (FUSE_SKIP_EMPTY if skip_empty else 0) | (FUSE_BNECK if bneck else 0) |
             (FUSE_SPARSE_TAIL if sparse_tail else 0)))
+
+    # -- image sharing (opt-in) ------------------------------------------------------
+    def set_image_sharing(self, enable: bool = True) -> None:
+        """Exemplar slots of one encoder pass that hold byte-identical uint8 images share one
+        trunk pass (ResNet trunks, pooled encode; the features keep their bits).  Off by
+        default; float images, `encode_spatial` and AlexNet ignore it."""
+        _check(self.lib.milan_set_image_sharing(self._h, int(bool(enable))))
+
+    @property
+    def image_sharing(self) -> bool:
+        return bool(self.lib.milan_get_image_sharing(self._h))
+
+    def image_sharing_stats(self, clear: bool = False) -> Tuple[int, int]:
+        """(slots, trunk_images) summed over the encoder passes run with sharing enabled:
+        exemplar slots seen and images that went through the trunk.  Synchronises."""
+        slots, trunk = ctypes.c_longlong(), ctypes.c_longlong()
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_image_sharing_stats(self._h, ctypes.byref(slots),
+                                                      ctypes.byref(trunk), int(clear),
+                                                      _stream(self.device)))
+        return int(slots.value), int(trunk.value)
 
     @property
     def precision(self) -> str:

@@ -10,7 +10,9 @@ call whose activations leave its range is rerun in exact fp32 with a warning;
 `f32` = the reference's arithmetic at a third of the speed) and multi-GPU sharding -- with
 `--gpus N` (the script starts its own N ranks) or under `torchrun
 --nproc-per-node N` every rank describes a contiguous block of the neurons and
-rank 0 writes the CSV in the reference's order.
+rank 0 writes the CSV in the reference's order.  `--share-images` (opt-in) lets
+exemplars of one chunk that show the same image share one trunk pass (same
+captions) and prints how many images went through the trunk.
 """
 import argparse
 import csv
@@ -52,6 +54,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument('--gpus', type=int, default=1,
                    help='GPUs of this node to shard the neurons over: N > 1 '
                    'without torchrun starts N ranks itself (default: 1)')
+    p.add_argument('--share-images', action='store_true',
+                   help='exemplars of one chunk that hold the same image share one '
+                   'trunk pass (same captions; prints trunk_images / slots)')
     return p.parse_args(argv)
 
 
@@ -104,12 +109,17 @@ def main(argv=None) -> None:
                                        device=device)
     if args.precision is not None:
         decoder.precision = args.precision
+    decoder.share_images = bool(args.share_images)
     dataset = milannotations.load(
         key, path=env_dir(args.data_dir, 'MILAN_DATA_DIR', 'data') / key)
     captions = describe_shard(decoder, dataset, world, rank,
                               strategy='rerank',
                               temperature=args.temperature,
                               beam_size=args.beam_size, device=device)
+    if args.share_images and getattr(decoder, '_ctx', None) is not None:
+        slots, trunk_images = decoder._ctx.image_sharing_stats()
+        print(f'image sharing (rank {rank}): trunk_images / slots = {trunk_images} / '
+              f'{slots} = {trunk_images / max(1, slots):.4f}')
     if rank == 0:
         out_dir = args.results_dir or env_dir(None, 'MILAN_RESULTS_DIR',
                                               'results') / 'descriptions'

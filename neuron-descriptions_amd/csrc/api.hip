@@ -431,9 +431,11 @@ int milan_conv2d_nhwc(const float* x, int n, int h, int w, int cin,
   MILAN_REQUIRE(x && weight_oihw && y, MILAN_ERR_ARG, "conv2d: null argument");
   set_status_word(nullptr);  // ctx-less entry point: nobody listens for saturation here
   // precision 3 (test hook only): split-f16 with the LDS-strip 3x3 kernel forced;
-  // precision 4 (test hook only): split-f16 with k in tap-major order (GemmArgs::Wt unset)
-  const bool force_strip = precision == 3, tap_major = precision == 4;
-  if (force_strip || tap_major) precision = MILAN_PRECISION_SPLIT_F16;
+  // precision 4 (test hook only): split-f16 with k in tap-major order (GemmArgs::Wt unset);
+  // precision 5 (test hook only): tap-inner, tiles in linear order (GemmArgs::tap_ncls = -1):
+  // what MILAN_TAP_SKIP=0 runs
+  const bool force_strip = precision == 3, tap_major = precision == 4, tap_linear = precision == 5;
+  if (force_strip || tap_major || tap_linear) precision = MILAN_PRECISION_SPLIT_F16;
   MILAN_REQUIRE(!force_strip || MILAN_EXPERIMENTS, MILAN_ERR_ARG,
                 "conv2d: the LDS-strip 3x3 kernel is only in an experiments build "
                 "(make EXPERIMENTS=1)");
@@ -476,6 +478,7 @@ int milan_conv2d_nhwc(const float* x, int n, int h, int w, int cin,
           if (hipMalloc((void**)&wst, sizeof(float) * (size_t)cout * Kp) == hipSuccess) {
             r = make_slice_major(wsp, cout, kh * kw, cin, 4, 2, wst, s);
             g.Wt = wst;
+            if (tap_linear) g.tap_ncls = -1;
           }
         }
         if (MILAN_EXPERIMENTS && r == 0 && kh == 3 && kw == 3 && stride == 1 &&

@@ -64,6 +64,7 @@ enum Epilogue : int {
 //   row m = (img, ho, wo), column kk = (kh, kw, cin) with cin fastest.
 // A plain linear layer is the 1x1 case with H = W = 1 and `a_pix_stride`
 // the row stride of the (possibly strided) input matrix.
+constexpr int MILAN_TAP_CLASSES = 9;  // 3 y-ranges x 3 x-ranges (GemmArgs::tap_cls)
 struct GemmArgs {
   const float* A;
   const float* W;     // packed [N][Kp], Kp = round_up(K, 32), zero padded
@@ -134,7 +135,16 @@ struct GemmArgs {
   // No host read-back, no hipStreamSynchronize (live_rows() below).
   const int* m_live;
   int m_live_mul;
+  // Border-class tiles of a tap-inner launch (gemm.hip, tap_classes(); MILAN_TAP_SKIP).  The
+  // output pixels of an image are grouped by WHICH taps fall inside the input: class c is the
+  // rectangle y0 <= ho < y0 + ny, x0 <= wo < x0 + nx with tap mask (bit kh * KW + kw).  A tile
+  // holds 256 pixels of one class (image-major) and runs only the taps of its mask.  Filled by
+  // the launcher, classes by descending tap count; 0 = linear tile order (all taps).  A caller
+  // sets tap_ncls = -1 to keep a launch on the linear order (test hook).
+  int tap_ncls;
+  int tap_cls[MILAN_TAP_CLASSES][5];  // y0, ny, x0, nx, mask
 };
+static_assert(sizeof(GemmArgs) % 4 == 0, "GemmArgs is reloaded word by word");
 
 enum OutMode : int { OUT_SCALAR = 0, OUT_VEC4 = 1, OUT_SPLIT8 = 2, OUT_F16 = 3 };
 

@@ -46,6 +46,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -142,12 +143,19 @@ __device__ __forceinline__ float row16_sum(float x) {
   return x;
 }
 
-template <int TM, int TN, bool SWZ64 = false>
+template <int TM, int TN, bool SWZ64 = false, bool ROWTAB = false>
 __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
                                              f32x16 (&acc)[TM][TN], float* smem,
                                              int wave, int lane, int row0,
-                                             int col0) {
+                                             int col0, const int* rowtab = nullptr) {
   static_assert(TN == 2, "epilogues assume 64-column wave tiles");
+  // ROWTAB: row r of this wave's tile is output row rowtab[r] (an entry >= M: nothing to
+  // store) instead of row0 + r -- the border-class tiles of the tap-inner ping-pong kernels,
+  // whose rows are not consecutive output pixels.  The table lives in LDS.
+  auto out_row = [&](int r) {
+    if constexpr (ROWTAB) return rowtab[r];
+    else return row0 + r;
+  };
   // ---- epilogues ----------------------------------------------------------------
   // D layout (32x32): col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
   // Staging rows: 64 floats + 4 of padding (the padding staggers consecutive rows over the
@@ -185,7 +193,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
     auto load_res = [&](int i, f32x4 (&r)[8]) {
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
-        const int m = row0 + i * 32 + it * 4 + (lane >> 4);
+        const int m = out_row(i * 32 + it * 4 + (lane >> 4));
         r[it] = (m < g.M && n_ok)
                     ? *reinterpret_cast<const f32x4*>(g.aux + (long)m * g.ldaux + n)
                     : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -201,7 +209,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
         const int row = it * 4 + (lane >> 4);
-        const int m = row0 + i * 32 + row;
+        const int m = out_row(i * 32 + row);
         f32x4 v = *reinterpret_cast<const f32x4*>(stage_out + row * SROW + sw(row, col4));
         if (m < g.M && n_ok) {
           v += bias4;
@@ -245,7 +253,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
     auto load_tgt = [&](int i, int (&t)[8]) {
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
-        const int m = row0 + i * 32 + it * 4 + (lane >> 4);
+        const int m = out_row(i * 32 + it * 4 + (lane >> 4));
         t[it] = m < g.M ? (int)g.lse_tgt[(long)m * g.lse_tgt_stride] : -1;
       }
     };
@@ -257,7 +265,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
         const int row = it * 4 + (lane >> 4);
-        const int m = row0 + i * 32 + row;
+        const int m = out_row(i * 32 + row);
         f32x4 v = *reinterpret_cast<const f32x4*>(stage_out + row * SROW + sw(row, col4));
         v += bias4;
         const bool ok = m < g.M && n_ok;
@@ -308,7 +316,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
     auto load_res = [&](int i, f32x4 (&r)[4][2]) {
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
-        const int m = row0 + i * 32 + it * 8 + (lane >> 3);
+        const int m = out_row(i * 32 + it * 8 + (lane >> 3));
         if (m < g.M && n_ok) {
           const float* ap = g.aux + (long)m * g.ldaux + n;
           r[it][0] = *reinterpret_cast<const f32x4*>(ap);
@@ -329,7 +337,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int row = it * 8 + (lane >> 3);
-        const int m = row0 + i * 32 + row;
+        const int m = out_row(i * 32 + row);
         const f32x4 v0 =
             *reinterpret_cast<const f32x4*>(stage_out + row * SROW + sw(row, col8));
         const f32x4 v1 =
@@ -388,7 +396,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
     auto load_res = [&](int i, f32x4 (&r)[4]) {   // one row-tile ahead (see epilogue_split8)
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
-        const int m = row0 + i * 32 + it * 8 + (lane >> 3);
+        const int m = out_row(i * 32 + it * 8 + (lane >> 3));
         r[it] = (m < g.M && n_ok)
                     ? *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(g.aux) +
                                                       ((long)m * g.ldaux * 4 + n * 2))
@@ -405,7 +413,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int row = it * 8 + (lane >> 3);
-        const int m = row0 + i * 32 + row;
+        const int m = out_row(i * 32 + row);
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(stage_out + row * SROW + sw(row, col8));
         const f32x4 v1 = *reinterpret_cast<const f32x4*>(stage_out + row * SROW + sw(row, col8 + 4));
         if (m < g.M && n_ok) {
@@ -456,7 +464,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
     auto load_c = [&](int i, f32x4 (&c)[2]) {
 #pragma unroll
       for (int it = 0; it < 2; ++it) {
-        const int m = row0 + i * 32 + it * 16 + (lane >> 2);
+        const int m = out_row(i * 32 + it * 16 + (lane >> 2));
         c[it] = (m < g.M && n_ok)
                     ? *reinterpret_cast<const f32x4*>(g.aux + (long)m * g.ldaux + u)
                     : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -470,7 +478,7 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
 #pragma unroll
       for (int it = 0; it < 2; ++it) {
         const int row = it * 16 + (lane >> 2);
-        const int m = row0 + i * 32 + row;
+        const int m = out_row(i * 32 + row);
         f32x4 p[4];
 #pragma unroll
         for (int gate = 0; gate < 4; ++gate)
@@ -518,10 +526,9 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
       const float bias = g.bias ? g.bias[n] : 0.f;
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        const int mbase = row0 + i * 32 + 4 * (lane >> 5);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int m = mbase + (r & 3) + 8 * (r >> 2);
+          const int m = out_row(i * 32 + 4 * (lane >> 5) + (r & 3) + 8 * (r >> 2));
           if (m >= g.M) continue;
           float v = acc[i][j][r] + bias;
           if constexpr (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
@@ -1726,7 +1733,63 @@ struct PpLoader {
   int hw0[4];  // (hi0 << 16) | (wi0 & 0xffff): the row's first input pixel (may be negative)
   unsigned mask[4];  // TAPI: bit kh * KW + kw = that tap of the row is inside the image
   int ia, iw, is_kh, is_kw, is_cin0, seg_soff, cin_limit;
+  unsigned a_bits, w_bits;  // TAPI: taps of the tile's mask still to come in the current slice,
+  int w_slice;              // the lowest set bit = the current one (A and W streams)
 };
+
+// One tile of a tap-inner launch (scalars): 256 pixels of the class rectangle (y0, ny, x0, nx),
+// image-major, from class row 256 * j on; `cnt` class rows exist (live images x ny x nx); only
+// the taps of `mask` are multiplied -- every other tap lies outside the image for EVERY pixel of
+// the class.  The linear tile order is the one class (0, Ho, 0, Wo) with all taps.
+struct TapTile {
+  int y0, ny, x0, nx;
+  unsigned mask;
+  int cnt, j, tile_n;
+};
+
+// Tile of workgroup blockIdx.x (false: none).  Class c owns the blocks [first_c, first_c +
+// round_up(T_c, 8)), T_c = ceil(images x ny x nx / 256) x tiles_n: a multiple of 8 so that a
+// block's XCD is blockIdx.x % 8 in every class and xcd_tile() spreads EACH class over the eight
+// XCDs (a class per XCD would give the interior class to some and the short corner tiles to
+// others).  Classes come by descending tap count = the long tiles are dispatched first.  The
+// image count is the live one (GemmArgs::m_live): the launcher sized the grid for all images.
+__device__ __forceinline__ bool tap_tile(const GemmArgs& g, int tiles_m, int tiles_n, TapTile* t) {
+  const int b = blockIdx.x;
+  if (g.tap_ncls == 0) {
+    const int T = tiles_m * tiles_n;
+    if (b >= T) return false;
+    const int tile = xcd_tile(b, T);
+    t->j = tile / tiles_n;
+    t->tile_n = tile - t->j * tiles_n;
+    t->y0 = 0; t->ny = g.Ho; t->x0 = 0; t->nx = g.Wo;
+    t->mask = 0xffffffffu >> (32 - g.KH * g.KW);
+    t->cnt = g.M;
+    return true;
+  }
+  // (the table is read from the kernel arguments themselves: indexing a by-value copy with a
+  // run-time class number would put the copy into scratch memory)
+  typedef const int __attribute__((address_space(4)))* KArgWords;
+  const KArgWords cw = (KArgWords)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(GemmArgs, tap_cls) / 4;
+  const int imgs = g.M / (g.Ho * g.Wo);
+  int first = 0, cls = -1, cfirst = 0, ctiles = 0;
+#pragma unroll
+  for (int c = 0; c < MILAN_TAP_CLASSES; ++c) {
+    const int T = c < g.tap_ncls ? ((imgs * cw[c * 5 + 1] * cw[c * 5 + 3] + 255) >> 8) * tiles_n : 0;
+    const int B = (T + 7) & ~7;
+    if (cls < 0 && b < first + B) { cls = c; cfirst = first; ctiles = T; }
+    first += B;
+  }
+  if (cls < 0) return false;
+  const int bl = b - cfirst;
+  if ((bl >> 3) >= (ctiles >> 3) + ((bl & 7) < (ctiles & 7))) return false;
+  const int tile = xcd_tile(bl, ctiles);
+  t->j = tile / tiles_n;
+  t->tile_n = tile - t->j * tiles_n;
+  t->y0 = cw[cls * 5]; t->ny = cw[cls * 5 + 1]; t->x0 = cw[cls * 5 + 2]; t->nx = cw[cls * 5 + 3];
+  t->mask = (unsigned)cw[cls * 5 + 4];
+  t->cnt = imgs * t->ny * t->nx;
+  return true;
+}
 
 // Persistent workgroups: a workgroup walks tiles q = blockIdx.x, + gridDim.x, ...  After a
 // tile's main loop the first pairs of the NEXT tile -- A(0), W(0), A(1): exactly the kernel's
@@ -1745,9 +1808,14 @@ struct PpLoader {
 // test of a row's taps is a 9-bit mask made once per tile, the per-pair step is 12 VALU + a
 // few scalar instructions in the read phase.  NOT the tap-major bits (the order of the fp32
 // additions differs); compile-time so that the other launches keep their loop.
+// A TAPI tile is 256 pixels of ONE border class (TapTile `tt`; tile_m = its index inside the
+// class) and steps over the taps that lie in the zero padding for all of them: a skipped pair
+// has an all-zero A operand, its products are +-0 and leave every accumulator as it is, so the
+// bits are those of the linear tile order (MILAN_TAP_SKIP=0: the one whole-image class).
 template <int BNW, bool F16 = false, bool TAPI = false>
 __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int tid, bool prefetched,
-                                                  bool has_next, int ntile_m, int ntile_n) {
+                                                  bool has_next, int ntile_m, int ntile_n,
+                                                  TapTile tt = TapTile{}) {
   const GemmArgs g = reload_gemm_args();
   constexpr int BM = 256, BN = 256, BKP = 32, TM = BNW == 256 ? 4 : 2, TN = 2;
   static_assert(BNW == 256 || BNW == 128, "ping-pong tile: 256 or 128 columns");
@@ -1761,16 +1829,20 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
   const int wm = BNW == 256 ? wave >> 2 : wave >> 1, wn = BNW == 256 ? wave & 3 : wave & 1;
   const int group = wave >> 2;   // ping-pong group: the row half of the tile
   const int HoWo = g.Ho * g.Wo;
-  const int np = g.Kp / BKP;  // k-tile pairs
+  // k-tile pairs (TAPI: the taps of the tile's mask, per 32-channel slice)
+  const int np = TAPI ? (g.Cin / BKP) * __builtin_popcount(tt.mask) : g.Kp / BKP;
   const int k1_pairs = g.A2 ? g.K1 / BKP : 0x7fffffff;
+  const int KHKW = g.KH * g.KW;
+  const int r_kw = 65536 / g.KW + 1;  // tap / KW = (tap * r_kw) >> 16, exact for tap < 32
 
   // ---- loader: piece `it` of this wave = rows it * 64 + wave * 8 .. + 7, one 128-B line each
   auto set_tap = [&](PpLoader& L) {  // per-lane bounds of tap (is_kh, is_kw): once per tap
     if constexpr (TAPI) {
-      const int t = L.is_kh * g.KW + L.is_kw;
+      const int t = __builtin_ctz(L.a_bits);
+      const int kh = (t * r_kw) >> 16, kw = t - kh * g.KW;
 #pragma unroll
       for (int it = 0; it < 4; ++it) L.voff[it] = (L.mask[it] >> t) & 1u ? L.row_off[it] : OOB;
-      L.seg_soff = (int)((((long)L.is_kh * g.Wd + L.is_kw) * g.a_pix_stride) * 4);
+      L.seg_soff = (int)((((long)kh * g.Wd + kw) * g.a_pix_stride) * 4);
       return;
     }
 #pragma unroll
@@ -1781,11 +1853,33 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
     }
     L.seg_soff = (int)((((long)L.is_kh * g.Wd + L.is_kw) * g.a_pix_stride) * 4);
   };
+  // Tile row -> output pixel.  Rows of a tile are consecutive rows m0 + row of the matrix
+  // (image, ho, wo) -- TAPI: of the tile's class rectangle, (image, y, x) with ny x nx pixels
+  // per image.  (The per-lane divisions run on rem0 + row < pixels per image + 256, exact in
+  // float arithmetic with one correction step -- a tenth of an integer division.)
+  const int pix_img = TAPI ? tt.ny * tt.nx : HoWo, pix_row = TAPI ? tt.nx : g.Wo;
+  const int rows_all = TAPI ? tt.cnt : g.M;
+  const float r_howo = 1.0f / (float)pix_img, r_wo = 1.0f / (float)pix_row;
+  auto row_pixel = [&](int m0, int rem0, int row, int* dimg_out, int* ho_out, int* wo_out) {
+    const bool ok = m0 + row < rows_all;
+    const int x = rem0 + (ok ? row : 0);
+    int dimg = (int)((float)x * r_howo);
+    dimg -= (dimg * pix_img > x);
+    dimg += ((dimg + 1) * pix_img <= x);
+    const int rem = x - dimg * pix_img;
+    int ho = (int)((float)rem * r_wo);
+    ho -= (ho * pix_row > rem);
+    ho += ((ho + 1) * pix_row <= rem);
+    *dimg_out = dimg;
+    *wo_out = rem - ho * pix_row + (TAPI ? tt.x0 : 0);
+    *ho_out = ho + (TAPI ? tt.y0 : 0);
+    return ok;
+  };
   auto setup = [&](PpLoader& L, int tm, int tn) {
     const int prow = lane >> 3, pos = lane & 7;
     const int m0 = tm * BM;
-    const int img0 = m0 / HoWo;       // scalar
-    const int rem0 = m0 - img0 * HoWo;
+    const int img0 = m0 / pix_img;       // scalar
+    const int rem0 = m0 - img0 * pix_img;
     // descriptors: A from (image img0, pixel (-pad, -pad)) so that every per-lane offset is
     // non-negative; W from the tile's first row.  Out-of-range offsets read as zeros.
     const long bias = ((long)g.pad * g.Wd + g.pad) * g.a_pix_stride;
@@ -1796,23 +1890,12 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
         0x00020000);
     L.srd_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.W + (long)tn * BNW * g.Kp), 0,
                                                 0x7fffffff, 0x00020000);
-    // (rows of a tile are consecutive: the per-lane divisions run on rem0 + row < HoWo + 256,
-    // exact in float arithmetic with one correction step -- a tenth of an integer division)
-    const float r_howo = 1.0f / (float)HoWo, r_wo = 1.0f / (float)g.Wo;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       const int row = it * 64 + wave * 8 + prow;
       const int q = pos ^ ((row >> 1) & 7);  // source chunk of this lane's LDS position
-      const bool ok = m0 + row < g.M;
-      const int x = rem0 + (ok ? row : 0);
-      int dimg = (int)((float)x * r_howo);
-      dimg -= (dimg * HoWo > x);
-      dimg += ((dimg + 1) * HoWo <= x);
-      const int rem = x - dimg * HoWo;
-      int ho = (int)((float)rem * r_wo);
-      ho -= (ho * g.Wo > rem);
-      ho += ((ho + 1) * g.Wo <= rem);
-      const int wo = rem - ho * g.Wo;
+      int dimg, ho, wo;
+      const bool ok = row_pixel(m0, rem0, row, &dimg, &ho, &wo);
       const int hi0 = ho * g.stride - g.pad, wi0 = wo * g.stride - g.pad;
       L.hw0[it] = (hi0 << 16) | (wi0 & 0xffff);
       if constexpr (TAPI) {
@@ -1834,6 +1917,8 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
       L.vb[it] = (row < BNW && tn * BNW + row < g.N) ? (unsigned)(((long)row * g.Kp + q * 4) * 4) : OOB;
     }
     L.ia = L.iw = L.is_kh = L.is_kw = L.is_cin0 = 0;
+    L.a_bits = L.w_bits = tt.mask;
+    L.w_slice = 0;
     L.cin_limit = g.Cin;
     L.cur_srd = L.srd_a;
     set_tap(L);
@@ -1853,12 +1938,10 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
                                                  L.voff[it], soff, 0, 0);
     }
     if constexpr (TAPI) {
-      if (L.ia + 1 < np) {
+      if (L.ia + 1 < np) {  // the next SET tap of the tile's mask, ascending inside a slice
         ++L.ia;
-        if (++L.is_kw == g.KW) {
-          L.is_kw = 0;
-          if (++L.is_kh == g.KH) { L.is_kh = 0; L.is_cin0 += BKP; }
-        }
+        L.a_bits &= L.a_bits - 1;
+        if (L.a_bits == 0) { L.a_bits = tt.mask; L.is_cin0 += BKP; }
         set_tap(L);
       }
       return;
@@ -1887,7 +1970,8 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
       int woff = wave * (8 * BKP);
       asm volatile("" : "+s"(woff));
       float* dst = w_slot(SLOT) + woff;
-      const int soff = L.iw * (BKP * 4);
+      // (TAPI: the weights keep all KH * KW taps per slice; the pair of (slice, tap))
+      const int soff = (TAPI ? L.w_slice * KHKW + (int)__builtin_ctz(L.w_bits) : L.iw) * (BKP * 4);
       // (128-column tiles: W rows 128..255 of a slot are never read -- wave tiles end at row 127 --
       // so their two pieces are not issued; every counted wait names the A pieces behind them)
 #pragma unroll
@@ -1895,7 +1979,13 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
         __builtin_amdgcn_raw_ptr_buffer_load_lds(L.srd_w, (LDS_AS void*)(dst + it * (64 * BKP)), 16,
                                                  L.vb[it], soff, 0, 0);
     }
-    if (L.iw + 1 < np) ++L.iw;
+    if (L.iw + 1 < np) {
+      ++L.iw;
+      if constexpr (TAPI) {
+        L.w_bits &= L.w_bits - 1;
+        if (L.w_bits == 0) { L.w_bits = tt.mask; ++L.w_slice; }
+      }
+    }
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -2095,8 +2185,26 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = acc[i][j] * ge.acc_scale;
   // staging: A slot 2 + W slot 1 (contiguous 64 KB; the prefetch goes to A0, A1, W0)
-  run_epilogue<TM, TN, true>(ge, acc, a_slot(2), wave, lane, tile_m * BM + wm * (TM * 32),
-                             tile_n * BNW + wn * 64);
+  if constexpr (TAPI) {
+    // Output rows of this wave's TM * 32 tile rows, once per tile, into A slot 0 (free: these
+    // kernels run one tile per workgroup, nothing is prefetched).  Every wave writes and reads
+    // its own copy -- same-wave LDS operations complete in order, no barrier.
+    int* tab = reinterpret_cast<int*>(a_slot(0)) + wave * (TM * 32);
+    const int m0 = tile_m * BM;
+    const int img0 = m0 / pix_img;
+    const int rem0 = m0 - img0 * pix_img;
+#pragma unroll
+    for (int e = 0; e < TM * 32 / 64; ++e) {
+      const int r = e * 64 + lane;
+      int dimg, ho, wo;
+      const bool ok = row_pixel(m0, rem0, wm * (TM * 32) + r, &dimg, &ho, &wo);
+      tab[r] = ok ? ((img0 + dimg) * ge.Ho + ho) * ge.Wo + wo : 0x7fffffff;
+    }
+    run_epilogue<TM, TN, true, true>(ge, acc, a_slot(2), wave, lane, 0, tile_n * BNW + wn * 64, tab);
+  } else {
+    run_epilogue<TM, TN, true>(ge, acc, a_slot(2), wave, lane, tile_m * BM + wm * (TM * 32),
+                               tile_n * BNW + wn * 64);
+  }
 }
 
 template <int BNW>
@@ -2149,28 +2257,33 @@ template <int BNW>
 __global__ __launch_bounds__(512, 2) void igemm_split16_pp32t_kernel(GemmArgs g, int tiles_m,
                                                                      int tiles_n) {
   tiles_m = live_tiles_m(g, tiles_m, 256);
-  const int T = tiles_m * tiles_n;
-  const int q = blockIdx.x;
-  if (q >= T) return;
-  const int tile = xcd_tile(q, T);
-  const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
+  TapTile tt;
+  if (!tap_tile(g, tiles_m, tiles_n, &tt)) return;
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
-  split16_pp32_tile<BNW, false, true>(tile_m, tile_n, tid, false, false, tile_m, tile_n);
+  split16_pp32_tile<BNW, false, true>(tt.j, tt.tile_n, tid, false, false, tt.j, tt.tile_n, tt);
 }
 
 // fast mode (GemmArgs::f16): the same tile with one MFMA per 16 real k
 template <int BNW, bool TAPI>
 __global__ __launch_bounds__(512, 2) void igemm_f16_pp32_kernel(GemmArgs g, int tiles_m, int tiles_n) {
   tiles_m = live_tiles_m(g, tiles_m, 256);
-  const int T = tiles_m * tiles_n;
-  const int q = blockIdx.x;
-  if (q >= T) return;
-  const int tile = xcd_tile(q, T);
-  const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
-  int tid = threadIdx.x;
-  asm volatile("" : "+v"(tid));
-  split16_pp32_tile<BNW, true, TAPI>(tile_m, tile_n, tid, false, false, tile_m, tile_n);
+  if constexpr (TAPI) {
+    TapTile tt;
+    if (!tap_tile(g, tiles_m, tiles_n, &tt)) return;
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    split16_pp32_tile<BNW, true, true>(tt.j, tt.tile_n, tid, false, false, tt.j, tt.tile_n, tt);
+  } else {
+    const int T = tiles_m * tiles_n;
+    const int q = blockIdx.x;
+    if (q >= T) return;
+    const int tile = xcd_tile(q, T);
+    const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    split16_pp32_tile<BNW, true, false>(tile_m, tile_n, tid, false, false, tile_m, tile_n);
+  }
 }
 
 __global__ __launch_bounds__(512, 2) void igemm_split16_pp_kernel(GemmArgs g, int tiles_m,
@@ -2747,6 +2860,69 @@ static bool tap_inner_wanted(const GemmArgs& g) {
          g.Cin % 32 == 0;
 }
 
+// Border classes of a tap-inner launch (GemmArgs::tap_cls) and its grid.  Along one axis the
+// taps k with 0 <= o * stride - pad + k < size form a set per output coordinate o; runs of equal
+// sets are ranges (a few leading coordinates, the middle, a few trailing ones), a class is a
+// (y-range, x-range) rectangle and its tap mask the product of the two sets.  A 3 x 3 kernel
+// gives at most 9.  The launch keeps the linear tile order (tap_ncls = 0, all taps, the grid
+// of tiles_m x tiles_n) when MILAN_TAP_SKIP=0, when the caller asked for it, when the geometry
+// has more classes than the table holds (5 x 5 / pad 2: 25), when some pixel has no tap inside
+// the image at all, or when a class tile -- up to 256 images for a one-pixel class -- would
+// span more input than a 32-bit buffer offset reaches.
+static int tap_classes(GemmArgs& t, int tiles_m, int tiles_n) {
+  static int on = -1;
+  if (on < 0) { const char* e = getenv("MILAN_TAP_SKIP"); on = e ? atoi(e) : 1; }
+  const bool wanted = on && t.tap_ncls >= 0;
+  t.tap_ncls = 0;
+  const int howo = t.Ho * t.Wo;
+  if (!wanted || howo <= 0 || t.M % howo != 0 || (t.m_live && t.m_live_mul % howo != 0))
+    return tiles_m * tiles_n;
+  struct Run { int o0, n; unsigned set; };
+  auto runs = [](int size, int out, int k, int stride, int pad, Run* r) {
+    int n = 0;
+    for (int o = 0; o < out; ++o) {
+      unsigned set = 0;
+      for (int i = 0; i < k; ++i)
+        if (o * stride - pad + i >= 0 && o * stride - pad + i < size) set |= 1u << i;
+      if (n > 0 && r[n - 1].set == set) { ++r[n - 1].n; continue; }
+      if (n == MILAN_TAP_CLASSES) return MILAN_TAP_CLASSES + 1;
+      r[n++] = Run{o, 1, set};
+    }
+    return n;
+  };
+  Run ry[MILAN_TAP_CLASSES], rx[MILAN_TAP_CLASSES];
+  const int nry = runs(t.H, t.Ho, t.KH, t.stride, t.pad, ry);
+  const int nrx = runs(t.Wd, t.Wo, t.KW, t.stride, t.pad, rx);
+  if (nry * nrx > MILAN_TAP_CLASSES) return tiles_m * tiles_n;
+  int cls[MILAN_TAP_CLASSES][5], n = 0, min_pix = howo;
+  for (int a = 0; a < nry; ++a)
+    for (int b = 0; b < nrx; ++b, ++n) {
+      unsigned mask = 0;
+      for (int kh = 0; kh < t.KH; ++kh)
+        for (int kw = 0; kw < t.KW; ++kw)
+          if ((ry[a].set >> kh & 1u) && (rx[b].set >> kw & 1u)) mask |= 1u << (kh * t.KW + kw);
+      if (mask == 0) return tiles_m * tiles_n;
+      const int c[5] = {ry[a].o0, ry[a].n, rx[b].o0, rx[b].n, (int)mask};
+      // insertion by descending tap count (stable): the long tiles are dispatched first
+      int at = n;
+      while (at > 0 && __builtin_popcount((unsigned)cls[at - 1][4]) < __builtin_popcount(mask)) {
+        memcpy(cls[at], cls[at - 1], sizeof(c));
+        --at;
+      }
+      memcpy(cls[at], c, sizeof(c));
+      if (ry[a].n * rx[b].n < min_pix) min_pix = ry[a].n * rx[b].n;
+    }
+  if ((256L / min_pix + 2) * t.a_img_stride * 4 + 64 >= 0x7fffffffL) return tiles_m * tiles_n;
+  const long imgs = t.M / howo;
+  long grid = 0;
+  for (int c = 0; c < n; ++c)
+    grid += ((imgs * cls[c][1] * cls[c][3] + 255) / 256 * tiles_n + 7) / 8 * 8;
+  if (grid >= 0x7fffffffL) return tiles_m * tiles_n;
+  t.tap_ncls = n;
+  memcpy(t.tap_cls, cls, sizeof(int) * 5 * n);
+  return (int)grid;
+}
+
 template <int BNW>
 static int launch_split16_pp32(const GemmArgs& g, hipStream_t s) {
   const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + BNW - 1) / BNW;
@@ -2755,10 +2931,11 @@ static int launch_split16_pp32(const GemmArgs& g, hipStream_t s) {
     GemmArgs t = g;
     t.W = g.Wt;
     t.tap_inner = 1;
+    const int grid = tap_classes(t, tiles_m, tiles_n);
     profile_tag_kernel(BNW == 256 ? MILAN_KERNEL_PP32T_256 : MILAN_KERNEL_PP32_128);
     auto kern = igemm_split16_pp32t_kernel<BNW>;
     MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, s, t, tiles_m, tiles_n);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, t, tiles_m, tiles_n);
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   }
@@ -2796,9 +2973,10 @@ static int launch_f16_pp32(const GemmArgs& g, hipStream_t s) {
     GemmArgs t = g;
     t.W = g.Wt;
     t.tap_inner = 1;
+    const int grid = tap_classes(t, tiles_m, tiles_n);
     auto kern = igemm_f16_pp32_kernel<BNW, true>;
     MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, s, t, tiles_m, tiles_n);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, t, tiles_m, tiles_n);
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   }

@@ -273,7 +273,14 @@ enum { MILAN_PRECISION_F32 = 0, MILAN_PRECISION_SPLIT_F16 = 1,
  *                     the shrunk mask: the last two bottlenecks run only at those pixels and
  *                     the 3x3 neighbourhoods they depend on (row sets built on the device
  *                     from the pooling's own pixel lists; dense when no masks are given).
- * Default: all seven (environment MILAN_CHAIN=<flags> overrides at context creation).
+ *   MILAN_FUSE_TAIL_LISTS  (needs MILAN_FUSE_SPARSE_TAIL: the flag without it is rejected) those
+ *                     row sets are handed to the GEMM tile itself as device-side row lists: a tile is 256 listed pixels, reads
+ *                     its operand rows and writes its output rows in place in the dense tensors
+ *                     -- no gather / scatter / im2col copies -- and the same treatment reaches
+ *                     down to the first block of the last stage (its c1 at the pixels its
+ *                     strided 3x3 reads) and to c2 / c3 of the last block of the stage before
+ *                     (at those pixels, the downsample's and the level-3 pooling's).  Same bits.
+ * Default: all eight (environment MILAN_CHAIN=<flags> overrides at context creation).
  * Not a flag but the same idea in the decoder: the rerank pass (decoders.py:495-512) scores
  * one LM row per distinct beam PREFIX instead of one per beam (csrc/decoder.hip,
  * lm_score_dedup; MILAN_LM_DEDUP=0 restores every row; same bits). */
@@ -284,8 +291,10 @@ enum { MILAN_FUSE_CHAIN = 1,       /* planes <= 128 (layer1, layer2): HBM-bound,
        MILAN_FUSE_CONV3 = 8,       /* layer1's 3x3 convs: weights in registers (csrc/conv3.hip) */
        MILAN_FUSE_SKIP_EMPTY = 16,
        MILAN_FUSE_BNECK = 32,      /* layer1: the 3x3 conv in front of the chain launch (round 6) */
-       MILAN_FUSE_SPARSE_TAIL = 64 };  /* the last two bottlenecks only at the pixels the level-4
+       MILAN_FUSE_SPARSE_TAIL = 64,    /* the last two bottlenecks only at the pixels the level-4
                                           pooling (and their 3x3 neighbourhoods) read (round 6) */
+       MILAN_FUSE_TAIL_LISTS = 128 };  /* ... on row lists inside the GEMM tile, and extended down
+                                          to the last block of the stage before */
 int milan_set_fusion(milan_ctx* ctx, int flags);
 int milan_set_precision(milan_ctx* ctx, int precision);
 int milan_get_precision(const milan_ctx* ctx);

@@ -134,6 +134,15 @@ struct GemmArgs {
   // tiles lie beyond it exit, the tile that straddles it masks its rows as for a ragged M.
   // No host read-back, no hipStreamSynchronize (live_rows() below).
   const int* m_live;
+  // Row list (gemm.hip, split16_pp32_tile<.., LIST>; encoder.hip, MILAN_FUSE_TAIL_LISTS): when
+  // row_list != nullptr the launch computes only the output rows row_list[0 .. *m_live)
+  // (m_live_mul = 1) -- ascending rows (slot * Ho + ho) * Wo + wo of the DENSE tensors: tile
+  // row r of tile tm is entry 256 * tm + r, its operand rows are read and its output row is
+  // written in place, unlisted rows are not touched.  256 consecutive entries must span at
+  // most 256 slots (the caller's guarantee; row_list_supported() checks the offset range of
+  // that many images).  Same products, same order, same roundings per output value as the
+  // dense launch.
+  const int* row_list;
   int m_live_mul;
   // Border-class tiles of a tap-inner launch (gemm.hip, tap_classes(); MILAN_TAP_SKIP).  The
   // output pixels of an image are grouped by WHICH taps fall inside the input: class c is the
@@ -149,6 +158,9 @@ static_assert(sizeof(GemmArgs) % 4 == 0, "GemmArgs is reloaded word by word");
 enum OutMode : int { OUT_SCALAR = 0, OUT_VEC4 = 1, OUT_SPLIT8 = 2, OUT_F16 = 3 };
 
 int launch_gemm(const GemmArgs& g, hipStream_t s);
+// whether launch_gemm() can run `g` on a row list (GemmArgs::row_list) with the bits of the
+// dense launch: the 256-column ping-pong tile, offsets of 256 images within 32 bits
+bool row_list_supported(const GemmArgs& g);
 // Status word of the context whose entry point is running on this thread (api.hip sets it
 // on entry): every kernel that writes split format ORs MILAN_STATUS_SATURATED into it when
 // its clamp to +-65504 was hit (split8_* below).  nullptr = nobody is listening.
@@ -509,7 +521,8 @@ struct milan_ctx {
                       // decoder, LM and the front of the trunk stay split)
   int trunk_f16 = 0;  // MILAN_PRECISION_F16: layer3 / layer4 of a bottleneck trunk on plain f16
   int fusion = MILAN_FUSE_CHAIN | MILAN_FUSE_CHAIN_WIDE | MILAN_FUSE_STEM | MILAN_FUSE_CONV3 |
-               MILAN_FUSE_SKIP_EMPTY | MILAN_FUSE_BNECK | MILAN_FUSE_SPARSE_TAIL;  // milan_set_fusion
+               MILAN_FUSE_SKIP_EMPTY | MILAN_FUSE_BNECK | MILAN_FUSE_SPARSE_TAIL |
+               MILAN_FUSE_TAIL_LISTS;  // milan_set_fusion
   // hipGraph cache of whole decode passes (milan_set_graph_capture)
   int graph_capture = 0;
   struct GraphEntry { std::vector<char> key; hipGraphExec_t exec = nullptr; int seen = 0; };

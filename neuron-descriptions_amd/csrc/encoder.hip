@@ -998,23 +998,28 @@ constexpr int kTailMaxP = 1024;   // pixels of the last stage per image (7 x 7 =
 // here as a byte map s0[c][p] (zero-filled; every writer stores the same 1).  Dilation
 // distributes over union, so sets 1 and 2 of tail_sets_kernel are then exactly the pixels
 // some member's pooling depends on.
+// (level 3: the same for the level-3 lists, which join set W of tail_sets3_kernel)
 __global__ __launch_bounds__(64) void tail_union_kernel(
     const int* __restrict__ list_idx, const int* __restrict__ list_n, Levels lv,
-    const int* __restrict__ class_of, int P, unsigned char* __restrict__ s0) {
+    const int* __restrict__ class_of, int P, unsigned char* __restrict__ s0, int level) {
   const int i = blockIdx.x, c = class_of[i];
   if (c < 0) return;
-  const long base = (long)i * lv.per_image + lv.off[4];
-  const int cnt = list_n[i * 5 + 4];
+  const long base = (long)i * lv.per_image + lv.off[level];
+  const int cnt = list_n[i * 5 + level];
   for (int e = threadIdx.x; e < cnt; e += 64) s0[(long)c * P + list_idx[base + e]] = 1;
 }
 
 // sets k = 0 (listed pixels), 1 (dilated once), 2 (dilated twice) of batch slot j, ascending
 // (s0 != nullptr: set 0 is given as a byte map, see tail_union_kernel)
+// dummy (MILAN_FUSE_TAIL_LISTS): a live slot whose set 0 is empty -- a mask that misses every
+// centre of the last level -- gets pixel 0, so that EVERY set of every live slot is non-empty
+// and 256 consecutive entries of a row list span at most 256 slots (GemmArgs::row_list).
+// Nothing reads the extra rows.
 __global__ __launch_bounds__(64) void tail_sets_kernel(
     const int* __restrict__ list_idx, const int* __restrict__ list_n, Levels lv,
     const int* __restrict__ order, const int* __restrict__ live, int n,
     int* __restrict__ loc, int* __restrict__ cnt,
-    const unsigned char* __restrict__ s0 = nullptr) {
+    const unsigned char* __restrict__ s0, int dummy) {
   __shared__ unsigned char s[3][kTailMaxP];
   const int j = blockIdx.x, lane = threadIdx.x;
   const int h = lv.h[4], w = lv.w[4], P = h * w;
@@ -1033,6 +1038,12 @@ __global__ __launch_bounds__(64) void tail_sets_kernel(
     for (int i = lane; i < c; i += 64) s[0][list_idx[base + i]] = 1;
   }
   __syncthreads();
+  if (dummy) {
+    int any = 0;
+    for (int p = lane; p < P; p += 64) any |= s[0][p];
+    if (__ballot(any != 0) == 0ull && lane == 0) s[0][0] = 1;
+    __syncthreads();
+  }
   for (int k = 1; k < 3; ++k) {
     for (int p = lane; p < P; p += 64) {
       const int y = p / w, x = p - y * w;
@@ -1057,6 +1068,68 @@ __global__ __launch_bounds__(64) void tail_sets_kernel(
       count += __popcll(m);
     }
     if (lane == 0) cnt[k * n + j] = count;
+  }
+}
+
+// Row sets of the stage BEFORE the last one (MILAN_FUSE_TAIL_LISTS), from set k0 of the last
+// stage = the pixels its first block's output is needed at.  That block's k x k / strided conv
+// c2 reads its c1 output -- a 1x1 conv: the block input -- at
+//   set 0 (V) = { (y * stride - pad + a, x * stride - pad + b) inside the image },
+// its downsample conv reads the block input at (y * ds_stride, x * ds_stride), and the pooling
+// of this stage reads its own pixel list:
+//   set 1 (W) = V + the downsample's pixels + the listed pixels (s3 != nullptr: their union
+//               over the members of the trunk slot, see tail_union_kernel)
+// is where the last block of this stage is needed.  Ascending, like tail_sets_kernel.
+constexpr int kTailMaxP3 = 4096;  // pixels of that stage per image (14 x 14 = 196 at 224 x 224)
+__global__ __launch_bounds__(64) void tail_sets3_kernel(
+    const int* __restrict__ loc, const int* __restrict__ cnt, int k0,
+    const int* __restrict__ list_idx, const int* __restrict__ list_n, Levels lv,
+    const int* __restrict__ order, const int* __restrict__ live, int n, int kh, int kw,
+    int stride, int pad, int ds_stride, const unsigned char* __restrict__ s3,
+    int* __restrict__ loc3, int* __restrict__ cnt3) {
+  __shared__ unsigned char s[2][kTailMaxP3];
+  const int j = blockIdx.x, lane = threadIdx.x;
+  const int w4 = lv.w[4], P4 = lv.h[4] * w4;
+  const int h3 = lv.h[3], w3 = lv.w[3], P3 = h3 * w3;
+  if (live != nullptr && j >= *live) {
+    if (lane < 2) cnt3[lane * n + j] = 0;
+    return;
+  }
+  for (int p = lane; p < P3; p += 64) {
+    s[0][p] = 0;
+    s[1][p] = s3 != nullptr ? s3[(long)j * P3 + p] : 0;
+  }
+  __syncthreads();
+  if (s3 == nullptr) {
+    const int img = order ? order[j] : j;
+    const long base = (long)img * lv.per_image + lv.off[3];
+    const int c = list_n[img * 5 + 3];
+    for (int i = lane; i < c; i += 64) s[1][list_idx[base + i]] = 1;
+  }
+  const int c0 = cnt[k0 * n + j];
+  const int* l0 = loc + ((long)k0 * n + j) * P4;
+  for (int i = lane; i < c0; i += 64) {
+    const int p = l0[i], y = p / w4, x = p - y * w4;
+    for (int a = 0; a < kh; ++a)
+      for (int b = 0; b < kw; ++b) {
+        const int yy = y * stride - pad + a, xx = x * stride - pad + b;
+        if (yy >= 0 && yy < h3 && xx >= 0 && xx < w3) { s[0][yy * w3 + xx] = 1; s[1][yy * w3 + xx] = 1; }
+      }
+    const int yd = y * ds_stride, xd = x * ds_stride;
+    if (yd < h3 && xd < w3) s[1][yd * w3 + xd] = 1;
+  }
+  __syncthreads();
+  for (int k = 0; k < 2; ++k) {
+    int count = 0;
+    int* out = loc3 + ((long)k * n + j) * P3;
+    for (int p0 = 0; p0 < P3; p0 += 64) {
+      const int p = p0 + lane;
+      const bool nz = p < P3 && s[k][p];
+      const unsigned long long m = __ballot(nz);
+      if (nz) out[count + __popcll(m & ((1ull << lane) - 1ull))] = p;
+      count += __popcll(m);
+    }
+    if (lane == 0) cnt3[k * n + j] = count;
   }
 }
 
@@ -1151,6 +1224,10 @@ struct EncPlan {
   void* sh_hash;
   int *sh_rep, *sh_flag, *class_of;
   unsigned char* tail_s0;
+  // MILAN_FUSE_TAIL_LISTS: sets V, W of the stage before the last (tail_sets3_kernel), laid
+  // out like the tail_* arrays above with 2 sets of P3 pixels; byte map of the level-3 unions
+  int *tail_loc3, *tail_cnt3, *tail_off3, *tail_rows3, *tail_U3;
+  unsigned char* tail_s3;
 };
 
 static int conv_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
@@ -1211,6 +1288,13 @@ static int plan(const milan_ctx* c, int n, int H, int W, Arena& a, EncPlan* pl) 
     pl->sh_flag = a.get<int>((size_t)n);
     pl->class_of = a.get<int>((size_t)n);
     pl->tail_s0 = a.get<unsigned char>(((size_t)n * P4 + 3) & ~(size_t)3);
+    const size_t P3 = (size_t)lv.h[3] * lv.w[3];
+    pl->tail_loc3 = a.get<int>(2 * (size_t)n * P3);
+    pl->tail_rows3 = a.get<int>(2 * (size_t)n * P3);
+    pl->tail_cnt3 = a.get<int>(2 * (size_t)n);
+    pl->tail_off3 = a.get<int>(2 * (size_t)n);
+    pl->tail_U3 = a.get<int>(4);
+    pl->tail_s3 = a.get<unsigned char>(((size_t)n * P3 + 3) & ~(size_t)3);
   }
   return 0;
 }
@@ -1652,16 +1736,18 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
     const size_t need = (size_t)P4 * ((size_t)2 * lb.c1.cin + lb.c3.cout + (size_t)11 * lb.c1.cout);
     tail = need <= (size_t)pl.h1 * pl.w1 * wd;
   }
+  // MILAN_FUSE_TAIL_LISTS: the row sets go to the GEMM tile as row lists (GemmArgs::row_list)
+  const bool lists = tail && (c->fusion & MILAN_FUSE_TAIL_LISTS);
   if (tail) {
     const unsigned char* s0 = nullptr;
     if (class_of != nullptr) {
       MILAN_TRY(launch_zero_fill(pl.tail_s0, ((size_t)n * P4 + 3) & ~(size_t)3, s));
       hipLaunchKernelGGL(tail_union_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
-                         class_of, P4, pl.tail_s0);
+                         class_of, P4, pl.tail_s0, 4);
       s0 = pl.tail_s0;
     }
     hipLaunchKernelGGL(tail_sets_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
-                       order, live, n, pl.tail_loc, pl.tail_cnt, s0);
+                       order, live, n, pl.tail_loc, pl.tail_cnt, s0, lists ? 1 : 0);
     hipLaunchKernelGGL(tail_scan_kernel, dim3(3), dim3(256), 0, s, pl.tail_cnt, n, pl.tail_off,
                        pl.tail_U);
     hipLaunchKernelGGL(tail_fill_kernel, dim3(n, 3), dim3(64), 0, s, pl.tail_loc, pl.tail_cnt,
@@ -1719,6 +1805,124 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   };
+
+  // ... the same block on row lists (MILAN_FUSE_TAIL_LISTS): the three convs as the dense pass
+  // launches them, each over its set's rows of the DENSE tensors -- no copy, no compact scratch
+  auto on_list = [&](GemmArgs g, const int* rows, const int* U) {
+    g.row_list = rows; g.m_live = U; g.m_live_mul = 1;
+    return g;
+  };
+  auto list_ok = [&](const GemmArgs& g) { return row_list_supported(on_list(g, pl.tail_rows, pl.tail_U)); };
+  auto tail_block_args = [&](const Bottleneck& b, const float* X, float* Y, float* T1, int hh,
+                             int ww, GemmArgs* g1, GemmArgs* g2, GemmArgs* g3) {
+    int h1, w1, h2, w2, h3, w3;
+    *g1 = conv_args(b.c1, X, n, hh, ww, T1, EPI_BIAS_RELU, nullptr, c->zero, &h1, &w1, true);
+    *g2 = conv_args(b.c2, T1, n, h1, w1, pl.t2, EPI_BIAS_RELU, nullptr, c->zero, &h2, &w2, true);
+    *g3 = conv_args(b.c3, pl.t2, n, h2, w2, Y, EPI_BIAS_RES_RELU, X, c->zero, &h3, &w3, true);
+  };
+  auto tail_block_lists_ok = [&](const Bottleneck& b, int hh, int ww) {
+    GemmArgs g1, g2, g3;
+    tail_block_args(b, pl.x0, pl.x1, pl.t1, hh, ww, &g1, &g2, &g3);
+    return lists && list_ok(g1) && list_ok(g2) && list_ok(g3);
+  };
+  auto tail_block_lists = [&](const Bottleneck& b, const float* X, float* Y, float* T1, int hh,
+                              int ww, int kM, int kO) -> int {
+    GemmArgs g1, g2, g3;
+    tail_block_args(b, X, Y, T1, hh, ww, &g1, &g2, &g3);
+    const int* rowsM = pl.tail_rows + (long)kM * n * P4;
+    const int* rowsO = pl.tail_rows + (long)kO * n * P4;
+    MILAN_TRY(launch_gemm(on_list(g1, rowsM, pl.tail_U + kM), s));
+    MILAN_TRY(launch_gemm(on_list(g2, rowsO, pl.tail_U + kO), s));
+    MILAN_TRY(launch_gemm(on_list(g3, rowsO, pl.tail_U + kO), s));
+    return 0;
+  };
+  // c3 and the downsample of a stage's first block as ONE GEMM over [t2 | x(strided)]
+  auto two_source_args = [&](const Bottleneck& b, const float* xin, float* yo, int hh, int ww,
+                             int h2, int w2, int* h3, int* w3) {
+    GemmArgs g3 = conv_args(b.c3d, pl.t2, n, h2, w2, yo, EPI_BIAS_RELU,
+                            nullptr, c->zero, h3, w3, true);
+    g3.Cin = b.c3.cin;              // geometry of source 1 (t2)
+    g3.a_pix_stride = b.c3.cin;
+    g3.a_img_stride = (long)h2 * w2 * b.c3.cin;
+    g3.A2 = xin; g3.K1 = b.c3.K; g3.H2 = hh; g3.W2d = ww;
+    g3.stride2 = b.down.stride;
+    g3.a2_pix_stride = b.down.cin;
+    g3.a2_img_stride = (long)hh * ww * b.down.cin;
+    g3.flop_k = b.c3.K + b.down.K;
+    return g3;
+  };
+  // ... extended downwards: the first block of the last stage feeds nothing but the tail blocks,
+  // which read it at tail set k0 -- its c2 and c3 + downsample run over that set, its c1 over
+  // the pixels V its strided c2 reads there; and the last block of the stage before feeds
+  // nothing but that block and its own stage's pooling: its c2 / c3 run over W
+  // (tail_sets3_kernel).  Decided here, before the stage loop, from the geometry alone.
+  const int h3l = pl.lv.h[3], w3l = pl.lv.w[3], P3 = h3l * w3l;
+  int k0 = -1;
+  bool lists_l3 = false;
+  // (experiments build: MILAN_TAPS_INNER re-orders the 3x3 launches of the stage loop, which
+  // have no list form then -- those blocks keep today's path)
+  bool lists_down = lists;
+#if MILAN_EXPERIMENTS
+  if (getenv("MILAN_TAPS_INNER") && atoi(getenv("MILAN_TAPS_INNER"))) lists_down = false;
+#endif
+  if (lists_down && c->blocks[3].size() >= 2 && c->blocks[3].size() <= 3 && P3 <= kTailMaxP3) {
+    const std::vector<Bottleneck>& b4 = c->blocks[3];
+    const Bottleneck& f = b4[0];
+    bool ok = true;
+    for (size_t bi = 1; bi < b4.size(); ++bi) ok = ok && tail_block_ok(b4[bi]);   // they run on sets
+    ok = ok && !f.basic && f.has_down && f.c3d.ws && f.c3d.cout > 64 && f.c1.kh == 1 && f.c1.kw == 1 &&
+         f.c1.stride == 1 && f.c1.pad == 0 && f.c3.kh == 1 && f.c3.kw == 1 && f.c3.stride == 1 &&
+         f.c3.pad == 0 && f.down.kh == 1 && f.down.kw == 1 && f.down.pad == 0 && f.c2.wst &&
+         f.c1.bias_s && f.c2.bias_s && f.c3d.bias_s &&
+         conv_out(h3l, f.c2.kh, f.c2.stride, f.c2.pad) == pl.lv.h[4] &&
+         conv_out(w3l, f.c2.kw, f.c2.stride, f.c2.pad) == pl.lv.w[4] &&
+         conv_out(h3l, 1, f.down.stride, 0) == pl.lv.h[4] &&
+         conv_out(w3l, 1, f.down.stride, 0) == pl.lv.w[4] &&
+         !(f.down.stride == 1 && (c->fusion & (f.c3.cin >= 256 ? MILAN_FUSE_CHAIN_WIDE : MILAN_FUSE_CHAIN)));
+    if (ok) {
+      int h1, w1, h2, w2, h3, w3;
+      GemmArgs g1 = conv_args(f.c1, pl.x0, n, h3l, w3l, pl.t1, EPI_BIAS_RELU, nullptr, c->zero, &h1, &w1, true);
+      GemmArgs g2 = conv_args(f.c2, pl.t1, n, h1, w1, pl.t2, EPI_BIAS_RELU, nullptr, c->zero, &h2, &w2, true);
+      GemmArgs g3 = two_source_args(f, pl.x0, pl.x1, h3l, w3l, h2, w2, &h3, &w3);
+      ok = list_ok(g1) && list_ok(g2) && list_ok(g3);
+    }
+    if (ok) k0 = (int)b4.size() - 1;
+    const std::vector<Bottleneck>& b3 = c->blocks[2];
+    if (ok && b3.size() >= 2) {
+      const Bottleneck& l = b3.back();
+      bool ok3 = !l.basic && !l.has_down && l.c2.wst && l.c2.bias_s && l.c3.bias_s && l.c2.stride == 1 &&
+                 l.c3.kh == 1 && l.c3.kw == 1 && l.c3.stride == 1 && l.c3.pad == 0 &&
+                 conv_out(h3l, l.c2.kh, 1, l.c2.pad) == h3l && conv_out(w3l, l.c2.kw, 1, l.c2.pad) == w3l;
+      if (ok3) {
+        int h2, w2, h3, w3;
+        GemmArgs g2 = conv_args(l.c2, pl.t1, n, h3l, w3l, pl.t2, EPI_BIAS_RELU, nullptr, c->zero, &h2, &w2, true);
+        GemmArgs g3 = conv_args(l.c3, pl.t2, n, h2, w2, pl.x1, EPI_BIAS_RES_RELU, pl.x0, c->zero, &h3, &w3, true);
+        ok3 = list_ok(g2) && list_ok(g3);
+      }
+      lists_l3 = ok3;
+    }
+  }
+  if (k0 >= 0) {
+    const Bottleneck& f = c->blocks[3][0];
+    const unsigned char* s3 = nullptr;
+    if (class_of != nullptr) {
+      // image sharing: a trunk slot's level-3 pixels are the union of its members' lists
+      MILAN_TRY(launch_zero_fill(pl.tail_s3, ((size_t)n * P3 + 3) & ~(size_t)3, s));
+      hipLaunchKernelGGL(tail_union_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
+                         class_of, P3, pl.tail_s3, 3);
+      s3 = pl.tail_s3;
+    }
+    hipLaunchKernelGGL(tail_sets3_kernel, dim3(n), dim3(64), 0, s, pl.tail_loc, pl.tail_cnt, k0,
+                       pl.list_idx, pl.list_n, pl.lv, order, live, n, f.c2.kh, f.c2.kw, f.c2.stride,
+                       f.c2.pad, f.down.stride, s3, pl.tail_loc3, pl.tail_cnt3);
+    hipLaunchKernelGGL(tail_scan_kernel, dim3(2), dim3(256), 0, s, pl.tail_cnt3, n, pl.tail_off3,
+                       pl.tail_U3);
+    hipLaunchKernelGGL(tail_fill_kernel, dim3(n, 2), dim3(64), 0, s, pl.tail_loc3, pl.tail_cnt3,
+                       pl.tail_off3, n, P3, pl.tail_rows3);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  const int* rowsV = pl.tail_rows3;
+  const int* rowsW = pl.tail_rows3 + (long)n * P3;
 
   // 4. bottleneck stages; tap after each stage
   float *x = pl.x0, *y = pl.x1;
@@ -1778,7 +1982,8 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
         // the last block is needed at the listed pixels (set 0) and its c1 at set 1; the block
         // before it at set 1 and its c1 at set 2
         const int kO = bi + 1 == blocks.size() ? 0 : 1;
-        MILAN_TRY(tail_block(b, x, y, t1buf, h, w, kO + 1, kO));
+        if (tail_block_lists_ok(b, h, w)) MILAN_TRY(tail_block_lists(b, x, y, t1buf, h, w, kO + 1, kO));
+        else MILAN_TRY(tail_block(b, x, y, t1buf, h, w, kO + 1, kO));
         float* tmp = x; x = y; y = tmp;
         continue;
       }
@@ -1864,6 +2069,28 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
           b.c1.kw == 1 && b.c1.stride == 1 && b.c1.cin == 64 && b.c1.cout == 64 &&
           b.c1.K == b.c1.Kp && h1 == h && w1 == w &&
           chain_conv_c1_supported(chain_P, b.down.cin, chain_NR, h1, w1);
+      if (k0 >= 0 && li == 3 && bi == 0 && !chain_plain && !chain_ds && h == h3l && w == w3l) {
+        // MILAN_FUSE_TAIL_LISTS: c1 at V, c2 and c3 + downsample at tail set k0
+        const int* rows0 = pl.tail_rows + (long)k0 * n * P4;
+        if (c1_pending) MILAN_TRY(launch_gemm(on_list(g1, rowsV, pl.tail_U3), s));
+        MILAN_TRY(launch_gemm(on_list(g2, rows0, pl.tail_U + k0), s));
+        GemmArgs g3 = two_source_args(b, x, y, h, w, h2, w2, &h3, &w3);
+        MILAN_TRY(launch_gemm(on_list(g3, rows0, pl.tail_U + k0), s));
+        float* tmp = x; x = y; y = tmp;
+        h = h3; w = w3;
+        continue;
+      }
+      if (lists_l3 && k0 >= 0 && li == 2 && last_of_stage && !chain_plain && !chain_ds &&
+          h == h3l && w == w3l) {
+        // ... the last block of the stage before: c1 as ever (dense), c2 and c3 at W
+        if (c1_pending) MILAN_TRY(gemm_t(g1));
+        MILAN_TRY(launch_gemm(on_list(g2, rowsW, pl.tail_U3 + 1), s));
+        GemmArgs g3 = conv_args(b.c3, pl.t2, n, h2, w2, y, EPI_BIAS_RES_RELU, x, c->zero, &h3, &w3, split);
+        MILAN_TRY(launch_gemm(on_list(g3, rowsW, pl.tail_U3 + 1), s));
+        float* tmp = x; x = y; y = tmp;
+        h = h3; w = w3;
+        continue;
+      }
       if (c1_pending && !c1_front) MILAN_TRY(gemm_t(g1));
       if (conv_front) {
         // (nothing to launch here)
@@ -1915,16 +2142,7 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
       if (b.has_down && split && b.c3d.ws && b.c3d.cout > 64) {
         // c3 and the downsample as ONE GEMM over [t2 | x(strided)]
         int h3, w3;
-        GemmArgs g3 = conv_args(b.c3d, pl.t2, n, h2, w2, y, EPI_BIAS_RELU,
-                                nullptr, c->zero, &h3, &w3, true);
-        g3.Cin = b.c3.cin;              // geometry of source 1 (t2)
-        g3.a_pix_stride = b.c3.cin;
-        g3.a_img_stride = (long)h2 * w2 * b.c3.cin;
-        g3.A2 = x; g3.K1 = b.c3.K; g3.H2 = h; g3.W2d = w;
-        g3.stride2 = b.down.stride;
-        g3.a2_pix_stride = b.down.cin;
-        g3.a2_img_stride = (long)h * w * b.down.cin;
-        g3.flop_k = b.c3.K + b.down.K;
+        GemmArgs g3 = two_source_args(b, x, y, h, w, h2, w2, &h3, &w3);
         MILAN_TRY(gemm_t(g3));
         float* tmp = x; x = y; y = tmp;
         h = h3; w = w3;

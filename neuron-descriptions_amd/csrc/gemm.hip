@@ -1454,6 +1454,9 @@ __global__ __launch_bounds__(512, 2) void igemm_split16_linp_kernel(GemmArgs g,
 // the next tile's set-up inputs nor the epilogue's arguments occupy scalar registers
 // during the main loop (they spilled into vector registers and from there to scratch --
 // VALU and VMEM traffic inside a loop whose waits count VMEM operations).
+// (DENSE_M: M stays the launch's dense row count -- the epilogue of a row-list tile bounds
+// its output rows by it, the list's length is read separately)
+template <bool DENSE_M = false>
 __device__ __forceinline__ GemmArgs reload_gemm_args() {
   typedef const int __attribute__((address_space(4)))* KArgWords;
   KArgWords kw = (KArgWords)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1463,7 +1466,8 @@ __device__ __forceinline__ GemmArgs reload_gemm_args() {
 #pragma unroll
   for (unsigned i = 0; i < sizeof(GemmArgs) / 4; ++i) words[i] = kw[i];
   __builtin_memcpy(&g, words, sizeof(GemmArgs));
-  g.M = live_rows(g.m_live, g.m_live_mul, g.M);   // (GemmArgs::m_live: row count on the device)
+  if constexpr (!DENSE_M)
+    g.M = live_rows(g.m_live, g.m_live_mul, g.M);   // (GemmArgs::m_live: row count on the device)
   return g;
 }
 
@@ -1812,7 +1816,15 @@ __device__ __forceinline__ bool tap_tile(const GemmArgs& g, int tiles_m, int til
 // class) and steps over the taps that lie in the zero padding for all of them: a skipped pair
 // has an all-zero A operand, its products are +-0 and leave every accumulator as it is, so the
 // bits are those of the linear tile order (MILAN_TAP_SKIP=0: the one whole-image class).
-template <int BNW, bool F16 = false, bool TAPI = false>
+// LIST (GemmArgs::row_list): tile row r of tile tile_m is the dense output row row_list[256 *
+// tile_m + r] = (slot, ho, wo), entries past the live count behave like rows past M.  The
+// descriptors start at the slot of the tile's FIRST entry (the list ascends, the caller bounds
+// the slots a tile spans: offsets stay non-negative and within 32 bits); the A offsets of both
+// sources and the tap mask follow from the entry's pixel, the epilogue stores (and reads its
+// residual) through the row table.  A TAPI list tile is given the whole-image class: all taps
+// with the per-row mask -- the products that are skipped elsewhere are +-0.  One tile per
+// workgroup (the row table lives in A slot 0).
+template <int BNW, bool F16 = false, bool TAPI = false, bool LIST = false>
 __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int tid, bool prefetched,
                                                   bool has_next, int ntile_m, int ntile_n,
                                                   TapTile tt = TapTile{}) {
@@ -1857,12 +1869,20 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
   // (image, ho, wo) -- TAPI: of the tile's class rectangle, (image, y, x) with ny x nx pixels
   // per image.  (The per-lane divisions run on rem0 + row < pixels per image + 256, exact in
   // float arithmetic with one correction step -- a tenth of an integer division.)
+  // (LIST: x = entry - first pixel of the tile's first slot < 257 slots' pixels; the launcher
+  // keeps that below 2^24, where the float quotient is within one of the exact one)
   const int pix_img = TAPI ? tt.ny * tt.nx : HoWo, pix_row = TAPI ? tt.nx : g.Wo;
   const int rows_all = TAPI ? tt.cnt : g.M;
   const float r_howo = 1.0f / (float)pix_img, r_wo = 1.0f / (float)pix_row;
+  // first slot of a list tile (scalar: the tile's first entry always exists)
+  auto list_slot0 = [&](int m0) {
+    return __builtin_amdgcn_readfirstlane(g.row_list[m0]) / pix_img;
+  };
   auto row_pixel = [&](int m0, int rem0, int row, int* dimg_out, int* ho_out, int* wo_out) {
     const bool ok = m0 + row < rows_all;
-    const int x = rem0 + (ok ? row : 0);
+    int x;
+    if constexpr (LIST) x = g.row_list[m0 + (ok ? row : 0)] - rem0;  // rem0: first pixel of slot0
+    else x = rem0 + (ok ? row : 0);
     int dimg = (int)((float)x * r_howo);
     dimg -= (dimg * pix_img > x);
     dimg += ((dimg + 1) * pix_img <= x);
@@ -1878,8 +1898,8 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
   auto setup = [&](PpLoader& L, int tm, int tn) {
     const int prow = lane >> 3, pos = lane & 7;
     const int m0 = tm * BM;
-    const int img0 = m0 / pix_img;       // scalar
-    const int rem0 = m0 - img0 * pix_img;
+    const int img0 = LIST ? list_slot0(m0) : m0 / pix_img;       // scalar
+    const int rem0 = LIST ? img0 * pix_img : m0 - img0 * pix_img;
     // descriptors: A from (image img0, pixel (-pad, -pad)) so that every per-lane offset is
     // non-negative; W from the tile's first row.  Out-of-range offsets read as zeros.
     const long bias = ((long)g.pad * g.Wd + g.pad) * g.a_pix_stride;
@@ -2179,13 +2199,24 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
     issue_w(N, I0{}, true);
     issue_a(N, I1{}, true);
   }
-  const GemmArgs ge = reload_gemm_args();  // the epilogue's arguments, loaded here
+  const GemmArgs ge = reload_gemm_args<LIST>();  // the epilogue's arguments, loaded here
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = acc[i][j] * ge.acc_scale;
   // staging: A slot 2 + W slot 1 (contiguous 64 KB; the prefetch goes to A0, A1, W0)
-  if constexpr (TAPI) {
+  if constexpr (LIST) {
+    // the listed rows themselves (ge.M is the dense row count here)
+    int* tab = reinterpret_cast<int*>(a_slot(0)) + wave * (TM * 32);
+    const int m0 = tile_m * BM;
+#pragma unroll
+    for (int e = 0; e < TM * 32 / 64; ++e) {
+      const int r = e * 64 + lane;
+      const int m = m0 + wm * (TM * 32) + r;
+      tab[r] = m < rows_all ? ge.row_list[m] : 0x7fffffff;
+    }
+    run_epilogue<TM, TN, true, true>(ge, acc, a_slot(2), wave, lane, 0, tile_n * BNW + wn * 64, tab);
+  } else if constexpr (TAPI) {
     // Output rows of this wave's TM * 32 tile rows, once per tile, into A slot 0 (free: these
     // kernels run one tile per workgroup, nothing is prefetched).  Every wave writes and reads
     // its own copy -- same-wave LDS operations complete in order, no barrier.
@@ -2262,6 +2293,28 @@ __global__ __launch_bounds__(512, 2) void igemm_split16_pp32t_kernel(GemmArgs g,
   int tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   split16_pp32_tile<BNW, false, true>(tt.j, tt.tile_n, tid, false, false, tt.j, tt.tile_n, tt);
+}
+
+// row-list launches (GemmArgs::row_list): 256-column tiles over 256 listed rows each, one tile
+// per workgroup; TAPI: a k x k conv in (slice, tap, channel) order, all taps, per-row mask
+template <bool TAPI>
+__global__ __launch_bounds__(512, 2) void igemm_split16_pp32l_kernel(GemmArgs g, int tiles_m,
+                                                                     int tiles_n) {
+  tiles_m = live_tiles_m(g, tiles_m, 256);
+  const int T = tiles_m * tiles_n;
+  const int q = blockIdx.x;
+  if (q >= T) return;
+  const int tile = xcd_tile(q, T);
+  const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
+  TapTile tt{};
+  if constexpr (TAPI) {
+    tt.ny = g.Ho; tt.nx = g.Wo;
+    tt.mask = 0xffffffffu >> (32 - g.KH * g.KW);
+    tt.cnt = g.M;
+  }
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  split16_pp32_tile<256, false, TAPI, true>(tile_m, tile_n, tid, false, false, tile_m, tile_n, tt);
 }
 
 // fast mode (GemmArgs::f16): the same tile with one MFMA per 16 real k
@@ -2923,10 +2976,29 @@ static int tap_classes(GemmArgs& t, int tiles_m, int tiles_n) {
   return (int)grid;
 }
 
+// set by the one launcher that has a row-list form: launch_gemm() fails a row-list launch that
+// the dispatch sent anywhere else (it would run densely, in another tile's order)
+static thread_local bool t_row_list_taken = false;
+
 template <int BNW>
 static int launch_split16_pp32(const GemmArgs& g, hipStream_t s) {
   const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + BNW - 1) / BNW;
   const size_t lds = size_t(5) * 256 * 32 * sizeof(float);
+  if (g.row_list != nullptr) {
+    // (launch_gemm checked row_list_supported(): BNW == 256 here)
+    if (BNW != 256) return MILAN_ERR_SHAPE;
+    t_row_list_taken = true;
+    GemmArgs t = g;
+    const bool tapi = tap_inner_wanted(g);
+    if (tapi) { t.W = g.Wt; t.tap_inner = 1; }
+    t.tap_ncls = 0;
+    profile_tag_kernel(tapi ? MILAN_KERNEL_PP32T_256 : MILAN_KERNEL_PP32_256);
+    auto kern = tapi ? igemm_split16_pp32l_kernel<true> : igemm_split16_pp32l_kernel<false>;
+    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
+    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, s, t, tiles_m, tiles_n);
+    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   if (tap_inner_wanted(g)) {
     GemmArgs t = g;
     t.W = g.Wt;
@@ -3130,6 +3202,33 @@ static int env_tile_hint() { return 0; }
 static int env_tile_override(int, int) { return 0; }
 #endif
 
+// Row-list launches (GemmArgs::row_list) exist for the layers the dense dispatch below gives to
+// the 256-column pair-staged ping-pong tile, in its k order (a k x k conv: tap-inner) -- the
+// conditions of launch_gemm_impl / launch_split16 on that way, spelled once more -- and when
+// 256 + 2 images of either source lie within a 32-bit byte offset and 257 images' pixels count
+// exactly in fp32.
+bool row_list_supported(const GemmArgs& g) {
+  static int pp = -1;
+  if (pp < 0) { const char* e = getenv("MILAN_PP"); pp = e ? atoi(e) : 1; }
+  const long howo = (long)g.Ho * g.Wo;
+  if (g.row_list == nullptr || g.m_live == nullptr || g.m_live_mul != 1) return false;
+  if (!g.a_split || g.f16 || g.chunk_major || g.aniso || g.tile_hint != 0 || env_tile_hint() != 0 ||
+      env_tile_override(g.N, g.K) != 0 || pp != 1)
+    return false;
+#if MILAN_EXPERIMENTS
+  if (conv3x3_enabled() || (getenv("MILAN_SCHED") && atoi(getenv("MILAN_SCHED")))) return false;
+#endif
+  if (g.epilogue == EPI_LSE || g.epilogue == EPI_LSTM || !g.out_split) return false;
+  if (g.N % 256 != 0 || g.Cin % 32 != 0 || g.K != g.Kp || !pp_eligible(g)) return false;
+  if (g.A2 && (g.K1 % 32 != 0 || g.KH != 1 || g.KW != 1)) return false;
+  if (g.KH * g.KW > 1 && !tap_inner_wanted(g)) return false;
+  if ((long)g.H + g.pad >= 32768 || (long)g.Wd + g.pad >= 32768) return false;
+  if (howo <= 0 || g.M % howo != 0 || 257 * howo >= (1L << 24)) return false;
+  if (258 * g.a_img_stride * 4 + 64 >= 0x7fffffffL) return false;
+  if (g.A2 && 258 * g.a2_img_stride * 4 + 64 >= 0x7fffffffL) return false;
+  return true;
+}
+
 static int launch_gemm_impl(GemmArgs g, hipStream_t s) {
   const bool cin32 = (g.Cin % 32 == 0);
   if (g.status == nullptr) g.status = status_word();
@@ -3287,15 +3386,32 @@ static int launch_gemm_impl(GemmArgs g, hipStream_t s) {
                : launch_cfg<128, 128, 2, false, false>(g, s);
 }
 
+static int launch_gemm_checked(const GemmArgs& g, hipStream_t s);
 int launch_gemm(const GemmArgs& g, hipStream_t s) {
   MILAN_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, MILAN_ERR_SHAPE,
                 "gemm: empty problem M=%d N=%d K=%d", g.M, g.N, g.K);
+  MILAN_REQUIRE(g.row_list == nullptr || row_list_supported(g), MILAN_ERR_SHAPE,
+                "gemm: no row-list form of this launch (N=%d Cin=%d %dx%d)", g.N, g.Cin, g.KH, g.KW);
   MILAN_REQUIRE(g.Cin % 4 == 0 && g.a_pix_stride % 4 == 0 &&
                     g.a_img_stride % 4 == 0 && g.Kp % 32 == 0 && aligned16(g.A) &&
                     aligned16(g.W),
                 MILAN_ERR_SHAPE,
                 "gemm: Cin=%d / strides must be multiples of 4 floats and "
                 "operands 16-byte aligned", g.Cin);
+  if (g.row_list != nullptr) {
+    // row_list_supported() restates the dispatch below; should the two ever part, the launch
+    // must not run on some other kernel unnoticed
+    t_row_list_taken = false;
+    const int r = launch_gemm_checked(g, s);
+    MILAN_REQUIRE(r != 0 || t_row_list_taken, MILAN_ERR_STATE,
+                  "gemm: a row-list launch was dispatched to a kernel without a list form "
+                  "(row_list_supported() no longer matches the dispatch)");
+    return r;
+  }
+  return launch_gemm_checked(g, s);
+}
+
+static int launch_gemm_checked(const GemmArgs& g, hipStream_t s) {
   if (!g_prof.on) return launch_gemm_impl(g, s);
   ProfRec* e = prof_next();
   MILAN_REQUIRE(e != nullptr, MILAN_ERR_STATE, "profiler: cannot create events");

@@ -28,6 +28,7 @@ PRECISION_F32, PRECISION_SPLIT_F16, PRECISION_F16 = 0, 1, 2
 # 'f16' = the fast mode: narrower than the reference's fp32 (include/milan_hip.h), never a default
 PRECISIONS = {'f32': PRECISION_F32, 'split_f16': PRECISION_SPLIT_F16, 'f16': PRECISION_F16}
 FUSE_CHAIN, FUSE_CHAIN_WIDE, FUSE_STEM, FUSE_CONV3, FUSE_SKIP_EMPTY, FUSE_BNECK, FUSE_SPARSE_TAIL = 1, 2, 4, 8, 16, 32, 64  # milan_set_fusion flags (include/milan_hip.h)
+FUSE_TAIL_LISTS = 128
 SKETCH_COMPACT, SKETCH_INSERT, SKETCH_MOVE, SKETCH_HALVE = 0, 1, 2, 3
 # milan_status bits (include/milan_hip.h)
 STATUS_SATURATED, STATUS_NONFINITE_INPUT = 1, 2
@@ -429,7 +430,8 @@ class Context:
             bits = int(os.environ['MILAN_CHAIN'])
             self.set_fusion(chain=bool(bits & 1), wide=bool(bits & 2), stem=bool(bits & 4),
                             conv3=bool(bits & 8), skip_empty=bool(bits & 16),
-                            bneck=bool(bits & 32), sparse_tail=bool(bits & 64))
+                            bneck=bool(bits & 32), sparse_tail=bool(bits & 64),
+                            tail_lists=bool(bits & 128))
         if os.environ.get('MILAN_SHARE_IMAGES'):  # opt-in image sharing (set_image_sharing)
             self.set_image_sharing(bool(int(os.environ['MILAN_SHARE_IMAGES'])))
         default = os.environ.get('MILAN_PRECISION')
@@ -477,7 +479,8 @@ class Context:
 
     def set_fusion(self, chain: bool = True, wide: Optional[bool] = None,
                    stem: bool = True, conv3: bool = True, skip_empty: bool = True,
-                   bneck: bool = True, sparse_tail: bool = True) -> None:
+                   bneck: bool = True, sparse_tail: bool = True,
+                   tail_lists: Optional[bool] = None) -> None:
         """Cross-layer fusions of the trunk (bitwise-neutral scheduling knob):
         `chain` the expand -> reduce launches of layer1 / layer2, `wide` those of
         layer3 (default: as `chain`), `stem` conv1 + bn1 + ReLU + maxpool as one launch, `conv3` the
@@ -485,13 +488,19 @@ class Context:
         with an all-zero mask (exact-zero features by the reference's rule) stay out of the trunk,
         `bneck` (round 6) layer1's 3x3 conv runs in front of its chain launch (needs `chain`),
         `sparse_tail` (round 6) the last two bottlenecks run only at the pixels the level-4 pooling
-        -- and their 3x3 neighbourhoods -- read."""
+        -- and their 3x3 neighbourhoods -- read, `tail_lists` (needs `sparse_tail`) those pixel
+        sets go to the GEMM tile as row lists -- no gather / scatter / im2col copies -- and reach
+        down to the first block of the last stage and c2 / c3 of the last block before it
+        (default: as `sparse_tail`; asking for it without `sparse_tail` is an error, here as in
+        `milan_set_fusion` and for a MILAN_CHAIN value with bit 128 but not bit 64)."""
+        tail_lists = sparse_tail if tail_lists is None else tail_lists
         wide = chain if wide is None else wide
         _check(self.lib.milan_set_fusion(
             self._h, (FUSE_CHAIN if chain else 0) | (FUSE_CHAIN_WIDE if wide else 0) |
             (FUSE_STEM if stem else 0) | (FUSE_CONV3 if conv3 else 0) |
             (FUSE_SKIP_EMPTY if skip_empty else 0) | (FUSE_BNECK if bneck else 0) |
-            (FUSE_SPARSE_TAIL if sparse_tail else 0)))
+            (FUSE_SPARSE_TAIL if sparse_tail else 0) |
+            (FUSE_TAIL_LISTS if tail_lists else 0)))
 
     # -- image sharing (opt-in) ------------------------------------------------------
     def set_image_sharing(self, enable: bool = True) -> None:

@@ -687,8 +687,12 @@ __global__ __launch_bounds__(256) void mask_pyramid_kernel(
     const T* __restrict__ masks, int H, int W, Levels lv,
     int* __restrict__ list_idx, float* __restrict__ list_w,
     int* __restrict__ list_n, int* __restrict__ bbox = nullptr) {
-  // every product/sum below is rounded as written (ATen's scalar formula), the
-  // same for the uint8 and float instantiations
+  // every product/sum below is rounded as written (ATen's scalar formula), the same for the
+  // uint8 and float instantiations -- except the source coordinate, which torch rounds ONCE
+  // (its builds contract scale * (dst + 0.5) - 0.5 into a fused multiply-add): the explicit
+  // fmaf below.  Rounded twice it is one ulp of the coordinate off at 48 of the halvings of
+  // 1..240 (up to 7.6e-6 in a resized weight at 131 -> 66), at none with a power-of-two scale
+  // (tests/test_trunk_ref_host.py restates both forms against F.interpolate).
 #pragma clang fp contract(off)
   __shared__ float red_sum[4], red_max[4];
   const int img = blockIdx.x, l = blockIdx.y;
@@ -701,8 +705,8 @@ __global__ __launch_bounds__(256) void mask_pyramid_kernel(
     if (m == nullptr) return 1.f;  // encoders.py:292-293: no masks == all ones
     const int oy = p / w, ox = p - oy * w;
     // ATen upsample_bilinear2d, align_corners=false
-    float fy = ((float)oy + 0.5f) * sy - 0.5f; fy = fy < 0.f ? 0.f : fy;
-    float fx = ((float)ox + 0.5f) * sx - 0.5f; fx = fx < 0.f ? 0.f : fx;
+    float fy = fmaf((float)oy + 0.5f, sy, -0.5f); fy = fy < 0.f ? 0.f : fy;
+    float fx = fmaf((float)ox + 0.5f, sx, -0.5f); fx = fx < 0.f ? 0.f : fx;
     const int y0 = (int)fy, x0 = (int)fx;
     const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
     const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;

@@ -35,6 +35,11 @@ CASES = [
     (4, 14, 14, 32, 256, 3, 2, 1),   # stride 2: leading classes only
     (3, 15, 15, 32, 256, 3, 2, 1),   # stride 2, odd size: a trailing class exists
     (2, 13, 13, 64, 256, 5, 1, 2),   # 25 classes: more than the table holds -> linear order
+    (3, 14, 15, 32, 256, 3, 2, 1),   # stride 2, non-square: a trailing class on the x axis only
+    (3, 15, 14, 32, 256, 3, 2, 1),   # ... on the y axis only
+    (2, 7, 1, 32, 128, 3, 1, 1),     # one column
+    (2, 28, 3, 32, 256, 3, 1, 1),    # no interior column
+    (5, 13, 10, 64, 256, 3, 1, 1),   # 130-pixel images: the classes straddle the tiles unevenly
 ]
 EPILOGUES = ['bias', 'relu', 'residual']
 

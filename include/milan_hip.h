@@ -176,6 +176,32 @@ int milan_decode(milan_ctx* ctx, const float* features, int n, int k,
                  int64_t* beam_tokens, float* beam_scores, int32_t* out_len,
                  void* workspace, size_t workspace_bytes, milan_stream stream);
 
+/* Beam width.  1 <= beam_size <= min(vocab_size, 1024); above 256 beams vocab_size must not
+ * exceed 36864 (the wide per-row top-k holds the row in LDS), else MILAN_ERR_ARG.  While a neuron's beam_size^2
+ * summed candidates fit 64 KiB of LDS (beam_size <= 124) they are merged there, exactly as
+ * before wide beams existed; from there on the merge reads them from
+ * global memory (every parent's list is sorted, so a threshold bisection with a binary
+ * search per parent finds the winners), and above 256 the per-row top-k runs its own
+ * kernels too (csrc/beam_wide.hip).  Both paths select by one rule -- value
+ * descending, ties to the lowest flat candidate index -- and give the same bits.
+ *   milan_set_beam_path  mode 0 (default): by width, as above.  mode 1: the wide merge at
+ *     every beam_size >= 2 and the wide per-row top-k wherever it applies.  An A/B and
+ *     test knob; results do not depend on it.
+ *   milan_beam_merge  one merge step on caller-supplied DEVICE arrays: per neuron the
+ *     `beam` best of cand_v[n][p][j] + last_lp[n][p] (last_lp NULL = zeros) over
+ *     p < beam_prev, j < beam.  Every list cand_v[n][p][:] must be sorted descending, as
+ *     the per-row top-k emits it.  new_lp (n,beam) is sorted by (value descending, flat
+ *     index p * beam + j ascending), new_tok = cand_i at the winner, new_bp = its p.
+ *     1 <= beam_prev <= beam <= 1024.  wide: 0 = the kernel milan_decode picks for this
+ *     `beam` in mode 0, 1 = the wide kernel.  workspace may be NULL (no scratch is used).
+ * Not part of every build of ABI 11: probe with dlsym / hasattr. */
+int milan_beam_merge(const float* cand_v, const int* cand_i, const float* last_lp,
+                     int n, int beam_prev, int beam, int wide, float* new_lp,
+                     int* new_tok, int* new_bp, void* workspace,
+                     size_t workspace_bytes, milan_stream stream);
+int milan_set_beam_path(milan_ctx* ctx, int mode);   /* default 0 */
+int milan_get_beam_path(const milan_ctx* ctx);
+
 /* LanguageModel.forward(inputs, reduce=True) (src/milan/lms.py:58-101),
  * including its stop-mask off-by-one.  seqs (rows,L) int64, first column is
  * the start token; out (rows).  seq_len: optional DEVICE int32 per row giving

@@ -227,7 +227,7 @@ struct DecodeCall {
   const float* features; int n, k, strategy, length, beam, mi; float temperature;
   int group; int64_t* tokens; float* scores; float* predictions; float* attentions;
   int64_t* beam_tokens; float* beam_scores; int32_t* out_len; void* ws;
-  size_t ws_bytes; hipStream_t stream; int precision;
+  size_t ws_bytes; hipStream_t stream; int precision; int beam_path;
 };
 
 static int decode_direct(milan_ctx* c, const DecodeCall& d) {
@@ -253,6 +253,7 @@ static int decode_maybe_graph(milan_ctx* c, const DecodeCall& d) {
     z.attentions = d.attentions; z.beam_tokens = d.beam_tokens;
     z.beam_scores = d.beam_scores; z.out_len = d.out_len; z.ws = d.ws;
     z.ws_bytes = d.ws_bytes; z.stream = d.stream; z.precision = c->precision;
+    z.beam_path = c->beam_path;
     memcpy(key.data(), &z, sizeof(z));
   }
   milan_ctx::GraphEntry* e = nullptr;
@@ -383,6 +384,27 @@ int milan_decode(milan_ctx* c, const float* features, int n, int k, int strategy
                (hipStream_t)stream, c->precision};
   return decode_maybe_graph(c, d);
 }
+
+int milan_beam_merge(const float* cand_v, const int* cand_i, const float* last_lp, int n,
+                     int beam_prev, int beam, int wide, float* new_lp, int* new_tok,
+                     int* new_bp, void* workspace, size_t workspace_bytes,
+                     milan_stream stream) {
+  MILAN_REQUIRE(cand_v && cand_i && new_lp && new_tok && new_bp, MILAN_ERR_ARG,
+                "milan_beam_merge: null argument");
+  MILAN_REQUIRE(wide == 0 || wide == 1, MILAN_ERR_ARG, "milan_beam_merge: wide=%d", wide);
+  (void)workspace; (void)workspace_bytes;  // neither kernel needs scratch
+  return decoder_beam_merge(cand_v, cand_i, last_lp, n, beam_prev, beam, wide, new_lp,
+                            new_tok, new_bp, (hipStream_t)stream);
+}
+
+int milan_set_beam_path(milan_ctx* c, int mode) {
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
+  MILAN_REQUIRE(mode == 0 || mode == 1, MILAN_ERR_ARG, "unknown beam path mode %d", mode);
+  c->beam_path = mode;
+  return 0;
+}
+
+int milan_get_beam_path(const milan_ctx* c) { return c ? c->beam_path : -1; }
 
 int milan_set_graph_capture(milan_ctx* c, int enable) {
   MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");

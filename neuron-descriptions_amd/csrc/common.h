@@ -556,6 +556,9 @@ struct milan_ctx {
   // a value hit the +-65504 clamp and by the input conversion when a pixel was not finite
   unsigned* status = nullptr;
   unsigned* calib = nullptr;   // != nullptr only inside milan_encoder_absmax
+  // beam-search path (milan_set_beam_path): 0 = by beam width, 1 = the wide kernels wherever
+  // they apply (an A/B and test knob; the two paths select the same beams, bit for bit)
+  int beam_path = 0;
   // image sharing (milan_set_image_sharing; share.hip): off by default
   int share_images = 0;
   int share_hash_bits = 64;            // MILAN_SHARE_HASH_BITS at milan_create (a test knob)
@@ -620,4 +623,18 @@ int decoder_lm_logprobs(milan_ctx* c, const int64_t* seqs, int rows, int L,
 int decoder_lm_score(milan_ctx* c, const int64_t* seqs, int rows, int L,
                      const int32_t* seq_len, float* out, Arena& ws,
                      hipStream_t s);
+// one merge step of the beam search on caller-supplied arrays (milan_beam_merge);
+// wide = 0 picks the kernel by `beam` as decoder_decode does in auto mode
+int decoder_beam_merge(const float* cand_v, const int* cand_i, const float* last_lp,
+                       int n, int beam_prev, int beam, int wide, float* new_lp,
+                       int* new_tok, int* new_bp, hipStream_t s);
+// beam_wide.hip: selection kernels for beams whose candidates do not fit LDS
+int launch_beam_merge_wide(const float* cand_v, const int* cand_i,
+                           const float* last_lp, int n, int beam_prev, int beam,
+                           float* new_lp, int* new_tok, int* new_bp, hipStream_t s);
+bool row_select_wide_ok(int V, int k);
+int launch_row_select_wide(const float* logits, const float* lm_logits,
+                           float lambda, int rows, int V, int k,
+                           const int64_t* last_tok, int stop, float* cand_v,
+                           int* cand_i, hipStream_t s);
 }  // namespace milan

@@ -1230,6 +1230,13 @@ static inline int nblk(long total, int cap = 16384) {
   long b = (total + 255) / 256;
   return (int)(b < cap ? (b < 1 ? 1 : b) : cap);
 }
+// Blocks of 256 threads for a kernel that handles ONE element per thread (no grid-stride
+// loop): every element needs its thread, so the count is not capped.  The callers bound
+// `total` below 2^31 * 256 (decoder_decode's requirements on n, beam_size and length).
+static inline unsigned nblk_all(long total) {
+  const long b = (total + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : b);
+}
 
 // y = epi(A W^T + b): fp32 MFMA, or -- in split-f16 mode, when the layer has a
 // split weight copy -- A is first rewritten as (hi,lo) f16 pairs into the
@@ -1378,7 +1385,8 @@ static void dec_plan(const milan_ctx* c, int n, int k, int beam, int T, bool lm,
     b->lm_alive = a.get<float>(R);
     b->lm_total = a.get<float>(R);
     // the rerank pass's prefix classes + gathered states (~2.6 k floats per row at Hl = 512)
-    b->lm_dedup_floats = beam > 1 ? lm_dedup_floats(d, R, T + 1, n) : 0;
+    // (groups above 256 rows -- beam > 256 -- leave the dedup path, see lm_score_impl)
+    b->lm_dedup_floats = beam > 1 && beam <= 256 ? lm_dedup_floats(d, R, T + 1, n) : 0;
     b->lm_dedup = b->lm_dedup_floats ? a.get<float>(b->lm_dedup_floats) : nullptr;
   }
 }
@@ -1532,7 +1540,11 @@ static int launch_row_select(const float* logits, const float* lm_logits,
                              float lambda, int rows, int V, int k,
                              const int64_t* last_tok, int stop, float* cand_v,
                              int* cand_i, float* pred_out, long pred_stride,
-                             hipStream_t s) {
+                             hipStream_t s, bool wide = false) {
+  // k > 256 (or `wide`: milan_set_beam_path): the kernels of beam_wide.hip
+  if (!pred_out && (k > 256 || wide) && row_select_wide_ok(V, k))
+    return launch_row_select_wide(logits, lm_logits, lambda, rows, V, k, last_tok,
+                                  stop, cand_v, cand_i, s);
   if (V <= kRowRegs * 256 && k <= 256 && (k <= 1 || k <= V)) {
     // ties straddling the k-th value are resolved for up to 16 picks in the
     // register kernel; larger tie groups are impossible for distinct logits
@@ -1841,7 +1853,7 @@ static int lm_score_dedup(milan_ctx* c, const int64_t* seqs, int rows, int L, in
   hipLaunchKernelGGL(lm_prefix_classes_kernel, dim3(G), dim3(256), 0, s, seqs, L, group, R, G,
                      rep, lrank, cnt);
   hipLaunchKernelGGL(lm_prefix_scan_kernel, dim3(L + 1), dim3(256), 0, s, cnt, G, offs, q.U);
-  hipLaunchKernelGGL(lm_prefix_assign_kernel, dim3(nblk(R)), dim3(256), 0, s, rep, lrank, offs,
+  hipLaunchKernelGGL(lm_prefix_assign_kernel, dim3(nblk_all(R)), dim3(256), 0, s, rep, lrank, offs,
                      L, group, R, G, q.cls, q.urow, q.par);
   MILAN_CHECK_HIP(hipGetLastError());
   // ---- zero state in front of step 0 (its classes have no parent state to gather) ----
@@ -1859,7 +1871,7 @@ static int lm_score_dedup(milan_ctx* c, const int64_t* seqs, int rows, int L, in
     LmState& st = b->lm[cur];
     LmState& nx = b->lm[cur ^ 1];
     // token of every class of seqs[..t], its embedding in split form
-    hipLaunchKernelGGL(lm_gather_tok_kernel, dim3(nblk(R)), dim3(256), 0, s, seqs, (long)L, t,
+    hipLaunchKernelGGL(lm_gather_tok_kernel, dim3(nblk_all(R)), dim3(256), 0, s, seqs, (long)L, t,
                        q.urow + (size_t)p1 * R, U1, q.tok_c);
     hipLaunchKernelGGL(embed_split_kernel, dim3(nblk((long)R * (El / 8))), dim3(256), 0, s,
                        c->lm_embedding, q.tok_c, R, El, emb_s, El, U1);
@@ -1898,7 +1910,7 @@ static int lm_score_dedup(milan_ctx* c, const int64_t* seqs, int rows, int L, in
     // one target (the class's last token) per row
     hipLaunchKernelGGL(lm_gather_rows_kernel, dim3(nblk((long)R * (Hl / 4), 8192)), dim3(256), 0, s,
                        (const float4*)in, q.par + (size_t)p2 * R, U2, Hl / 4, (float4*)q.gv);
-    hipLaunchKernelGGL(lm_gather_tok_kernel, dim3(nblk(R)), dim3(256), 0, s, seqs, (long)L, t + 1,
+    hipLaunchKernelGGL(lm_gather_tok_kernel, dim3(nblk_all(R)), dim3(256), 0, s, seqs, (long)L, t + 1,
                        q.urow + (size_t)p2 * R, U2, q.tgt_c);
     {
       GemmArgs g = linear_args(q.gv, Hl, c->lm_out.ws, c->lm_out.b, b->lm_logits, V, R,
@@ -1956,7 +1968,7 @@ static int lm_score_impl(milan_ctx* c, const int64_t* seqs, int rows, int L,
       lm_dedup_floats(d, (size_t)rows, L, rows / group) <= dedup_floats)
     return lm_score_dedup(c, seqs, rows, L, group, seq_len, len_div, total, b, dedup_scratch, s);
   for (int t = 0; t + 1 < L; ++t) {
-    hipLaunchKernelGGL(gather_col_kernel, dim3(nblk(rows)), dim3(256), 0, s, seqs,
+    hipLaunchKernelGGL(gather_col_kernel, dim3(nblk_all(rows)), dim3(256), 0, s, seqs,
                        (long)rows, (long)L, t, b->tok);
     if (split && lse) {
       // the vocabulary GEMM leaves the log-softmax statistics of every row, not the logits
@@ -2020,7 +2032,7 @@ int decoder_lm_logprobs(milan_ctx* c, const int64_t* seqs, int rows, int L,
   MILAN_TRY(launch_zero_fill(b.lm[0].c, st_bytes, s));
   int cur = 0;
   for (int t = 0; t < L; ++t) {
-    hipLaunchKernelGGL(gather_col_kernel, dim3(nblk(rows)), dim3(256), 0, s, seqs,
+    hipLaunchKernelGGL(gather_col_kernel, dim3(nblk_all(rows)), dim3(256), 0, s, seqs,
                        (long)rows, (long)L, t, b.tok);
     MILAN_TRY(lm_step(c, b.tok, rows, b.lm[cur], b.lm[cur ^ 1], b.lm_emb,
                       b.lm_gates, b.lm_logits, s));
@@ -2031,6 +2043,32 @@ int decoder_lm_logprobs(milan_ctx* c, const int64_t* seqs, int rows, int L,
                                 (long)L * d.vocab_size, s));
     cur ^= 1;
   }
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// beam_merge_kernel keeps a neuron's beam^2 summed candidates (and its outputs and
+// scratch) in LDS: beam^2 + 2 beam + 544 floats fit 64 KiB up to beam 124 (125 needs 140
+// bytes more: it never ran there).  Wider beams run beam_merge_wide_kernel.
+constexpr int kMaxBeam = 1024;
+static size_t merge_lds_bytes(int beam) {
+  return sizeof(float) * ((size_t)beam * beam + 2 * beam + 16 + 528);
+}
+
+int decoder_beam_merge(const float* cand_v, const int* cand_i, const float* last_lp,
+                       int n, int beam_prev, int beam, int wide, float* new_lp,
+                       int* new_tok, int* new_bp, hipStream_t s) {
+  MILAN_REQUIRE(n > 0 && beam >= 1 && beam <= kMaxBeam && beam_prev >= 1 &&
+                    beam_prev <= beam,
+                MILAN_ERR_ARG,
+                "beam merge: beam_size=%d must be in 1..%d and beam_prev=%d in 1..beam_size",
+                beam, kMaxBeam, beam_prev);
+  const size_t merge_lds = merge_lds_bytes(beam);
+  if (beam >= 2 && (wide || merge_lds > 64 * 1024))
+    return launch_beam_merge_wide(cand_v, cand_i, last_lp, n, beam_prev, beam, new_lp,
+                                  new_tok, new_bp, s);
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(n), dim3(256), merge_lds, s, cand_v,
+                     cand_i, last_lp, beam_prev, beam, new_lp, new_tok, new_bp);
   MILAN_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2059,10 +2097,25 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
                 "teacher forcing needs the predictions output");
   MILAN_REQUIRE(beam >= 1 && beam <= V, MILAN_ERR_ARG,
                 "beam_size=%d must be in 1..vocab_size (%d)", beam, c->d.vocab_size);
+  MILAN_REQUIRE(beam <= kMaxBeam, MILAN_ERR_ARG,
+                "beam_size=%d too large: the selection kernels hold at most %d beams; pass a "
+                "smaller beam_size=", beam, kMaxBeam);
+  // above 256 beams the per-row top-k is beam_wide.hip's, whose LDS kernel holds a row of at
+  // most 36864 logits (the k-rounds block argmax of row_select_kernel is no path to run)
+  MILAN_REQUIRE(beam <= 256 || row_select_wide_ok(V, beam), MILAN_ERR_ARG,
+                "beam_size=%d above 256 needs vocab_size <= 36864 (it is %d); pass a smaller "
+                "beam_size=", beam, V);
+  // every row index and row count of the search is an int (R = n * beam rows, GEMM M), and
+  // the one-element-per-thread kernels get a grid of (R * (length + 1)) / 256 blocks
+  MILAN_REQUIRE((long)n * (beam > k ? beam : k) <= 0x7fffffffL / 2 &&
+                    (long)n * beam * ((long)length + 1) <= 0x7fffffffL * 256,
+                MILAN_ERR_ARG,
+                "decode: %d neurons x beam_size=%d rows (x length %d) overflow the 32-bit row "
+                "index or launch grid; lower chunk_size or beam_size", n, beam, length);
   MILAN_REQUIRE(greedy || (beam_tokens && beam_scores), MILAN_ERR_ARG,
                 "beam search needs beam_tokens and beam_scores outputs");
   MILAN_REQUIRE(tokens && scores, MILAN_ERR_ARG, "tokens/scores outputs required");
-  if (group_size <= 0) group_size = n;
+  if (group_size <= 0 || group_size > n) group_size = n;  // (beam * group_size stays an int)
   const bool need_lm = mi || strategy == MILAN_RERANK;
   DecBuf b;
   dec_plan(c, n, k, beam, length, need_lm, ws, &b);
@@ -2079,7 +2132,7 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
     MILAN_TRY(project_keys(c, features, n * k, b.keys, s));
     MILAN_TRY(init_state_impl(c, features, n, k, b.pooled, b.h, b.cc, s));
   }
-  hipLaunchKernelGGL(fill_i64_kernel, dim3(nblk(n)), dim3(256), 0, s, b.tok,
+  hipLaunchKernelGGL(fill_i64_kernel, dim3(nblk_all(n)), dim3(256), 0, s, b.tok,
                      (long)n, (int64_t)d.start_index);
   int lmcur = 0;
   if (mi) {
@@ -2105,11 +2158,11 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
           b.cand_i, predictions ? predictions + (long)t * V : nullptr,
           (long)length * V, s));
       if (forced)
-        hipLaunchKernelGGL(forced_record_kernel, dim3(nblk(n)), dim3(256), 0, s,
+        hipLaunchKernelGGL(forced_record_kernel, dim3(nblk_all(n)), dim3(256), 0, s,
                            predictions + (long)t * V, (long)length * V, V, b.att,
                            n, k, t, length, tokens, scores, attentions, b.tok);
       else
-        hipLaunchKernelGGL(greedy_record_kernel, dim3(nblk(n)), dim3(256), 0, s,
+        hipLaunchKernelGGL(greedy_record_kernel, dim3(nblk_all(n)), dim3(256), 0, s,
                            b.cand_v, b.cand_i, b.att, n, k, t, length, tokens,
                            scores, attentions, b.tok);
       float* tmp = h; h = hn; hn = tmp;
@@ -2120,11 +2173,7 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
   }
 
   // ---- beam search (allennlp 2.10 semantics, fixed `length` steps) ----------
-  const size_t merge_lds = sizeof(float) * ((size_t)beam * beam + 2 * beam + 16 + 528);
-  MILAN_REQUIRE(merge_lds <= 64 * 1024, MILAN_ERR_ARG,
-                "beam_size=%d too large for the merge kernel: beam^2 + 2 beam + 544 floats must "
-                "fit 64 KiB of LDS (beam_size <= 125); pass a smaller beam_size=",
-                beam);
+  const bool wide = c->beam_path == 1;  // milan_set_beam_path: the wide kernels at every beam
   int beam_prev = 1, rows = n, lpcur = 0;
   std::optional<StageScope> search_scope;
   search_scope.emplace(MILAN_STAGE_DEC_SEARCH, s);
@@ -2140,10 +2189,10 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
     }
     MILAN_TRY(launch_row_select(b.logits, lm_logits, temperature, rows, V, beam,
                                 t == 0 ? nullptr : b.tok, d.stop_index, b.cand_v,
-                                b.cand_i, nullptr, 0, s));
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(n), dim3(256), merge_lds, s,
-                       b.cand_v, b.cand_i, t == 0 ? nullptr : b.last_lp[lpcur],
-                       beam_prev, beam, b.last_lp[lpcur ^ 1], b.new_tok, b.new_bp);
+                                b.cand_i, nullptr, 0, s, wide));
+    MILAN_TRY(decoder_beam_merge(b.cand_v, b.cand_i, t == 0 ? nullptr : b.last_lp[lpcur],
+                                 n, beam_prev, beam, wide, b.last_lp[lpcur ^ 1], b.new_tok,
+                                 b.new_bp, s));
     lpcur ^= 1;
     // reorder: (hn,cn)[src] -> (h,cc)[r]; LM new state -> the other LM buffer
     hipLaunchKernelGGL(
@@ -2156,7 +2205,7 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
     beam_prev = beam;
     rows = R;
   }
-  hipLaunchKernelGGL(beam_finalize_kernel, dim3(nblk(R)), dim3(256), 0, s,
+  hipLaunchKernelGGL(beam_finalize_kernel, dim3(nblk_all(R)), dim3(256), 0, s,
                      b.hist_tok, b.hist_bp, n, beam, length, beam_tokens);
   MILAN_CHECK_HIP(hipMemcpyAsync(beam_scores, b.last_lp[lpcur],
                                  sizeof(float) * R, hipMemcpyDeviceToDevice, s));
@@ -2168,17 +2217,17 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
   StageScope lm_scope(MILAN_STAGE_DEC_LM, s);
   const float* lm_scores = nullptr;
   if (strategy == MILAN_RERANK) {
-    hipLaunchKernelGGL(build_lm_seqs_kernel, dim3(nblk((long)R * (length + 1))),
+    hipLaunchKernelGGL(build_lm_seqs_kernel, dim3(nblk_all((long)R * (length + 1))),
                        dim3(256), 0, s, beam_tokens, (long)R, length,
                        (int64_t)d.start_index, b.seqs);
-    hipLaunchKernelGGL(len_plus_one_kernel, dim3(nblk(groups)), dim3(256), 0, s,
+    hipLaunchKernelGGL(len_plus_one_kernel, dim3(nblk_all(groups)), dim3(256), 0, s,
                        lens, groups, b.len1);
     b.lm[0].rows = b.lm[1].rows = R;
     MILAN_TRY(lm_score_impl(c, b.seqs, R, length + 1, b.len1, beam * group_size,
                             b.lm_total, &b, s, beam, b.lm_dedup, b.lm_dedup_floats));
     lm_scores = b.lm_total;
   }
-  hipLaunchKernelGGL(rerank_select_kernel, dim3(nblk(n)), dim3(256), 0, s,
+  hipLaunchKernelGGL(rerank_select_kernel, dim3(nblk_all(n)), dim3(256), 0, s,
                      beam_scores, lm_scores, temperature, n, beam, length,
                      beam_tokens, tokens, scores);
   MILAN_CHECK_HIP(hipGetLastError());

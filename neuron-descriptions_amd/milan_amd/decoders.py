@@ -34,7 +34,10 @@ What differs by design:
   * `bert_score` scores with `metrics.bert_score`: the encoder and the token
     matching run in HIP (milan_amd.bertscore, DESIGN.md 4.15);
   * `DecoderWithCLIP` reranks the beam with CLIP (milan_amd.rerankers: both
-    towers in HIP).
+    towers in HIP, DESIGN.md 4.14);
+  * `beam_size` goes up to min(vocabulary, 1024) -- `DecoderWithCLIP`'s default
+    of 1000 runs as it stands; beyond that the library raises ValueError naming
+    `beam_size=`.  Nothing is clamped here.
 """
 import os
 import weakref

@@ -139,6 +139,10 @@ SIGNATURES = {
         _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P,
         _P, _P, _P, _P, _P, _P, _SZ, _P
     ]),
+    'milan_beam_merge': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _SZ,
+                              _P]),
+    'milan_set_beam_path': (_I, [_P, _I]),
+    'milan_get_beam_path': (_I, [_P]),
     'milan_set_graph_capture': (_I, [_P, _I]),
     'milan_graph_stats': (_I, [
         _P, ctypes.POINTER(ctypes.c_longlong),
@@ -248,7 +252,8 @@ SIGNATURES = {
 # entry points added without a new ABI version: a library built before them
 # (an older MILAN_LIB) still loads, and the calls that need them say so
 PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
-          'milan_lm_backward')
+          'milan_lm_backward', 'milan_beam_merge', 'milan_set_beam_path',
+          'milan_get_beam_path')
 
 _lib = None
 
@@ -508,6 +513,21 @@ class Context:
         trunk pass (ResNet trunks, pooled encode; the features keep their bits).  Off by
         default; float images, `encode_spatial` and AlexNet ignore it."""
         _check(self.lib.milan_set_image_sharing(self._h, int(bool(enable))))
+
+    def set_beam_path(self, mode: int) -> None:
+        """Which selection kernels the beam search runs: 0 (default) by beam width -- the
+        LDS merge while beam^2 candidates fit LDS (124 beams), the wide merge above, the wide
+        per-row top-k above 256 -- or 1, the wide kernels at every beam_size >= 2.  An A/B and test knob: both
+        paths select the same beams, bit for bit."""
+        if not hasattr(self.lib, 'milan_set_beam_path'):
+            raise HipUnavailableError('this build of libmilan_hip has no milan_set_beam_path')
+        _check(self.lib.milan_set_beam_path(self._h, int(mode)))
+
+    @property
+    def beam_path(self) -> int:
+        if not hasattr(self.lib, 'milan_get_beam_path'):
+            return 0
+        return int(self.lib.milan_get_beam_path(self._h))
 
     @property
     def image_sharing(self) -> bool:
@@ -1628,6 +1648,41 @@ def conv2d_nhwc(x: torch.Tensor,
                                   y.data_ptr(), _CONV_PRECISIONS[precision],
                                   _stream(device)))
     return y
+
+
+def beam_merge(cand_v: torch.Tensor,
+               cand_i: torch.Tensor,
+               last_lp: Optional[torch.Tensor] = None,
+               wide: bool = False,
+               lib: Optional[ctypes.CDLL] = None):
+    """One merge step of the beam search (milan_beam_merge): per neuron the `beam`
+    best of cand_v[n, p, j] + last_lp[n, p].  cand_v (n, beam_prev, beam) float32 with
+    every list sorted descending, cand_i the same shape int32, last_lp (n, beam_prev)
+    or None (zeros).  Returns (new_lp, new_tok, new_bp), each (n, beam).  `wide`: the
+    wide kernel whatever the beam (default: the kernel `Context.decode` runs)."""
+    lib = lib if lib is not None else load_library()
+    if not hasattr(lib, 'milan_beam_merge'):
+        raise HipUnavailableError('this build of libmilan_hip has no milan_beam_merge')
+    device = require_device(cand_v.device)
+    n, beam_prev, beam = cand_v.shape
+    if tuple(cand_i.shape) != (n, beam_prev, beam):
+        raise ValueError(f'cand_i shape {tuple(cand_i.shape)} != {(n, beam_prev, beam)}')
+    if last_lp is not None and tuple(last_lp.shape) != (n, beam_prev):
+        raise ValueError(f'last_lp shape {tuple(last_lp.shape)} != {(n, beam_prev)}')
+    cand_v = _dev(cand_v, device, torch.float32)
+    cand_i = _dev(cand_i, device, torch.int32)
+    if last_lp is not None:
+        last_lp = _dev(last_lp, device, torch.float32)
+    new_lp = torch.empty(n, beam, device=device)
+    new_tok = torch.empty(n, beam, dtype=torch.int32, device=device)
+    new_bp = torch.empty(n, beam, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(
+            lib.milan_beam_merge(cand_v.data_ptr(), cand_i.data_ptr(), _ptr(last_lp),
+                                 n, beam_prev, beam, int(bool(wide)),
+                                 new_lp.data_ptr(), new_tok.data_ptr(),
+                                 new_bp.data_ptr(), None, 0, _stream(device)))
+    return new_lp, new_tok, new_bp
 
 
 def make_dims(state_dict: Dict[str, torch.Tensor],

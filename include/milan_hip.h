@@ -44,8 +44,11 @@ enum {
   MILAN_ERR_SHAPE = -2,     /* shape/dim mismatch (-> ValueError)            */
   MILAN_ERR_STATE = -3,     /* call order (weights missing / not finalized)  */
   MILAN_ERR_WORKSPACE = -4, /* workspace too small                           */
-  MILAN_ERR_NO_LM = -5      /* MI / rerank requested without an LM
+  MILAN_ERR_NO_LM = -5,     /* MI / rerank requested without an LM
                                (src/milan/decoders.py:397-398)               */
+  MILAN_ERR_INDEX = -6      /* a unit index beyond its layer's channel count
+                               (-> IndexError, as `mask[:, units] = 0` raises
+                               in src/utils/ablations.py:39)                 */
 };
 
 enum { MILAN_DTYPE_U8 = 0, MILAN_DTYPE_F32 = 1 };
@@ -99,8 +102,8 @@ void milan_destroy(milan_ctx* ctx);
  * "attend.key_to_hidden.weight", "lm.lstm.weight_hh_l1",
  * "encoder.encoder.model.layer3.7.bn2.running_var".  `data` is a device float*
  * that must stay valid until milan_finalize_weights() returns.  Unknown names
- * ("...num_batches_tracked", "...fc.weight": computed-and-discarded by the
- * reference) are accepted and ignored.  Replaces load_state_dict
+ * ("...num_batches_tracked") are accepted and ignored; "...fc.weight" / "...fc.bias" of a
+ * ResNet trunk are kept for milan_classify (the describe path never reads them).  Replaces load_state_dict
  * (src/utils/serialize.py:222-252). */
 int milan_set_weight(milan_ctx* ctx, const char* name, const float* data,
                      const int64_t* shape, int ndim);
@@ -134,6 +137,53 @@ int milan_encode_spatial(milan_ctx* ctx, const void* images, int image_dtype,
                          const void* masks, int mask_dtype, int n_images,
                          int height, int width, float* out, void* workspace,
                          size_t workspace_bytes, milan_stream stream);
+
+/* Unit ablation and classification on the ResNet trunks: src/utils/ablations.py (`zero`,
+ * `ablated`, ImageClassifier.predict) over torchvision's ResNet._forward_impl in eval mode.
+ * The head comes from the state dict: when `<prefix>fc.weight` (classes, C4) and
+ * `<prefix>fc.bias` were uploaded, milan_finalize_weights keeps them (fp32, as they are); the
+ * class count is fc.weight's first extent.  A context without them behaves as before and the
+ * classify calls return MILAN_ERR_STATE; an AlexNet context gets MILAN_ERR_ARG.
+ *
+ * The five places an edit can sit are the reference's LAYERS.RESNET18 (src/exemplars/models.py:
+ * 48-52), edited as nethook edits a module's OUTPUT: level 0 = `conv1`, the raw stem conv
+ * output before bn1 / ReLU / maxpool; level L = `layerL`, the post-ReLU output of the stage's
+ * last block.
+ *   milan_set_ablation  installs the set {(levels[i], units[i])} (HOST arrays; count == 0
+ *     clears it) as 0/1 channel masks in device memory owned by the context.  Order and
+ *     duplicates do not matter.  A level outside 0..4 is MILAN_ERR_ARG, a unit outside the
+ *     level's channels MILAN_ERR_INDEX.  Synchronises `stream`; the other calls do not.  Only
+ *     the classify calls read the set: milan_encode* / milan_describe ignore it.
+ *   milan_classify  images (n,3,H,W) float NCHW, fed AS THEY ARE (the reference's classifier
+ *     gets normalised tensors: the context's mean / std are not applied); logits (n,classes)
+ *     and predictions (n) int64 = argmax by torch's rule (lowest index among equal maxima, a
+ *     NaN counts as the maximum); either may be NULL, not both.  Every level's tensor is
+ *     multiplied by its mask before anything reads it.  Runs in MILAN_PRECISION_F32 or
+ *     MILAN_PRECISION_SPLIT_F16 (MILAN_PRECISION_F16 is refused: MILAN_ERR_ARG); the head
+ *     (average pool, fc) is exact fp32 in both, in a fixed summation order that depends on
+ *     neither n nor the launch grid, so a batch gives the bits of its parts.  Saturation of
+ *     the split format is reported through the status word.  Sub-batches of MILAN_ENC_SUB.
+ *   milan_classify_sweep  for every listed unit j (HOST arrays levels / units) the result of
+ *     milan_classify under the set `current + {(levels[j], units[j])}`, bit for bit: the same
+ *     kernels on the same operands.  predictions (count,n) int64 or NULL; correct (count) int32
+ *     = #{i : predictions[j][i] == targets[i]} or NULL (then targets, (n) int64, is NULL
+ *     too); not both NULL.  Units are grouped by level: the forward up to and including the
+ *     level runs once per sub-batch and is held, each unit costs one masked copy of the held
+ *     tensor plus the rest of the network; level-4 units run the head alone.
+ *   milan_classify_workspace_bytes  scratch for n_images at H x W; sweep_units = the largest
+ *     `count` of a milan_classify_sweep call (0: milan_classify only).
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them. */
+int milan_set_ablation(milan_ctx* ctx, const int32_t* levels, const int32_t* units,
+                       int count, milan_stream stream);
+size_t milan_classify_workspace_bytes(const milan_ctx* ctx, int n_images, int height,
+                                      int width, int sweep_units);
+int milan_classify(milan_ctx* ctx, const float* images, int n_images, int height,
+                   int width, float* logits, int64_t* predictions, void* workspace,
+                   size_t workspace_bytes, milan_stream stream);
+int milan_classify_sweep(milan_ctx* ctx, const float* images, int n_images, int height,
+                         int width, const int32_t* levels, const int32_t* units, int count,
+                         const int64_t* targets, int32_t* correct, int64_t* predictions,
+                         void* workspace, size_t workspace_bytes, milan_stream stream);
 
 /* Decoder.init_state (src/milan/decoders.py:548-574).
  * features (n,k,F) -> h,c (n,hidden). */

@@ -195,6 +195,7 @@ int milan_finalize_weights(milan_ctx* c, milan_stream stream) {
   MILAN_CHECK_HIP(hipSetDevice(c->device));
   set_status_word(nullptr);  // (weight packing is not a saturation event of a call)
   MILAN_TRY(encoder_finalize(c, s));
+  MILAN_TRY(classify_finalize(c, s));
   MILAN_TRY(decoder_finalize(c, s));
   MILAN_REQUIRE(c->stem.w || c->lstm_ih.w || c->lm_out.w, MILAN_ERR_STATE,
                 "no encoder, decoder or language-model weights were uploaded");
@@ -323,6 +324,49 @@ int milan_encode(milan_ctx* c, const void* images, int image_dtype,
   MILAN_TRY(make_arena(workspace, workspace_bytes, &a));
   return encoder_run(c, images, image_dtype, masks, mask_dtype, n_images, height,
                      width, features, a, (hipStream_t)stream);
+}
+
+int milan_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* units, int count,
+                       milan_stream stream) {
+  MILAN_REQUIRE(c && count >= 0 && (count == 0 || (levels && units)), MILAN_ERR_ARG,
+                "milan_set_ablation: bad argument");
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  return classify_set_ablation(c, levels, units, count, (hipStream_t)stream);
+}
+
+size_t milan_classify_workspace_bytes(const milan_ctx* c, int n_images, int height, int width,
+                                      int sweep_units) {
+  if (!c || !c->finalized) return 0;
+  return classify_workspace(c, n_images, height, width, sweep_units) + 256;
+}
+
+int milan_classify(milan_ctx* c, const float* images, int n_images, int height, int width,
+                   float* logits, int64_t* predictions, void* workspace, size_t workspace_bytes,
+                   milan_stream stream) {
+  MILAN_REQUIRE(c && images && (logits || predictions), MILAN_ERR_ARG,
+                "milan_classify: null argument");
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  set_status_word(c->status);
+  Arena a;
+  MILAN_TRY(make_arena(workspace, workspace_bytes, &a));
+  return classify_run(c, images, n_images, height, width, logits, predictions, a,
+                      (hipStream_t)stream);
+}
+
+int milan_classify_sweep(milan_ctx* c, const float* images, int n_images, int height, int width,
+                         const int32_t* levels, const int32_t* units, int count,
+                         const int64_t* targets, int32_t* correct, int64_t* predictions,
+                         void* workspace, size_t workspace_bytes, milan_stream stream) {
+  MILAN_REQUIRE(c && images && count >= 0 && (count == 0 || (levels && units)) &&
+                    (correct || predictions) && ((correct != nullptr) == (targets != nullptr)),
+                MILAN_ERR_ARG, "milan_classify_sweep: bad argument");
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  set_status_word(c->status);
+  Arena a;
+  MILAN_TRY(make_arena(workspace, workspace_bytes, &a));
+  return classify_sweep(c, images, n_images, height, width, levels, units, count, targets,
+                        correct, predictions, a, (hipStream_t)stream);
 }
 
 int milan_encode_spatial(milan_ctx* c, const void* images, int image_dtype,

@@ -575,6 +575,13 @@ struct milan_ctx {
   std::vector<milan::LinearW> lm_cat;        // [W_ih | W_hh] per layer
   milan::LinearW lm_out;
   float* lm_embedding = nullptr;
+  // classifier head (<prefix>fc.weight / fc.bias, fp32 as uploaded) and the ablation set of
+  // milan_set_ablation: 0/1 channel masks of the five levels (conv1, layer1..4) back to back in
+  // one device array, ones until a set is installed; abl_count = distinct units per level
+  float *fc_w = nullptr, *fc_b = nullptr;
+  int fc_classes = 0, fc_in = 0;
+  float* abl_mask = nullptr;
+  int abl_off[5] = {0, 0, 0, 0, 0}, abl_ch[5] = {0, 0, 0, 0, 0}, abl_count[5] = {0, 0, 0, 0, 0};
 };
 
 namespace milan {
@@ -602,6 +609,27 @@ int encoder_run_spatial(milan_ctx* c, const void* images, int image_dtype,
 int encoder_run(milan_ctx* c, const void* images, int image_dtype,
                 const void* masks, int mask_dtype, int n_images, int H, int W,
                 float* features, Arena& ws, hipStream_t s);
+// ... the plain schedule's pieces, for classify.hip (the encode paths do not use them)
+int encoder_sub_batch_size();
+GemmArgs encoder_conv_args(const ConvW& cw, const float* in, int n, int H, int W, float* out,
+                           int epi, const float* aux, const float* zero, int* Ho, int* Wo,
+                           bool split);
+int launch_raw_input(const float* images, int n, int H, int W, bool pairs, float* out,
+                     unsigned* status, hipStream_t s);
+GemmArgs encoder_stem_args(const milan_ctx* c, const float* in4, int n, int H, int W, float* raw,
+                           bool pair_stem);
+int launch_stem_tail(const milan_ctx* c, const float* raw, int n, int h1, int w1, int hp, int wp,
+                     bool split, float* y, hipStream_t s);
+// classify.hip: classifier head and unit ablation on the ResNet trunks (milan_classify*)
+int classify_finalize(milan_ctx* c, hipStream_t s);
+int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* units, int count,
+                          hipStream_t s);
+size_t classify_workspace(const milan_ctx* c, int n, int H, int W, int sweep_units);
+int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* logits,
+                 int64_t* predictions, Arena& ws, hipStream_t s);
+int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
+                   const int32_t* units, int count, const int64_t* targets, int32_t* correct,
+                   int64_t* predictions, Arena& ws, hipStream_t s);
 // decoder.hip
 int decoder_finalize(milan_ctx* c, hipStream_t s);
 size_t decoder_workspace(const milan_ctx* c, int n, int k, int beam, int length);

@@ -2198,6 +2198,70 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Pieces of the plain schedule that classify.hip drives on its own (milan_classify*): the
+// input conversion without normalisation, the stem conv's arguments, the unfused stem tail
+// and conv_args.  encoder_run_batch above does not call them.
+// ---------------------------------------------------------------------------
+int encoder_sub_batch_size() { return encoder_sub_batch(); }
+
+GemmArgs encoder_conv_args(const ConvW& cw, const float* in, int n, int H, int W, float* out,
+                           int epi, const float* aux, const float* zero, int* Ho, int* Wo,
+                           bool split) {
+  return conv_args(cw, in, n, H, W, out, epi, aux, zero, Ho, Wo, split);
+}
+
+// (n,3,H,W) float NCHW, taken as it is (mean 0, std 1: (v - 0) / 1 is v) -> NHWC4 fp32, or
+// pixel-pair groups in split format for the pair stem
+int launch_raw_input(const float* images, int n, int H, int W, bool pairs, float* out,
+                     unsigned* status, hipStream_t s) {
+  const int G = (W + 2) / 2;
+  const long np = pairs ? (long)n * H * G : (long)n * H * W;
+  const int blocks = (int)((np + 255) / 256 < 8192 ? (np + 255) / 256 : 8192);
+  if (pairs)
+    hipLaunchKernelGGL(preprocess_pairs_kernel<float>, dim3(blocks), dim3(256), 0, s, images, np,
+                       H, W, G, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, out, nullptr, 1, nullptr, status);
+  else
+    hipLaunchKernelGGL(preprocess_kernel<float>, dim3(blocks), dim3(256), 0, s, images, np, H * W,
+                       0.f, 0.f, 0.f, 1.f, 1.f, 1.f, (float4*)out, nullptr, 1, nullptr, nullptr);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// conv1 7x7/2 as encoder_run_batch's unfused stem launches it: raw fp32 output (n, h1, w1, width)
+GemmArgs encoder_stem_args(const milan_ctx* c, const float* in4, int n, int H, int W, float* raw,
+                           bool pair_stem) {
+  int ho, wo;
+  GemmArgs g = conv_args(c->stem, in4, n, H, W, raw, EPI_BIAS, nullptr, c->zero, &ho, &wo);
+  if (pair_stem) {
+    const int G = (W + 2) / 2;
+    g = conv_args(c->stem_pair, in4, n, H, G, raw, EPI_BIAS, nullptr, c->zero, &ho, &wo, true);
+    g.Ho = conv_out(H, 7, 2, 3); g.Wo = conv_out(W, 7, 2, 3);
+    g.M = n * g.Ho * g.Wo;
+    g.aniso = 1; g.stride_w = 1; g.pad_w = 1;
+    g.out_split = 0;
+    g.flop_k = c->stem.kh * c->stem.kw * c->stem.cin_real;
+  }
+  return g;
+}
+
+// bn1 + ReLU + maxpool 3x3/2 of the raw conv1 tensor -> fp32 or split format (activation scale)
+int launch_stem_tail(const milan_ctx* c, const float* raw, int n, int h1, int w1, int hp, int wp,
+                     bool split, float* y, hipStream_t s) {
+  const int wd = c->d.trunk_width;
+  const long total = (long)n * hp * wp * (wd / (split ? 8 : 4));
+  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  if (split)
+    hipLaunchKernelGGL(bn_relu_maxpool_split_kernel, dim3(blocks), dim3(256), 0, s, raw, n, h1, w1,
+                       wd, hp, wp, c->bn1_scale_s, c->bn1_shift_s, y, c->status, nullptr);
+  else
+    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(blocks), dim3(256), 0, s, (const float4*)raw, n,
+                       h1, w1, wd / 4, hp, wp, (const float4*)c->bn1_scale,
+                       (const float4*)c->bn1_shift, (float4*)y, nullptr);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // milan_set_act_scale_log2: the pre-multiplied copies of every folded bias / bn1 vector are
 // rewritten in place for the new activation scale (exact: a power of two)
 int encoder_rescale(milan_ctx* c, hipStream_t s) {

@@ -1,0 +1,181 @@
+"""Image classifiers whose eval-mode forward runs on the HIP trunk.
+
+`ResNetClassifier` is the CNN the reference's experiments dissect and edit
+(`experiments/analyze.py`, `experiments/edit.py`: a torchvision ResNet handed to
+`src/utils/ablations.ImageClassifier`).  It is an `nn.Module` with torchvision's module
+tree and key names (`conv1.weight`, `bn1.*`, `layerL.B.convK.weight`, `downsample.0/1`,
+`fc.weight/bias`), so a torchvision checkpoint loads with `load_state_dict`,
+`named_modules()` finds `fc`, `conv1` and `layer1..4`, and
+`ImageClassifier.fit(layers=['fc'])` works.
+
+`forward(images)`:
+  - eval mode, under `no_grad`, GPU tensor: `hip.Context.classify` -- the whole forward in
+    libmilan_hip, with the ablation set `ablations.ablated` installed;
+  - otherwise (training mode, grad required, CPU tensors): the torch modules below, the
+    same arithmetic the reference's torchvision model runs (batch-statistic BatchNorm in
+    training mode).  That path is what `fit` trains through.
+"""
+from typing import Optional, Sequence, Tuple
+
+import torch
+from torch import nn
+
+from milan_amd import hip, synthetic
+
+LAYERS = ('conv1', 'layer1', 'layer2', 'layer3', 'layer4')
+
+
+class _BasicBlock(nn.Module):
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride, downsample):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+
+    def forward(self, x):
+        identity = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn2(self.conv2(out))
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        return self.relu(out + identity)
+
+
+class _Bottleneck(nn.Module):
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride, downsample):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+
+    def forward(self, x):
+        identity = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn3(self.conv3(out))
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        return self.relu(out + identity)
+
+
+class ResNetClassifier(nn.Module):
+    """torchvision-shaped ResNet (v1.5 blocks) with a native eval-mode forward.
+
+    `config`: 'resnet18' / 'resnet34' (basic blocks) or 'resnet50' / 'resnet101' /
+    'resnet152' (bottlenecks); `width` 64 is torchvision's.  `precision`: 'auto' (split-f16
+    with an exact-fp32 rerun of a call that saturated), 'split_f16' or 'f32'.  Weights start
+    as `nn.Conv2d` / `nn.Linear` leave them; load a checkpoint with `load_state_dict`.
+    """
+
+    layers: Tuple[str, ...] = LAYERS
+
+    def __init__(self,
+                 config: str = 'resnet18',
+                 num_classes: int = 1000,
+                 width: int = 64,
+                 precision: str = 'auto'):
+        super().__init__()
+        if config not in synthetic.RESNET_BLOCKS:
+            raise ValueError(f'classifier not supported: {config} (AlexNet and its '
+                             'fc6 / fc7 / linear8 layers are not built)')
+        if precision not in ('auto', 'split_f16', 'f32'):
+            raise ValueError(f'unknown precision: {precision}')
+        self.config = config
+        self.blocks = synthetic.RESNET_BLOCKS[config]
+        self.width = int(width)
+        self.num_classes = int(num_classes)
+        self.precision = precision
+        block = _BasicBlock if config in synthetic.BASIC_BLOCK_CONFIGS else _Bottleneck
+        self.conv1 = nn.Conv2d(3, width, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        inplanes = width
+        for li, count in enumerate(self.blocks):
+            planes = width * 2**li
+            stage = []
+            for bi in range(count):
+                stride = 2 if (bi == 0 and li > 0) else 1
+                downsample = None
+                if stride != 1 or inplanes != planes * block.expansion:
+                    downsample = nn.Sequential(
+                        nn.Conv2d(inplanes, planes * block.expansion, 1, stride,
+                                  bias=False),
+                        nn.BatchNorm2d(planes * block.expansion))
+                stage.append(block(inplanes, planes, stride, downsample))
+                inplanes = planes * block.expansion
+            setattr(self, f'layer{li + 1}', nn.Sequential(*stage))
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Linear(inplanes, num_classes)
+        self._ctx: Optional[hip.Context] = None
+        self._ctx_key = None
+        # the set `ablations.ablated` installed: (layer, unit) pairs for the native path
+        # (the eager path sees the same set through forward hooks), and whether its rule
+        # is one the library has a kernel for
+        self._ablation: Sequence[Tuple[str, int]] = ()
+        self._ablation_native = True
+        self._ctx_ablation = None
+
+    # -- the two forwards -----------------------------------------------------------
+    def forward_eager(self, images: torch.Tensor) -> torch.Tensor:
+        """torchvision's `ResNet._forward_impl` on this module's own parameters."""
+        x = self.maxpool(self.relu(self.bn1(self.conv1(images))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+    def runs_natively(self, images: torch.Tensor) -> bool:
+        return (not self.training and not torch.is_grad_enabled() and
+                images.device.type == 'cuda')
+
+    def forward(self, images: torch.Tensor) -> torch.Tensor:
+        if not self.runs_natively(images):
+            return self.forward_eager(images)
+        return self._native_context().classify(images)
+
+    # -- HIP context, rebuilt when device or weights change ---------------------------
+    def _context(self) -> hip.Context:
+        device = hip.require_device(self.fc.weight.device)
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = (device, tuple(t._version for t in tensors),
+               tuple(t.data_ptr() for t in tensors))
+        if self._ctx is None or self._ctx_key != key:
+            sd = {'encoder.encoder.model.' + k: v for k, v in self.state_dict().items()}
+            dims = hip.make_dims(sd, 1, blocks=self.blocks)
+            self._ctx = hip.Context(dims, sd, device)
+            if self.precision == 'auto':
+                self._ctx.set_precision('split_f16')
+                self._ctx.on_saturation = 'f32'
+            else:
+                self._ctx.set_precision(self.precision)
+            self._ctx_key = key
+            self._ctx_ablation = None
+        return self._ctx
+
+    def _native_context(self) -> hip.Context:
+        """The context with this module's current ablation set installed."""
+        if not self._ablation_native:
+            raise ValueError('only the `zero` rule has a kernel: a custom ablation rule '
+                             'runs in training mode / with grad enabled (the torch path), '
+                             'not in the native eval-mode forward')
+        ctx = self._context()
+        wanted = tuple(sorted(set(self._ablation)))
+        if self._ctx_ablation != wanted:
+            ctx.set_ablation(wanted)
+            self._ctx_ablation = wanted
+        return ctx
+
+    def classify_sweep(self, images: torch.Tensor, units, targets=None):
+        """`hip.Context.classify_sweep` under this module's current ablation set."""
+        return self._native_context().classify_sweep(images, list(units), targets)

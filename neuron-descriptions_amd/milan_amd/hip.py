@@ -53,6 +53,7 @@ _CONV_PRECISIONS = dict(f32=0, split_f16=1, split_f16_strip=3, split_f16_tap_maj
 DTYPE_U8, DTYPE_F32 = 0, 1
 
 ERR_ARG, ERR_SHAPE, ERR_STATE, ERR_WORKSPACE, ERR_NO_LM = -1, -2, -3, -4, -5
+ERR_INDEX = -6  # a unit beyond its layer's channels (milan_set_ablation): IndexError
 
 
 class HipUnavailableError(RuntimeError):
@@ -143,6 +144,11 @@ SIGNATURES = {
                               _P]),
     'milan_set_beam_path': (_I, [_P, _I]),
     'milan_get_beam_path': (_I, [_P]),
+    'milan_set_ablation': (_I, [_P, _P, _P, _I, _P]),
+    'milan_classify_workspace_bytes': (_SZ, [_P, _I, _I, _I, _I]),
+    'milan_classify': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    'milan_classify_sweep':
+        (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _SZ, _P]),
     'milan_set_graph_capture': (_I, [_P, _I]),
     'milan_graph_stats': (_I, [
         _P, ctypes.POINTER(ctypes.c_longlong),
@@ -253,7 +259,9 @@ SIGNATURES = {
 # (an older MILAN_LIB) still loads, and the calls that need them say so
 PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_lm_backward', 'milan_beam_merge', 'milan_set_beam_path',
-          'milan_get_beam_path')
+          'milan_get_beam_path', 'milan_set_ablation',
+          'milan_classify_workspace_bytes', 'milan_classify',
+          'milan_classify_sweep')
 
 _lib = None
 
@@ -306,6 +314,8 @@ def _check(code: int) -> None:
     msg = load_library().milan_last_error().decode(errors='replace')
     if code in (ERR_ARG, ERR_SHAPE, ERR_NO_LM):
         raise ValueError(msg)  # the reference raises ValueError for these
+    if code == ERR_INDEX:
+        raise IndexError(msg)  # `mask[:, units] = 0` (src/utils/ablations.py:39)
     raise RuntimeError(f'libmilan_hip error {code}: {msg}')
 
 
@@ -409,6 +419,8 @@ class Context:
                 self.lib.milan_create(ctypes.byref(self._h), self.device.index,
                                       ctypes.byref(dims)))
             keep = []
+            fc = state_dict.get('encoder.encoder.model.fc.weight')
+            self.num_classes = int(fc.shape[0]) if fc is not None else 0
             for name, tensor in state_dict.items():
                 if not tensor.dtype.is_floating_point:
                     continue  # e.g. num_batches_tracked
@@ -776,6 +788,104 @@ class Context:
             return out
 
         return self._guarded('encode_spatial', run, check)
+
+    # -- unit ablation and classification (ResNet trunks with an `fc` head) -----------
+    ABLATION_LEVELS = ('conv1', 'layer1', 'layer2', 'layer3', 'layer4')
+
+    def _need(self, name: str):
+        if not hasattr(self.lib, name):
+            raise HipUnavailableError(f'this build of libmilan_hip has no {name}')
+        return getattr(self.lib, name)
+
+    def _unit_arrays(self, pairs):
+        """[(level, unit), ...] -> two host int32 arrays; a level is 0..4 or its layer name."""
+        levels, units = [], []
+        for level, unit in pairs:
+            if isinstance(level, str):
+                if level not in self.ABLATION_LEVELS:
+                    raise ValueError(f'layer {level!r} cannot be ablated natively; the '
+                                     f'layers are {self.ABLATION_LEVELS}')
+                level = self.ABLATION_LEVELS.index(level)
+            levels.append(int(level))
+            units.append(int(unit))
+        count = len(levels)
+        return ((ctypes.c_int32 * max(1, count))(*levels),
+                (ctypes.c_int32 * max(1, count))(*units), count)
+
+    def set_ablation(self, pairs=()) -> None:
+        """Install the set of (level, unit) pairs the classify calls zero (level 0..4 or
+        'conv1', 'layer1'..'layer4'); an empty sequence clears it.  Duplicates and order do
+        not matter.  `encode*` / `describe` never read it.  Synchronises the stream."""
+        fn = self._need('milan_set_ablation')
+        levels, units, count = self._unit_arrays(pairs)
+        with torch.cuda.device(self.device):
+            _check(fn(self._h, levels, units, count, _stream(self.device)))
+
+    def _classify_ws(self, n: int, h: int, w: int, sweep: int) -> torch.Tensor:
+        need = int(self._need('milan_classify_workspace_bytes')(self._h, n, h, w, sweep))
+        ws = getattr(self, '_cls_ws', None)
+        if ws is None or ws.numel() < need:
+            self._cls_ws = None  # free before growing
+            self._cls_ws = ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _classify_images(self, images: torch.Tensor) -> torch.Tensor:
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise ValueError(f'images must be (n,3,H,W), got {tuple(images.shape)}')
+        if images.shape[0] < 1:
+            raise ValueError('classify needs at least one image')
+        return _dev(images.detach(), self.device, torch.float32)
+
+    def classify(self, images: torch.Tensor, return_logits: bool = True,
+                 check: bool = True) -> torch.Tensor:
+        """(n,3,H,W) float images, fed as they are (normalised by the caller), through the
+        trunk and its `fc` head under the current ablation set: the (n, classes) logits, or
+        with `return_logits=False` the (n,) int64 argmax (torch's tie / NaN rule)."""
+        fn = self._need('milan_classify')
+        images = self._classify_images(images)
+        n, _, h, w = images.shape
+        ws = self._classify_ws(n, h, w, 0)
+        classes = max(1, self.num_classes)
+        logits = (torch.empty(n, classes, dtype=torch.float32, device=self.device)
+                  if return_logits else None)
+        preds = (None if return_logits else
+                 torch.empty(n, dtype=torch.int64, device=self.device))
+
+        def run():
+            with torch.cuda.device(self.device):
+                _check(fn(self._h, images.data_ptr(), n, h, w, _ptr(logits), _ptr(preds),
+                          ws.data_ptr(), ws.numel(), _stream(self.device)))
+            return logits if return_logits else preds
+
+        return self._guarded('classify', run, check)
+
+    def classify_sweep(self, images: torch.Tensor, pairs,
+                       targets: Optional[torch.Tensor] = None, check: bool = True):
+        """For every (level, unit) of `pairs` the predictions of `classify` under the current
+        set plus that one unit, bit for bit, sharing the forward pass up to the unit's level.
+        Returns predictions (len(pairs), n) int64, or with `targets` (n,) the pair
+        (predictions, correct) where correct[j] counts predictions[j] == targets."""
+        fn = self._need('milan_classify_sweep')
+        images = self._classify_images(images)
+        n, _, h, w = images.shape
+        levels, units, count = self._unit_arrays(pairs)
+        preds = torch.empty(count, n, dtype=torch.int64, device=self.device)
+        correct = None
+        if targets is not None:
+            if tuple(targets.shape) != (n,):
+                raise ValueError(f'targets shape {tuple(targets.shape)} != {(n,)}')
+            targets = _dev(targets, self.device, torch.int64)
+            correct = torch.zeros(count, dtype=torch.int32, device=self.device)
+        ws = self._classify_ws(n, h, w, max(1, count))
+
+        def run():
+            with torch.cuda.device(self.device):
+                _check(fn(self._h, images.data_ptr(), n, h, w, levels, units, count,
+                          _ptr(targets), _ptr(correct), preds.data_ptr(), ws.data_ptr(),
+                          ws.numel(), _stream(self.device)))
+            return preds if targets is None else (preds, correct)
+
+        return self._guarded('classify_sweep', run, check)
 
     def init_state(self, features: torch.Tensor):
         n, k, _ = features.shape

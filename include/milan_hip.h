@@ -433,6 +433,36 @@ int milan_encoder_absmax(milan_ctx* ctx, const void* images, int image_dtype,
                          void* workspace, size_t workspace_bytes,
                          milan_stream stream);
 
+/* The split-f16 decoder's feature scale.  The decoder's feature-carrying operands (the pooled
+ * features of init_h / init_c, the features of the hoisted key_to_hidden, the gated context of
+ * the cell's [emb | ctx * gate | h]) are converted to split format as x * 2^k and the factor is
+ * undone exactly (accumulator scale; feature columns of the cell's split weight copy), so
+ * features far below 1 keep the fp32 class (`lo` leaves the f16 normal range below
+ * 2^-3 / 2^k) and features above 65504 / 2^k are reported (MILAN_STATUS_SATURATED).  A
+ * property of the context, never of a call's data; default 2^0, at which every bit is what
+ * it was before this entry point existed.  The exact-fp32 mode does not know about it.
+ *   milan_set_feature_scale_log2  k in [-MAX, MAX]; rewrites the cell's split weight copy,
+ *                           drops captured decode graphs, synchronises `stream`.
+ *   milan_get_feature_absmax     what bounds |feature| for the last milan_encoder_absmax
+ *                           sample under ANY mask: the largest |value| of the five pyramid
+ *                           taps (a pooled feature is a mask-weighted mean of them); 0 before
+ *                           the first.
+ *   milan_set_embedding_scale_log2  the same for the embedding columns of the two LSTM inputs
+ *                           (decoder and LM layer 0): the tables are gathered as e * 2^k, those
+ *                           weight columns hold W / 2^k; an embedding beyond 65504 / 2^k is
+ *                           reported.  milan_get_embedding_absmax: the largest |entry| of the
+ *                           tables (computed on first use, on the legacy stream).
+ * A NaN feature is not a saturation: it crosses the conversion as an f16 NaN and poisons what
+ * fp32 arithmetic would poison.
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them. */
+#define MILAN_FEATURE_SCALE_LOG2_MAX 30
+int milan_set_feature_scale_log2(milan_ctx* ctx, int log2_scale, milan_stream stream);
+int milan_get_feature_scale_log2(const milan_ctx* ctx);
+float milan_get_feature_absmax(const milan_ctx* ctx);
+int milan_set_embedding_scale_log2(milan_ctx* ctx, int log2_scale, milan_stream stream);
+int milan_get_embedding_scale_log2(const milan_ctx* ctx);
+float milan_get_embedding_absmax(milan_ctx* ctx);
+
 /* Measurement hook (bench.py's roofline leg): while enabled, every launch of
  * the implicit-GEMM MFMA kernel is bracketed by HIP events on its launch
  * stream.  milan_profile_read synchronises the device and returns the summed

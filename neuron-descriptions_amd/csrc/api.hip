@@ -73,6 +73,53 @@ int make_split_weight(milan_ctx* c, const float* w, int n, int kp, float** ws,
   return split_weight_into(w, n, kp, *ws, ws_inv, d_max, s);
 }
 
+// dst = w with columns [0, c0) of every row multiplied by `f0` and columns [c0, c1) by `f1`
+// (powers of two)
+__global__ void scale_cols_kernel(const float* __restrict__ w, long n, int kp, int c0, int c1,
+                                  float f0, float f1, float* __restrict__ dst) {
+  const long total = n * kp;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total;
+       i += (long)gridDim.x * blockDim.x) {
+    const int col = (int)(i % kp);
+    dst[i] = col < c0 ? w[i] * f0 : (col < c1 ? w[i] * f1 : w[i]);
+  }
+}
+
+// The split copy of an LSTM's concatenated weight [W_ih | W_hh] again, its embedding columns
+// [0, E) divided by the context's embedding scale and its feature columns [E, E + F) (the
+// decoder's cell; F = 0 for the LM's layer 0) by the feature scale, written over the old
+// copy; the layer's weight scale follows the new maximum.
+static int resplit_cat(milan_ctx* c, LinearW& w, int E, int F, hipStream_t s) {
+  if (!w.ws) return 0;
+  float* tmp = nullptr;
+  MILAN_CHECK_HIP(hipMalloc((void**)&tmp, sizeof(float) * (size_t)w.n * w.kp));
+  const long total = (long)w.n * w.kp;
+  const long blocks = (total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096;
+  hipLaunchKernelGGL(scale_cols_kernel, dim3((int)blocks), dim3(256), 0, s, w.w, (long)w.n,
+                     w.kp, E, E + F, 1.f / c->emb_scale, 1.f / c->feat_scale, tmp);
+  unsigned int* d_max = reinterpret_cast<unsigned int*>(c->zero) + 32;  // scratch
+  set_status_word(nullptr);  // (weight packing is not a saturation event of a call)
+  int r = (int)hipGetLastError();
+  if (r == 0) r = split_weight_into(tmp, w.n, w.kp, w.ws, &w.ws_inv, d_max, s);
+  const hipError_t e = hipStreamSynchronize(s);
+  (void)hipFree(tmp);
+  MILAN_TRY(r);
+  MILAN_CHECK_HIP(e);
+  return 0;
+}
+
+static int resplit_lstm_cats(milan_ctx* c, hipStream_t s) {
+  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  // a captured decode graph holds the old scales in its kernel arguments
+  for (auto& g : c->graphs)
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  c->graphs.clear();
+  MILAN_TRY(resplit_cat(c, c->lstm_cat, c->d.embedding_size, c->d.feature_size, s));
+  if (!c->lm_cat.empty())
+    MILAN_TRY(resplit_cat(c, c->lm_cat[0], c->d.lm_embedding_size, 0, s));
+  return 0;
+}
+
 }  // namespace milan
 
 using namespace milan;
@@ -664,6 +711,74 @@ int milan_set_act_scale_log2(milan_ctx* c, int k, milan_stream stream) {
 
 int milan_get_act_scale_log2(const milan_ctx* c) { return c ? c->act_scale_log2 : -1; }
 
+int milan_set_feature_scale_log2(milan_ctx* c, int k, milan_stream stream) {
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
+  MILAN_REQUIRE(k >= -MILAN_FEATURE_SCALE_LOG2_MAX && k <= MILAN_FEATURE_SCALE_LOG2_MAX,
+                MILAN_ERR_ARG, "feature scale 2^%d outside 2^-%d .. 2^%d", k,
+                MILAN_FEATURE_SCALE_LOG2_MAX, MILAN_FEATURE_SCALE_LOG2_MAX);
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  if (k == c->feat_scale_log2) return 0;
+  // (the operand scale and the weight copy move together: a failed resplit restores the old
+  // scale and rebuilds the old copy)
+  const int old = c->feat_scale_log2;
+  c->feat_scale = ldexpf(1.f, k);
+  c->feat_scale_log2 = k;
+  const int r = resplit_lstm_cats(c, (hipStream_t)stream);
+  if (r != 0) {
+    c->feat_scale = ldexpf(1.f, old);
+    c->feat_scale_log2 = old;
+    (void)resplit_lstm_cats(c, (hipStream_t)stream);
+  }
+  return r;
+}
+
+int milan_get_feature_scale_log2(const milan_ctx* c) { return c ? c->feat_scale_log2 : 0; }
+
+float milan_get_feature_absmax(const milan_ctx* c) { return c ? c->feat_absmax : 0.f; }
+
+int milan_set_embedding_scale_log2(milan_ctx* c, int k, milan_stream stream) {
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
+  MILAN_REQUIRE(k >= -MILAN_FEATURE_SCALE_LOG2_MAX && k <= MILAN_FEATURE_SCALE_LOG2_MAX,
+                MILAN_ERR_ARG, "embedding scale 2^%d outside 2^-%d .. 2^%d", k,
+                MILAN_FEATURE_SCALE_LOG2_MAX, MILAN_FEATURE_SCALE_LOG2_MAX);
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  if (k == c->emb_scale_log2) return 0;
+  const int old = c->emb_scale_log2;
+  c->emb_scale = ldexpf(1.f, k);
+  c->emb_scale_log2 = k;
+  const int r = resplit_lstm_cats(c, (hipStream_t)stream);
+  if (r != 0) {  // (as milan_set_feature_scale_log2)
+    c->emb_scale = ldexpf(1.f, old);
+    c->emb_scale_log2 = old;
+    (void)resplit_lstm_cats(c, (hipStream_t)stream);
+  }
+  return r;
+}
+
+int milan_get_embedding_scale_log2(const milan_ctx* c) { return c ? c->emb_scale_log2 : 0; }
+
+float milan_get_embedding_absmax(milan_ctx* c) {
+  // largest |entry| of the decoder's and the LM's embedding table (legacy stream, synchronous)
+  if (!c || !c->finalized) return 0.f;
+  if (c->emb_absmax > 0.f) return c->emb_absmax;
+  if (hipSetDevice(c->device) != hipSuccess) return 0.f;
+  // (a word of its own next to the status word -- not the split conversion's scratch, which a
+  // call on another stream may be using; the tables never change after finalize)
+  unsigned int* d_max = c->status + 10;
+  if (hipMemset(d_max, 0, sizeof(unsigned int)) != hipSuccess) return 0.f;
+  const float* tables[2] = {c->embedding, c->lm_embedding};
+  const long sizes[2] = {(long)c->d.vocab_size * c->d.embedding_size,
+                         (long)c->d.vocab_size * c->d.lm_embedding_size};
+  for (int i = 0; i < 2; ++i)
+    if (tables[i])
+      hipLaunchKernelGGL(absmax_kernel, dim3(256), dim3(256), 0, nullptr, tables[i], sizes[i],
+                         d_max);
+  unsigned bits = 0;
+  if (hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost) != hipSuccess) return 0.f;
+  memcpy(&c->emb_absmax, &bits, sizeof(float));
+  return c->emb_absmax;
+}
+
 int milan_encoder_absmax(milan_ctx* c, const void* images, int image_dtype, int n_images,
                          int height, int width, float* absmax, void* workspace,
                          size_t workspace_bytes, milan_stream stream) {
@@ -678,8 +793,8 @@ int milan_encoder_absmax(milan_ctx* c, const void* images, int image_dtype, int 
   MILAN_REQUIRE(feats, MILAN_ERR_WORKSPACE, "absmax: workspace too small");
   Arena enc;
   enc.base = a.base + a.off; enc.size = a.size - a.off; enc.off = 0;
-  unsigned* word = c->status + 8;
-  MILAN_CHECK_HIP(hipMemsetAsync(word, 0, sizeof(unsigned), s));
+  unsigned* word = c->status + 8;   // [0] activations, [1] what bounds the features
+  MILAN_CHECK_HIP(hipMemsetAsync(word, 0, 2 * sizeof(unsigned), s));
   const int saved = c->precision;
   c->precision = MILAN_PRECISION_F32;
   c->calib = word;
@@ -689,10 +804,25 @@ int milan_encoder_absmax(milan_ctx* c, const void* images, int image_dtype, int 
   c->calib = nullptr;
   c->precision = saved;
   MILAN_TRY(r);
-  unsigned bits = 0;
-  MILAN_CHECK_HIP(hipMemcpyAsync(&bits, word, sizeof(bits), hipMemcpyDeviceToHost, s));
+  // ... and next to it what bounds the FEATURES under any mask (the decoder's feature scale
+  // is picked from it): a pooled feature is a mask-weighted mean of tap activations, so the
+  // largest |value| of the five taps bounds it.  Taps 1..4 are activations counted above;
+  // tap 0, the raw conv1 output, was folded into this word by the pass; the unmasked
+  // features of the sample join for good measure.
+  unsigned* fword = word + 1;
+  {
+    const long total = (long)n_images * c->d.feature_size;
+    const long blocks = (total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024;
+    hipLaunchKernelGGL(absmax_kernel, dim3((int)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s,
+                       feats, total, fword);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  unsigned bits[2] = {0, 0};
+  MILAN_CHECK_HIP(hipMemcpyAsync(bits, word, sizeof(bits), hipMemcpyDeviceToHost, s));
   MILAN_CHECK_HIP(hipStreamSynchronize(s));
-  memcpy(absmax, &bits, sizeof(float));
+  memcpy(absmax, &bits[0], sizeof(float));
+  memcpy(&c->feat_absmax, &bits[1], sizeof(float));
+  if (*absmax > c->feat_absmax) c->feat_absmax = *absmax;
   return 0;
 }
 

@@ -175,8 +175,11 @@ void profile_tag_kernel(int family);
 // feature rows of empty-mask exemplars and the LM's initial state came back as garbage:
 // tools/graph_describe.py, tests/test_gpu_skip_empty.py).
 int launch_zero_fill(void* p, size_t bytes, hipStream_t s);
+// A NaN crosses as an f16 NaN in `hi` (not a saturation); with `nanrow` it leaves as 0 and
+// nanrow[row] = stamp marks its row instead.
 int launch_f32_to_split(const float* src, long ld_src, float* dst, long ld_dst,
-                        long rows, int K, float scale, hipStream_t s);
+                        long rows, int K, float scale, hipStream_t s, int* nanrow = nullptr,
+                        int stamp = 0);
 int gemm_profile_enable(int enable);
 // per-device launch state (gemm.hip): dynamic-LDS opt-in of a kernel, CU count in octets
 int ensure_lds_attr(const void* kern, int bytes);
@@ -551,6 +554,23 @@ struct milan_ctx {
   float act_scale = 32.f;
   int act_scale_log2 = 5;
   float *bn1_scale_s = nullptr, *bn1_shift_s = nullptr;
+  // Split-f16 decoder: the feature-carrying A operands (pooled features of init_h / init_c,
+  // features of key_to_hidden, the gated context in [emb | ctx * gate | h]) are converted as
+  // x * feat_scale, an exact power of two (milan_set_feature_scale_log2, default 2^0), for the
+  // same reason as act_scale above: features far below 1 lose `lo` to the f16 subnormals.
+  // Undone exactly: acc_scale / feat_scale for the three single-source products, and the
+  // feature columns of lstm_cat's split copy hold W / feat_scale.  A property of the context,
+  // never of a call's data.  Neither the exact-fp32 mode nor a layer without a split copy
+  // knows about it.
+  // emb_scale (milan_set_embedding_scale_log2): the same for the embedding columns of the two
+  // LSTM inputs (decoder: [emb | ...] of lstm_cat, LM: layer 0 of lm_cat); the tables are
+  // gathered as e * emb_scale and those weight columns hold W / emb_scale.
+  float feat_scale = 1.f;
+  int feat_scale_log2 = 0;
+  float emb_scale = 1.f;
+  int emb_scale_log2 = 0;
+  float emb_absmax = 0.f;    // largest |entry| of the embedding tables (milan_get_embedding_absmax)
+  float feat_absmax = 0.f;   // largest |feature| of the last milan_encoder_absmax sample
   unsigned* stem_lut = nullptr;  // byte -> split value table of the uint8 stem (StemArgs::lut), lazily
   // device status word (MILAN_STATUS_* bits, milan_status): ORed by the split epilogues when
   // a value hit the +-65504 clamp and by the input conversion when a pixel was not finite

@@ -210,17 +210,28 @@ static int lm_finalize(milan_ctx* c, hipStream_t s) {
 // small kernels
 // ---------------------------------------------------------------------------
 // pooled[n][f] = mean_k features[n][k][f]      (decoders.py:564)
+// `status` != nullptr (split-f16 mode): a feature whose split form would clamp,
+// |x * scale| >= 65504, is reported here as by the key projection's conversion, so that
+// init_state on its own is as loud as step / decode (the mean of k values may be in range
+// where one of them is not).  A NaN is not a saturation (fmaxf drops it).
 __global__ void mean_k_kernel(const float* __restrict__ feat, int n, int k,
-                              int F, float* __restrict__ pooled) {
+                              int F, float* __restrict__ pooled, float scale,
+                              unsigned* status) {
   const long total = (long)n * F;
+  float sat = 0.f;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
        idx += (long)gridDim.x * blockDim.x) {
     const long i = idx / F;
     const int f = idx - i * F;
     float s = 0.f;
-    for (int j = 0; j < k; ++j) s += feat[(i * k + j) * F + f];
+    for (int j = 0; j < k; ++j) {
+      const float x = feat[(i * k + j) * F + f];
+      sat = fmaxf(sat, fabsf(x * scale));
+      s += x;
+    }
     pooled[idx] = s / (float)k;
   }
+  report_saturation(status, sat);
 }
 
 // att[r][:] = softmax_k( w . tanh(q[r] + keys[neuron][k]) + b )
@@ -228,7 +239,9 @@ __global__ void mean_k_kernel(const float* __restrict__ feat, int n, int k,
 __global__ __launch_bounds__(256) void attend_kernel(
     const float* __restrict__ q, const float* __restrict__ keys,
     const float* __restrict__ w, const float* __restrict__ b, int rows, int rpn,
-    int k, int A, float* __restrict__ att) {
+    int k, int A, float* __restrict__ att, const int* __restrict__ nanrow, int stamp) {
+  // (nanrow[r] == stamp: the row's h was NaN and left its conversion as 0 -- step_core; its
+  // attention is NaN, as a NaN query makes it)
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= rows) return;
@@ -247,7 +260,8 @@ __global__ __launch_bounds__(256) void attend_kernel(
   float e = lane < k ? expf(mine - mx) : 0.f;
   float sum = e;
   for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  if (lane < k) att[(long)r * k + lane] = e / sum;
+  const bool bad = nanrow != nullptr && nanrow[r] == stamp;
+  if (lane < k) att[(long)r * k + lane] = bad ? __builtin_nanf("") : e / sum;
 }
 
 // The same for k <= 16 exemplars and A <= 512 attention units (MILAN: 15, 512), one
@@ -267,7 +281,7 @@ __device__ __forceinline__ float tanh_exp2(float x) {
 __global__ __launch_bounds__(256) void attend16_kernel(
     const float* __restrict__ q, const float* __restrict__ keys,
     const float* __restrict__ w, const float* __restrict__ b, int rows, int rpn,
-    int k, int A, float* __restrict__ att) {
+    int k, int A, float* __restrict__ att, const int* __restrict__ nanrow, int stamp) {
   const int neuron = blockIdx.x;
   // (blockIdx.y, wave): which of the neuron's rows, stride 4 gridDim.y
   const int wave = blockIdx.y * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -331,12 +345,14 @@ __global__ __launch_bounds__(256) void attend16_kernel(
     float sum = ev;
 #pragma unroll
     for (int X = 4; X < 64; X <<= 1) sum += __shfl_xor(sum, X);
-    if (writer) att[(long)r * k + j] = ev / sum;
+    const bool bad = nanrow != nullptr && nanrow[r] == stamp;  // (see attend_kernel)
+    if (writer) att[(long)r * k + j] = bad ? __builtin_nanf("") : ev / sum;
   }
 }
 
 static void launch_attend(const float* q, const float* keys, const float* w, const float* b,
-                          int rows, int rpn, int k, int A, float* att, hipStream_t s) {
+                          int rows, int rpn, int k, int A, float* att, const int* nanrow,
+                          int stamp, hipStream_t s) {
   // MILAN_ATTEND_FAST=0: libm tanhf (A/B timing)
   static const bool fast = !(getenv("MILAN_ATTEND_FAST") && atoi(getenv("MILAN_ATTEND_FAST")) == 0);
   if (fast && k <= kAttMaxK && A <= 64 * kAttMaxE) {
@@ -346,10 +362,10 @@ static void launch_attend(const float* q, const float* keys, const float* w, con
     const int rs_max = (rpn + 3) / 4;
     rs = rs < 1 ? 1 : (rs > rs_max ? rs_max : rs);
     hipLaunchKernelGGL(attend16_kernel, dim3(neurons, rs), dim3(256), 0, s, q, keys, w, b, rows,
-                       rpn, k, A, att);
+                       rpn, k, A, att, nanrow, stamp);
   } else {
     hipLaunchKernelGGL(attend_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, q, keys, w, b,
-                       rows, rpn, k, A, att);
+                       rows, rpn, k, A, att, nanrow, stamp);
   }
 }
 
@@ -365,7 +381,15 @@ constexpr int kCtxMaxK = 16;  // register-resident exemplars (k = 15 in MILAN)
 template <bool RESIDENT>
 __global__ __launch_bounds__(256) void context_kernel(
     const float* __restrict__ att, const float* __restrict__ feat, int rows,
-    int rpn, int k, int F, float* __restrict__ ctx) {
+    int rpn, int k, int F, float* __restrict__ ctx, float scale,
+    int* __restrict__ nanrow, int stamp) {
+  // `scale`: the context's feature scale (a power of two, 1 unless the cell's product runs on
+  // the split copy of [W_ih | W_hh], whose feature columns hold W / scale): ctx leaves as
+  // ctx * scale, exactly.
+  // `nanrow` != nullptr (the consumer writes split format in a GEMM epilogue, which would
+  // clamp a NaN to -65504 and report a saturation): a NaN leaves as 0 and its row is marked,
+  // nanrow[r] = stamp; embed_split_kernel then poisons the row's embedding columns, which
+  // makes every gate of the row NaN -- what any NaN in [emb | ctx * gate] does.
   const int neuron = blockIdx.x;
   const int f = (blockIdx.y * 256 + threadIdx.x) * 4;
   if (f >= F) return;
@@ -399,31 +423,42 @@ __global__ __launch_bounds__(256) void context_kernel(
         s2 = fmaf(aj, w.z, s2); s3 = fmaf(aj, w.w, s3);
       }
     }
-    *reinterpret_cast<float4*>(ctx + (long)r * F + f) = make_float4(s0, s1, s2, s3);
+    float4 o = make_float4(s0 * scale, s1 * scale, s2 * scale, s3 * scale);
+    if (nanrow != nullptr && (o.x != o.x || o.y != o.y || o.z != o.z || o.w != o.w)) {
+      nanrow[r] = stamp;  // (every writer of a row stores the same value)
+      o.x = o.x != o.x ? 0.f : o.x; o.y = o.y != o.y ? 0.f : o.y;
+      o.z = o.z != o.z ? 0.f : o.z; o.w = o.w != o.w ? 0.f : o.w;
+    }
+    *reinterpret_cast<float4*>(ctx + (long)r * F + f) = o;
   }
 }
 
-// dst[r][0:E] = table[tok[r]]
+// dst[r][0:E] = table[tok[r]] * scale   (scale: the context's embedding scale where the
+// consumer is the split copy of an LSTM's concatenated weight, else 1)
 __global__ void embed_kernel(const float* __restrict__ table,
                              const int64_t* __restrict__ tok, int rows, int E,
-                             float* __restrict__ dst, int ldd) {
+                             float* __restrict__ dst, int ldd, float scale) {
   const long total = (long)rows * E;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
        idx += (long)gridDim.x * blockDim.x) {
     const long r = idx / E;
     const int e = idx - r * E;
-    dst[r * ldd + e] = table[tok[r] * E + e];
+    dst[r * ldd + e] = table[tok[r] * E + e] * scale;
   }
 }
 
-// same, written in split format (groups of 8 channels [hi x8 | lo x8])
+// same, written in split format (groups of 8 channels [hi x8 | lo x8]); an embedding that
+// leaves the f16 range under `scale` is reported like any other clamped split value
 __global__ void embed_split_kernel(const float* __restrict__ table,
                                    const int64_t* __restrict__ tok, int rows, int E,
-                                   float* __restrict__ dst, int ldd,
-                                   const int* __restrict__ live = nullptr) {
+                                   float* __restrict__ dst, int ldd, float scale,
+                                   unsigned* status,
+                                   const int* __restrict__ live = nullptr,
+                                   const int* __restrict__ nanrow = nullptr, int stamp = 0) {
   if (live) rows = min(rows, *live);   // (row count on the device: lm_score_dedup)
   const int g8 = E >> 3;
   const long total = (long)rows * g8;
+  float sat = 0.f;
   for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
        idx += (long)gridDim.x * blockDim.x) {
     const long r = idx / g8;
@@ -432,14 +467,20 @@ __global__ void embed_split_kernel(const float* __restrict__ table,
     _Float16 hi[8], lo[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float x = fminf(fmaxf(sp[e], -65504.f), 65504.f);
+      const float x = fminf(fmaxf(sp[e] * scale, -65504.f), 65504.f);
+      sat = fmaxf(sat, fabsf(x));
       hi[e] = (_Float16)x;
       lo[e] = (_Float16)(x - (float)hi[e]);
+    }
+    if (nanrow != nullptr && nanrow[r] == stamp) {  // context_kernel: this row's context is NaN
+#pragma unroll
+      for (int e = 0; e < 8; ++e) hi[e] = (_Float16)__builtin_nanf("");
     }
     float4* d = reinterpret_cast<float4*>(dst + r * ldd + q * 8);
     d[0] = *reinterpret_cast<const float4*>(hi);
     d[1] = *reinterpret_cast<const float4*>(lo);
   }
+  report_saturation(status, sat);
 }
 
 // torch LSTM cell pointwise, gate order i,f,g,o.
@@ -1241,19 +1282,21 @@ static inline unsigned nblk_all(long total) {
 // y = epi(A W^T + b): fp32 MFMA, or -- in split-f16 mode, when the layer has a
 // split weight copy -- A is first rewritten as (hi,lo) f16 pairs into the
 // context's scratch and the 3xf16 MFMA kernel runs (outputs stay fp32).
+// `a_scale` (a power of two; the context's feature scale for a feature-carrying A): the
+// split path converts A * a_scale and divides the accumulators by it again, both exactly.
 static int lin(milan_ctx* c, const float* A, long lda, const LinearW& w, float* C,
                int ldc, int M, int epi, hipStream_t s,
-               const float* aux = nullptr, int ldaux = 0) {
+               const float* aux = nullptr, int ldaux = 0, float a_scale = 1.f) {
   GemmArgs g = linear_args(A, lda, w.w, w.b, C, ldc, M, w.n, w.k, epi, c->zero,
                            aux, ldaux);
   if (c->precision == MILAN_PRECISION_SPLIT_F16 && w.ws && c->scratch &&
       (size_t)M * w.k <= c->scratch_floats) {
-    MILAN_TRY(launch_f32_to_split(A, lda, c->scratch, w.k, M, w.k, 1.f, s));
+    MILAN_TRY(launch_f32_to_split(A, lda, c->scratch, w.k, M, w.k, a_scale, s));
     g.A = c->scratch;
     g.a_pix_stride = g.a_img_stride = w.k;
     g.W = w.ws;
     g.a_split = 1;
-    g.acc_scale = w.ws_inv;
+    g.acc_scale = w.ws_inv * (1.f / a_scale);
   }
   return launch_gemm(g, s);
 }
@@ -1306,8 +1349,13 @@ static int lm_step(milan_ctx* c, const int64_t* tok, int rows, LmState& st,
                    hipStream_t s) {
   const milan_dims& d = c->d;
   const int Hl = d.lm_hidden_size, El = d.lm_embedding_size, V = d.vocab_size;
+  // (the embedding scale where layer 0 runs on the split copy of [W_ih | W_hh]: lstm_layer's
+  // own condition)
+  const bool cat_split = c->precision == MILAN_PRECISION_SPLIT_F16 && c->lm_cat[0].ws &&
+                         c->scratch && (size_t)rows * c->lm_cat[0].k <= c->scratch_floats;
   hipLaunchKernelGGL(embed_kernel, dim3(nblk((long)rows * El)), dim3(256), 0, s,
-                     c->lm_embedding, tok, rows, El, emb, El);
+                     c->lm_embedding, tok, rows, El, emb, El,
+                     cat_split ? c->emb_scale : 1.f);
   const float* in = emb;
   int in_dim = El;
   for (int l = 0; l < d.lm_layers; ++l) {
@@ -1337,6 +1385,10 @@ struct DecBuf {
   int32_t* len1;
   float* scratch;
   size_t scratch_floats;
+  // rows whose context vector is NaN in step `nan_stamp` (context_kernel; zeroed once per
+  // call, a step's mark is its 1-based number)
+  int* nanrow;
+  int nan_stamp;
 };
 
 static size_t lm_dedup_floats(const milan_dims& d, size_t R, int L, int G);
@@ -1364,6 +1416,8 @@ static void dec_plan(const milan_ctx* c, int n, int k, int beam, int T, bool lm,
   b->tok = a.get<int64_t>(R);
   b->seqs = a.get<int64_t>(R * (T + 1));
   b->len1 = a.get<int32_t>(2 * (size_t)n + 2);
+  b->nanrow = a.get<int>(R);
+  b->nan_stamp = 0;
   {
     const size_t rows = R > (size_t)n * k ? R : (size_t)n * k;
     // widest split-format A operand: the LSTM's concatenated [x | h]
@@ -1412,17 +1466,22 @@ static int check_dims(const milan_ctx* c, int k) {
 static int project_keys(milan_ctx* c, const float* features, int nk, float* keys,
                         hipStream_t s) {
   const milan_dims& d = c->d;
-  return lin(c, features, d.feature_size, c->k2h, keys, d.attention_size, nk, EPI_BIAS, s);
+  return lin(c, features, d.feature_size, c->k2h, keys, d.attention_size, nk, EPI_BIAS, s,
+             nullptr, 0, c->feat_scale);
 }
 
 static int init_state_impl(milan_ctx* c, const float* features, int n, int k,
                            float* pooled, float* h, float* cc, hipStream_t s) {
   const milan_dims& d = c->d;
   const int F = d.feature_size, H = d.hidden_size;
+  const bool split = c->precision == MILAN_PRECISION_SPLIT_F16;
   hipLaunchKernelGGL(mean_k_kernel, dim3(nblk((long)n * F)), dim3(256), 0, s,
-                     features, n, k, F, pooled);
-  MILAN_TRY(lin(c, pooled, F, c->init_h, h, H, n, EPI_BIAS_TANH, s));
-  MILAN_TRY(lin(c, pooled, F, c->init_c, cc, H, n, EPI_BIAS_TANH, s));
+                     features, n, k, F, pooled, c->feat_scale,
+                     split ? status_word() : nullptr);
+  MILAN_TRY(lin(c, pooled, F, c->init_h, h, H, n, EPI_BIAS_TANH, s, nullptr, 0,
+                c->feat_scale));
+  MILAN_TRY(lin(c, pooled, F, c->init_c, cc, H, n, EPI_BIAS_TANH, s, nullptr, 0,
+                c->feat_scale));
   return 0;
 }
 
@@ -1437,15 +1496,16 @@ int decoder_init_state(milan_ctx* c, const float* features, int n, int k,
 }
 
 static void launch_context(const float* att, const float* features, int rows,
-                           int rpn, int k, int F, float* ctx, hipStream_t s) {
+                           int rpn, int k, int F, float* ctx, float scale,
+                           int* nanrow, int stamp, hipStream_t s) {
   const int gy = (F / 4 + 255) / 256;
   const int neurons = (rows + rpn - 1) / rpn;
   if (k <= kCtxMaxK)
     hipLaunchKernelGGL(context_kernel<true>, dim3(neurons, gy), dim3(256), 0, s,
-                       att, features, rows, rpn, k, F, ctx);
+                       att, features, rows, rpn, k, F, ctx, scale, nanrow, stamp);
   else
     hipLaunchKernelGGL(context_kernel<false>, dim3(neurons, gy), dim3(256), 0, s,
-                       att, features, rows, rpn, k, F, ctx);
+                       att, features, rows, rpn, k, F, ctx, scale, nanrow, stamp);
 }
 
 // Everything of Decoder.step up to the vocabulary logits, for `rows` rows that
@@ -1467,11 +1527,24 @@ static int step_core(milan_ctx* c, const float* features, const float* keys,
                      c->q2h.ws && c->gate.ws && c->lstm_cat.ws && c->out.ws &&
                      E % 16 == 0 && F % 8 == 0 && H % 16 == 0 &&
                      (size_t)rows * (ldx + H) <= c->scratch_floats;
+  // the cell's product on the split copy of [W_ih | W_hh] (here, or in lstm_layer below --
+  // its own condition): the context leaves its kernel times the feature scale, which that
+  // copy's feature columns undo
+  const bool cat_split = c->precision == MILAN_PRECISION_SPLIT_F16 && c->lstm_cat.ws &&
+                         c->scratch && (size_t)rows * c->lstm_cat.k <= c->scratch_floats;
+  const float fs = cat_split ? c->feat_scale : 1.f;
   if (fused) {
     float* xs = c->scratch;                       // (rows, E+F) split
     float* hs = c->scratch + (size_t)rows * ldx;  // (rows, H) split
     float* hs2 = b->gates;  // h' split (vocabulary GEMM); the gate matrix is unused here
-    MILAN_TRY(launch_f32_to_split(h, H, hs, H, rows, H, 1.f, s));
+    // A NaN must not reach the gate product: its epilogue writes split format, which turns a
+    // NaN into -65504 and reports a saturation.  So a row whose h or context holds one is
+    // MARKED (b->nanrow[r] = this step's stamp) and computed on zeros: the conversion of h and
+    // context_kernel mark, attend* answers NaN for a marked row, embed_split_kernel poisons
+    // its embedding columns -- every gate, h', c' and logit of the row is NaN from there on,
+    // as fp32 arithmetic makes them, and no other row sees any of it.
+    const int stamp = ++b->nan_stamp;
+    MILAN_TRY(launch_f32_to_split(h, H, hs, H, rows, H, 1.f, s, b->nanrow, stamp));
     auto split_lin = [&](const LinearW& w, float* C, int ldc, int epi,
                          const float* aux, int ldaux) {
       GemmArgs g = linear_args(hs, H, w.ws, w.b, C, ldc, rows, w.n, w.k, epi,
@@ -1481,15 +1554,16 @@ static int step_core(milan_ctx* c, const float* features, const float* keys,
       return g;
     };
     MILAN_TRY(launch_gemm(split_lin(c->q2h, b->q, A, EPI_BIAS, nullptr, 0), s));
-    launch_attend(b->q, keys, c->att_w, c->att_b, rows, rpn, k, A, b->att, s);
-    launch_context(b->att, features, rows, rpn, k, F, b->ctx, s);
+    launch_attend(b->q, keys, c->att_w, c->att_b, rows, rpn, k, A, b->att, b->nanrow, stamp, s);
+    launch_context(b->att, features, rows, rpn, k, F, b->ctx, fs, b->nanrow, stamp, s);
     {
       GemmArgs g = split_lin(c->gate, xs + E, ldx, EPI_BIAS_SIGMUL, b->ctx, F);
       g.out_split = 1;  // aux stays fp32
       MILAN_TRY(launch_gemm(g, s));
     }
     hipLaunchKernelGGL(embed_split_kernel, dim3(nblk((long)rows * (E / 8))),
-                       dim3(256), 0, s, c->embedding, tok, rows, E, xs, ldx);
+                       dim3(256), 0, s, c->embedding, tok, rows, E, xs, ldx, c->emb_scale,
+                       status_word(), nullptr, b->nanrow, stamp);
     {
       // gates = [x | h] [W_ih | W_hh]^T: x from xs (k < E+F), h from hs
       const LinearW& w = c->lstm_cat;
@@ -1521,12 +1595,12 @@ static int step_core(milan_ctx* c, const float* features, const float* keys,
     return 0;
   }
   MILAN_TRY(lin(c, h, H, c->q2h, b->q, A, rows, EPI_BIAS, s));
-  launch_attend(b->q, keys, c->att_w, c->att_b, rows, rpn, k, A, b->att, s);
-  launch_context(b->att, features, rows, rpn, k, F, b->ctx, s);
+  launch_attend(b->q, keys, c->att_w, c->att_b, rows, rpn, k, A, b->att, nullptr, 0, s);
+  launch_context(b->att, features, rows, rpn, k, F, b->ctx, fs, nullptr, 0, s);
   // gated = sigmoid(W_g h + b_g) * ctx  -> x[:, E:]
   MILAN_TRY(lin(c, h, H, c->gate, b->x + E, ldx, rows, EPI_BIAS_SIGMUL, s, b->ctx, F));
   hipLaunchKernelGGL(embed_kernel, dim3(nblk((long)rows * E)), dim3(256), 0, s,
-                     c->embedding, tok, rows, E, b->x, ldx);
+                     c->embedding, tok, rows, E, b->x, ldx, cat_split ? c->emb_scale : 1.f);
   MILAN_TRY(lstm_layer(c, b->x, ldx, c->lstm_ih, h, H, c->lstm_hh, c->lstm_cat,
                        b->gates, cc, hn, cn, rows, s));
   MILAN_TRY(lin(c, hn, H, c->out, b->logits, V, rows, EPI_BIAS, s));
@@ -1589,6 +1663,7 @@ int decoder_step(milan_ctx* c, const float* features, int rows, int k,
   // per-row keys: the public step takes per-row features (un-hoisted API)
   MILAN_REQUIRE(ws.off <= ws.size, MILAN_ERR_WORKSPACE,
                 "step: workspace too small (%zu needed)", ws.off);
+  MILAN_TRY(launch_zero_fill(b.nanrow, sizeof(int) * (size_t)rows, s));
   MILAN_TRY(project_keys(c, features, rows * k, b.keys, s));
   MILAN_TRY(step_core(c, features, b.keys, rows, 1, k, tokens, h, cc, h_out,
                       c_out, &b, s));
@@ -1648,7 +1723,8 @@ static int lm_step_split(milan_ctx* c, const int64_t* tok, int rows, LmState& st
   const int Hl = d.lm_hidden_size, El = d.lm_embedding_size, V = d.vocab_size;
   float* emb_s = c->scratch;
   hipLaunchKernelGGL(embed_split_kernel, dim3(nblk((long)rows * (El / 8))),
-                     dim3(256), 0, s, c->lm_embedding, tok, rows, El, emb_s, El);
+                     dim3(256), 0, s, c->lm_embedding, tok, rows, El, emb_s, El, c->emb_scale,
+                     status_word());
   const size_t layer_sz = (size_t)rows * Hl;
   const float* in = emb_s;
   int in_dim = El;
@@ -1874,7 +1950,8 @@ static int lm_score_dedup(milan_ctx* c, const int64_t* seqs, int rows, int L, in
     hipLaunchKernelGGL(lm_gather_tok_kernel, dim3(nblk_all(R)), dim3(256), 0, s, seqs, (long)L, t,
                        q.urow + (size_t)p1 * R, U1, q.tok_c);
     hipLaunchKernelGGL(embed_split_kernel, dim3(nblk((long)R * (El / 8))), dim3(256), 0, s,
-                       c->lm_embedding, q.tok_c, R, El, emb_s, El, U1);
+                       c->lm_embedding, q.tok_c, R, El, emb_s, El, c->emb_scale, status_word(),
+                       U1);
     if (t > 0) {
       // the parent class's state of every layer: h (split form) and c
       for (int l = 0; l < d.lm_layers; ++l) {
@@ -2126,6 +2203,7 @@ int decoder_decode(milan_ctx* c, const float* features, int n, int k,
                 ws.size);
   const int R = n * beam;
   const int Hl = d.lm_hidden_size;
+  MILAN_TRY(launch_zero_fill(b.nanrow, sizeof(int) * (size_t)R, s));
 
   {
     StageScope scope(MILAN_STAGE_DEC_INIT, s);

@@ -1459,10 +1459,13 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
   // float inputs can carry NaN / Inf pixels (uint8 ones cannot): image-level poison flags
   int* const poison = image_dtype == MILAN_DTYPE_F32 ? pl.poison : nullptr;
   // calibration pass (milan_encoder_absmax): max |x| over every activation tensor
-  auto track = [&](const float* t, long count) -> int {
+  // (`word` 1: the word next to it, which bounds the FEATURES -- milan_encoder_absmax folds
+  // the raw conv1 output in there, pyramid tap 0, which is no split activation)
+  auto track = [&](const float* t, long count, int word = 0) -> int {
     if (c->calib == nullptr || count <= 0) return 0;
     const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-    hipLaunchKernelGGL(act_absmax_kernel, dim3(blocks), dim3(256), 0, s, t, count, c->calib);
+    hipLaunchKernelGGL(act_absmax_kernel, dim3(blocks), dim3(256), 0, s, t, count,
+                       c->calib + word);
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   };
@@ -1701,6 +1704,7 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
       StageScope scope(MILAN_STAGE_ENC_STEM, s);
       MILAN_TRY(launch_live(g));
     }
+    if (c->calib && !split) MILAN_TRY(track(g.C, (long)g.M * g.N, 1));
     MILAN_TRY(pool(pl.raw, 0, wd, 0));
     stage.emplace(MILAN_STAGE_ENC_STEM_TAIL, s);
     const long total = (long)n * pl.hp * pl.wp * (wd / (split ? 8 : 4));

@@ -117,6 +117,26 @@ __device__ inline void split8(const float* v, f32x4* hi_out, f32x4* lo_out, floa
   split8_rne(v, hi_out, lo_out, sat);
 }
 __device__ inline void join8(f32x4 hi, f32x4 lo, float* v) { join8_exact(hi, lo, v); }
+// split8 of the conversion kernel, whose operands come from OUTSIDE the trunk (the decoder's
+// features and what is computed from them): a NaN is not a saturation.  It leaves as an f16 NaN in `hi` (lo = 0),
+// so the MFMA propagates it as fp32 would, and it stays out of `sat`; every other value has
+// split8's bits.  (split8 itself turns a NaN into -65504 and flags it: common.h.)
+__device__ inline void split8_nan(const float* v, f32x4* hi_out, f32x4* lo_out, float* sat) {
+  float z[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) z[e] = v[e] != v[e] ? 0.f : v[e];
+  f32x4 hi, lo;
+  split8_rne(z, &hi, &lo, sat);
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    unsigned w = __float_as_uint(hi[d]);
+    if (v[2 * d] != v[2 * d]) w = (w & 0xffff0000u) | 0x00007e00u;
+    if (v[2 * d + 1] != v[2 * d + 1]) w = (w & 0x0000ffffu) | 0x7e000000u;
+    hi[d] = __uint_as_float(w);
+  }
+  *hi_out = hi;
+  *lo_out = lo;
+}
 
 // ---------------------------------------------------------------------------
 // epilogue shared by all tile configurations (wave tile = TM x TN MFMA tiles,
@@ -501,7 +521,9 @@ __device__ __forceinline__ void run_epilogue(const GemmArgs& g,
             f16x4 hi, lo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float x = fminf(fmaxf(h4[e], -65504.f), 65504.f);
+              // no clamp: |h'| = |o * tanh(c')| <= 1, and a NaN h' (the neuron of a NaN
+              // feature) must reach the vocabulary product as NaN, not as fminf's -65504
+              const float x = h4[e];
               const _Float16 hh = (_Float16)x;
               hi[e] = hh;
               lo[e] = (_Float16)(x - (float)hh);
@@ -2624,7 +2646,8 @@ static int launch_conv3x3(const GemmArgs& g, hipStream_t s) {
 // ---------------------------------------------------------------------------
 __global__ void f32_to_split_kernel(const float* __restrict__ src, long lds_,
                                     float* __restrict__ dst, long ldd, long rows,
-                                    int K, float scale, unsigned* status) {
+                                    int K, float scale, unsigned* status,
+                                    int* __restrict__ nanrow, int stamp) {
   const int g8 = K >> 3;
   const long total = rows * g8;
   float sat = 0.f;
@@ -2638,8 +2661,19 @@ __global__ void f32_to_split_kernel(const float* __restrict__ src, long lds_,
     float v[8];
 #pragma unroll
     for (int e = 0; e < 4; ++e) { v[e] = a[e] * scale; v[4 + e] = b[e] * scale; }
+    if (nanrow != nullptr) {
+      // the consumer cannot take a NaN (a GEMM whose epilogue writes split format): the NaN
+      // leaves as 0 and its row is marked instead (decoder.hip, step_core)
+      bool bad = false;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        bad |= v[e] != v[e];
+        v[e] = v[e] != v[e] ? 0.f : v[e];
+      }
+      if (bad) nanrow[r] = stamp;  // (every writer of a row stores the same value)
+    }
     f32x4 hi, lo;
-    split8(v, &hi, &lo, &sat);
+    split8_nan(v, &hi, &lo, &sat);
     float* d = dst + r * ldd + q * 8;
     *reinterpret_cast<f32x4*>(d) = hi;
     *reinterpret_cast<f32x4*>(d + 4) = lo;
@@ -2648,7 +2682,7 @@ __global__ void f32_to_split_kernel(const float* __restrict__ src, long lds_,
 }
 
 int launch_f32_to_split(const float* src, long ld_src, float* dst, long ld_dst,
-                        long rows, int K, float scale, hipStream_t s) {
+                        long rows, int K, float scale, hipStream_t s, int* nanrow, int stamp) {
   MILAN_REQUIRE(K % 8 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0, MILAN_ERR_SHAPE,
                 "f32_to_split: K=%d must be a multiple of 8", K);
   const long total = rows * (K >> 3);
@@ -2656,7 +2690,7 @@ int launch_f32_to_split(const float* src, long ld_src, float* dst, long ld_dst,
   if (blocks > 16384) blocks = 16384;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(f32_to_split_kernel, dim3((int)blocks), dim3(256), 0, s, src,
-                     ld_src, dst, ld_dst, rows, K, scale, status_word());
+                     ld_src, dst, ld_dst, rows, K, scale, status_word(), nanrow, stamp);
   MILAN_CHECK_HIP(hipGetLastError());
   return 0;
 }

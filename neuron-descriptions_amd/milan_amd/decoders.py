@@ -328,8 +328,10 @@ class Decoder(nn.Module):
         images ((M,3,H,W) or (N,k,3,H,W), uint8 or float): the trunk runs once in the
         exact-fp32 mode, the largest |activation| of any tensor it stores is observed,
         and the scale becomes the largest power of two that leaves `headroom` x that
-        maximum below the f16 range.  Returns log2 of the scale.  Not in the reference
-        (its fp32 needs none); with the default scale 2^5 activations beyond 2047 raise
+        maximum below the f16 range.  The decoder's feature and embedding scales follow by
+        the same rule, from the largest feature of the sample and the largest entry of the
+        embedding tables (`hip.Context.calibrate`).  Returns log2 of the activation scale.
+        Not in the reference (its fp32 needs none); with the default scale 2^5 activations beyond 2047 raise
         FloatingPointError instead of being clamped silently."""
         if not self._has_hip_encoder():
             raise ValueError('calibrate() needs the native pyramid encoder')

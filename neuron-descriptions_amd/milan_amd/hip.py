@@ -32,6 +32,7 @@ FUSE_TAIL_LISTS = 128
 SKETCH_COMPACT, SKETCH_INSERT, SKETCH_MOVE, SKETCH_HALVE = 0, 1, 2, 3
 # milan_status bits (include/milan_hip.h)
 STATUS_SATURATED, STATUS_NONFINITE_INPUT = 1, 2
+FEATURE_SCALE_LOG2_MAX = 30  # MILAN_FEATURE_SCALE_LOG2_MAX
 # enum milan_kernel_family (milan_profile_read_kernels)
 KERNEL_FAMILIES = ('other', 'pp32_256', 'pp32_128', 'split_other', 'f32', 'chain',
                    'chain_wide', 'stem', 'conv3', 'f16', 'pp32t_256', 'bneck')
@@ -174,6 +175,12 @@ SIGNATURES = {
     'milan_status': (_I, [_P, ctypes.POINTER(ctypes.c_uint32), _I, _P]),
     'milan_set_act_scale_log2': (_I, [_P, _I, _P]),
     'milan_get_act_scale_log2': (_I, [_P]),
+    'milan_set_feature_scale_log2': (_I, [_P, _I, _P]),
+    'milan_get_feature_scale_log2': (_I, [_P]),
+    'milan_get_feature_absmax': (_F, [_P]),
+    'milan_set_embedding_scale_log2': (_I, [_P, _I, _P]),
+    'milan_get_embedding_scale_log2': (_I, [_P]),
+    'milan_get_embedding_absmax': (_F, [_P]),
     'milan_encoder_absmax':
         (_I, [_P, _P, _I, _I, _I, _I, ctypes.POINTER(_F), _P, _SZ, _P]),
     'milan_exemplar_topk_update':
@@ -581,6 +588,41 @@ class Context:
             _check(self.lib.milan_set_act_scale_log2(self._h, int(k),
                                                      _stream(self.device)))
 
+    @property
+    def feature_scale_log2(self) -> int:
+        return int(self.lib.milan_get_feature_scale_log2(self._h))
+
+    def set_feature_scale_log2(self, k: int) -> None:
+        """Feature scale 2^k of the split-f16 decoder (default 0): its feature-carrying
+        operands are converted as x * 2^k and the factor is undone exactly, so features
+        down to 0.125 / 2^k keep full precision and features above 65504 / 2^k raise.  A
+        property of the context: set it once (or let `calibrate` do it), never per call."""
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_set_feature_scale_log2(self._h, int(k),
+                                                         _stream(self.device)))
+
+    @property
+    def embedding_scale_log2(self) -> int:
+        return int(self.lib.milan_get_embedding_scale_log2(self._h))
+
+    def set_embedding_scale_log2(self, k: int) -> None:
+        """Embedding scale 2^k of the split-f16 decoder and LM (default 0): the embedding
+        tables are gathered as e * 2^k, the LSTM weight columns they meet hold W / 2^k."""
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_set_embedding_scale_log2(self._h, int(k),
+                                                           _stream(self.device)))
+
+    @staticmethod
+    def feature_scale_log2_for(absmax: float, headroom: float = 8.0) -> int:
+        """The feature scale `calibrate` picks for features of magnitude up to `absmax`:
+        the largest power of two that keeps `headroom` x that maximum below the f16 range
+        (the rule of the activation scale, without its 0..10 limits)."""
+        import math
+        if not absmax > 0 or not math.isfinite(absmax):
+            return 0
+        k = int(math.floor(math.log2(65504.0 / (absmax * headroom))))
+        return max(-FEATURE_SCALE_LOG2_MAX, min(FEATURE_SCALE_LOG2_MAX, k))
+
     def encoder_absmax(self, images: torch.Tensor) -> float:
         """Largest |activation| any tensor of the ResNet trunk holds for `images`
         ((M,3,H,W), uint8 or float), measured in the exact-fp32 mode."""
@@ -602,7 +644,12 @@ class Context:
         two that keeps `headroom` x the observed maximum below the f16 range.  Returns
         the chosen log2 scale.  (The default 2^5 suits activations up to 2047; a
         network whose residual stream grows beyond that needs a smaller scale, one
-        whose activations sit at 1e-3 a larger one -- DESIGN.md section 4.2.)"""
+        whose activations sit at 1e-3 a larger one -- DESIGN.md section 4.2.)  A context
+        with a decoder also gets its feature scale, by the same rule without the 0..10
+        limit, from the largest value of the sample's five pyramid taps (which bounds every
+        mask-weighted mean the pooling can produce, whatever the masks), and its embedding
+        scale, from the largest entry of its embedding tables (`feature_scale_log2`, `embedding_scale_log2`; DESIGN.md section
+        4.21)."""
         import math
         amax = self.encoder_absmax(images)
         if not math.isfinite(amax):
@@ -610,16 +657,30 @@ class Context:
         k = 10 if amax <= 0 else int(math.floor(math.log2(65504.0 / (amax * headroom))))
         k = max(0, min(10, k))
         self.set_act_scale_log2(k)
+        if self.dims.hidden_size > 0 and hasattr(self.lib, 'milan_get_feature_absmax'):
+            # The sample's features were pooled without masks (global averages); under a small
+            # mask a feature is a mean over few pixels and can be far larger.  Every pooled
+            # feature is a convex combination of the values of its pyramid tap, so the largest
+            # |value| of the five taps (the activations and the raw conv1 output) bounds it
+            # under ANY mask: that is what milan_get_feature_absmax returns.
+            fmax = max(amax, float(self.lib.milan_get_feature_absmax(self._h)))
+            self.set_feature_scale_log2(self.feature_scale_log2_for(fmax, headroom))
+            with torch.cuda.device(self.device):
+                emax = float(self.lib.milan_get_embedding_absmax(self._h))
+            self.set_embedding_scale_log2(self.feature_scale_log2_for(emax, headroom))
         return k
 
-    def _guarded(self, what: str, run, check: bool = True):
+    def _guarded(self, what: str, run, check: bool = True, decoder: bool = False):
         """Run one computing call and act on the status word it leaves behind.
 
         MILAN_STATUS_SATURATED: a split-format value hit the +-65504 clamp -- the
         reference's fp32 would not have, so the result is NOT returned: raise
         FloatingPointError, or (on_saturation == 'f32') rerun the call in the exact-fp32
         mode.  MILAN_STATUS_NONFINITE_INPUT: a float input pixel was NaN / Inf; the
-        features of its image are NaN as in the reference -- a RuntimeWarning says so."""
+        features of its image are NaN as in the reference -- a RuntimeWarning says so.
+        `decoder`: the call reads features, not images (init_state, step, decode, lm_*):
+        what saturates there is a feature beyond 65504 / 2^feature_scale_log2.  A NaN
+        feature is no saturation: it poisons its neuron as in the reference, silently."""
         out = run()
         if not check or self.on_saturation == 'ignore':
             return out
@@ -630,11 +691,28 @@ class Context:
                           'features are NaN (as in the reference)', RuntimeWarning,
                           stacklevel=3)
         if flags & STATUS_SATURATED:
-            limit = 65504.0 / 2 ** self.act_scale_log2
-            msg = (f'milan_amd: {what}: a split-f16 activation exceeded {limit:g} '
-                   f'(65504 / 2^{self.act_scale_log2}) and was clamped; the exact-fp32 '
-                   "mode (precision='f32'), Decoder.precision = 'auto' or a smaller "
-                   'activation scale (Context.calibrate) avoid it')
+            if what == 'describe':
+                msg = (f'milan_amd: {what}: a split-f16 value was clamped: a trunk activation '
+                       f'beyond {65504.0 / 2 ** self.act_scale_log2:g} (65504 / '
+                       f'2^{self.act_scale_log2}), or a decoder operand (a feature, an '
+                       f'embedding) beyond {65504.0 / 2.0 ** self.feature_scale_log2:g} / '
+                       f'{65504.0 / 2.0 ** self.embedding_scale_log2:g} (65504 / '
+                       f'2^{self.feature_scale_log2}, 2^{self.embedding_scale_log2}); the '
+                       "exact-fp32 mode (precision='f32'), Decoder.precision = 'auto' or "
+                       'smaller scales (Context.calibrate) avoid it')
+            elif decoder:
+                limit = 65504.0 / 2.0 ** self.feature_scale_log2
+                msg = (f'milan_amd: {what}: a split-f16 decoder operand (a feature, or what '
+                       f'the step computes from it) exceeded {limit:g} (65504 / '
+                       f'2^{self.feature_scale_log2}) and was clamped; the exact-fp32 mode '
+                       "(precision='f32'), Decoder.precision = 'auto' or a smaller feature "
+                       'scale (Context.set_feature_scale_log2, Context.calibrate) avoid it')
+            else:
+                limit = 65504.0 / 2 ** self.act_scale_log2
+                msg = (f'milan_amd: {what}: a split-f16 activation exceeded {limit:g} '
+                       f'(65504 / 2^{self.act_scale_log2}) and was clamped; the exact-fp32 '
+                       "mode (precision='f32'), Decoder.precision = 'auto' or a smaller "
+                       'activation scale (Context.calibrate) avoid it')
             if self.on_saturation != 'f32' or self.precision == 'f32':
                 raise FloatingPointError(msg)
             import warnings
@@ -887,43 +965,56 @@ class Context:
 
         return self._guarded('classify_sweep', run, check)
 
-    def init_state(self, features: torch.Tensor):
+    def init_state(self, features: torch.Tensor, check: bool = True):
+        """(n, k, F) features -> (h, c).  `check` (here and in `step`, `decode`, `lm_score`,
+        `lm_logprobs`): read the status word afterwards, as `encode` does (`_guarded`)."""
         n, k, _ = features.shape
         features = _dev(features, self.device, torch.float32)
         h = torch.empty(n, self.dims.hidden_size, device=self.device)
         c = torch.empty_like(h)
         ws = self.workspace(n, k, 0, 1, 1)
-        with torch.cuda.device(self.device):
-            _check(
-                self.lib.milan_init_state(self._h, features.data_ptr(), n, k,
-                                          h.data_ptr(), c.data_ptr(),
-                                          ws.data_ptr(), ws.numel(),
-                                          _stream(self.device)))
-        return h, c
 
-    def step(self, features, tokens, h, c, h_lm, c_lm, temperature):
+        def run():
+            with torch.cuda.device(self.device):
+                _check(
+                    self.lib.milan_init_state(self._h, features.data_ptr(), n, k,
+                                              h.data_ptr(), c.data_ptr(),
+                                              ws.data_ptr(), ws.numel(),
+                                              _stream(self.device)))
+            return h, c
+
+        return self._guarded('init_state', run, check, decoder=True)
+
+    def step(self, features, tokens, h, c, h_lm, c_lm, temperature, check: bool = True):
         rows, k, _ = features.shape
         features = _dev(features, self.device, torch.float32)
         tokens = _dev(tokens, self.device, torch.long)
         h = _dev(h, self.device, torch.float32)
         c = _dev(c, self.device, torch.float32)
         if h_lm is not None:
-            h_lm = _dev(h_lm, self.device, torch.float32).clone()
-            c_lm = _dev(c_lm, self.device, torch.float32).clone()
+            h_lm = _dev(h_lm, self.device, torch.float32)
+            c_lm = _dev(c_lm, self.device, torch.float32)
         pred = torch.empty(rows, self.dims.vocab_size, device=self.device)
         att = torch.empty(rows, k, device=self.device)
         h2, c2 = torch.empty_like(h), torch.empty_like(c)
         ws = self.workspace(rows, k, 0, 1, 1)
-        with torch.cuda.device(self.device):
-            _check(
-                self.lib.milan_step(self._h, features.data_ptr(), rows, k,
-                                    tokens.data_ptr(), h.data_ptr(),
-                                    c.data_ptr(), _ptr(h_lm), _ptr(c_lm),
-                                    float(temperature), pred.data_ptr(),
-                                    att.data_ptr(), h2.data_ptr(),
-                                    c2.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    _stream(self.device)))
-        return pred, att, h2, c2, h_lm, c_lm
+
+        def run():
+            # (the LM state is updated in place: every run starts from the caller's)
+            hl = None if h_lm is None else h_lm.clone()
+            cl = None if c_lm is None else c_lm.clone()
+            with torch.cuda.device(self.device):
+                _check(
+                    self.lib.milan_step(self._h, features.data_ptr(), rows, k,
+                                        tokens.data_ptr(), h.data_ptr(),
+                                        c.data_ptr(), _ptr(hl), _ptr(cl),
+                                        float(temperature), pred.data_ptr(),
+                                        att.data_ptr(), h2.data_ptr(),
+                                        c2.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        _stream(self.device)))
+            return pred, att, h2, c2, hl, cl
+
+        return self._guarded('step', run, check, decoder=True)
 
     def _alloc_outputs(self, n, k, strategy, length, beam, want_full,
                        forced=None):
@@ -969,31 +1060,40 @@ class Context:
                temperature: float,
                group_size: int = 0,
                want_full: bool = True,
-               forced: Optional[torch.Tensor] = None):
+               forced: Optional[torch.Tensor] = None,
+               check: bool = True):
         n, k, _ = features.shape
         features = _dev(features, self.device, torch.float32)
         if getattr(self, '_graphs', False) and strategy != FORCED:
-            return self._decode_graphed(features, strategy, length, beam, mi,
-                                        temperature, group_size, want_full)
-        out = self._alloc_outputs(n, k, strategy, length, beam, want_full,
-                                  forced)
+            # (the status word is read after the replay; an f32 rerun is a call of its own,
+            # outside any capture)
+            return self._guarded(
+                'decode', lambda: self._decode_graphed(features, strategy, length, beam, mi,
+                                                       temperature, group_size, want_full),
+                check, decoder=True)
         groups = (n + group_size - 1) // group_size if group_size > 0 else 1
-        out['out_len'] = torch.full((groups,),
-                                    length,
-                                    dtype=torch.int32,
-                                    device=self.device)
         ws = self.workspace(n, k, 0, beam, length)
-        with torch.cuda.device(self.device):
-            _check(
-                self.lib.milan_decode(
-                    self._h, features.data_ptr(), n, k, strategy, length, beam,
-                    int(bool(mi)), float(temperature), group_size,
-                    out['tokens'].data_ptr(), out['scores'].data_ptr(),
-                    _ptr(out['predictions']), _ptr(out['attentions']),
-                    _ptr(out['beam_tokens']), _ptr(out['beam_scores']),
-                    out['out_len'].data_ptr(), ws.data_ptr(), ws.numel(),
-                    _stream(self.device)))
-        return out
+
+        def run():
+            out = self._alloc_outputs(n, k, strategy, length, beam, want_full,
+                                      forced)
+            out['out_len'] = torch.full((groups,),
+                                        length,
+                                        dtype=torch.int32,
+                                        device=self.device)
+            with torch.cuda.device(self.device):
+                _check(
+                    self.lib.milan_decode(
+                        self._h, features.data_ptr(), n, k, strategy, length, beam,
+                        int(bool(mi)), float(temperature), group_size,
+                        out['tokens'].data_ptr(), out['scores'].data_ptr(),
+                        _ptr(out['predictions']), _ptr(out['attentions']),
+                        _ptr(out['beam_tokens']), _ptr(out['beam_scores']),
+                        out['out_len'].data_ptr(), ws.data_ptr(), ws.numel(),
+                        _stream(self.device)))
+            return out
+
+        return self._guarded('decode', run, check, decoder=True)
 
     def _decode_graphed(self, features, strategy, length, beam, mi, temperature,
                         group_size, want_full):
@@ -1032,32 +1132,40 @@ class Context:
                 v.record_stream(cur)
         return out
 
-    def lm_score(self, seqs: torch.Tensor) -> torch.Tensor:
+    def lm_score(self, seqs: torch.Tensor, check: bool = True) -> torch.Tensor:
         rows, length = seqs.shape
         seqs = _dev(seqs, self.device, torch.long)
         out = torch.empty(rows, device=self.device)
         ws = self.workspace(rows, 1, 0, 1, 1)
-        with torch.cuda.device(self.device):
-            _check(
-                self.lib.milan_lm_score(self._h, seqs.data_ptr(), rows, length,
-                                        None, out.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), _stream(self.device)))
-        return out
 
-    def lm_logprobs(self, seqs: torch.Tensor) -> torch.Tensor:
+        def run():
+            with torch.cuda.device(self.device):
+                _check(
+                    self.lib.milan_lm_score(self._h, seqs.data_ptr(), rows, length,
+                                            None, out.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), _stream(self.device)))
+            return out
+
+        return self._guarded('lm_score', run, check, decoder=True)
+
+    def lm_logprobs(self, seqs: torch.Tensor, check: bool = True) -> torch.Tensor:
         """(rows, L) token ids -> (rows, L, V) next-token log-probs."""
         rows, length = seqs.shape
         seqs = _dev(seqs, self.device, torch.long)
         out = torch.empty(rows, length, self.dims.vocab_size,
                           device=self.device)
         ws = self.workspace(rows, 1, 0, 1, 1)
-        with torch.cuda.device(self.device):
-            _check(
-                self.lib.milan_lm_logprobs(self._h, seqs.data_ptr(), rows,
-                                           length, out.data_ptr(),
-                                           ws.data_ptr(), ws.numel(),
-                                           _stream(self.device)))
-        return out
+
+        def run():
+            with torch.cuda.device(self.device):
+                _check(
+                    self.lib.milan_lm_logprobs(self._h, seqs.data_ptr(), rows,
+                                               length, out.data_ptr(),
+                                               ws.data_ptr(), ws.numel(),
+                                               _stream(self.device)))
+            return out
+
+        return self._guarded('lm_logprobs', run, check, decoder=True)
 
     # -- LanguageModel training (include/milan_hip.h, milan_lm_train_step) --
     def _lm_train_call(self, params, inputs, targets):

@@ -15,6 +15,8 @@ not a test file).  DESIGN.md section 4.19.
     there, change it here, or the case table no longer provably reaches what it names.
   * `CASES`: the table.  Every GPU test parametrises over it x `PRECISIONS`.
   * The bound: `STATE_CLASS`, `ATT_CLASS`, `LOGP_CLASS`.
+  * `rescaled`: the homogeneity transform of tests/test_gpu_decoder_range.py,
+    with its scales and cases.
 """
 import collections
 import functools
@@ -122,7 +124,7 @@ def forced_length(case):
 @functools.lru_cache(maxsize=None)
 def weights(geom, seed=0, dims=None):
     """fp32 state dict of a geometry (decoder + 2-layer LM of the same H / E)."""
-    d = dims or GEOMETRIES[geom]
+    d = dims or (CAT_DIMS if geom == 'cat' else GEOMETRIES[geom])
     return synthetic.decoder_state_dict(d.V, feature_size=d.F, hidden_size=d.H,
                                         embedding_size=d.E, attention_hidden_size=d.A,
                                         lm_hidden_size=d.H, lm_embedding_size=d.E,
@@ -181,6 +183,59 @@ def promote(x, dtype=torch.float64):
     if isinstance(x, dict):
         return {k: promote(v, dtype) for k, v in x.items()}
     return x.to(dtype) if x.is_floating_point() else x
+
+
+# ---- off the unit operand scale -------------------------------------------
+# (log2 feature scale, log2 embedding scale) of tests/test_gpu_decoder_range.py: the feature
+# sweep, the embedding sweep, and one combined case whose column blocks of `lstm.weight_ih`
+# sit 2^16 apart under the layer's single weight scale.
+FEATURE_SCALES = (-14, -10, -6, 6, 10)
+EMBEDDING_SCALES = (-10, 6)
+SCALES = (tuple((f, 0) for f in FEATURE_SCALES) + tuple((0, e) for e in EMBEDDING_SCALES) +
+          ((-10, 6),))
+RANGE_CASES = (Case('small', 'small', GEOMETRIES['small'], 15, 257),
+               Case('prod', 'prod', GEOMETRIES['prod'], 15, 3))
+# E % 16 != 0 with (E + F) % 32 == 0 and H % 32 == 0: step_core's NON-fused branch, whose cell
+# product still runs on the split copy of [W_ih | W_hh] (lstm_layer) -- the scales reach it
+# through embed_kernel and the fp32 gate product instead of the split-format producers.  Not a
+# row of the 4.19 table: only bit-for-bit statements are made about it.
+CAT_DIMS = Dims(64, 8, 152, 64, 2300)
+CAT_CASE = Case('cat', 'cat', CAT_DIMS, 15, 70)
+
+
+def rescaled(sd, feats, log2_feat=0, log2_emb=0):
+    """(sd', feats'): the same decoder in other units.  feats' = feats * 2^f with 2^-f on
+    every weight column that multiplies a feature (init_h, init_c, key_to_hidden, the feature
+    columns of lstm.weight_ih); the embedding tables * 2^e with 2^-e on the columns that
+    multiply an embedding (decoder and LM).  Powers of two: exact in fp32 and float64 while
+    nothing under- or overflows, so the float64 reference of the rescaled case is the
+    reference of the original (tests/test_decoder_ref_host.py asserts it at every scale
+    used).  Works on fp32 and on promoted float64 state dicts."""
+    f, e = 2.0 ** log2_feat, 2.0 ** log2_emb
+    emb = sd['embedding.weight'].shape[1]
+    out = dict(sd)
+    for name in ('init_h.0.weight', 'init_c.0.weight', 'attend.key_to_hidden.weight'):
+        out[name] = sd[name] / f
+    w = sd['lstm.weight_ih'].clone()
+    w[:, :emb] /= e
+    w[:, emb:] /= f
+    out['lstm.weight_ih'] = w
+    out['embedding.weight'] = sd['embedding.weight'] * e
+    if 'lm.embedding.weight' in sd:
+        out['lm.embedding.weight'] = sd['lm.embedding.weight'] * e
+        out['lm.lstm.weight_ih_l0'] = sd['lm.lstm.weight_ih_l0'] / e
+    return out, feats * f
+
+
+def resolution_hook(grid=2.0 ** -24):
+    """The defect the scale sweep exists for, as a hook for `step`: a feature operand whose
+    `lo` half fell into the f16 subnormals keeps an absolute resolution of 2^-24.  The
+    context vector is rounded to that grid ('ctx'; the keys' features are rounded by the
+    caller, who projects them)."""
+    def hook(name, value, env):
+        if name == 'ctx':
+            return torch.round(value / grid) * grid
+    return hook
 
 
 # ---- the reference --------------------------------------------------------------------

@@ -8,7 +8,11 @@
      hook, exceeds the bound at least tenfold.
   5. The beam cases: seeds with no near-tie at n <= 7, and the fp32 oracle itself within
      the excuse cap above.
-DESIGN.md section 4.19."""
+  6. Off the unit operand scale (tests/test_gpu_decoder_range.py): `decref.rescaled` is
+     exact under the fp32 oracle and under float64 at every scale used, so the bounds hold
+     unchanged there; and a feature operand left with the absolute resolution of a
+     subnormal `lo` exceeds them.
+DESIGN.md sections 4.19 and 4.21."""
 import functools
 
 import pytest
@@ -406,3 +410,100 @@ def test_beam_seeds(geom, n, beam, mi):
     assert float((got.scores.double() - D.rescore(feats.double(), got.tokens, D.promote(sd),
                                                   start, stop, mi)).abs().max()) \
         <= D.BEAM_LENGTH * D.LOGP_CLASS / 4
+
+
+# ---- 6. off the unit operand scale --------------------------------------------------------------
+def _everything(feats, sd, case):
+    """init_state, the single step of the GPU test and teacher forcing (both MI settings) in
+    the dtype of `sd`, as one flat list of tensors."""
+    d = case.dims
+    start, _ = D.specials(d)
+    out = []
+    st0 = D.init_state(feats, sd, lm=True)
+    out += [st0.h, st0.c]
+    keys = D.project_keys(feats, sd)
+    _, _, st1 = D.step(feats, keys, torch.full((case.n,), start), st0, sd)
+    p, a, st2 = D.step(feats, keys, D.edge_tokens(d, case.n), st1, sd)
+    out += [p, a, st2.h, st2.c, st2.h_lm, st2.c_lm]
+    targets = D.forced_targets(d, case.n, D.forced_length(case))
+    for mi in (False, True):
+        f = D.teacher_forced(feats, sd, start, targets, mi=mi)
+        out += [f.predictions, f.attentions, f.scores]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _unscaled(case, double):
+    sd = D.weights(case.geom)
+    feats = D.features(case.dims, case.n, case.k)
+    if double:
+        sd, feats = D.promote(sd), feats.double()
+    return _everything(feats, sd, case)
+
+
+@pytest.mark.parametrize('log2_feat,log2_emb', D.SCALES,
+                         ids=[f'f{f}-e{e}' for f, e in D.SCALES])
+@pytest.mark.parametrize('case', D.RANGE_CASES, ids=[D.case_id(c) for c in D.RANGE_CASES])
+def test_rescaled_is_exact(case, log2_feat, log2_emb):
+    """The rescaled case under the fp32 oracle's arithmetic, and under float64, gives the
+    bits of the unscaled one: nothing underflows or overflows and the transform is right.
+    Hence the oracle's error against float64 is one figure for every scale, and the GPU test
+    keeps STATE_CLASS / ATT_CLASS / LOGP_CLASS unchanged."""
+    sd, feats = D.rescaled(D.weights(case.geom), D.features(case.dims, case.n, case.k),
+                           log2_feat, log2_emb)
+    assert torch.equal(feats, D.features(case.dims, case.n, case.k) * 2.0 ** log2_feat)
+    assert torch.isfinite(feats).all() and float(feats[feats > 0].min()) > 2.0 ** -100
+    worst = 0.0
+    for double in (False, True):
+        got = _everything(feats.double(), D.promote(sd), case) if double else \
+            _everything(feats, sd, case)
+        for g, w in zip(got, _unscaled(case, double)):
+            assert torch.equal(g, w)
+    for g32, g64 in zip(_unscaled(case, False), _unscaled(case, True)):
+        worst = max(worst, float((g32.double() - g64).abs().max()))
+    print(f'{D.case_id(case)} f={log2_feat} e={log2_emb}: bit-exact in fp32 and float64; '
+          f'fp32 oracle vs float64 (any quantity) {worst:.2e} at every scale')
+
+
+def test_range_cases_are_table_cases():
+    """The sweep's two cases are rows of the 4.19 table (so the constants cover them), and
+    at 2^10 the largest feature is far below the clamp."""
+    for case in D.RANGE_CASES:
+        assert case in D.CASES and D.fused(case.dims)
+        top = float(D.features(case.dims, case.n, case.k).max()) * 2.0 ** max(D.FEATURE_SCALES)
+        assert top < 65504 / 8, top
+    assert set(D.SCALES) >= {(f, 0) for f in D.FEATURE_SCALES} | {(-10, 6)}
+    # the extra geometry of test_feature_scale_is_undone_exactly: not fused, but the cell's
+    # product has a concatenated split copy (decoder.hip, cat_linear / lstm_layer)
+    c = D.CAT_DIMS
+    assert not D.fused(c) and (c.E + c.F) % 32 == 0 and c.H % 32 == 0 and c.E % 16 != 0
+    assert [g[0] for g in D.step_gemms(c, D.CAT_CASE.n, 'split_f16')] == \
+        ['q', 'gate', 'lstm', 'vocab']
+
+
+def test_subnormal_lo_exceeds_the_bound():
+    """Resolution: at feature scale 2^-14 on `prod`, the feature operands of the float64
+    reference (the features the keys are projected from, the context vector) rounded to an
+    absolute grid of 2^-24 -- what a `lo` half in the f16 subnormals leaves of them -- move a
+    step by at least 10 x the bound.  The sweep sees the defect it exists for."""
+    case = D.RANGE_CASES[1]
+    assert case.geom == 'prod'
+    d = case.dims
+    sd, feats = D.rescaled(D.promote(D.weights(case.geom)),
+                           D.features(d, case.n, case.k).double(), -14, 0)
+    start, _ = D.specials(d)
+    keys = D.project_keys(feats, sd)
+    st0 = D.init_state(feats, sd)
+    _, _, st1 = D.step(feats, keys, torch.full((case.n,), start), st0, sd)
+    tok = D.edge_tokens(d, case.n)
+    want = D.step(feats, keys, tok, st1, sd)
+    grid = 2.0 ** -24
+    coarse = torch.round(feats / grid) * grid
+    got = D.step(feats, D.project_keys(coarse, sd), tok, st1, sd, hook=D.resolution_hook(grid))
+    ratios = dict(pred=float((got[0] - want[0]).abs().max()) / D.LOGP_CLASS,
+                  att=float((got[1] - want[1]).abs().max()) / D.ATT_CLASS,
+                  h2=float((got[2].h - want[2].h).abs().max()) / D.STATE_CLASS,
+                  c2=float((got[2].c - want[2].c).abs().max()) / D.STATE_CLASS)
+    print('2^-24 grid on the feature operands at 2^-14, prod: error / bound: ' +
+          '  '.join(f'{q} {r:.3g}' for q, r in ratios.items()))
+    assert max(ratios.values()) >= 10, ratios

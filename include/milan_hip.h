@@ -244,7 +244,19 @@ int milan_decode(milan_ctx* ctx, const float* features, int n, int k,
  *     index p * beam + j ascending), new_tok = cand_i at the winner, new_bp = its p.
  *     1 <= beam_prev <= beam <= 1024.  wide: 0 = the kernel milan_decode picks for this
  *     `beam` in mode 0, 1 = the wide kernel.  workspace may be NULL (no scratch is used).
+ *   milan_row_select  one per-row top-k on caller-supplied DEVICE arrays: per row the k
+ *     best of log_softmax(logits) [- lambda * log_softmax(lm_logits)] (lm_logits NULL =
+ *     none), logits (rows,V); cand_v / cand_i (rows,k) sorted by (value descending, index
+ *     ascending).  A row with last_tok[row] == stop (last_tok NULL = no such row) gets the
+ *     forced candidates of a finished beam.  1 <= k <= min(V, 1024).  path: 0 = the kernel
+ *     milan_decode picks in mode 0, 1 = the wide kernels (k >= 2, V <= 36864), 2 = the
+ *     threshold path and 3 = the first rank-count path of the register kernel (both
+ *     2 <= k <= 256, V <= 6144); a shape the path does not take is MILAN_ERR_ARG.  Every
+ *     path gives the same bits.
  * Not part of every build of ABI 11: probe with dlsym / hasattr. */
+int milan_row_select(const float* logits, const float* lm_logits, float lambda, int rows,
+                     int V, int k, const int64_t* last_tok, int stop, float* cand_v,
+                     int* cand_i, int path, milan_stream stream);
 int milan_beam_merge(const float* cand_v, const int* cand_i, const float* last_lp,
                      int n, int beam_prev, int beam, int wide, float* new_lp,
                      int* new_tok, int* new_bp, void* workspace,

@@ -488,6 +488,15 @@ int milan_beam_merge(const float* cand_v, const int* cand_i, const float* last_l
                             new_tok, new_bp, (hipStream_t)stream);
 }
 
+int milan_row_select(const float* logits, const float* lm_logits, float lambda, int rows,
+                     int V, int k, const int64_t* last_tok, int stop, float* cand_v,
+                     int* cand_i, int path, milan_stream stream) {
+  MILAN_REQUIRE(logits && cand_v && cand_i, MILAN_ERR_ARG, "milan_row_select: null argument");
+  MILAN_REQUIRE(path >= 0 && path <= 3, MILAN_ERR_ARG, "milan_row_select: path=%d", path);
+  return decoder_row_select(logits, lm_logits, lambda, rows, V, k, last_tok, stop, cand_v,
+                            cand_i, path, (hipStream_t)stream);
+}
+
 int milan_set_beam_path(milan_ctx* c, int mode) {
   MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
   MILAN_REQUIRE(mode == 0 || mode == 1, MILAN_ERR_ARG, "unknown beam path mode %d", mode);

@@ -676,6 +676,11 @@ int decoder_lm_score(milan_ctx* c, const int64_t* seqs, int rows, int L,
 int decoder_beam_merge(const float* cand_v, const int* cand_i, const float* last_lp,
                        int n, int beam_prev, int beam, int wide, float* new_lp,
                        int* new_tok, int* new_bp, hipStream_t s);
+// one per-row top-k on caller-supplied arrays (milan_row_select); path 0 picks the
+// kernel as decoder_decode does in auto mode, 1 = wide, 2 = threshold, 3 = legacy rank
+int decoder_row_select(const float* logits, const float* lm_logits, float lambda,
+                       int rows, int V, int k, const int64_t* last_tok, int stop,
+                       float* cand_v, int* cand_i, int path, hipStream_t s);
 // beam_wide.hip: selection kernels for beams whose candidates do not fit LDS
 int launch_beam_merge_wide(const float* cand_v, const int* cand_i,
                            const float* last_lp, int n, int beam_prev, int beam,

@@ -750,106 +750,201 @@ __global__ __launch_bounds__(256) void row_select_kernel(
 }
 
 // Register-resident variant of row_select_kernel for V <= 24*256: the row, its
-// log-softmax and the order-preserving keys never leave the VGPRs (24 values
-// per thread); LDS holds only reduction scratch and the <= 256 winners.  Same
-// results as row_select_kernel (same float operations, same tie rule).
+// log-softmax and the order-preserving keys never leave the VGPRs (NR values per
+// thread, NR = ceil(V / 256) rounded up to a multiple of 4: padding slots add
+// nothing to a sum, so the bits do not depend on NR); LDS holds only reduction
+// scratch and the gathered candidates.  Same results as row_select_kernel (same
+// float operations, same tie rule).  rank_select: 0 = threshold path, 1 = rank
+// counting; kLegacy: the rank counting is that of the first version
+// (MILAN_ROW_SELECT=legacy), kept out of the shipped instances' register budget.
 constexpr int kRowRegs = 24;
 
 __device__ inline float funkey(unsigned key) {
   return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
 }
 
+template <int NR, bool kLegacy = false>
 __global__ __launch_bounds__(256) void row_select_reg_kernel(
     const float* __restrict__ logits, const float* __restrict__ lm_logits,
     float lambda, int V, int k, const int64_t* __restrict__ last_tok, int stop,
     float* __restrict__ cand_v, int* __restrict__ cand_i,
     float* __restrict__ pred_out, long pred_stride, int rank_select) {
+  static_assert(NR >= 4 && NR <= kRowRegs && NR % 4 == 0, "slot count");
   __shared__ float red[8];
   __shared__ unsigned scratch[528];
   const int r = blockIdx.x, tid = threadIdx.x;
+  // the launch picks NR with 256 * (NR - 4) <= V: only the last four slots can hold
+  // padding, the others need no bounds test
+  constexpr int kFull = kLegacy ? 0 : NR - 4;
+  auto live = [&](int j) { return j < kFull || tid + 256 * j < V; };
+  float* out_v = cand_v + (long)r * k;
+  int* out_i = cand_i + (long)r * k;
+  // a finished row's candidates are constants: nothing of the row is needed
+  const bool finished = k > 0 && last_tok && last_tok[r] == stop;  // block-uniform
+  auto forced_row = [&]() {
+    for (int j = tid; j < k; j += 256) {
+      out_v[j] = j == 0 ? 0.f : kFloatMin;
+      out_i[j] = j == 0 ? stop : (j - 1 < stop ? j - 1 : j);
+    }
+  };
+  if (finished && !pred_out) { forced_row(); return; }
   const float* x = logits + (long)r * V;
-  float p[kRowRegs];
+  float p[NR];
   float mx = -INFINITY;
 #pragma unroll
-  for (int j = 0; j < kRowRegs; ++j) {
-    const int i = tid + 256 * j;
-    p[j] = i < V ? x[i] : -INFINITY;
+  for (int j = 0; j < NR; ++j) {
+    p[j] = live(j) ? x[tid + 256 * j] : -INFINITY;
     mx = fmaxf(mx, p[j]);
   }
   mx = block_max(mx, red);
   float s = 0.f;
 #pragma unroll
-  for (int j = 0; j < kRowRegs; ++j)
-    if (tid + 256 * j < V) s += expf(p[j] - mx);
+  for (int j = 0; j < NR; ++j)
+    if (live(j)) s += expf(p[j] - mx);
   s = block_sum(s, red);
   const float ls = logf(s);
   if (lm_logits) {
     const float* y = lm_logits + (long)r * V;
-    float q[kRowRegs];
+    float q[NR];
     float my = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j) {
-      const int i = tid + 256 * j;
-      q[j] = i < V ? y[i] : -INFINITY;
+    for (int j = 0; j < NR; ++j) {
+      q[j] = live(j) ? y[tid + 256 * j] : -INFINITY;
       my = fmaxf(my, q[j]);
     }
     my = block_max(my, red);
     float sy = 0.f;
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j)
-      if (tid + 256 * j < V) sy += expf(q[j] - my);
+    for (int j = 0; j < NR; ++j)
+      if (live(j)) sy += expf(q[j] - my);
     sy = block_sum(sy, red);
     const float lsy = logf(sy);
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j)
+    for (int j = 0; j < NR; ++j)
       p[j] = ((p[j] - mx) - ls) - lambda * ((q[j] - my) - lsy);
   } else {
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j) p[j] = (p[j] - mx) - ls;
+    for (int j = 0; j < NR; ++j) p[j] = (p[j] - mx) - ls;
   }
   if (pred_out) {
     float* po = pred_out + (long)r * pred_stride;
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j)
-      if (tid + 256 * j < V) po[tid + 256 * j] = p[j];
+    for (int j = 0; j < NR; ++j)
+      if (live(j)) po[tid + 256 * j] = p[j];
   }
   if (k <= 0) return;
-  float* out_v = cand_v + (long)r * k;
-  int* out_i = cand_i + (long)r * k;
-  if (last_tok && last_tok[r] == stop) {
-    for (int j = tid; j < k; j += 256) {
-      out_v[j] = j == 0 ? 0.f : kFloatMin;
-      out_i[j] = j == 0 ? stop : (j - 1 < stop ? j - 1 : j);
-    }
-    return;
-  }
-  unsigned key[kRowRegs];
+  if (finished) { forced_row(); return; }
+  unsigned key[NR];
 #pragma unroll
-  for (int j = 0; j < kRowRegs; ++j)
-    key[j] = tid + 256 * j < V ? fkey(p[j]) : 0u;
+  for (int j = 0; j < NR; ++j)
+    key[j] = live(j) ? fkey(p[j]) : 0u;
   unsigned* cnt = scratch;
   float* cv = reinterpret_cast<float*>(scratch + 8);
   int* ci = reinterpret_cast<int*>(scratch + 8 + 256);
   // Exact top-k without a search over the key range.  A lower bound T0 that is
-  // itself close to the k-th largest element comes from the per-thread maxima
-  // (see below); the few elements >= T0 are gathered and each one's rank (key
-  // descending, index ascending among equals: the order the threshold path
-  // produces) is counted against the others -- ranks < k are the answer, already
-  // in output order.  One barrier-free wave pass and two LDS passes instead of
-  // ~25 bisection rounds with two barriers each.  Falls through to the threshold
-  // path when a wave holds fewer than ceil(k/4) elements or the gather overflows
-  // (long runs of equal log-probs).
-  if (k >= 2) {
+  // itself close to the k-th largest element comes from the per-thread maxima:
+  // T0 = min over the 4 waves of the wave's m-th largest thread maximum,
+  // m = ceil(k / 4): every wave then holds >= m elements >= T0, >= k in all.
+  // The few elements >= T0 are gathered and each one's rank (key descending,
+  // index ascending among equals: the order the threshold path produces) is
+  // counted against the others -- ranks < k are the answer, already in output
+  // order.  Falls through to the threshold path when a wave holds fewer than
+  // ceil(k/4) elements (T0 = 0) or the gather overflows (long runs of equal
+  // log-probs).
+  if (!kLegacy && k >= 2 && rank_select == 1) {
+    // a candidate is one 64-bit word, key above ~index: a larger word ranks first
+    __shared__ unsigned long long gw[kGatherCap];
+    __shared__ int grank[kGatherCap];
+    __shared__ unsigned wave_t[4], wave_c[4];
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned tmax = 0u;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) tmax = max(tmax, key[j]);  // invalid = 0
+    // the wave's m-th largest thread maximum, bit by bit from the top: the largest
+    // t with m lanes >= t.  One compare per round, the rest is scalar.
+    const int m_need = (k + 3) >> 2;
+    unsigned t = 0u;
+#pragma unroll
+    for (int b = 31; b >= 0; --b) {
+      const unsigned c = t | (1u << b);
+      if (__builtin_popcountll(__builtin_amdgcn_ballot_w64(tmax >= c)) >= m_need) t = c;
+    }
+    grank[tid] = 0;
+    grank[tid + 256] = 0;
+    if (lane == 0) wave_t[w] = t;
+    __syncthreads();
+    const unsigned T0 = min(min(wave_t[0], wave_t[1]), min(wave_t[2], wave_t[3]));
+    if (T0 != 0u) {  // block-uniform
+      // every wave counts its candidates per slot (ballot); the list positions are
+      // prefix sums over waves, slots and lanes: no atomic, no overflow to guard
+      unsigned long long hit[NR];
+      int mine = 0;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        hit[j] = __builtin_amdgcn_ballot_w64(key[j] >= T0);  // invalid keys are 0 < T0
+        mine += __builtin_popcountll(hit[j]);
+      }
+      if (lane == 0) wave_c[w] = (unsigned)mine;
+      __syncthreads();
+      const int c0 = (int)wave_c[0], c1 = (int)wave_c[1], c2 = (int)wave_c[2];
+      const int total = c0 + c1 + c2 + (int)wave_c[3];
+      if (total <= kGatherCap) {  // block-uniform
+        int base = (w > 0 ? c0 : 0) + (w > 1 ? c1 : 0) + (w > 2 ? c2 : 0);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+          if (key[j] >= T0) {
+            const unsigned before = __builtin_amdgcn_mbcnt_hi(
+                (unsigned)(hit[j] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)hit[j], 0u));
+            gw[base + (int)before] =
+                ((unsigned long long)key[j] << 32) | (unsigned)~(tid + 256 * j);
+          }
+          base += __builtin_popcountll(hit[j]);
+        }
+        __syncthreads();
+        // wave w compares every candidate with its quarter of the list; lane l
+        // holds candidates l and l + 64 of each group of 128
+        const int per = (total + 3) >> 2;
+        const int u0 = w * per, u1 = min(total, u0 + per);
+        for (int g = 0; g < total; g += 128) {
+          const int a = g + lane, b = a + 64;
+          const unsigned long long wa = a < total ? gw[a] : ~0ull;
+          const unsigned long long wb = b < total ? gw[b] : ~0ull;
+          int ra = 0, rb = 0;
+#pragma unroll 4
+          for (int u = u0; u < u1; ++u) {
+            const unsigned long long o = gw[u];
+            ra += o > wa;
+            rb += o > wb;
+          }
+          if (a < total) atomicAdd(&grank[a], ra);
+          if (b < total) atomicAdd(&grank[b], rb);
+        }
+        __syncthreads();
+        for (int c = tid; c < total; c += 256) {
+          const int r2 = grank[c];
+          if (r2 < k) {
+            const unsigned long long o = gw[c];
+            out_v[r2] = funkey((unsigned)(o >> 32));
+            out_i[r2] = (int)~(unsigned)o;
+          }
+        }
+        return;
+      }
+    }
+    __syncthreads();
+  }
+  if (kLegacy && k >= 2 && rank_select != 0) {
+    // The first version of the rank counting: a lane ranks its maximum inside its
+    // wave by readlane, one LDS atomic per gathered element, ranks counted by the
+    // first `total` threads.
     __shared__ unsigned gk[kGatherCap];
     __shared__ float gp[kGatherCap];
     __shared__ int gi[kGatherCap];
     __shared__ unsigned wave_t[4], gcount;
     unsigned tmax = 0u;
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j) tmax = max(tmax, key[j]);  // invalid = 0
-    // T0 = min over the 4 waves of the wave's m-th largest thread maximum,
-    // m = ceil(k / 4): every wave then holds >= m elements >= T0, >= k in all.
-    // The rank of a lane's maximum inside its wave needs no LDS (readlane).
+    for (int j = 0; j < NR; ++j) tmax = max(tmax, key[j]);  // invalid = 0
     const int m_need = (k + 3) >> 2;
     const int lane = tid & 63;
     int rank = 0;
@@ -859,15 +954,15 @@ __global__ __launch_bounds__(256) void row_select_reg_kernel(
       rank += (m > tmax) || (m == tmax && u < lane);
     }
     if (tid == 0) gcount = 0u;
-    if (rank == m_need - 1) wave_t[tid >> 6] = rank_select ? tmax : 0u;
+    if (rank == m_need - 1) wave_t[tid >> 6] = tmax;
     __syncthreads();
     const unsigned T0 = min(min(wave_t[0], wave_t[1]), min(wave_t[2], wave_t[3]));
     if (T0 != 0u) {  // block-uniform
 #pragma unroll
-      for (int j = 0; j < kRowRegs; ++j)
+      for (int j = 0; j < NR; ++j)
         if (key[j] >= T0) {  // invalid keys are 0 < T0
           const unsigned q = atomicAdd(&gcount, 1u);
-          if (q < (unsigned)kGatherCap) { gk[q] = key[j]; gp[q] = p[j]; gi[q] = tid + 256 * j; }
+          if (q < (unsigned)kGatherCap) { gk[q] = key[j]; gp[q] = funkey(key[j]); gi[q] = tid + 256 * j; }
         }
       __syncthreads();
       const int total = (int)gcount;
@@ -890,8 +985,8 @@ __global__ __launch_bounds__(256) void row_select_reg_kernel(
   // greedy argmax and the threshold path work from the key range
   unsigned kmax = 0u, kmin = 0xFFFFFFFFu;
 #pragma unroll
-  for (int j = 0; j < kRowRegs; ++j)
-    if (tid + 256 * j < V) { kmax = max(kmax, key[j]); kmin = min(kmin, key[j]); }
+  for (int j = 0; j < NR; ++j)
+    if (live(j)) { kmax = max(kmax, key[j]); kmin = min(kmin, key[j]); }
   for (int o = 32; o > 0; o >>= 1) {
     kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o));
     kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o));
@@ -904,8 +999,8 @@ __global__ __launch_bounds__(256) void row_select_reg_kernel(
   if (k == 1) {  // greedy argmax: the maximum, lowest index among equals
     int best = 0x7fffffff;
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j)
-      if (key[j] == hi && tid + 256 * j < V) best = min(best, tid + 256 * j);
+    for (int j = 0; j < NR; ++j)
+      if (key[j] == hi && live(j)) best = min(best, tid + 256 * j);
     for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
     __syncthreads();
     if ((tid & 63) == 0) cnt[tid >> 6] = (unsigned)best;
@@ -921,7 +1016,7 @@ __global__ __launch_bounds__(256) void row_select_reg_kernel(
     const unsigned mid = lo + ((hi - lo) >> 1) + ((hi - lo) & 1u);
     int c = 0;
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j) c += key[j] >= mid;
+    for (int j = 0; j < NR; ++j) c += key[j] >= mid;
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
     __syncthreads();
     if ((tid & 63) == 0) cnt[tid >> 6] = (unsigned)c;
@@ -934,12 +1029,12 @@ __global__ __launch_bounds__(256) void row_select_reg_kernel(
   if (tid == 0) { cnt[4] = 0u; cnt[5] = 0u; }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < kRowRegs; ++j) {
+  for (int j = 0; j < NR; ++j) {
     const int i = tid + 256 * j;
-    if (i < V) {
+    if (live(j)) {
       if (key[j] > T) {
         const unsigned q = atomicAdd(&cnt[4], 1u);
-        cv[q] = p[j]; ci[q] = i;
+        cv[q] = funkey(key[j]); ci[q] = i;
       } else if (key[j] == T) {
         atomicAdd(&cnt[5], 1u);
       }
@@ -950,11 +1045,11 @@ __global__ __launch_bounds__(256) void row_select_reg_kernel(
   __syncthreads();
   if (neq == need) {
 #pragma unroll
-    for (int j = 0; j < kRowRegs; ++j) {
+    for (int j = 0; j < NR; ++j) {
       const int i = tid + 256 * j;
-      if (i < V && key[j] == T) {
+      if (live(j) && key[j] == T) {
         const unsigned q = atomicAdd(&cnt[4], 1u);
-        cv[q] = p[j]; ci[q] = i;
+        cv[q] = funkey(T); ci[q] = i;
       }
     }
   } else {
@@ -965,9 +1060,9 @@ __global__ __launch_bounds__(256) void row_select_reg_kernel(
     for (int round = 0; round < need; ++round) {
       int best = 0x7fffffff;
 #pragma unroll
-      for (int j = 0; j < kRowRegs; ++j) {
+      for (int j = 0; j < NR; ++j) {
         const int i = tid + 256 * j;
-        if (i < V && key[j] == T && i > prev) best = min(best, i);
+        if (live(j) && key[j] == T && i > prev) best = min(best, i);
       }
       for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o));
       __syncthreads();
@@ -1609,27 +1704,47 @@ static int step_core(milan_ctx* c, const float* features, const float* keys,
 }
 
 static size_t row_select_lds(int V) { return sizeof(float) * (V + 8 + 528); }
+static bool row_select_reg_ok(int V, int k) {
+  return V <= kRowRegs * 256 && k <= 256 && (k <= 1 || k <= V);
+}
 
 static int launch_row_select(const float* logits, const float* lm_logits,
                              float lambda, int rows, int V, int k,
                              const int64_t* last_tok, int stop, float* cand_v,
                              int* cand_i, float* pred_out, long pred_stride,
-                             hipStream_t s, bool wide = false) {
+                             hipStream_t s, bool wide = false, int select = -1) {
   // k > 256 (or `wide`: milan_set_beam_path): the kernels of beam_wide.hip
   if (!pred_out && (k > 256 || wide) && row_select_wide_ok(V, k))
     return launch_row_select_wide(logits, lm_logits, lambda, rows, V, k, last_tok,
                                   stop, cand_v, cand_i, s);
-  if (V <= kRowRegs * 256 && k <= 256 && (k <= 1 || k <= V)) {
+  if (row_select_reg_ok(V, k)) {
     // ties straddling the k-th value are resolved for up to 16 picks in the
     // register kernel; larger tie groups are impossible for distinct logits
-    // MILAN_ROW_SELECT=threshold keeps the key-bisection path (A/B timing)
-    static const int rank_select = [] {
+    // MILAN_ROW_SELECT=threshold keeps the key-bisection path, =legacy the first
+    // rank-count path on all 24 slots (A/B timing); `select` >= 0 overrides both
+    static const int from_env = [] {
       const char* e = getenv("MILAN_ROW_SELECT");
-      return (e && e[0] == 't') ? 0 : 1;
+      return (e && e[0] == 't') ? 0 : (e && e[0] == 'l') ? 2 : 1;
     }();
-    hipLaunchKernelGGL(row_select_reg_kernel, dim3(rows), dim3(256), 0, s,
-                       logits, lm_logits, lambda, V, k, last_tok, stop, cand_v,
-                       cand_i, pred_out, pred_stride, rank_select);
+    const int rank_select = select >= 0 ? select : from_env;
+    // slots per thread: ceil(V / 256) rounded up to a multiple of 4
+    const int nr = rank_select == 2 ? 0 : max(4, ((V + 255) / 256 + 3) & ~3);
+#define MILAN_ROW_SELECT_REG(CASE, ...)                                              \
+  case CASE:                                                                         \
+    hipLaunchKernelGGL((row_select_reg_kernel<__VA_ARGS__>), dim3(rows), dim3(256), 0, s, \
+                       logits, lm_logits, lambda, V, k, last_tok, stop, cand_v,      \
+                       cand_i, pred_out, pred_stride, rank_select);                  \
+    break;
+    switch (nr) {
+      MILAN_ROW_SELECT_REG(0, kRowRegs, true)
+      MILAN_ROW_SELECT_REG(4, 4)
+      MILAN_ROW_SELECT_REG(8, 8)
+      MILAN_ROW_SELECT_REG(12, 12)
+      MILAN_ROW_SELECT_REG(16, 16)
+      MILAN_ROW_SELECT_REG(20, 20)
+      MILAN_ROW_SELECT_REG(24, 24)
+    }
+#undef MILAN_ROW_SELECT_REG
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   }
@@ -2148,6 +2263,26 @@ int decoder_beam_merge(const float* cand_v, const int* cand_i, const float* last
                      cand_i, last_lp, beam_prev, beam, new_lp, new_tok, new_bp);
   MILAN_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+// one per-row top-k on caller-supplied arrays (milan_row_select)
+int decoder_row_select(const float* logits, const float* lm_logits, float lambda,
+                       int rows, int V, int k, const int64_t* last_tok, int stop,
+                       float* cand_v, int* cand_i, int path, hipStream_t s) {
+  MILAN_REQUIRE(rows > 0 && V >= 1 && k >= 1 && k <= kMaxBeam && k <= V, MILAN_ERR_ARG,
+                "row select: rows=%d, k=%d must be in 1..min(%d, vocab_size %d)", rows, k,
+                kMaxBeam, V);
+  if (path == 0)
+    return launch_row_select(logits, lm_logits, lambda, rows, V, k, last_tok, stop,
+                             cand_v, cand_i, nullptr, 0, s);
+  if (path == 1)
+    return launch_row_select_wide(logits, lm_logits, lambda, rows, V, k, last_tok, stop,
+                                  cand_v, cand_i, s);
+  MILAN_REQUIRE(k >= 2 && row_select_reg_ok(V, k), MILAN_ERR_ARG,
+                "row select: path %d needs 2 <= k <= 256 and vocab_size <= %d (k=%d, "
+                "vocab_size %d)", path, kRowRegs * 256, k, V);
+  return launch_row_select(logits, lm_logits, lambda, rows, V, k, last_tok, stop, cand_v,
+                           cand_i, nullptr, 0, s, false, path == 2 ? 0 : 2);
 }
 
 int decoder_decode(milan_ctx* c, const float* features, int n, int k,

@@ -143,6 +143,7 @@ SIGNATURES = {
     ]),
     'milan_beam_merge': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _SZ,
                               _P]),
+    'milan_row_select': (_I, [_P, _P, _F, _I, _I, _I, _P, _I, _P, _P, _I, _P]),
     'milan_set_beam_path': (_I, [_P, _I]),
     'milan_get_beam_path': (_I, [_P]),
     'milan_set_ablation': (_I, [_P, _P, _P, _I, _P]),
@@ -265,7 +266,7 @@ SIGNATURES = {
 # entry points added without a new ABI version: a library built before them
 # (an older MILAN_LIB) still loads, and the calls that need them say so
 PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
-          'milan_lm_backward', 'milan_beam_merge', 'milan_set_beam_path',
+          'milan_lm_backward', 'milan_beam_merge', 'milan_row_select', 'milan_set_beam_path',
           'milan_get_beam_path', 'milan_set_ablation',
           'milan_classify_workspace_bytes', 'milan_classify',
           'milan_classify_sweep')
@@ -1901,6 +1902,48 @@ def beam_merge(cand_v: torch.Tensor,
                                  new_lp.data_ptr(), new_tok.data_ptr(),
                                  new_bp.data_ptr(), None, 0, _stream(device)))
     return new_lp, new_tok, new_bp
+
+
+ROW_SELECT_PATHS = {'auto': 0, 'wide': 1, 'threshold': 2, 'legacy': 3}
+
+
+def row_select(logits: torch.Tensor,
+               k: int,
+               lm_logits: Optional[torch.Tensor] = None,
+               lam: float = 0.,
+               last_tok: Optional[torch.Tensor] = None,
+               stop: int = 0,
+               path: str = 'auto',
+               lib: Optional[ctypes.CDLL] = None):
+    """One per-row top-k of the beam search (milan_row_select): per row the `k` best of
+    log_softmax(logits) - lam * log_softmax(lm_logits), logits (rows, V) float32.  A row
+    with last_tok[row] == stop gets the forced candidates of a finished beam.  Returns
+    (cand_v, cand_i), each (rows, k), sorted by (value descending, index ascending).
+    `path`: 'auto' (the kernel `Context.decode` runs), 'wide', 'threshold' or 'legacy';
+    a shape the path does not take raises ValueError.  Every path gives the same bits."""
+    lib = lib if lib is not None else load_library()
+    if not hasattr(lib, 'milan_row_select'):
+        raise HipUnavailableError('this build of libmilan_hip has no milan_row_select')
+    device = require_device(logits.device)
+    rows, V = logits.shape
+    if lm_logits is not None and tuple(lm_logits.shape) != (rows, V):
+        raise ValueError(f'lm_logits shape {tuple(lm_logits.shape)} != {(rows, V)}')
+    if last_tok is not None and tuple(last_tok.shape) != (rows,):
+        raise ValueError(f'last_tok shape {tuple(last_tok.shape)} != {(rows,)}')
+    logits = _dev(logits, device, torch.float32)
+    if lm_logits is not None:
+        lm_logits = _dev(lm_logits, device, torch.float32)
+    if last_tok is not None:
+        last_tok = _dev(last_tok, device, torch.int64)
+    cand_v = torch.empty(rows, k, device=device)
+    cand_i = torch.empty(rows, k, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(
+            lib.milan_row_select(logits.data_ptr(), _ptr(lm_logits), float(lam), rows, V,
+                                 int(k), _ptr(last_tok), int(stop), cand_v.data_ptr(),
+                                 cand_i.data_ptr(), ROW_SELECT_PATHS[path],
+                                 _stream(device)))
+    return cand_v, cand_i
 
 
 def make_dims(state_dict: Dict[str, torch.Tensor],

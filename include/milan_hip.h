@@ -185,6 +185,30 @@ int milan_classify_sweep(milan_ctx* ctx, const float* images, int n_images, int 
                          const int64_t* targets, int32_t* correct, int64_t* predictions,
                          void* workspace, size_t workspace_bytes, milan_stream stream);
 
+/* Activation taps on the ResNet trunks: what nethook.retain_layers hands out for the five
+ * layers above, computed by the walk of milan_classify.
+ *   milan_activations  images (n,3,H,W) float NCHW, fed as they are (milan_classify's
+ *     contract).  levels: a HOST array of `count` >= 1 distinct levels in 0..4, in any order;
+ *     outputs[i]: a DEVICE pointer to (n, C_level, h_level, w_level) fp32 NCHW for levels[i]
+ *     (the layout the exemplar kernels read), `outputs` itself a HOST array.  The tensor is the
+ *     module's OUTPUT after the installed ablation set's mask: what the next layer reads.
+ *     Level 0 is the raw stem conv output (negative values included; a zero is always handed
+ *     out as +0, also where the mask's product with a negative value was -0).  The walk runs once per
+ *     sub-batch (MILAN_ENC_SUB) up to the highest requested level and no further; no head
+ *     runs, so a context without fc.weight is accepted.  Each requested level is converted
+ *     from the trunk's layout (NHWC, fp32 or split f16 at the activation scale, which is
+ *     removed exactly) when it is produced.  Runs in MILAN_PRECISION_F32 or
+ *     MILAN_PRECISION_SPLIT_F16; MILAN_PRECISION_F16 and AlexNet: MILAN_ERR_ARG, as is a level
+ *     outside 0..4 or one listed twice.  Saturation goes to the status word; no host
+ *     synchronisation.
+ *   milan_activations_workspace_bytes  scratch for n_images at H x W.
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them. */
+size_t milan_activations_workspace_bytes(const milan_ctx* ctx, int n_images, int height,
+                                         int width);
+int milan_activations(milan_ctx* ctx, const float* images, int n_images, int height, int width,
+                      const int32_t* levels, int count, float* const* outputs,
+                      void* workspace, size_t workspace_bytes, milan_stream stream);
+
 /* Decoder.init_state (src/milan/decoders.py:548-574).
  * features (n,k,F) -> h,c (n,hidden). */
 int milan_init_state(milan_ctx* ctx, const float* features, int n, int k,

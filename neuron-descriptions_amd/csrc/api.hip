@@ -416,6 +416,25 @@ int milan_classify_sweep(milan_ctx* c, const float* images, int n_images, int he
                         correct, predictions, a, (hipStream_t)stream);
 }
 
+size_t milan_activations_workspace_bytes(const milan_ctx* c, int n_images, int height,
+                                         int width) {
+  if (!c || !c->finalized) return 0;
+  return activations_workspace(c, n_images, height, width) + 256;
+}
+
+int milan_activations(milan_ctx* c, const float* images, int n_images, int height, int width,
+                      const int32_t* levels, int count, float* const* outputs, void* workspace,
+                      size_t workspace_bytes, milan_stream stream) {
+  MILAN_REQUIRE(c && images && count >= 1 && levels && outputs, MILAN_ERR_ARG,
+                "milan_activations: bad argument");
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  set_status_word(c->status);
+  Arena a;
+  MILAN_TRY(make_arena(workspace, workspace_bytes, &a));
+  return activations_run(c, images, n_images, height, width, levels, count, outputs, a,
+                         (hipStream_t)stream);
+}
+
 int milan_encode_spatial(milan_ctx* c, const void* images, int image_dtype,
                          const void* masks, int mask_dtype, int n_images,
                          int height, int width, float* out, void* workspace,

@@ -1,6 +1,6 @@
-// Unit ablation and classification on the ResNet trunks (milan_set_ablation, milan_classify,
-// milan_classify_sweep): the reference's src/utils/ablations.py on torchvision's
-// ResNet._forward_impl, eval mode.
+// Unit ablation, classification and activation taps on the ResNet trunks (milan_set_ablation,
+// milan_classify, milan_classify_sweep, milan_activations): the reference's
+// src/utils/ablations.py on torchvision's ResNet._forward_impl, eval mode.
 //
 // The forward is a plain walker of its own: stem conv, bn1 + ReLU + maxpool, every block's convs
 // through launch_gemm with the epilogues the encoder uses, then the head.  It materialises the
@@ -95,6 +95,64 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const float* __restrict__ 
     sum += v;
   }
   out[img * C + c] = sum / (float)P;
+}
+
+// Activation tap (milan_activations): a level tensor (n, P, C) in the trunk's layout -> fp32
+// (n, C, P), the NCHW tensor the exemplar kernels read.  One workgroup moves a tile of
+// TAP_P pixels x TAP_C channels through LDS: the global reads are 16-byte pieces contiguous
+// along C (one float4, or one [hi x8 | lo x8] group = two pieces), the global writes run
+// along P, one wavefront per 256-byte run.  LDS rows are pixels, padded by one dword: the
+// writes of a 32-lane half (c-piece fastest, then pixel) and the column reads (lane = pixel)
+// both land on 32 distinct banks.  fp32: a copy of the value, except that -0 becomes +0.
+// SPLIT: the value is (float(hi) + float(lo)) * inv_scale, avgpool_kernel's decode.  Both
+// tile edges are guarded (P is anything >= 1, C a multiple of 8).
+// grid (ceil(P / TAP_P), ceil(C / TAP_C), n).
+constexpr int TAP_P = 64, TAP_C = 32, TAP_LD = TAP_C + 1;
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void tap_nchw_kernel(const float* __restrict__ x, int P, int C,
+                                                       float inv_scale, float* __restrict__ out) {
+  __shared__ float tile[TAP_P * TAP_LD];
+  const int t = threadIdx.x;
+  const int p0 = blockIdx.x * TAP_P, c0 = blockIdx.y * TAP_C;
+  const size_t img = blockIdx.z;
+  const float* src = x + img * (size_t)P * C;
+  if constexpr (SPLIT) {
+    // 4 groups of 8 channels per pixel: one group per thread
+    const int g = t & 3, p = t >> 2;
+    const int c = c0 + g * 8;
+    if (p0 + p < P && c < C) {
+      const float* q = src + (size_t)(p0 + p) * C + c;
+      const cf16x8_t hi = *reinterpret_cast<const cf16x8_t*>(q);
+      const cf16x8_t lo = *reinterpret_cast<const cf16x8_t*>(q + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        tile[p * TAP_LD + g * 8 + e] = ((float)hi[e] + (float)lo[e]) * inv_scale;
+    }
+  } else {
+    // 8 float4 per pixel: 32 pixels per pass, two passes.  A zero leaves as +0: the raw conv1
+    // tensor has negative values, and the mask's product with one of them is -0.
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int c4 = t & 7, p = (t >> 3) + r * 32;
+      const int c = c0 + c4 * 4;
+      if (p0 + p < P && c < C) {
+        const cf32x4_t v = *reinterpret_cast<const cf32x4_t*>(src + (size_t)(p0 + p) * C + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tile[p * TAP_LD + c4 * 4 + e] = v[e] == 0.f ? 0.f : v[e];
+      }
+    }
+  }
+  __syncthreads();
+  // wavefront w writes channels w*8 .. w*8+7, lane = pixel
+  const int lane = t & 63, wv = t >> 6;
+  if (p0 + lane < P) {
+    float* dst = out + img * (size_t)C * P + (size_t)p0 + lane;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int cc = wv * 8 + k;
+      if (c0 + cc < C) dst[(size_t)(c0 + cc) * P] = tile[lane * TAP_LD + cc];
+    }
+  }
 }
 
 // logits[img][j] = bias[j] + pooled[img] . W[j], exact fp32, one wavefront per output (see the
@@ -328,9 +386,26 @@ struct Walker {
     return 0;
   }
 
+  // the masked level tensor `x` -> tap[level] as fp32 NCHW (milan_activations).  Level 0 is
+  // the raw conv1 output: fp32 without any scale in both modes (the pair stem's weight scale
+  // leaves in the GEMM's acc_scale, the activation scale enters only with bn1_scale_s).
+  int emit(int level, const float* x) const {
+    const int C = c->abl_ch[level], P = pl.h[level] * pl.w[level];
+    const dim3 grid((P + TAP_P - 1) / TAP_P, (C + TAP_C - 1) / TAP_C, n);
+    if (split && level > 0)
+      hipLaunchKernelGGL(tap_nchw_kernel<true>, grid, dim3(256), 0, s, x, P, C,
+                         1.f / c->act_scale, tap[level]);
+    else
+      hipLaunchKernelGGL(tap_nchw_kernel<false>, grid, dim3(256), 0, s, x, P, C, 1.f,
+                         tap[level]);
+    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
+
   // Runs the forward from level `from` (-1: from `src` = the images; otherwise `src` is the
   // level's tensor with its mask already applied) up to and including level `to`, applying the
-  // context's masks to every level it produces.  *out = the level-`to` tensor.
+  // context's masks to every level it produces.  *out = the level-`to` tensor.  Every level
+  // it produces that has a tap[] pointer is also written there, after its mask.
   int walk(int from, int to, const float* src, const float** out) const {
     const float* x = src;
     if (from < 0) {
@@ -340,6 +415,7 @@ struct Walker {
       if (c->abl_count[0] > 0) MILAN_TRY(mask(0, pl.raw, pl.raw, -1));
       x = pl.raw;
       from = 0;
+      if (tap[0]) MILAN_TRY(emit(0, x));
     }
     if (to == from) { *out = x; return 0; }
     float* y = pl.x0;
@@ -380,6 +456,7 @@ struct Walker {
                     "internal: stage %d geometry mismatch", li + 1);
       if (c->abl_count[li + 1] > 0)
         MILAN_TRY(mask(li + 1, x, const_cast<float*>(x), -1));
+      if (tap[li + 1]) MILAN_TRY(emit(li + 1, x));
     }
     *out = x;
     return 0;
@@ -403,14 +480,16 @@ struct Walker {
   }
 
   int hin = 0, win = 0;
+  float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
-static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split) {
+// `head`: the call runs avgpool + fc (milan_activations stops before them and does not)
+static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool head = true) {
   MILAN_REQUIRE(resnet_trunk(c), MILAN_ERR_ARG,
                 "classification needs a ResNet trunk (AlexNet's classifier is not built)");
   MILAN_REQUIRE(c->stem.w != nullptr && c->abl_mask != nullptr, MILAN_ERR_STATE,
                 "encoder weights were not uploaded");
-  MILAN_REQUIRE(c->fc_w != nullptr, MILAN_ERR_STATE,
+  MILAN_REQUIRE(!head || c->fc_w != nullptr, MILAN_ERR_STATE,
                 "this context was created without fc.weight: it has no classifier head");
   MILAN_REQUIRE(!c->trunk_f16, MILAN_ERR_ARG,
                 "classification runs in the f32 and split_f16 modes, not in the fast f16 mode");
@@ -493,6 +572,47 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
     hipLaunchKernelGGL(correct_count_kernel, dim3(count), dim3(256), 0, s, preds_all,
                        (const long long*)targets, n, correct);
     MILAN_CHECK_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// milan_activations: the walk of classify_run, once per sub-batch up to the highest requested
+// level, each requested level converted to fp32 NCHW when it is produced; no head
+size_t activations_workspace(const milan_ctx* c, int n_images, int H, int W) {
+  return classify_workspace(c, n_images, H, W, 0);
+}
+
+int activations_run(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
+                    int count, float* const* outputs, Arena& ws, hipStream_t s) {
+  bool split;
+  MILAN_TRY(classify_checks(c, n, H, W, &split, false));
+  int slot[5] = {-1, -1, -1, -1, -1}, top = -1;
+  for (int i = 0; i < count; ++i) {
+    MILAN_REQUIRE(levels[i] >= 0 && levels[i] <= 4, MILAN_ERR_ARG,
+                  "milan_activations: level %d is not one of 0..4 (conv1, layer1..layer4)",
+                  levels[i]);
+    MILAN_REQUIRE(slot[levels[i]] < 0, MILAN_ERR_ARG,
+                  "milan_activations: level %d is requested twice", levels[i]);
+    MILAN_REQUIRE(outputs[i] != nullptr, MILAN_ERR_ARG,
+                  "milan_activations: outputs[%d] is null", i);
+    slot[levels[i]] = i;
+    top = std::max(top, (int)levels[i]);
+  }
+  const int sub = encoder_sub_batch_size();
+  for (int lo = 0; lo < n; lo += sub) {
+    const int cnt = n - lo < sub ? n - lo : sub;
+    Arena a = ws;  // every pass reuses the same scratch
+    ClsPlan pl;
+    cls_plan(c, cnt, H, W, 0, 0, a, &pl);
+    MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
+                  "activations: workspace too small (%zu needed, %zu given)", a.off, a.size);
+    MILAN_REQUIRE(cnt <= 65535, MILAN_ERR_ARG, "activations: sub-batch of %d images", cnt);
+    Walker wk{c, pl, cnt, split, s};
+    wk.hin = H; wk.win = W;
+    for (int l = 0; l < 5; ++l)
+      if (slot[l] >= 0) wk.tap[l] = outputs[slot[l]] + (size_t)lo * pl.lvl_sz[l];
+    const float* x;
+    MILAN_TRY(wk.walk(-1, top, images + (size_t)lo * 3 * H * W, &x));
   }
   return 0;
 }

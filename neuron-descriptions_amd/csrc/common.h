@@ -650,6 +650,9 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
 int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
                    const int32_t* units, int count, const int64_t* targets, int32_t* correct,
                    int64_t* predictions, Arena& ws, hipStream_t s);
+size_t activations_workspace(const milan_ctx* c, int n, int H, int W);
+int activations_run(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
+                    int count, float* const* outputs, Arena& ws, hipStream_t s);
 // decoder.hip
 int decoder_finalize(milan_ctx* c, hipStream_t s);
 size_t decoder_workspace(const milan_ctx* c, int n, int k, int beam, int length);

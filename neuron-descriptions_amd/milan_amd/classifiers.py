@@ -15,7 +15,7 @@ tree and key names (`conv1.weight`, `bn1.*`, `layerL.B.convK.weight`, `downsampl
     same arithmetic the reference's torchvision model runs (batch-statistic BatchNorm in
     training mode).  That path is what `fit` trains through.
 """
-from typing import Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -143,6 +143,45 @@ class ResNetClassifier(nn.Module):
         if not self.runs_natively(images):
             return self.forward_eager(images)
         return self._native_context().classify(images)
+
+    def activations(self, images: torch.Tensor, layers) -> Dict[str, torch.Tensor]:
+        """The outputs of the named modules for `images`, under the current ablation set and
+        after its edit (what the next layer reads; what `nethook.retain_layers` retains).
+
+        `layers`: a name or a sequence of names from `named_modules()`.  When the forward
+        would run natively (`runs_natively`) and every name is one of `self.layers`, the
+        tensors come from `hip.Context.activations`: one walk of the HIP trunk up to the
+        deepest layer asked for.  Anything else -- CPU tensors, training mode, grad enabled,
+        a layer such as 'layer2.0.conv1' or 'fc' -- runs `forward_eager` under `no_grad`
+        with forward hooks.  An unknown name is a KeyError."""
+        names = [layers] if isinstance(layers, str) else list(layers)
+        modules = dict(self.named_modules())
+        for name in names:
+            if not name or name not in modules:
+                raise KeyError(f'layer not found: {name}')
+        if self.runs_natively(images) and all(name in self.layers for name in names):
+            return self._native_context().activations(images, names)
+        retained: Dict[str, torch.Tensor] = {}
+        handles = []
+
+        def retain(name):
+            def hook(module, inputs, output):
+                # (nethook's retain: detached, not copied -- an in-place ReLU that follows
+                # the module shows in it, as it does there)
+                retained[name] = output.detach()
+            return hook
+
+        # (registered now: after the hooks of an `ablations.ablated` block around this call,
+        # so they see the edited output)
+        for name in dict.fromkeys(names):
+            handles.append(modules[name].register_forward_hook(retain(name)))
+        try:
+            with torch.no_grad():
+                self.forward_eager(images)
+        finally:
+            for handle in handles:
+                handle.remove()
+        return {name: retained[name] for name in names}
 
     # -- HIP context, rebuilt when device or weights change ---------------------------
     def _context(self) -> hip.Context:

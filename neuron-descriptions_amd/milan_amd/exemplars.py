@@ -861,10 +861,22 @@ def discriminative(model: nn.Module,
         return directory
 
     layer = str(layer) if layer is not None else None
-    hook = _Retain(model, layer)
+    # A model that hands its layers out itself (an `activations(images, layers)` method plus
+    # `layers`, e.g. classifiers.ResNetClassifier) is asked: its native forward runs no torch
+    # sub-module, so a forward hook on one would never fire.
+    taps = (layer is not None and callable(getattr(model, 'activations', None)) and
+            hasattr(model, 'layers'))
+    hook = _Retain(model, None if taps else layer)
 
     def hiddens(*args):
         inputs = transform_inputs(*map_location(args, device))
+        if taps:
+            if not isinstance(inputs, (tuple, dict)):
+                raise ValueError(f'inputs must be a tuple or dict, got {type(inputs)}')
+            with torch.no_grad():
+                retained = (model.activations(layers=layer, **inputs) if isinstance(
+                    inputs, dict) else model.activations(*inputs, layer))
+            return transform_hiddens(retained[layer])
         with torch.no_grad():
             outputs = _run_model(model, inputs)
         return transform_hiddens(outputs if layer is None else hook.output)

@@ -151,6 +151,8 @@ SIGNATURES = {
     'milan_classify': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     'milan_classify_sweep':
         (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    'milan_activations_workspace_bytes': (_SZ, [_P, _I, _I, _I]),
+    'milan_activations': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
     'milan_set_graph_capture': (_I, [_P, _I]),
     'milan_graph_stats': (_I, [
         _P, ctypes.POINTER(ctypes.c_longlong),
@@ -269,7 +271,8 @@ PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_lm_backward', 'milan_beam_merge', 'milan_row_select', 'milan_set_beam_path',
           'milan_get_beam_path', 'milan_set_ablation',
           'milan_classify_workspace_bytes', 'milan_classify',
-          'milan_classify_sweep')
+          'milan_classify_sweep', 'milan_activations_workspace_bytes',
+          'milan_activations')
 
 _lib = None
 
@@ -900,8 +903,11 @@ class Context:
         with torch.cuda.device(self.device):
             _check(fn(self._h, levels, units, count, _stream(self.device)))
 
-    def _classify_ws(self, n: int, h: int, w: int, sweep: int) -> torch.Tensor:
-        need = int(self._need('milan_classify_workspace_bytes')(self._h, n, h, w, sweep))
+    def _classify_ws(self, n: int, h: int, w: int, sweep: int = 0,
+                     need: Optional[int] = None) -> torch.Tensor:
+        """The scratch the classify family shares (`need`: bytes asked for by the caller)."""
+        if need is None:
+            need = int(self._need('milan_classify_workspace_bytes')(self._h, n, h, w, sweep))
         ws = getattr(self, '_cls_ws', None)
         if ws is None or ws.numel() < need:
             self._cls_ws = None  # free before growing
@@ -965,6 +971,52 @@ class Context:
             return preds if targets is None else (preds, correct)
 
         return self._guarded('classify_sweep', run, check)
+
+    def activations(self, images: torch.Tensor, levels, check: bool = True) -> dict:
+        """The tensors of the requested edit points under the current ablation set, after
+        its masks: {level as given: (n, C, h, w) float32 NCHW}.  `levels`: distinct entries,
+        each 0..4 or 'conv1', 'layer1'..'layer4', in any order.  One walk of the trunk up to
+        the highest level; no head runs (a state dict without `fc` will do).  Level 0 is the
+        raw conv1 output, before bn1 / ReLU / maxpool."""
+        fn = self._need('milan_activations')
+        images = self._classify_images(images)
+        n, _, h, w = images.shape
+        keys = list(levels)
+        if not keys:
+            raise ValueError('activations needs at least one level')
+        idx = []
+        for level in keys:
+            if isinstance(level, str):
+                if level not in self.ABLATION_LEVELS:
+                    raise ValueError(f'layer {level!r} has no native tap; the layers are '
+                                     f'{self.ABLATION_LEVELS}')
+                level = self.ABLATION_LEVELS.index(level)
+            idx.append(int(level))
+        ws = self._classify_ws(
+            n, h, w, need=int(self._need('milan_activations_workspace_bytes')(self._h, n, h, w)))
+        # level extents: conv1 7x7/2 pad 3, then the maxpool and every later stage 3x3/2 pad 1
+        basic = self.dims.trunk_kind == TRUNK_BASIC
+        outs = []
+        for level in idx:
+            if not 0 <= level <= 4:  # (the library reports it; the shape is a placeholder)
+                outs.append(torch.empty(1, dtype=torch.float32, device=self.device))
+                continue
+            hl, wl = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
+            for _ in range(level):
+                hl, wl = (hl + 2 - 3) // 2 + 1, (wl + 2 - 3) // 2 + 1
+            width = self.dims.trunk_width
+            ch = width if level == 0 else (width if basic else width * 4) << (level - 1)
+            outs.append(torch.empty(n, ch, hl, wl, dtype=torch.float32, device=self.device))
+        c_levels = (ctypes.c_int32 * len(idx))(*idx)
+        c_outs = (ctypes.c_void_p * len(idx))(*[o.data_ptr() for o in outs])
+
+        def run():
+            with torch.cuda.device(self.device):
+                _check(fn(self._h, images.data_ptr(), n, h, w, c_levels, len(idx), c_outs,
+                          ws.data_ptr(), ws.numel(), _stream(self.device)))
+            return dict(zip(keys, outs))
+
+        return self._guarded('activations', run, check)
 
     def init_state(self, features: torch.Tensor, check: bool = True):
         """(n, k, F) features -> (h, c).  `check` (here and in `step`, `decode`, `lm_score`,

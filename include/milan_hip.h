@@ -143,7 +143,8 @@ int milan_encode_spatial(milan_ctx* ctx, const void* images, int image_dtype,
  * The head comes from the state dict: when `<prefix>fc.weight` (classes, C4) and
  * `<prefix>fc.bias` were uploaded, milan_finalize_weights keeps them (fp32, as they are); the
  * class count is fc.weight's first extent.  A context without them behaves as before and the
- * classify calls return MILAN_ERR_STATE; an AlexNet context gets MILAN_ERR_ARG.
+ * classify calls return MILAN_ERR_STATE; an AlexNet context gets MILAN_ERR_ARG until
+ * milan_set_alexnet_head (below) has installed its head.
  *
  * The five places an edit can sit are the reference's LAYERS.RESNET18 (src/exemplars/models.py:
  * 48-52), edited as nethook edits a module's OUTPUT: level 0 = `conv1`, the raw stem conv
@@ -198,7 +199,7 @@ int milan_classify_sweep(milan_ctx* ctx, const float* images, int n_images, int 
  *     runs, so a context without fc.weight is accepted.  Each requested level is converted
  *     from the trunk's layout (NHWC, fp32 or split f16 at the activation scale, which is
  *     removed exactly) when it is produced.  Runs in MILAN_PRECISION_F32 or
- *     MILAN_PRECISION_SPLIT_F16; MILAN_PRECISION_F16 and AlexNet: MILAN_ERR_ARG, as is a level
+ *     MILAN_PRECISION_SPLIT_F16; MILAN_PRECISION_F16 and a headless AlexNet: MILAN_ERR_ARG, as is a level
  *     outside 0..4 or one listed twice.  Saturation goes to the status word; no host
  *     synchronisation.
  *   milan_activations_workspace_bytes  scratch for n_images at H x W.
@@ -208,6 +209,46 @@ size_t milan_activations_workspace_bytes(const milan_ctx* ctx, int n_images, int
 int milan_activations(milan_ctx* ctx, const float* images, int n_images, int height, int width,
                       const int32_t* levels, int count, float* const* outputs,
                       void* workspace, size_t workspace_bytes, milan_stream stream);
+
+/* The same calls on AlexNet: `alexnet_seq` (conv1..conv5, fc6, fc7, linear8) in eval mode, the
+ * second CNN of the reference's editing experiment.  An AlexNet context (features.0/3/6/8/10)
+ * answers milan_set_ablation / milan_classify* / milan_activations* with MILAN_ERR_ARG, as
+ * described above, until this call has installed its three Linear layers; `classifier.1/4/6`
+ * keys of the state dict switch nothing on.
+ *   milan_set_alexnet_head  DEVICE fp32 pointers: row-major weights (out, in) and biases (out).
+ *     fc6_in must be C5 x 36 (C5 = features.10's channels), fc7_in == fc6_out, linear8_in ==
+ *     fc7_out (MILAN_ERR_SHAPE otherwise); linear8_out is the class count.  The weights are
+ *     packed into memory the context owns; the call synchronises `stream`, and the caller's
+ *     tensors may go afterwards.  Calling it again with the same widths replaces the values.
+ * From then on: levels 0..4 are conv1..conv5, each tensor relu(conv + bias) x mask, which is
+ * what the next layer reads and what milan_activations hands out (level 0 too: post-ReLU, fp32
+ * in both precision modes).  The tail -- 3x3/2 max-pool, AdaptiveAvgPool2d((6, 6)), flatten in
+ * (C, h, w) order -- and the three Linear layers are exact fp32 in both modes; dropout is the
+ * identity.  Images are fed as they are and must be at least 63 x 63 (MILAN_ERR_SHAPE).
+ * milan_encode* on the context is unchanged.
+ *
+ * The Linear layer itself, without a context: y (rows, n_out) = act(x (rows, n_in) W^T + bias)
+ * on the fp32 MFMA, act = ReLU when `relu` != 0, bias may be NULL.  The summation order of an
+ * output depends on n_in alone (zero-padded to a multiple of 8; chunks of 256 each summed from
+ * zero by one k-ordered fmaf chain; chunks j, j + 4, ... added in order into four totals;
+ * (t0 + t1) + (t2 + t3), then the bias): a batch gives the bits of its rows.
+ *   milan_linear_packed_bytes / milan_linear_pack  the packed copy of a row-major (n_out, n_in)
+ *     weight that milan_linear reads, once per weight.
+ *   milan_linear_rowwise  the ResNet head's kernel (one wavefront per output and row) on a
+ *     row-major weight: kept callable as the baseline of tools/bench_alexnet.py.
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them. */
+int milan_set_alexnet_head(milan_ctx* ctx, const float* fc6_weight, const float* fc6_bias,
+                           int fc6_out, int fc6_in, const float* fc7_weight,
+                           const float* fc7_bias, int fc7_out, int fc7_in,
+                           const float* linear8_weight, const float* linear8_bias,
+                           int linear8_out, int linear8_in, milan_stream stream);
+size_t milan_linear_packed_bytes(int n_out, int n_in);
+int milan_linear_pack(const float* weight, int n_out, int n_in, float* packed,
+                      milan_stream stream);
+int milan_linear(const float* x, const float* packed, const float* bias, int rows, int n_in,
+                 int n_out, int relu, float* y, milan_stream stream);
+int milan_linear_rowwise(const float* x, const float* weight, const float* bias, int rows,
+                         int n_in, int n_out, float* y, milan_stream stream);
 
 /* Decoder.init_state (src/milan/decoders.py:548-574).
  * features (n,k,F) -> h,c (n,hidden). */

@@ -382,6 +382,42 @@ int milan_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* units
   return classify_set_ablation(c, levels, units, count, (hipStream_t)stream);
 }
 
+int milan_set_alexnet_head(milan_ctx* c, const float* fc6_weight, const float* fc6_bias, int fc6_out,
+                           int fc6_in, const float* fc7_weight, const float* fc7_bias,
+                           int fc7_out, int fc7_in, const float* linear8_weight,
+                           const float* linear8_bias, int linear8_out, int linear8_in,
+                           milan_stream stream) {
+  MILAN_REQUIRE(c && fc6_weight && fc6_bias && fc7_weight && fc7_bias && linear8_weight &&
+                    linear8_bias,
+                MILAN_ERR_ARG, "milan_set_alexnet_head: null argument");
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  const float* w[3] = {fc6_weight, fc7_weight, linear8_weight};
+  const float* b[3] = {fc6_bias, fc7_bias, linear8_bias};
+  const int out[3] = {fc6_out, fc7_out, linear8_out}, in[3] = {fc6_in, fc7_in, linear8_in};
+  return classify_set_alexnet_head(c, w, b, out, in, (hipStream_t)stream);
+}
+
+size_t milan_linear_packed_bytes(int n_out, int n_in) {
+  if (n_out < 1 || n_in < 1) return 0;
+  return sizeof(float) * linear_packed_floats(n_out, n_in);
+}
+
+int milan_linear_pack(const float* weight, int n_out, int n_in, float* packed,
+                      milan_stream stream) {
+  return linear_pack(weight, n_out, n_in, packed, (hipStream_t)stream);
+}
+
+int milan_linear(const float* x, const float* packed, const float* bias, int rows, int n_in,
+                 int n_out, int relu, float* y, milan_stream stream) {
+  return linear_run(x, packed, bias, rows, n_in, n_out, relu != 0, y, (hipStream_t)stream);
+}
+
+int milan_linear_rowwise(const float* x, const float* weight, const float* bias, int rows,
+                         int n_in, int n_out, float* y, milan_stream stream) {
+  return linear_rowwise_run(x, weight, bias, rows, n_in, n_out, y, (hipStream_t)stream);
+}
+
 size_t milan_classify_workspace_bytes(const milan_ctx* c, int n_images, int height, int width,
                                       int sweep_units) {
   if (!c || !c->finalized) return 0;

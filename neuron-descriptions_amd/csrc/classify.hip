@@ -1,6 +1,8 @@
 // Unit ablation, classification and activation taps on the ResNet trunks (milan_set_ablation,
 // milan_classify, milan_classify_sweep, milan_activations): the reference's
-// src/utils/ablations.py on torchvision's ResNet._forward_impl, eval mode.
+// src/utils/ablations.py on torchvision's ResNet._forward_impl, eval mode.  The same calls on
+// AlexNet (alexnet_seq: conv1..conv5, fc6, fc7, linear8) have a walker, a tail kernel and a
+// Linear kernel of their own further down.
 //
 // The forward is a plain walker of its own: stem conv, bn1 + ReLU + maxpool, every block's convs
 // through launch_gemm with the epilogues the encoder uses, then the head.  It materialises the
@@ -211,10 +213,234 @@ __global__ __launch_bounds__(256) void correct_count_kernel(const long long* __r
 }
 
 // ---------------------------------------------------------------------------
+// AlexNet: the tail of the trunk and the Linear layers
+// ---------------------------------------------------------------------------
+// pool5 + AdaptiveAvgPool2d((6, 6)) + flatten of the masked level-4 tensor (n, H, W, C), fp32 or
+// split (avgpool_kernel<true>'s decode) -> fp32 (n, C * 36), column c * 36 + i * 6 + j.
+// pool5 is the 3x3 / stride 2 max-pool without padding, (Hp, Wp) its extent; bin (i, j) covers
+// pooled rows floor(i Hp / 6) .. ceil((i + 1) Hp / 6) - 1 and the columns likewise (torch's
+// rule), added in ascending (row, column) order, then one division by the bin's size.
+// A thread per (image, bin, channel), channels fastest.  grid (ceil(36 C / 256), n).
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void alex_tail_kernel(const float* __restrict__ x, int H, int W,
+                                                        int C, int Hp, int Wp, float inv_scale,
+                                                        float* __restrict__ out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 36 * C) return;
+  const int c = idx % C, bin = idx / C, bi = bin / 6, bj = bin % 6;
+  const size_t img = blockIdx.y;
+  const float* src = x + img * (size_t)H * W * C;
+  const int r0 = (bi * Hp) / 6, r1 = ((bi + 1) * Hp + 5) / 6;
+  const int q0 = (bj * Wp) / 6, q1 = ((bj + 1) * Wp + 5) / 6;
+  float sum = 0.f;
+  for (int r = r0; r < r1; ++r)
+    for (int q = q0; q < q1; ++q) {
+      float best = -INFINITY;
+      for (int dy = 0; dy < 3; ++dy)
+        for (int dx = 0; dx < 3; ++dx) {
+          const float* px = src + ((size_t)(2 * r + dy) * W + (2 * q + dx)) * C;
+          float v;
+          if constexpr (SPLIT) {
+            const _Float16* g = reinterpret_cast<const _Float16*>(px + (c >> 3) * 8);
+            v = ((float)g[c & 7] + (float)g[8 + (c & 7)]) * inv_scale;
+          } else {
+            v = px[c];
+          }
+          best = fmaxf(best, v);
+        }
+      sum += best;
+    }
+  out[img * (size_t)C * 36 + (size_t)c * 36 + bin] = sum / (float)((r1 - r0) * (q1 - q0));
+}
+
+// Linear layer y (M, N) = act(x (M, K) W^T + bias) on v_mfma_f32_32x32x2_f32: exact fp32, and
+// per output a k-ordered fmaf chain.  The summation order of an output depends on K alone:
+//   - K is padded with zeros to Kp (a multiple of 8) and cut into chunks of 256;
+//   - a chunk is one chain from zero: acc = fmaf(x[k], w[k], acc), k ascending;
+//   - wavefront v of the workgroup's four owns chunks v, v + 4, v + 8, ... and adds their sums
+//     in that order to its total (from zero);
+//   - the output is ((total0 + total1) + (total2 + total3)) + bias.
+// Neither M, the grid nor a row's place in its tile enters: rows of the A operand are
+// independent in the MFMA, so a batch gives the bits of its parts.
+//
+// A workgroup computes one tile of 32 rows of x by 32 rows of W, so W is streamed once per 32
+// images.  W is packed once (linear_pack_kernel) into the order the B fragments are read: tile
+// t = n / 32, then groups of 8 k, then lane l, then 4 floats = the lane's B operand of 4
+// consecutive MFMAs, k = 8 g + 2 e + (l >> 5), n = 32 t + (l & 31); one 16-byte load per lane
+// and 4 MFMAs, 1 KiB contiguous per wavefront.  x goes through LDS, 64 k at a time per
+// wavefront: read along k (256-byte runs), stored k-major with rows padded to 33 dwords, so that
+// the stores (bank 4 (l & 15) + (l >> 4) + const) and the per-MFMA reads (lane = row, two k)
+// are free of bank conflicts but for one pair.
+constexpr int LIN_SUB = 64, LIN_CHUNK = 256, LIN_LD = 33, LIN_WAVES = 4;
+typedef float cf32x16_t __attribute__((ext_vector_type(16)));
+
+__global__ void linear_pack_kernel(const float* __restrict__ W, int N, int K, int Kp, long total,
+                                   float* __restrict__ out) {
+  const int groups = Kp / 8;
+  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
+       idx += (long)gridDim.x * blockDim.x) {
+    const int e = (int)(idx & 3), l = (int)((idx >> 2) & 63);
+    const long tg = idx >> 8;
+    const int g = (int)(tg % groups), t = (int)(tg / groups);
+    const int n = t * 32 + (l & 31), k = g * 8 + 2 * e + (l >> 5);
+    out[idx] = (n < N && k < K) ? W[(long)n * K + k] : 0.f;
+  }
+}
+
+// VEC: K % 4 == 0, x rows are read as float4.  grid (ceil(N / 32), ceil(M / 32)).
+template <bool VEC>
+__global__ __launch_bounds__(256) void linear_mfma_kernel(const float* __restrict__ x,
+                                                          const float* __restrict__ Wp,
+                                                          const float* __restrict__ bias, int M,
+                                                          int K, int Kp, int N, int relu,
+                                                          float* __restrict__ y) {
+  __shared__ float lds[LIN_WAVES * LIN_SUB * LIN_LD];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int n0 = blockIdx.x * 32, m0 = blockIdx.y * 32;
+  float* xs = lds + wv * (LIN_SUB * LIN_LD);
+  const int groups = Kp / 8;
+  const cf32x4_t* wt =
+      reinterpret_cast<const cf32x4_t*>(Wp) + (size_t)blockIdx.x * groups * 64 + lane;
+  const int chunks = (Kp + LIN_CHUNK - 1) / LIN_CHUNK;
+  const int rounds = (chunks + LIN_WAVES - 1) / LIN_WAVES;
+  const int kq = lane & 15, rq = lane >> 4;   // staging: 16 lanes along k, 4 rows per pass
+  cf32x16_t total;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) total[i] = 0.f;
+  // One step = 64 k of this wavefront's chunk: step t is sub-step t & 3 of the chunk of round
+  // t >> 2.  The loads of step t + 1 (B operands and the x tile, in registers) are issued
+  // before the MFMAs of step t and waited for after them.  A step at or past Kp loads nothing
+  // and computes nothing (the same decision in all 64 lanes; every wavefront meets the barriers).
+  constexpr int SUBS = LIN_CHUNK / LIN_SUB;
+  const int steps = rounds * SUBS;
+  cf32x4_t wn[LIN_SUB / 8], xn[8];
+  auto fetch = [&](int t) {
+    const int k0 = ((t / SUBS) * LIN_WAVES + wv) * LIN_CHUNK + (t % SUBS) * LIN_SUB;
+    if (k0 >= Kp) return;
+#pragma unroll
+    for (int g = 0; g < LIN_SUB / 8; ++g) {
+      const int gi = k0 / 8 + g;
+      cf32x4_t w = {0.f, 0.f, 0.f, 0.f};
+      if (gi < groups) w = wt[(size_t)gi * 64];
+      wn[g] = w;
+    }
+    const int k = k0 + 4 * kq;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int m = m0 + rq + 4 * i;
+      cf32x4_t v = {0.f, 0.f, 0.f, 0.f};
+      if (m < M) {
+        const float* px = x + (size_t)m * K + k;
+        if constexpr (VEC) {
+          if (k < K) v = *reinterpret_cast<const cf32x4_t*>(px);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (k + e < K) v[e] = px[e];
+        }
+      }
+      xn[i] = v;
+    }
+  };
+  cf32x16_t acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  fetch(0);
+  for (int t = 0; t < steps; ++t) {
+    const bool live = ((t / SUBS) * LIN_WAVES + wv) * LIN_CHUNK + (t % SUBS) * LIN_SUB < Kp;
+    cf32x4_t wr[LIN_SUB / 8];
+    if (live) {
+#pragma unroll
+      for (int g = 0; g < LIN_SUB / 8; ++g) wr[g] = wn[g];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xs[(4 * kq + e) * LIN_LD + rq + 4 * i] = xn[i][e];
+    }
+    __syncthreads();
+    if (t + 1 < steps) fetch(t + 1);
+    if (live) {
+#pragma unroll
+      for (int p = 0; p < LIN_SUB / 2; ++p) {
+        const float a = xs[(2 * p + (lane >> 5)) * LIN_LD + (lane & 31)];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wr[p >> 2][p & 3], acc, 0, 0, 0);
+      }
+    }
+    __syncthreads();
+    if (t % SUBS == SUBS - 1) {   // the chunk is complete: into the total, and from zero again
+      total += acc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    }
+  }
+  // the four totals through LDS ([wavefront][register][lane]); wavefront v finishes registers
+  // 4 v .. 4 v + 3.  D layout: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+  float* red = lds;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) red[(wv * 16 + i) * 64 + lane] = total[i];
+  __syncthreads();
+  const int n = n0 + (lane & 31);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int i = wv * 4 + q;
+    const float s = (red[i * 64 + lane] + red[(16 + i) * 64 + lane]) +
+                    (red[(32 + i) * 64 + lane] + red[(48 + i) * 64 + lane]);
+    const int m = m0 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+    if (m < M && n < N) {
+      float v = s + (bias ? bias[n] : 0.f);
+      if (relu) v = v < 0.f ? 0.f : v;
+      y[(size_t)m * N + n] = v;
+    }
+  }
+}
+
+size_t linear_packed_floats(int N, int K) {
+  const size_t kp = ((size_t)K + 7) / 8 * 8;
+  return ((size_t)N + 31) / 32 * 32 * kp;
+}
+
+int linear_pack(const float* W, int N, int K, float* packed, hipStream_t s) {
+  MILAN_REQUIRE(W && packed && N >= 1 && K >= 1, MILAN_ERR_ARG, "linear_pack: bad argument");
+  const long total = (long)linear_packed_floats(N, K);
+  const long b = (total + 255) / 256;
+  hipLaunchKernelGGL(linear_pack_kernel, dim3((int)(b < 8192 ? b : 8192)), dim3(256), 0, s, W, N,
+                     K, (K + 7) / 8 * 8, total, packed);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+int linear_run(const float* x, const float* packed, const float* bias, int M, int K, int N,
+               bool relu, float* y, hipStream_t s) {
+  MILAN_REQUIRE(x && packed && y && M >= 1 && K >= 1 && N >= 1, MILAN_ERR_ARG,
+                "linear: bad argument");
+  const int mt = (M + 31) / 32;
+  MILAN_REQUIRE(mt <= 65535, MILAN_ERR_ARG, "linear: %d rows in one call", M);
+  const dim3 grid((N + 31) / 32, mt);
+  const int Kp = (K + 7) / 8 * 8;
+  if (K % 4 == 0 && ((uintptr_t)x & 15) == 0)
+    hipLaunchKernelGGL(linear_mfma_kernel<true>, grid, dim3(256), 0, s, x, packed, bias, M, K, Kp,
+                       N, relu ? 1 : 0, y);
+  else
+    hipLaunchKernelGGL(linear_mfma_kernel<false>, grid, dim3(256), 0, s, x, packed, bias, M, K,
+                       Kp, N, relu ? 1 : 0, y);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // weights and the ablation set
 // ---------------------------------------------------------------------------
 static bool resnet_trunk(const milan_ctx* c) {
   return c->d.trunk_kind == MILAN_TRUNK_BOTTLENECK || c->d.trunk_kind == MILAN_TRUNK_BASIC;
+}
+// an AlexNet context classifies once milan_set_alexnet_head has installed its three Linear
+// layers; until then it is refused as before
+static bool alex_trunk(const milan_ctx* c) {
+  return c->d.trunk_kind == MILAN_TRUNK_ALEXNET && c->ahead.installed;
+}
+static bool classifier_trunk(const milan_ctx* c) { return resnet_trunk(c) || alex_trunk(c); }
+static const char* level_names(const milan_ctx* c) {
+  return alex_trunk(c) ? "conv1..conv5" : "conv1, layer1..layer4";
 }
 static int level_channels(const milan_ctx* c, int level) {
   const int wd = c->d.trunk_width;
@@ -263,7 +489,7 @@ static int check_units(const milan_ctx* c, const int32_t* levels, const int32_t*
                        const char* what) {
   for (int i = 0; i < count; ++i) {
     MILAN_REQUIRE(levels[i] >= 0 && levels[i] <= 4, MILAN_ERR_ARG,
-                  "%s: level %d is not one of 0..4 (conv1, layer1..layer4)", what, levels[i]);
+                  "%s: level %d is not one of 0..4 (%s)", what, levels[i], level_names(c));
     MILAN_REQUIRE(units[i] >= 0 && units[i] < c->abl_ch[levels[i]], MILAN_ERR_INDEX,
                   "%s: index %d is out of bounds for level %d with %d units", what, units[i],
                   levels[i], c->abl_ch[levels[i]]);
@@ -273,7 +499,9 @@ static int check_units(const milan_ctx* c, const int32_t* levels, const int32_t*
 
 int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* units, int count,
                           hipStream_t s) {
-  MILAN_REQUIRE(resnet_trunk(c), MILAN_ERR_ARG, "unit ablation needs a ResNet trunk");
+  MILAN_REQUIRE(classifier_trunk(c), MILAN_ERR_ARG,
+                "unit ablation needs a ResNet trunk, or an AlexNet trunk whose head "
+                "milan_set_alexnet_head has installed");
   MILAN_REQUIRE(c->abl_mask != nullptr, MILAN_ERR_STATE, "encoder weights were not uploaded");
   MILAN_TRY(check_units(c, levels, units, count, "milan_set_ablation"));
   const int total = c->abl_off[4] + c->abl_ch[4];
@@ -344,7 +572,10 @@ static void cls_plan(const milan_ctx* c, int n, int H, int W, int sweep_units, i
   }
 }
 
+static size_t alex_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units);
+
 size_t classify_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
+  if (alex_trunk(c)) return alex_workspace(c, n_images, H, W, sweep_units);
   if (!resnet_trunk(c) || n_images <= 0 || H < 1 || W < 1) return 0;
   Arena a; a.dry = true;
   const int sub = encoder_sub_batch_size();
@@ -483,19 +714,320 @@ struct Walker {
   float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
+// ---------------------------------------------------------------------------
+// AlexNet driver: torchvision's alexnet_seq in eval mode.  Levels 0..4 are
+// conv1..conv5; a level's tensor is relu(conv + bias) * mask, the conv run with the encoder's
+// bias + ReLU epilogue and the mask kernels above (no launch for a level without units).
+// Level 0 is fp32 in both modes (3 input channels), levels 1..4 are split at scale 1 in the
+// split mode.  Every level has a buffer of its own, so the sweep holds a level where it is.
+// ---------------------------------------------------------------------------
+struct AlexClsPlan {
+  int h[5], w[5];     // conv1..conv5 outputs
+  int hq[3], wq[3];   // pool1, pool2, pool5
+  size_t lvl_sz[5];
+  float *in4, *a[5], *q[2], *work, *flat, *f6, *f7, *logits;
+  long long* preds;
+};
+
+static void alex_cls_plan(const milan_ctx* c, int n, int H, int W, int sweep_units, int n_total,
+                          Arena& a, AlexClsPlan* pl) {
+  pl->h[0] = cls_out(H, 11, 4, 2); pl->w[0] = cls_out(W, 11, 4, 2);
+  pl->hq[0] = cls_out(pl->h[0], 3, 2, 0); pl->wq[0] = cls_out(pl->w[0], 3, 2, 0);
+  pl->h[1] = pl->hq[0]; pl->w[1] = pl->wq[0];
+  pl->hq[1] = cls_out(pl->h[1], 3, 2, 0); pl->wq[1] = cls_out(pl->w[1], 3, 2, 0);
+  for (int l = 2; l < 5; ++l) { pl->h[l] = pl->hq[1]; pl->w[l] = pl->wq[1]; }
+  pl->hq[2] = cls_out(pl->h[4], 3, 2, 0); pl->wq[2] = cls_out(pl->w[4], 3, 2, 0);
+  size_t lvl_max = 0;
+  for (int l = 0; l < 5; ++l) {
+    // (an image too small for the trunk is refused before anything is carved: see alex_geometry)
+    pl->lvl_sz[l] = (size_t)std::max(pl->h[l], 0) * std::max(pl->w[l], 0) * c->abl_ch[l];
+    lvl_max = std::max(lvl_max, pl->lvl_sz[l]);
+  }
+  const milan_ctx::AlexHead& hd = c->ahead;
+  pl->preds = sweep_units > 0 ? a.get<long long>((size_t)sweep_units * n_total) : nullptr;
+  pl->in4 = a.get<float>((size_t)n * H * W * 4);
+  for (int l = 0; l < 5; ++l) pl->a[l] = a.get<float>((size_t)n * pl->lvl_sz[l]);
+  for (int l = 0; l < 2; ++l)
+    pl->q[l] = a.get<float>((size_t)n * std::max(pl->hq[l], 0) * std::max(pl->wq[l], 0) *
+                            c->abl_ch[l]);
+  pl->flat = a.get<float>((size_t)n * hd.in[0]);
+  pl->f6 = a.get<float>((size_t)n * hd.out[0]);
+  pl->f7 = a.get<float>((size_t)n * hd.out[1]);
+  pl->logits = a.get<float>((size_t)n * hd.out[2]);
+  pl->work = sweep_units > 0 ? a.get<float>((size_t)n * lvl_max) : nullptr;
+}
+
+static size_t alex_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
+  if (n_images <= 0 || H < 1 || W < 1) return 0;
+  Arena a; a.dry = true;
+  const int sub = encoder_sub_batch_size();
+  AlexClsPlan pl;
+  alex_cls_plan(c, n_images < sub ? n_images : sub, H, W, sweep_units < 0 ? 0 : sweep_units,
+                n_images, a, &pl);
+  return a.off;
+}
+
+struct AlexWalker {
+  milan_ctx* c;
+  const AlexClsPlan& pl;
+  int n;
+  bool split;
+  hipStream_t s;
+  int hin = 0, win = 0;
+  float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+
+  int mask(int level, const float* x, float* y, int extra) const {
+    const int C = c->abl_ch[level];
+    const long px = (long)n * pl.h[level] * pl.w[level];
+    const float* m = c->abl_mask + c->abl_off[level];
+    if (split && level > 0) {
+      const long groups = px * (C / 8);
+      hipLaunchKernelGGL(channel_mask_split_kernel, dim3(grid_for(groups)), dim3(256), 0, s, x, y,
+                         groups, C / 8, m, extra);
+    } else {
+      const long total4 = px * (C / 4);
+      hipLaunchKernelGGL(channel_mask_f32_kernel, dim3(grid_for(total4)), dim3(256), 0, s,
+                         (const cf32x4_t*)x, (cf32x4_t*)y, total4, C / 4, (const cf32x4_t*)m,
+                         extra);
+    }
+    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
+
+  // the masked level tensor -> tap[level], fp32 NCHW; every level is post-ReLU, and the split
+  // levels are stored at scale 1
+  int emit(int level, const float* x) const {
+    const int C = c->abl_ch[level], P = pl.h[level] * pl.w[level];
+    const dim3 grid((P + TAP_P - 1) / TAP_P, (C + TAP_C - 1) / TAP_C, n);
+    if (split && level > 0)
+      hipLaunchKernelGGL(tap_nchw_kernel<true>, grid, dim3(256), 0, s, x, P, C, 1.f, tap[level]);
+    else
+      hipLaunchKernelGGL(tap_nchw_kernel<false>, grid, dim3(256), 0, s, x, P, C, 1.f,
+                         tap[level]);
+    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
+
+  // Walker::walk's contract: from level `from` (-1: `src` = the images; otherwise `src` is that
+  // level's tensor, masked) up to and including level `to`
+  int walk(int from, int to, const float* src, const float** out) const {
+    const float* x = src;
+    int ho, wo;
+    if (from < 0) {
+      MILAN_TRY(launch_raw_input(src, n, hin, win, false, pl.in4, c->status, s));
+      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[0], pl.in4, n, hin, win, pl.a[0],
+                                              EPI_BIAS_RELU, nullptr, c->zero, &ho, &wo, false),
+                            s));
+      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, pl.a[0], pl.a[0], -1));
+      x = pl.a[0];
+      from = 0;
+      if (tap[0]) MILAN_TRY(emit(0, x));
+    }
+    for (int l = from + 1; l <= to; ++l) {
+      int h = pl.h[l - 1], w = pl.w[l - 1];
+      if (l <= 2) {
+        // pool1 / pool2 (level 0 is fp32; the pool writes the format conv2 / conv3 read)
+        MILAN_TRY(launch_maxpool3s2(x, n, h, w, c->abl_ch[l - 1], pl.hq[l - 1], pl.wq[l - 1],
+                                    split, split && l == 2, pl.q[l - 1], c->status, s));
+        x = pl.q[l - 1];
+        h = pl.hq[l - 1]; w = pl.wq[l - 1];
+      }
+      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[l], x, n, h, w, pl.a[l], EPI_BIAS_RELU,
+                                              nullptr, c->zero, &ho, &wo, split, false), s));
+      MILAN_REQUIRE(ho == pl.h[l] && wo == pl.w[l], MILAN_ERR_SHAPE,
+                    "internal: alexnet level %d geometry mismatch", l);
+      if (c->abl_count[l] > 0) MILAN_TRY(mask(l, pl.a[l], pl.a[l], -1));
+      x = pl.a[l];
+      if (tap[l]) MILAN_TRY(emit(l, x));
+    }
+    *out = x;
+    return 0;
+  }
+
+  // pool5 + adaptive average pool + flatten, fc6 / fc7 / linear8 (+ argmax) of the masked
+  // level-4 tensor; dropout is the identity in eval mode
+  int head(const float* x4, float* logits, long long* preds) const {
+    const milan_ctx::AlexHead& hd = c->ahead;
+    const int C = c->abl_ch[4];
+    const dim3 grid((36 * C + 255) / 256, n);
+    if (split)
+      hipLaunchKernelGGL(alex_tail_kernel<true>, grid, dim3(256), 0, s, x4, pl.h[4], pl.w[4], C,
+                         pl.hq[2], pl.wq[2], 1.f, pl.flat);
+    else
+      hipLaunchKernelGGL(alex_tail_kernel<false>, grid, dim3(256), 0, s, x4, pl.h[4], pl.w[4], C,
+                         pl.hq[2], pl.wq[2], 1.f, pl.flat);
+    MILAN_CHECK_HIP(hipGetLastError());
+    MILAN_TRY(linear_run(pl.flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, pl.f6, s));
+    MILAN_TRY(linear_run(pl.f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, pl.f7, s));
+    MILAN_TRY(linear_run(pl.f7, hd.w[2], hd.b[2], n, hd.in[2], hd.out[2], false, logits, s));
+    if (preds) {
+      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, logits, hd.out[2], preds);
+      MILAN_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+  }
+};
+
+// the smallest image leaves one pixel after pool5 (63 x 63)
+static int alex_geometry(const AlexClsPlan& pl, int H, int W) {
+  // (the three pools need 3 pixels each way: C's division rounds a negative extent to zero)
+  MILAN_REQUIRE(pl.h[0] >= 3 && pl.w[0] >= 3 && pl.h[1] >= 3 && pl.w[1] >= 3 && pl.h[4] >= 3 &&
+                    pl.w[4] >= 3,
+                MILAN_ERR_SHAPE, "classify: image %dx%d is too small for AlexNet (63x63 at least)",
+                H, W);
+  return 0;
+}
+
+// milan_classify (taps == nullptr: walk to level 4, then the head) and milan_activations
+// (taps[l] != nullptr for the requested levels, `top` the highest: no head) on AlexNet
+static int alex_run(milan_ctx* c, const float* images, int n, int H, int W, bool split,
+                    float* logits, int64_t* predictions, float* const* taps, int top,
+                    Arena& ws, hipStream_t s) {
+  const int sub = encoder_sub_batch_size();
+  for (int lo = 0; lo < n; lo += sub) {
+    const int cnt = n - lo < sub ? n - lo : sub;
+    Arena a = ws;  // every pass reuses the same scratch
+    AlexClsPlan pl;
+    alex_cls_plan(c, cnt, H, W, 0, 0, a, &pl);
+    MILAN_TRY(alex_geometry(pl, H, W));
+    MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
+                  "classify: workspace too small (%zu needed, %zu given)", a.off, a.size);
+    MILAN_REQUIRE(cnt <= 65535, MILAN_ERR_ARG, "classify: sub-batch of %d images", cnt);
+    AlexWalker wk{c, pl, cnt, split, s};
+    wk.hin = H; wk.win = W;
+    const float* x;
+    if (taps) {
+      for (int l = 0; l < 5; ++l)
+        if (taps[l]) wk.tap[l] = taps[l] + (size_t)lo * pl.lvl_sz[l];
+      MILAN_TRY(wk.walk(-1, top, images + (size_t)lo * 3 * H * W, &x));
+      continue;
+    }
+    MILAN_TRY(wk.walk(-1, 4, images + (size_t)lo * 3 * H * W, &x));
+    float* lg = logits ? logits + (size_t)lo * c->ahead.out[2] : pl.logits;
+    MILAN_TRY(wk.head(x, lg, predictions ? (long long*)predictions + lo : nullptr));
+  }
+  return 0;
+}
+
+static int alex_sweep(milan_ctx* c, const float* images, int n, int H, int W, bool split,
+                      const int32_t* levels, const int32_t* units, int count,
+                      const int64_t* targets, int32_t* correct, int64_t* predictions, Arena& ws,
+                      hipStream_t s) {
+  const int sub = encoder_sub_batch_size();
+  long long* preds_all = (long long*)predictions;
+  for (int lo = 0; lo < n; lo += sub) {
+    const int cnt = n - lo < sub ? n - lo : sub;
+    Arena a = ws;
+    AlexClsPlan pl;
+    alex_cls_plan(c, cnt, H, W, count, n, a, &pl);
+    MILAN_TRY(alex_geometry(pl, H, W));
+    MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
+                  "classify_sweep: workspace too small (%zu needed, %zu given)", a.off, a.size);
+    MILAN_REQUIRE(cnt <= 65535, MILAN_ERR_ARG, "classify_sweep: sub-batch of %d images", cnt);
+    if (preds_all == nullptr) preds_all = pl.preds;   // (the same address in every pass)
+    AlexWalker wk{c, pl, cnt, split, s};
+    wk.hin = H; wk.win = W;
+    // ascending levels: the walk to level L continues from the held level before it (the
+    // suffixes write levels above their own, and the working tensor, never a held one)
+    const float* held = images + (size_t)lo * 3 * H * W;
+    int at = -1;
+    for (int level = 0; level < 5; ++level) {
+      bool any = false;
+      for (int j = 0; j < count && !any; ++j) any = levels[j] == level;
+      if (!any) continue;
+      MILAN_TRY(wk.walk(at, level, held, &held));
+      at = level;
+      for (int j = 0; j < count; ++j) {
+        if (levels[j] != level) continue;
+        MILAN_TRY(wk.mask(level, held, pl.work, units[j]));
+        const float* x4;
+        MILAN_TRY(wk.walk(level, 4, pl.work, &x4));
+        MILAN_TRY(wk.head(x4, pl.logits, preds_all + (size_t)j * n + lo));
+      }
+    }
+  }
+  if (correct != nullptr) {
+    hipLaunchKernelGGL(correct_count_kernel, dim3(count), dim3(256), 0, s, preds_all,
+                       (const long long*)targets, n, correct);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// milan_set_alexnet_head: fc6 / fc7 / linear8 (device fp32, row-major (out, in)) packed into
+// library-owned memory; switches the classify family on for this AlexNet context
+int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
+                              const int* out, const int* in, hipStream_t s) {
+  MILAN_REQUIRE(c->d.trunk_kind == MILAN_TRUNK_ALEXNET, MILAN_ERR_ARG,
+                "milan_set_alexnet_head: the context's trunk is not AlexNet");
+  MILAN_REQUIRE(c->stem.w != nullptr, MILAN_ERR_STATE, "encoder weights were not uploaded");
+  const int c5 = c->alex[4].cout;
+  MILAN_REQUIRE(out[0] >= 1 && out[1] >= 1 && out[2] >= 1 && in[0] == c5 * 36 &&
+                    in[1] == out[0] && in[2] == out[1],
+                MILAN_ERR_SHAPE,
+                "milan_set_alexnet_head: fc6 (%d, %d), fc7 (%d, %d), linear8 (%d, %d) do not "
+                "chain from %d x 36 features",
+                out[0], in[0], out[1], in[1], out[2], in[2], c5);
+  milan_ctx::AlexHead& hd = c->ahead;
+  for (int i = 0; i < 3; ++i) {
+    // (a second call with the same widths reuses the first one's memory)
+    MILAN_REQUIRE(hd.w[i] == nullptr || (hd.out[i] == out[i] && hd.in[i] == in[i]),
+                  MILAN_ERR_STATE, "milan_set_alexnet_head: a head of other widths is installed");
+    if (hd.w[i] == nullptr) {
+      MILAN_TRY(dev_alloc(c, (void**)&hd.w[i], sizeof(float) * linear_packed_floats(out[i], in[i])));
+      MILAN_TRY(dev_alloc(c, (void**)&hd.b[i], sizeof(float) * (size_t)out[i]));
+    }
+    hd.out[i] = out[i]; hd.in[i] = in[i];
+    MILAN_TRY(linear_pack(w[i], out[i], in[i], hd.w[i], s));
+    MILAN_CHECK_HIP(hipMemcpyAsync(hd.b[i], b[i], sizeof(float) * (size_t)out[i],
+                                   hipMemcpyDeviceToDevice, s));
+  }
+  if (c->abl_mask == nullptr) {
+    int total = 0;
+    for (int l = 0; l < 5; ++l) {
+      c->abl_ch[l] = c->alex[l].cout;
+      c->abl_off[l] = total;
+      total += c->abl_ch[l];
+      c->abl_count[l] = 0;
+    }
+    MILAN_TRY(dev_alloc(c, (void**)&c->abl_mask, sizeof(float) * total));
+    hipLaunchKernelGGL(fill_ones_kernel, dim3((total + 255) / 256), dim3(256), 0, s, c->abl_mask,
+                       total);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  // (the caller's tensors may go once this returns)
+  MILAN_CHECK_HIP(hipStreamSynchronize(s));
+  c->fc_classes = out[2];
+  c->fc_in = in[2];
+  hd.installed = true;
+  return 0;
+}
+
+int linear_rowwise_run(const float* x, const float* W, const float* bias, int M, int K, int N,
+                       float* y, hipStream_t s) {
+  MILAN_REQUIRE(x && W && y && M >= 1 && M <= 65535 && K >= 1 && N >= 1, MILAN_ERR_ARG,
+                "linear_rowwise: bad argument");
+  hipLaunchKernelGGL(fc_kernel, dim3((N + 3) / 4, M), dim3(256), 0, s, x, W, bias, K, N, y);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // `head`: the call runs avgpool + fc (milan_activations stops before them and does not)
 static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool head = true) {
-  MILAN_REQUIRE(resnet_trunk(c), MILAN_ERR_ARG,
-                "classification needs a ResNet trunk (AlexNet's classifier is not built)");
+  MILAN_REQUIRE(classifier_trunk(c), MILAN_ERR_ARG,
+                "classification needs a ResNet trunk, or an AlexNet trunk whose head "
+                "milan_set_alexnet_head has installed (the Places365 AlexNet is not built)");
   MILAN_REQUIRE(c->stem.w != nullptr && c->abl_mask != nullptr, MILAN_ERR_STATE,
                 "encoder weights were not uploaded");
-  MILAN_REQUIRE(!head || c->fc_w != nullptr, MILAN_ERR_STATE,
+  MILAN_REQUIRE(!head || alex_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
                 "this context was created without fc.weight: it has no classifier head");
   MILAN_REQUIRE(!c->trunk_f16, MILAN_ERR_ARG,
                 "classification runs in the f32 and split_f16 modes, not in the fast f16 mode");
   MILAN_REQUIRE(n > 0 && H >= 1 && W >= 1, MILAN_ERR_SHAPE,
                 "classify: need n>0 and H,W>=1 (got n=%d H=%d W=%d)", n, H, W);
   bool sp = c->precision == MILAN_PRECISION_SPLIT_F16 && c->d.trunk_width % 8 == 0;
+  // (AlexNet: conv1 has 3 input channels and stays fp32, as in alexnet_run_batch)
+  for (int l = 1; l < 5 && sp && alex_trunk(c); ++l) sp = c->alex[l].ws != nullptr;
   for (int li = 0; li < 4 && sp; ++li)
     for (const Bottleneck& b : c->blocks[li])
       sp = sp && b.c1.ws && b.c2.ws && (b.basic || b.c3.ws) && (!b.has_down || b.down.ws);
@@ -507,6 +1039,8 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
                  int64_t* predictions, Arena& ws, hipStream_t s) {
   bool split;
   MILAN_TRY(classify_checks(c, n, H, W, &split));
+  if (alex_trunk(c))
+    return alex_run(c, images, n, H, W, split, logits, predictions, nullptr, 4, ws, s);
   const int sub = encoder_sub_batch_size();
   for (int lo = 0; lo < n; lo += sub) {
     const int cnt = n - lo < sub ? n - lo : sub;
@@ -532,6 +1066,9 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
   MILAN_TRY(classify_checks(c, n, H, W, &split));
   MILAN_TRY(check_units(c, levels, units, count, "milan_classify_sweep"));
   if (count == 0) return 0;
+  if (alex_trunk(c))
+    return alex_sweep(c, images, n, H, W, split, levels, units, count, targets, correct,
+                      predictions, ws, s);
   const int sub = encoder_sub_batch_size();
   long long* preds_all = (long long*)predictions;
   for (int lo = 0; lo < n; lo += sub) {
@@ -589,14 +1126,20 @@ int activations_run(milan_ctx* c, const float* images, int n, int H, int W, cons
   int slot[5] = {-1, -1, -1, -1, -1}, top = -1;
   for (int i = 0; i < count; ++i) {
     MILAN_REQUIRE(levels[i] >= 0 && levels[i] <= 4, MILAN_ERR_ARG,
-                  "milan_activations: level %d is not one of 0..4 (conv1, layer1..layer4)",
-                  levels[i]);
+                  "milan_activations: level %d is not one of 0..4 (%s)", levels[i],
+                  level_names(c));
     MILAN_REQUIRE(slot[levels[i]] < 0, MILAN_ERR_ARG,
                   "milan_activations: level %d is requested twice", levels[i]);
     MILAN_REQUIRE(outputs[i] != nullptr, MILAN_ERR_ARG,
                   "milan_activations: outputs[%d] is null", i);
     slot[levels[i]] = i;
     top = std::max(top, (int)levels[i]);
+  }
+  if (alex_trunk(c)) {
+    float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int l = 0; l < 5; ++l)
+      if (slot[l] >= 0) taps[l] = outputs[slot[l]];
+    return alex_run(c, images, n, H, W, split, nullptr, nullptr, taps, top, ws, s);
   }
   const int sub = encoder_sub_batch_size();
   for (int lo = 0; lo < n; lo += sub) {

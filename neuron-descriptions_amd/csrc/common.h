@@ -602,6 +602,14 @@ struct milan_ctx {
   int fc_classes = 0, fc_in = 0;
   float* abl_mask = nullptr;
   int abl_off[5] = {0, 0, 0, 0, 0}, abl_ch[5] = {0, 0, 0, 0, 0}, abl_count[5] = {0, 0, 0, 0, 0};
+  // AlexNet head (milan_set_alexnet_head; `installed` switches the classify family on for an
+  // AlexNet context): fc6 / fc7 / linear8 in linear_mfma_kernel's packed order, biases as given
+  struct AlexHead {
+    bool installed = false;
+    float* w[3] = {nullptr, nullptr, nullptr};
+    float* b[3] = {nullptr, nullptr, nullptr};
+    int out[3] = {0, 0, 0}, in[3] = {0, 0, 0};
+  } ahead;
 };
 
 namespace milan {
@@ -633,7 +641,11 @@ int encoder_run(milan_ctx* c, const void* images, int image_dtype,
 int encoder_sub_batch_size();
 GemmArgs encoder_conv_args(const ConvW& cw, const float* in, int n, int H, int W, float* out,
                            int epi, const float* aux, const float* zero, int* Ho, int* Wo,
-                           bool split);
+                           bool split, bool scaled_bias = true);
+// 3x3 / stride 2 max-pool without padding over NHWC (the AlexNet trunk): fp32 -> fp32, or with
+// `split` fp32 / split (`in_split`) -> split at scale 1
+int launch_maxpool3s2(const float* x, int n, int H, int W, int C, int Ho, int Wo, bool split,
+                      bool in_split, float* y, unsigned* status, hipStream_t s);
 int launch_raw_input(const float* images, int n, int H, int W, bool pairs, float* out,
                      unsigned* status, hipStream_t s);
 GemmArgs encoder_stem_args(const milan_ctx* c, const float* in4, int n, int H, int W, float* raw,
@@ -650,6 +662,16 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
 int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
                    const int32_t* units, int count, const int64_t* targets, int32_t* correct,
                    int64_t* predictions, Arena& ws, hipStream_t s);
+int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
+                              const int* out, const int* in, hipStream_t s);
+// y (M, N) = act(x (M, K) W^T + bias) on the fp32 MFMA; `packed` from linear_pack
+size_t linear_packed_floats(int N, int K);
+int linear_pack(const float* W, int N, int K, float* packed, hipStream_t s);
+int linear_run(const float* x, const float* packed, const float* bias, int M, int K, int N,
+               bool relu, float* y, hipStream_t s);
+// the ResNet head's fc_kernel on caller-supplied operands (a measurement baseline)
+int linear_rowwise_run(const float* x, const float* W, const float* bias, int M, int K, int N,
+                       float* y, hipStream_t s);
 size_t activations_workspace(const milan_ctx* c, int n, int H, int W);
 int activations_run(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
                     int count, float* const* outputs, Arena& ws, hipStream_t s);

@@ -2211,8 +2211,8 @@ int encoder_sub_batch_size() { return encoder_sub_batch(); }
 
 GemmArgs encoder_conv_args(const ConvW& cw, const float* in, int n, int H, int W, float* out,
                            int epi, const float* aux, const float* zero, int* Ho, int* Wo,
-                           bool split) {
-  return conv_args(cw, in, n, H, W, out, epi, aux, zero, Ho, Wo, split);
+                           bool split, bool scaled_bias) {
+  return conv_args(cw, in, n, H, W, out, epi, aux, zero, Ho, Wo, split, scaled_bias);
 }
 
 // (n,3,H,W) float NCHW, taken as it is (mean 0, std 1: (v - 0) / 1 is v) -> NHWC4 fp32, or
@@ -2374,6 +2374,24 @@ __global__ void maxpool3s2_split_kernel(const float* __restrict__ x, int n, int 
     *reinterpret_cast<f32x4_t*>(d + 4) = lo4;
   }
   report_saturation(status, sat);
+}
+
+// alexnet_run_batch's `maxpool`, for classify.hip's AlexNet walker
+int launch_maxpool3s2(const float* x, int n, int H, int W, int C, int Ho, int Wo, bool split,
+                      bool in_split, float* y, unsigned* status, hipStream_t s) {
+  const long total = (long)n * Ho * Wo * (C / (split ? 8 : 4));
+  const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+  if (!split)
+    hipLaunchKernelGGL(maxpool3s2_f32_kernel, dim3(blocks), dim3(256), 0, s, (const float4*)x, n,
+                       H, W, C / 4, Ho, Wo, 0, (float4*)y);
+  else if (in_split)
+    hipLaunchKernelGGL(maxpool3s2_split_kernel<true>, dim3(blocks), dim3(256), 0, s, x, n, H, W,
+                       C, Ho, Wo, 0, y, status);
+  else
+    hipLaunchKernelGGL(maxpool3s2_split_kernel<false>, dim3(blocks), dim3(256), 0, s, x, n, H, W,
+                       C, Ho, Wo, 0, y, status);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 struct AlexPlan {

@@ -6,14 +6,17 @@ Same surface -- `zero`, `ablated`, `ImageClassifier` with `forward` / `fit` / `p
 experiment (`experiments/edit.py:295-301`) as one call.
 
 Two kinds of model:
-  - a `classifiers.ResNetClassifier`: in eval mode under `no_grad` on the GPU the ablation
+  - a `classifiers.ResNetClassifier` or `classifiers.AlexNetClassifier` (a
+    `classifiers.NativeClassifier`): in eval mode under `no_grad` on the GPU the ablation
     set is installed in libmilan_hip (`hip.Context.set_ablation`) and the forward runs there;
     in training mode the same set acts through forward hooks on the torch path;
   - any other `nn.Module`: the named modules' outputs are edited through forward hooks, what
     the reference does with nethook's `InstrumentedModel.edit_layer`.
 
-Not built: AlexNet and its `fc6` / `fc7` / `linear8` layers, which `experiments/edit.py`
-also offers.  One deliberate difference: `fit` keeps a COPY of the best state (the
+Both CNNs of `experiments/edit.py --cnn` are built; `zero` refuses 2-D features, so
+AlexNet's `fc6` / `fc7` are trained (`fit(layers=...)`) but never edited.  Not built: the
+Places365 AlexNet of `src/deps/alexnet.py` (grouped convs, an unpadded conv1, `fc8`), a
+different network.  One deliberate difference: `fit` keeps a COPY of the best state (the
 reference keeps `self.state_dict()`, whose tensors alias the live parameters, so its
 restore on early stopping restores nothing).
 """
@@ -95,15 +98,15 @@ def ablated(model: nn.Module,
     edits: Dict[str, List[int]] = collections.defaultdict(list)
     for layer, unit in units:
         edits[str(layer)].append(unit)
-    native = isinstance(model, classifiers.ResNetClassifier)
+    native = isinstance(model, classifiers.NativeClassifier)
     if native:
         for layer in edits:
             if layer not in model.layers:
-                raise ValueError(f'Layer {layer} not found in model: a ResNetClassifier '
-                                 f'is edited at {model.layers}')
+                raise ValueError(f'Layer {layer} not found in model: a '
+                                 f'{type(model).__name__} is edited at {model.layers}')
         if rule is not zero and not model.training:
             raise ValueError('only the `zero` rule has a kernel: a custom rule cannot '
-                             'edit a ResNetClassifier in eval mode')
+                             f'edit a {type(model).__name__} in eval mode')
     retain = _Retain(model, {layer: rule(sorted(uns)) for layer, uns in edits.items()})
     if native:
         saved = (model._ablation, model._ablation_native)
@@ -313,7 +316,7 @@ class ImageClassifier(nn.Module):
 
             [self.accuracy(dataset, ablate=[*(ablate or []), u]) for u in units]
 
-        the loop of `experiments/edit.py:295-301`.  On a `ResNetClassifier` on the GPU every
+        the loop of `experiments/edit.py:295-301`.  On a `NativeClassifier` on the GPU every
         batch goes through `hip.Context.classify_sweep`: all units of one layer share the
         forward pass up to that layer, and the numbers are those of the loop, bit for bit.
         Any other model runs the loop itself.
@@ -322,7 +325,7 @@ class ImageClassifier(nn.Module):
         if device is not None:
             self.to(device)
         model = self.model
-        native = (isinstance(model, classifiers.ResNetClassifier) and
+        native = (isinstance(model, classifiers.NativeClassifier) and
                   next(model.parameters()).device.type == 'cuda')
         if not native:
             return [
@@ -338,8 +341,8 @@ class ImageClassifier(nn.Module):
             ]
         for layer, _ in units:
             if str(layer) not in model.layers:
-                raise ValueError(f'Layer {layer} not found in model: a ResNetClassifier '
-                                 f'is edited at {model.layers}')
+                raise ValueError(f'Layer {layer} not found in model: a '
+                                 f'{type(model).__name__} is edited at {model.layers}')
         size = len(cast(Sized, dataset))
         loader = _progress(
             data.DataLoader(dataset, num_workers=num_workers, batch_size=batch_size),

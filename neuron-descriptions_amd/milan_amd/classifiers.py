@@ -1,5 +1,13 @@
 """Image classifiers whose eval-mode forward runs on the HIP trunk.
 
+`ResNetClassifier` and `AlexNetClassifier` are the two CNNs `experiments/edit.py --cnn`
+offers.  `AlexNetClassifier` has the module tree of the reference's `alexnet_seq`
+(`src/deps/ext/torchvision/models.py`: `conv1 .. conv5`, `fc6`, `fc7`, `linear8`), so a
+checkpoint that experiment saved loads with `load_state_dict` and
+`ImageClassifier.fit(layers=['fc6', 'fc7', 'linear8'])` finds its layers; it is edited and
+tapped at `conv1 .. conv5`.  The Places365 AlexNet of `src/deps/alexnet.py` (grouped convs,
+an unpadded conv1, `fc8`) is a different network and is not built.
+
 `ResNetClassifier` is the CNN the reference's experiments dissect and edit
 (`experiments/analyze.py`, `experiments/edit.py`: a torchvision ResNet handed to
 `src/utils/ablations.ImageClassifier`).  It is an `nn.Module` with torchvision's module
@@ -23,6 +31,7 @@ from torch import nn
 from milan_amd import hip, synthetic
 
 LAYERS = ('conv1', 'layer1', 'layer2', 'layer3', 'layer4')
+ALEXNET_LAYERS = ('conv1', 'conv2', 'conv3', 'conv4', 'conv5')
 
 
 class _BasicBlock(nn.Module):
@@ -70,55 +79,15 @@ class _Bottleneck(nn.Module):
         return self.relu(out + identity)
 
 
-class ResNetClassifier(nn.Module):
-    """torchvision-shaped ResNet (v1.5 blocks) with a native eval-mode forward.
+class NativeClassifier(nn.Module):
+    """What the classifiers with a HIP forward share: the choice between the two forwards,
+    the taps, the context cache and the ablation set `ablations.ablated` installs.  A
+    subclass sets `layers`, calls `_init_native` last in its `__init__`, and provides
+    `forward_eager` and `_make_context`."""
 
-    `config`: 'resnet18' / 'resnet34' (basic blocks) or 'resnet50' / 'resnet101' /
-    'resnet152' (bottlenecks); `width` 64 is torchvision's.  `precision`: 'auto' (split-f16
-    with an exact-fp32 rerun of a call that saturated), 'split_f16' or 'f32'.  Weights start
-    as `nn.Conv2d` / `nn.Linear` leave them; load a checkpoint with `load_state_dict`.
-    """
+    layers: Tuple[str, ...] = ()
 
-    layers: Tuple[str, ...] = LAYERS
-
-    def __init__(self,
-                 config: str = 'resnet18',
-                 num_classes: int = 1000,
-                 width: int = 64,
-                 precision: str = 'auto'):
-        super().__init__()
-        if config not in synthetic.RESNET_BLOCKS:
-            raise ValueError(f'classifier not supported: {config} (AlexNet and its '
-                             'fc6 / fc7 / linear8 layers are not built)')
-        if precision not in ('auto', 'split_f16', 'f32'):
-            raise ValueError(f'unknown precision: {precision}')
-        self.config = config
-        self.blocks = synthetic.RESNET_BLOCKS[config]
-        self.width = int(width)
-        self.num_classes = int(num_classes)
-        self.precision = precision
-        block = _BasicBlock if config in synthetic.BASIC_BLOCK_CONFIGS else _Bottleneck
-        self.conv1 = nn.Conv2d(3, width, 7, 2, 3, bias=False)
-        self.bn1 = nn.BatchNorm2d(width)
-        self.relu = nn.ReLU(inplace=True)
-        self.maxpool = nn.MaxPool2d(3, 2, 1)
-        inplanes = width
-        for li, count in enumerate(self.blocks):
-            planes = width * 2**li
-            stage = []
-            for bi in range(count):
-                stride = 2 if (bi == 0 and li > 0) else 1
-                downsample = None
-                if stride != 1 or inplanes != planes * block.expansion:
-                    downsample = nn.Sequential(
-                        nn.Conv2d(inplanes, planes * block.expansion, 1, stride,
-                                  bias=False),
-                        nn.BatchNorm2d(planes * block.expansion))
-                stage.append(block(inplanes, planes, stride, downsample))
-                inplanes = planes * block.expansion
-            setattr(self, f'layer{li + 1}', nn.Sequential(*stage))
-        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
-        self.fc = nn.Linear(inplanes, num_classes)
+    def _init_native(self) -> None:
         self._ctx: Optional[hip.Context] = None
         self._ctx_key = None
         # the set `ablations.ablated` installed: (layer, unit) pairs for the native path
@@ -128,12 +97,11 @@ class ResNetClassifier(nn.Module):
         self._ablation_native = True
         self._ctx_ablation = None
 
-    # -- the two forwards -----------------------------------------------------------
     def forward_eager(self, images: torch.Tensor) -> torch.Tensor:
-        """torchvision's `ResNet._forward_impl` on this module's own parameters."""
-        x = self.maxpool(self.relu(self.bn1(self.conv1(images))))
-        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        return self.fc(torch.flatten(self.avgpool(x), 1))
+        raise NotImplementedError
+
+    def _make_context(self, device: torch.device) -> hip.Context:
+        raise NotImplementedError
 
     def runs_natively(self, images: torch.Tensor) -> bool:
         return (not self.training and not torch.is_grad_enabled() and
@@ -185,14 +153,12 @@ class ResNetClassifier(nn.Module):
 
     # -- HIP context, rebuilt when device or weights change ---------------------------
     def _context(self) -> hip.Context:
-        device = hip.require_device(self.fc.weight.device)
+        device = hip.require_device(next(self.parameters()).device)
         tensors = list(self.parameters()) + list(self.buffers())
         key = (device, tuple(t._version for t in tensors),
                tuple(t.data_ptr() for t in tensors))
         if self._ctx is None or self._ctx_key != key:
-            sd = {'encoder.encoder.model.' + k: v for k, v in self.state_dict().items()}
-            dims = hip.make_dims(sd, 1, blocks=self.blocks)
-            self._ctx = hip.Context(dims, sd, device)
+            self._ctx = self._make_context(device)
             if self.precision == 'auto':
                 self._ctx.set_precision('split_f16')
                 self._ctx.on_saturation = 'f32'
@@ -218,3 +184,136 @@ class ResNetClassifier(nn.Module):
     def classify_sweep(self, images: torch.Tensor, units, targets=None):
         """`hip.Context.classify_sweep` under this module's current ablation set."""
         return self._native_context().classify_sweep(images, list(units), targets)
+
+
+class ResNetClassifier(NativeClassifier):
+    """torchvision-shaped ResNet (v1.5 blocks) with a native eval-mode forward.
+
+    `config`: 'resnet18' / 'resnet34' (basic blocks) or 'resnet50' / 'resnet101' /
+    'resnet152' (bottlenecks); `width` 64 is torchvision's.  `precision`: 'auto' (split-f16
+    with an exact-fp32 rerun of a call that saturated), 'split_f16' or 'f32'.  Weights start
+    as `nn.Conv2d` / `nn.Linear` leave them; load a checkpoint with `load_state_dict`.
+    """
+
+    layers: Tuple[str, ...] = LAYERS
+
+    def __init__(self,
+                 config: str = 'resnet18',
+                 num_classes: int = 1000,
+                 width: int = 64,
+                 precision: str = 'auto'):
+        super().__init__()
+        if config not in synthetic.RESNET_BLOCKS:
+            raise ValueError(f'classifier not supported: {config} (AlexNet is '
+                             '`AlexNetClassifier`)')
+        if precision not in ('auto', 'split_f16', 'f32'):
+            raise ValueError(f'unknown precision: {precision}')
+        self.config = config
+        self.blocks = synthetic.RESNET_BLOCKS[config]
+        self.width = int(width)
+        self.num_classes = int(num_classes)
+        self.precision = precision
+        block = _BasicBlock if config in synthetic.BASIC_BLOCK_CONFIGS else _Bottleneck
+        self.conv1 = nn.Conv2d(3, width, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        inplanes = width
+        for li, count in enumerate(self.blocks):
+            planes = width * 2**li
+            stage = []
+            for bi in range(count):
+                stride = 2 if (bi == 0 and li > 0) else 1
+                downsample = None
+                if stride != 1 or inplanes != planes * block.expansion:
+                    downsample = nn.Sequential(
+                        nn.Conv2d(inplanes, planes * block.expansion, 1, stride,
+                                  bias=False),
+                        nn.BatchNorm2d(planes * block.expansion))
+                stage.append(block(inplanes, planes, stride, downsample))
+                inplanes = planes * block.expansion
+            setattr(self, f'layer{li + 1}', nn.Sequential(*stage))
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Linear(inplanes, num_classes)
+        self._init_native()
+
+    # -- the two forwards -----------------------------------------------------------
+    def forward_eager(self, images: torch.Tensor) -> torch.Tensor:
+        """torchvision's `ResNet._forward_impl` on this module's own parameters."""
+        x = self.maxpool(self.relu(self.bn1(self.conv1(images))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+    def _make_context(self, device: torch.device) -> hip.Context:
+        sd = {'encoder.encoder.model.' + k: v for k, v in self.state_dict().items()}
+        dims = hip.make_dims(sd, 1, blocks=self.blocks)
+        return hip.Context(dims, sd, device)
+
+
+class AlexNetClassifier(NativeClassifier):
+    """The reference's `alexnet_seq` (torchvision's AlexNet as one `nn.Sequential`-shaped
+    tree) with a native eval-mode forward.
+
+    Named children, in order: conv1, relu1, pool1, conv2, relu2, pool2, conv3, relu3, conv4,
+    relu4, conv5, relu5, pool5, avgpool, flatten, dropout6, fc6, relu6, dropout7, fc7, relu7,
+    linear8.  Channels are `width` x (1, 3, 6, 4, 4); `width` 64 and `hidden` 4096 are
+    torchvision's.  `precision` as for `ResNetClassifier`.  Edited and tapped at
+    `layers` = conv1 .. conv5: a conv's output is followed by an in-place ReLU, so what the
+    next layer reads, and what a retain hook sees, is relu(conv + bias) x mask.  Images of at
+    least 63 x 63.
+    """
+
+    layers: Tuple[str, ...] = ALEXNET_LAYERS
+
+    def __init__(self,
+                 num_classes: int = 1000,
+                 width: int = 64,
+                 hidden: int = 4096,
+                 precision: str = 'auto'):
+        super().__init__()
+        if precision not in ('auto', 'split_f16', 'f32'):
+            raise ValueError(f'unknown precision: {precision}')
+        self.width = int(width)
+        self.hidden = int(hidden)
+        self.num_classes = int(num_classes)
+        self.precision = precision
+        ch = [c * self.width for c in synthetic.ALEXNET_CHANNELS]
+        self.conv1 = nn.Conv2d(3, ch[0], 11, 4, 2)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.pool1 = nn.MaxPool2d(3, 2)
+        self.conv2 = nn.Conv2d(ch[0], ch[1], 5, 1, 2)
+        self.relu2 = nn.ReLU(inplace=True)
+        self.pool2 = nn.MaxPool2d(3, 2)
+        self.conv3 = nn.Conv2d(ch[1], ch[2], 3, 1, 1)
+        self.relu3 = nn.ReLU(inplace=True)
+        self.conv4 = nn.Conv2d(ch[2], ch[3], 3, 1, 1)
+        self.relu4 = nn.ReLU(inplace=True)
+        self.conv5 = nn.Conv2d(ch[3], ch[4], 3, 1, 1)
+        self.relu5 = nn.ReLU(inplace=True)
+        self.pool5 = nn.MaxPool2d(3, 2)
+        self.avgpool = nn.AdaptiveAvgPool2d((6, 6))
+        self.flatten = nn.Flatten()
+        self.dropout6 = nn.Dropout()
+        self.fc6 = nn.Linear(ch[4] * 36, self.hidden)
+        self.relu6 = nn.ReLU(inplace=True)
+        self.dropout7 = nn.Dropout()
+        self.fc7 = nn.Linear(self.hidden, self.hidden)
+        self.relu7 = nn.ReLU(inplace=True)
+        self.linear8 = nn.Linear(self.hidden, self.num_classes)
+        self._init_native()
+
+    def forward_eager(self, images: torch.Tensor) -> torch.Tensor:
+        """`alexnet_seq`'s forward: the named children in order."""
+        x = images
+        for module in self.children():
+            x = module(x)
+        return x
+
+    def _make_context(self, device: torch.device) -> hip.Context:
+        sd = {}
+        for conv, index in zip(self.layers, (0, 3, 6, 8, 10)):
+            module = getattr(self, conv)
+            sd[f'encoder.encoder.model.features.{index}.weight'] = module.weight
+            sd[f'encoder.encoder.model.features.{index}.bias'] = module.bias
+        head = [t for fc in (self.fc6, self.fc7, self.linear8) for t in (fc.weight, fc.bias)]
+        return hip.Context(hip.make_dims(sd, 1), sd, device, alexnet_head=head)

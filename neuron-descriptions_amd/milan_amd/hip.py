@@ -153,6 +153,12 @@ SIGNATURES = {
         (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _SZ, _P]),
     'milan_activations_workspace_bytes': (_SZ, [_P, _I, _I, _I]),
     'milan_activations': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
+    'milan_set_alexnet_head':
+        (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P]),
+    'milan_linear_packed_bytes': (_SZ, [_I, _I]),
+    'milan_linear_pack': (_I, [_P, _I, _I, _P, _P]),
+    'milan_linear': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    'milan_linear_rowwise': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     'milan_set_graph_capture': (_I, [_P, _I]),
     'milan_graph_stats': (_I, [
         _P, ctypes.POINTER(ctypes.c_longlong),
@@ -272,7 +278,8 @@ PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_get_beam_path', 'milan_set_ablation',
           'milan_classify_workspace_bytes', 'milan_classify',
           'milan_classify_sweep', 'milan_activations_workspace_bytes',
-          'milan_activations')
+          'milan_activations', 'milan_set_alexnet_head', 'milan_linear_packed_bytes',
+          'milan_linear_pack', 'milan_linear', 'milan_linear_rowwise')
 
 _lib = None
 
@@ -418,9 +425,11 @@ class Context:
     """Owns one `milan_ctx` (packed weights on one GPU) plus a workspace."""
 
     def __init__(self, dims: Dims, state_dict: Dict[str, torch.Tensor],
-                 device: torch.device, finalize: bool = True):
+                 device: torch.device, finalize: bool = True,
+                 alexnet_head: Optional[Sequence[torch.Tensor]] = None):
         """`finalize=False`: a context that only carries `dims` (no weights,
-        no packed arena) -- what the LM training calls need."""
+        no packed arena) -- what the LM training calls need.  `alexnet_head`: the six
+        tensors of `set_alexnet_head`, installed once the weights are finalized."""
         self.lib = load_library()
         self.device = require_device(device)
         self.dims = dims
@@ -468,6 +477,8 @@ class Context:
             self.on_saturation = 'f32'
         elif default:
             self.set_precision(default)
+        if alexnet_head is not None:
+            self.set_alexnet_head(*alexnet_head)
 
     # -- hipGraph replay of the decode stage ------------------------------------
     def enable_graphs(self, enable: bool = True) -> None:
@@ -871,8 +882,37 @@ class Context:
 
         return self._guarded('encode_spatial', run, check)
 
-    # -- unit ablation and classification (ResNet trunks with an `fc` head) -----------
+    # -- unit ablation and classification (ResNet trunks with an `fc` head; AlexNet once
+    # `set_alexnet_head` has installed fc6 / fc7 / linear8) ----------------------------
     ABLATION_LEVELS = ('conv1', 'layer1', 'layer2', 'layer3', 'layer4')
+    ALEXNET_LEVELS = ('conv1', 'conv2', 'conv3', 'conv4', 'conv5')
+
+    @property
+    def ablation_levels(self) -> Tuple[str, ...]:
+        """The names of levels 0..4 on this context's trunk."""
+        if self.dims.trunk_kind == TRUNK_ALEXNET:
+            return self.ALEXNET_LEVELS
+        return self.ABLATION_LEVELS
+
+    def set_alexnet_head(self, fc6_weight, fc6_bias, fc7_weight, fc7_bias, linear8_weight,
+                         linear8_bias) -> None:
+        """Install `alexnet_seq`'s three Linear layers on an AlexNet context (weights (out, in),
+        biases (out,)): from then on `set_ablation`, `classify`, `classify_sweep` and
+        `activations` accept it, with levels 'conv1'..'conv5'.  The library keeps packed
+        copies.  The widths must chain from conv5's channels x 36 (ValueError)."""
+        fn = self._need('milan_set_alexnet_head')
+        tensors = [_dev(t.detach(), self.device, torch.float32)
+                   for t in (fc6_weight, fc6_bias, fc7_weight, fc7_bias, linear8_weight,
+                             linear8_bias)]
+        args = []
+        for weight, bias in zip(tensors[0::2], tensors[1::2]):
+            if weight.dim() != 2 or tuple(bias.shape) != (weight.shape[0],):
+                raise ValueError(f'a Linear layer needs weight (out, in) and bias (out,), got '
+                                 f'{tuple(weight.shape)} and {tuple(bias.shape)}')
+            args += [weight.data_ptr(), bias.data_ptr(), weight.shape[0], weight.shape[1]]
+        with torch.cuda.device(self.device):
+            _check(fn(self._h, *args, _stream(self.device)))
+        self.num_classes = int(tensors[4].shape[0])
 
     def _need(self, name: str):
         if not hasattr(self.lib, name):
@@ -884,10 +924,10 @@ class Context:
         levels, units = [], []
         for level, unit in pairs:
             if isinstance(level, str):
-                if level not in self.ABLATION_LEVELS:
+                if level not in self.ablation_levels:
                     raise ValueError(f'layer {level!r} cannot be ablated natively; the '
-                                     f'layers are {self.ABLATION_LEVELS}')
-                level = self.ABLATION_LEVELS.index(level)
+                                     f'layers are {self.ablation_levels}')
+                level = self.ablation_levels.index(level)
             levels.append(int(level))
             units.append(int(unit))
         count = len(levels)
@@ -895,8 +935,9 @@ class Context:
                 (ctypes.c_int32 * max(1, count))(*units), count)
 
     def set_ablation(self, pairs=()) -> None:
-        """Install the set of (level, unit) pairs the classify calls zero (level 0..4 or
-        'conv1', 'layer1'..'layer4'); an empty sequence clears it.  Duplicates and order do
+        """Install the set of (level, unit) pairs the classify calls zero (level 0..4 or its
+        name in `ablation_levels`: 'conv1', 'layer1'..'layer4' on a ResNet, 'conv1'..'conv5'
+        on AlexNet); an empty sequence clears it.  Duplicates and order do
         not matter.  `encode*` / `describe` never read it.  Synchronises the stream."""
         fn = self._need('milan_set_ablation')
         levels, units, count = self._unit_arrays(pairs)
@@ -975,9 +1016,10 @@ class Context:
     def activations(self, images: torch.Tensor, levels, check: bool = True) -> dict:
         """The tensors of the requested edit points under the current ablation set, after
         its masks: {level as given: (n, C, h, w) float32 NCHW}.  `levels`: distinct entries,
-        each 0..4 or 'conv1', 'layer1'..'layer4', in any order.  One walk of the trunk up to
+        each 0..4 or a name of `ablation_levels`, in any order.  One walk of the trunk up to
         the highest level; no head runs (a state dict without `fc` will do).  Level 0 is the
-        raw conv1 output, before bn1 / ReLU / maxpool."""
+        raw conv1 output, before bn1 / ReLU / maxpool, on a ResNet; on AlexNet every level
+        is relu(conv + bias) x mask."""
         fn = self._need('milan_activations')
         images = self._classify_images(images)
         n, _, h, w = images.shape
@@ -987,10 +1029,10 @@ class Context:
         idx = []
         for level in keys:
             if isinstance(level, str):
-                if level not in self.ABLATION_LEVELS:
+                if level not in self.ablation_levels:
                     raise ValueError(f'layer {level!r} has no native tap; the layers are '
-                                     f'{self.ABLATION_LEVELS}')
-                level = self.ABLATION_LEVELS.index(level)
+                                     f'{self.ablation_levels}')
+                level = self.ablation_levels.index(level)
             idx.append(int(level))
         ws = self._classify_ws(
             n, h, w, need=int(self._need('milan_activations_workspace_bytes')(self._h, n, h, w)))
@@ -1000,6 +1042,15 @@ class Context:
         for level in idx:
             if not 0 <= level <= 4:  # (the library reports it; the shape is a placeholder)
                 outs.append(torch.empty(1, dtype=torch.float32, device=self.device))
+                continue
+            if self.dims.trunk_kind == TRUNK_ALEXNET:
+                # conv1 11x11/4 pad 2; pool1, pool2 3x3/2 before conv2, conv3; the rest keep
+                hl, wl = (h + 4 - 11) // 4 + 1, (w + 4 - 11) // 4 + 1
+                for _ in range(min(level, 2)):
+                    hl, wl = (hl - 3) // 2 + 1, (wl - 3) // 2 + 1
+                ch = self.dims.trunk_width * (1, 3, 6, 4, 4)[level]
+                outs.append(torch.empty(n, ch, max(hl, 1), max(wl, 1), dtype=torch.float32,
+                                        device=self.device))
                 continue
             hl, wl = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
             for _ in range(level):
@@ -1996,6 +2047,70 @@ def row_select(logits: torch.Tensor,
                                  cand_i.data_ptr(), ROW_SELECT_PATHS[path],
                                  _stream(device)))
     return cand_v, cand_i
+
+
+# -- the Linear kernel of the AlexNet head on caller-supplied operands -----------------------
+def _need_export(name: str):
+    lib = load_library()
+    if not hasattr(lib, name):
+        raise HipUnavailableError(f'this build of libmilan_hip has no {name}')
+    return getattr(lib, name)
+
+
+def _linear_args(x, bias, n_in, n_out, device):
+    x = _dev(x.detach(), device, torch.float32)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != n_in:
+        raise ValueError(f'x must be (rows >= 1, {n_in}), got {tuple(x.shape)}')
+    if bias is not None:
+        bias = _dev(bias.detach(), device, torch.float32)
+        if tuple(bias.shape) != (n_out,):
+            raise ValueError(f'bias must be ({n_out},), got {tuple(bias.shape)}')
+    return x, bias, torch.empty(x.shape[0], n_out, dtype=torch.float32, device=device)
+
+
+def linear_pack(weight: torch.Tensor):
+    """The packed copy of a GPU (n_out, n_in) weight that `linear` reads, made once per
+    weight: (packed, n_out, n_in)."""
+    device = require_device(weight.device)
+    weight = _dev(weight.detach(), device, torch.float32)
+    if weight.dim() != 2 or min(weight.shape) < 1:
+        raise ValueError(f'weight must be (n_out, n_in), got {tuple(weight.shape)}')
+    n_out, n_in = weight.shape
+    nbytes = int(_need_export('milan_linear_packed_bytes')(n_out, n_in))
+    packed = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _check(_need_export('milan_linear_pack')(weight.data_ptr(), n_out, n_in,
+                                                 packed.data_ptr(), _stream(device)))
+    return packed, n_out, n_in
+
+
+def linear(x: torch.Tensor, packed, bias: Optional[torch.Tensor] = None,
+           relu: bool = False) -> torch.Tensor:
+    """act(x W^T + bias) by the fp32-MFMA kernel of the AlexNet head; `packed` from
+    `linear_pack`.  A row's bits depend on neither the other rows nor their number."""
+    weight, n_out, n_in = packed
+    device = weight.device
+    x, bias, y = _linear_args(x, bias, n_in, n_out, device)
+    with torch.cuda.device(device):
+        _check(_need_export('milan_linear')(x.data_ptr(), weight.data_ptr(), _ptr(bias),
+                                            x.shape[0], n_in, n_out, int(relu), y.data_ptr(),
+                                            _stream(device)))
+    return y
+
+
+def linear_rowwise(x: torch.Tensor, weight: torch.Tensor,
+                   bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x W^T + bias by the ResNet head's kernel, one wavefront per output and row: the
+    baseline `tools/bench_alexnet.py` measures `linear` against."""
+    device = require_device(weight.device)
+    weight = _dev(weight.detach(), device, torch.float32)
+    n_out, n_in = weight.shape
+    x, bias, y = _linear_args(x, bias, n_in, n_out, device)
+    with torch.cuda.device(device):
+        _check(_need_export('milan_linear_rowwise')(x.data_ptr(), weight.data_ptr(), _ptr(bias),
+                                                    x.shape[0], n_in, n_out, y.data_ptr(),
+                                                    _stream(device)))
+    return y
 
 
 def make_dims(state_dict: Dict[str, torch.Tensor],

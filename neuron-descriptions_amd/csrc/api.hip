@@ -455,7 +455,7 @@ int milan_classify_sweep(milan_ctx* c, const float* images, int n_images, int he
 size_t milan_activations_workspace_bytes(const milan_ctx* c, int n_images, int height,
                                          int width) {
   if (!c || !c->finalized) return 0;
-  return activations_workspace(c, n_images, height, width) + 256;
+  return classify_workspace(c, n_images, height, width, 0) + 256;
 }
 
 int milan_activations(milan_ctx* c, const float* images, int n_images, int height, int width,

@@ -1,16 +1,16 @@
 // Unit ablation, classification and activation taps on the ResNet trunks (milan_set_ablation,
 // milan_classify, milan_classify_sweep, milan_activations): the reference's
 // src/utils/ablations.py on torchvision's ResNet._forward_impl, eval mode.  The same calls on
-// AlexNet (alexnet_seq: conv1..conv5, fc6, fc7, linear8) have a walker, a tail kernel and a
-// Linear kernel of their own further down.
+// AlexNet (alexnet_seq: conv1..conv5, fc6, fc7, linear8) run through the same driver with a
+// walk, a tail kernel and a Linear kernel of their own.
 //
-// The forward is a plain walker of its own: stem conv, bn1 + ReLU + maxpool, every block's convs
-// through launch_gemm with the epilogues the encoder uses, then the head.  It materialises the
-// five tensors an edit must see -- the raw conv1 output (level 0: nethook edits the module's
-// output, before bn1) and the post-ReLU output of every stage (levels 1..4) -- and multiplies
-// each by the context's 0/1 channel mask before anything reads it.  None of the encoder's fused
-// launches (chain, fused stem, conv-front, row lists) is used: those are the paths that never
-// write such a tensor.
+// The ResNet forward is a plain walker of its own: stem conv, bn1 + ReLU + maxpool, every
+// block's convs through launch_gemm with the epilogues the encoder uses, then the head.  It
+// materialises the five tensors an edit must see -- the raw conv1 output (level 0: nethook
+// edits the module's output, before bn1) and the post-ReLU output of every stage (levels 1..4)
+// -- and multiplies each by the context's 0/1 channel mask before anything reads it.  None of
+// the encoder's fused launches (chain, fused stem, conv-front, row lists) is used: those are
+// the paths that never write such a tensor.
 //
 // Head: pooled[c] = (sum over pixels p = 0 .. h*w-1, ascending, one fp32 add
 // each) / (h*w); logit[j] = bias[j] + sum_k pooled[k] * W[j][k] with lane l of one wavefront
@@ -448,21 +448,29 @@ static int level_channels(const milan_ctx* c, int level) {
   return (c->d.trunk_kind == MILAN_TRUNK_BASIC ? wd : wd * 4) << (level - 1);
 }
 
-// called from milan_finalize_weights after encoder_finalize: keeps fc.weight / fc.bias when the
-// state dict has them (a context without them runs everything but the classify calls)
-int classify_finalize(milan_ctx* c, hipStream_t s) {
-  if (!resnet_trunk(c) || c->stem.w == nullptr) return 0;
+// the context's mask table: `channels[l]` units on level l, none of them ablated
+static int init_mask_table(milan_ctx* c, const int* channels, hipStream_t s) {
   int total = 0;
   for (int l = 0; l < 5; ++l) {
-    c->abl_ch[l] = level_channels(c, l);
+    c->abl_ch[l] = channels[l];
     c->abl_off[l] = total;
-    total += c->abl_ch[l];
+    total += channels[l];
     c->abl_count[l] = 0;
   }
   MILAN_TRY(dev_alloc(c, (void**)&c->abl_mask, sizeof(float) * total));
   hipLaunchKernelGGL(fill_ones_kernel, dim3((total + 255) / 256), dim3(256), 0, s, c->abl_mask,
                      total);
   MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// called from milan_finalize_weights after encoder_finalize: keeps fc.weight / fc.bias when the
+// state dict has them (a context without them runs everything but the classify calls)
+int classify_finalize(milan_ctx* c, hipStream_t s) {
+  if (!resnet_trunk(c) || c->stem.w == nullptr) return 0;
+  int channels[5];
+  for (int l = 0; l < 5; ++l) channels[l] = level_channels(c, l);
+  MILAN_TRY(init_mask_table(c, channels, s));
   const std::string p = "encoder.encoder.model.";
   auto w = c->raw.find(p + "fc.weight");
   if (w == c->raw.end()) return 0;
@@ -520,88 +528,40 @@ int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* un
 }
 
 // ---------------------------------------------------------------------------
-// driver
+// driver: one pass loop, one sweep loop and one workspace dry run, written over
+// a trunk.  A trunk (ResNetTrunk, AlexTrunk) is one pass's plan and walker: it derives from
+// Trunk, fills h / w / lvl_sz and split_tap_scale when it is made, and supplies
+//   carve(a)           its own buffers out of the arena, in its own order
+//   carve_hold(a, f)   the sweep's room of `f` floats for a held level, if it needs one
+//   check_geometry()   what it asks of the image extent
+//   walk(from, to, src, &out)   the forward between two levels (see ResNetTrunk::walk)
+//   head(x4, logits, preds)     from the masked level-4 tensor to logits (+ argmax)
+//   hold_level(images, at, level, &held)   the sweep's step to the next level with units
 // ---------------------------------------------------------------------------
-struct ClsPlan {
-  int h[5], w[5];   // level 0 = conv1 output, 1 = after the maxpool / layer1, 2..4 = layer2..4
-  size_t lvl_sz[5]; // floats per image of the level's tensor (split format takes the same room)
-  float *in4, *raw, *x0, *x1, *ds, *t1, *t2, *hold, *work, *pooled, *logits;
-  long long* preds;
-};
-
 static int cls_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
-
-static void cls_plan(const milan_ctx* c, int n, int H, int W, int sweep_units, int n_total,
-                     Arena& a, ClsPlan* pl) {
-  const int wd = c->d.trunk_width;
-  pl->h[0] = cls_out(H, 7, 2, 3); pl->w[0] = cls_out(W, 7, 2, 3);
-  for (int l = 1; l < 5; ++l) {
-    pl->h[l] = cls_out(pl->h[l - 1], 3, 2, 1);
-    pl->w[l] = cls_out(pl->w[l - 1], 3, 2, 1);
-  }
-  // (levels 1: the maxpool's and layer1's output have the same extent)
-  const int exp = c->d.trunk_kind == MILAN_TRUNK_BASIC ? 1 : 4;
-  size_t x_sz = (size_t)pl->h[1] * pl->w[1] * wd, t1_sz = 0, t2_sz = 0, lvl_max = 0;
-  for (int li = 0; li < 4; ++li) {
-    const size_t planes = (size_t)wd << li;
-    const size_t in_px = (size_t)pl->h[li == 0 ? 1 : li] * pl->w[li == 0 ? 1 : li];
-    const size_t out_px = (size_t)pl->h[li + 1] * pl->w[li + 1];
-    x_sz = std::max(x_sz, out_px * planes * exp);
-    t1_sz = std::max(t1_sz, in_px * planes);
-    t2_sz = std::max(t2_sz, out_px * planes);
-  }
-  for (int l = 0; l < 5; ++l) {
-    pl->lvl_sz[l] = (size_t)pl->h[l] * pl->w[l] * level_channels(c, l);
-    lvl_max = std::max(lvl_max, pl->lvl_sz[l]);
-  }
-  // (first, so that its address does not depend on the pass's image count)
-  pl->preds = sweep_units > 0 ? a.get<long long>((size_t)sweep_units * n_total) : nullptr;
-  pl->in4 = a.get<float>((size_t)n * H * (W + 2) * 4);
-  pl->raw = a.get<float>((size_t)n * pl->lvl_sz[0]);
-  pl->x0 = a.get<float>((size_t)n * x_sz);
-  pl->x1 = a.get<float>((size_t)n * x_sz);
-  pl->ds = a.get<float>((size_t)n * x_sz);
-  pl->t1 = a.get<float>((size_t)n * t1_sz);
-  pl->t2 = a.get<float>((size_t)n * t2_sz);
-  pl->pooled = a.get<float>((size_t)n * level_channels(c, 4));
-  pl->logits = a.get<float>((size_t)n * (c->fc_classes > 0 ? c->fc_classes : 1));
-  pl->hold = pl->work = nullptr;
-  if (sweep_units > 0) {
-    pl->hold = a.get<float>((size_t)n * lvl_max);
-    pl->work = a.get<float>((size_t)n * lvl_max);
-  }
-}
-
-static size_t alex_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units);
-
-size_t classify_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
-  if (alex_trunk(c)) return alex_workspace(c, n_images, H, W, sweep_units);
-  if (!resnet_trunk(c) || n_images <= 0 || H < 1 || W < 1) return 0;
-  Arena a; a.dry = true;
-  const int sub = encoder_sub_batch_size();
-  ClsPlan pl;
-  cls_plan(c, n_images < sub ? n_images : sub, H, W, sweep_units < 0 ? 0 : sweep_units, n_images,
-           a, &pl);
-  return a.off;
-}
 
 static int grid_for(long items) {
   const long b = (items + 255) / 256;
   return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
 }
 
-struct Walker {
-  milan_ctx* c;
-  const ClsPlan& pl;
-  int n;
+struct Trunk {
+  const milan_ctx* c;
+  int n, hin, win;        // the pass's images and their extent
   bool split;
   hipStream_t s;
+  float split_tap_scale;  // what a split level's stored value is multiplied by on its way out
+  int h[5], w[5];         // extent of the five level tensors
+  size_t lvl_sz[5];       // floats per image of a level's tensor (split takes the same room)
+  long long* preds = nullptr;
+  float *logits = nullptr, *work = nullptr;
+  float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 
   // level tensor `x` -> `y` (x == y: in place), times the context's mask of that level and with
   // unit `extra` (>= 0) zeroed too
   int mask(int level, const float* x, float* y, int extra) const {
     const int C = c->abl_ch[level];
-    const long px = (long)n * pl.h[level] * pl.w[level];
+    const long px = (long)n * h[level] * w[level];
     const float* m = c->abl_mask + c->abl_off[level];
     if (split && level > 0) {
       const long groups = px * (C / 8);
@@ -618,20 +578,75 @@ struct Walker {
   }
 
   // the masked level tensor `x` -> tap[level] as fp32 NCHW (milan_activations).  Level 0 is
-  // the raw conv1 output: fp32 without any scale in both modes (the pair stem's weight scale
-  // leaves in the GEMM's acc_scale, the activation scale enters only with bn1_scale_s).
+  // fp32 without any scale in both modes on both trunks.
   int emit(int level, const float* x) const {
-    const int C = c->abl_ch[level], P = pl.h[level] * pl.w[level];
+    const int C = c->abl_ch[level], P = h[level] * w[level];
     const dim3 grid((P + TAP_P - 1) / TAP_P, (C + TAP_C - 1) / TAP_C, n);
     if (split && level > 0)
-      hipLaunchKernelGGL(tap_nchw_kernel<true>, grid, dim3(256), 0, s, x, P, C,
-                         1.f / c->act_scale, tap[level]);
+      hipLaunchKernelGGL(tap_nchw_kernel<true>, grid, dim3(256), 0, s, x, P, C, split_tap_scale,
+                         tap[level]);
     else
       hipLaunchKernelGGL(tap_nchw_kernel<false>, grid, dim3(256), 0, s, x, P, C, 1.f,
                          tap[level]);
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   }
+};
+
+// `preds` comes first, so that its address does not depend on the pass's image count; then the
+// trunk's buffers, the logits of one pass and the sweep's held and working tensors
+template <class T>
+static void carve(T& t, int sweep_units, int n_total, Arena& a) {
+  const size_t lvl_max = *std::max_element(t.lvl_sz, t.lvl_sz + 5);
+  t.preds = sweep_units > 0 ? a.get<long long>((size_t)sweep_units * n_total) : nullptr;
+  t.carve(a);
+  t.logits = a.get<float>((size_t)t.n * (t.c->fc_classes > 0 ? t.c->fc_classes : 1));
+  if (sweep_units > 0) {
+    t.carve_hold(a, (size_t)t.n * lvl_max);
+    t.work = a.get<float>((size_t)t.n * lvl_max);
+  }
+}
+
+// ResNet: level 0 is the raw conv1 output (fp32 in both modes: the pair stem's weight scale
+// leaves in the GEMM's acc_scale, the activation scale enters only with bn1_scale_s), level 1
+// the maxpool's and layer1's extent, levels 2..4 layer2..4.  Levels 1..4 live in two ping-pong
+// buffers, split at the context's activation scale in the split mode.
+struct ResNetTrunk : Trunk {
+  float *in4, *raw, *x0, *x1, *ds, *t1, *t2, *hold = nullptr, *pooled;
+
+  ResNetTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
+      : Trunk{c, n, H, W, split, s, 1.f / c->act_scale} {
+    h[0] = cls_out(H, 7, 2, 3); w[0] = cls_out(W, 7, 2, 3);
+    for (int l = 1; l < 5; ++l) {
+      h[l] = cls_out(h[l - 1], 3, 2, 1);
+      w[l] = cls_out(w[l - 1], 3, 2, 1);
+    }
+    for (int l = 0; l < 5; ++l) lvl_sz[l] = (size_t)h[l] * w[l] * level_channels(c, l);
+  }
+
+  void carve(Arena& a) {
+    const int wd = c->d.trunk_width;
+    const int exp = c->d.trunk_kind == MILAN_TRUNK_BASIC ? 1 : 4;
+    size_t x_sz = (size_t)h[1] * w[1] * wd, t1_sz = 0, t2_sz = 0;
+    for (int li = 0; li < 4; ++li) {
+      const size_t planes = (size_t)wd << li;
+      const size_t in_px = (size_t)h[li == 0 ? 1 : li] * w[li == 0 ? 1 : li];
+      const size_t out_px = (size_t)h[li + 1] * w[li + 1];
+      x_sz = std::max(x_sz, out_px * planes * exp);
+      t1_sz = std::max(t1_sz, in_px * planes);
+      t2_sz = std::max(t2_sz, out_px * planes);
+    }
+    in4 = a.get<float>((size_t)n * hin * (win + 2) * 4);
+    raw = a.get<float>((size_t)n * lvl_sz[0]);
+    x0 = a.get<float>((size_t)n * x_sz);
+    x1 = a.get<float>((size_t)n * x_sz);
+    ds = a.get<float>((size_t)n * x_sz);
+    t1 = a.get<float>((size_t)n * t1_sz);
+    t2 = a.get<float>((size_t)n * t2_sz);
+    pooled = a.get<float>((size_t)n * level_channels(c, 4));
+  }
+  void carve_hold(Arena& a, size_t floats) { hold = a.get<float>(floats); }
+  int check_geometry() const { return 0; }
 
   // Runs the forward from level `from` (-1: from `src` = the images; otherwise `src` is the
   // level's tensor with its mask already applied) up to and including level `to`, applying the
@@ -641,49 +656,49 @@ struct Walker {
     const float* x = src;
     if (from < 0) {
       const bool pair_stem = split && c->stem_pair.ws != nullptr;
-      MILAN_TRY(launch_raw_input(src, n, hin, win, pair_stem, pl.in4, c->status, s));
-      MILAN_TRY(launch_gemm(encoder_stem_args(c, pl.in4, n, hin, win, pl.raw, pair_stem), s));
-      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, pl.raw, pl.raw, -1));
-      x = pl.raw;
+      MILAN_TRY(launch_raw_input(src, n, hin, win, pair_stem, in4, c->status, s));
+      MILAN_TRY(launch_gemm(encoder_stem_args(c, in4, n, hin, win, raw, pair_stem), s));
+      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, raw, raw, -1));
+      x = raw;
       from = 0;
       if (tap[0]) MILAN_TRY(emit(0, x));
     }
     if (to == from) { *out = x; return 0; }
-    float* y = pl.x0;
+    float* y = x0;
     if (from == 0) {
-      MILAN_TRY(launch_stem_tail(c, x, n, pl.h[0], pl.w[0], pl.h[1], pl.w[1], split, pl.x0, s));
-      x = pl.x0; y = pl.x1;
+      MILAN_TRY(launch_stem_tail(c, x, n, h[0], w[0], h[1], w[1], split, x0, s));
+      x = x0; y = x1;
     }
-    int h = pl.h[from == 0 ? 1 : from], w = pl.w[from == 0 ? 1 : from];
+    int hh = h[from == 0 ? 1 : from], ww = w[from == 0 ? 1 : from];
     for (int li = from == 0 ? 0 : from; li < 4 && li < to; ++li) {
       for (const Bottleneck& b : c->blocks[li]) {
         int h1, w1, h2, w2, h3, w3, hd, wdn;
         const float* identity = x;
         if (b.has_down) {
-          MILAN_TRY(launch_gemm(encoder_conv_args(b.down, x, n, h, w, pl.ds, EPI_BIAS, nullptr,
+          MILAN_TRY(launch_gemm(encoder_conv_args(b.down, x, n, hh, ww, ds, EPI_BIAS, nullptr,
                                                   c->zero, &hd, &wdn, split), s));
-          identity = pl.ds;
+          identity = ds;
         }
-        MILAN_TRY(launch_gemm(encoder_conv_args(b.c1, x, n, h, w, pl.t1, EPI_BIAS_RELU, nullptr,
+        MILAN_TRY(launch_gemm(encoder_conv_args(b.c1, x, n, hh, ww, t1, EPI_BIAS_RELU, nullptr,
                                                 c->zero, &h1, &w1, split), s));
         if (b.basic) {
           // BasicBlock: relu(bn2(conv2(relu(bn1(conv1(x))))) + identity)
-          MILAN_TRY(launch_gemm(encoder_conv_args(b.c2, pl.t1, n, h1, w1, y, EPI_BIAS_RES_RELU,
+          MILAN_TRY(launch_gemm(encoder_conv_args(b.c2, t1, n, h1, w1, y, EPI_BIAS_RES_RELU,
                                                   identity, c->zero, &h3, &w3, split), s));
         } else {
-          MILAN_TRY(launch_gemm(encoder_conv_args(b.c2, pl.t1, n, h1, w1, pl.t2, EPI_BIAS_RELU,
+          MILAN_TRY(launch_gemm(encoder_conv_args(b.c2, t1, n, h1, w1, t2, EPI_BIAS_RELU,
                                                   nullptr, c->zero, &h2, &w2, split), s));
-          MILAN_TRY(launch_gemm(encoder_conv_args(b.c3, pl.t2, n, h2, w2, y, EPI_BIAS_RES_RELU,
+          MILAN_TRY(launch_gemm(encoder_conv_args(b.c3, t2, n, h2, w2, y, EPI_BIAS_RES_RELU,
                                                   identity, c->zero, &h3, &w3, split), s));
         }
         // the block's output becomes the next input; the other ping-pong buffer the next output
         // (an input that came from outside -- the sweep's working tensor -- is left alone)
         const float* nx = y;
-        y = (x == pl.x0 || x == pl.x1) ? const_cast<float*>(x) : (y == pl.x0 ? pl.x1 : pl.x0);
+        y = (x == x0 || x == x1) ? const_cast<float*>(x) : (y == x0 ? x1 : x0);
         x = nx;
-        h = h3; w = w3;
+        hh = h3; ww = w3;
       }
-      MILAN_REQUIRE(h == pl.h[li + 1] && w == pl.w[li + 1], MILAN_ERR_SHAPE,
+      MILAN_REQUIRE(hh == h[li + 1] && ww == w[li + 1], MILAN_ERR_SHAPE,
                     "internal: stage %d geometry mismatch", li + 1);
       if (c->abl_count[li + 1] > 0)
         MILAN_TRY(mask(li + 1, x, const_cast<float*>(x), -1));
@@ -694,150 +709,106 @@ struct Walker {
   }
 
   // avgpool + fc (+ argmax) of the masked level-4 tensor
-  int head(const float* x4, float* logits, long long* preds) const {
-    const int C = c->abl_ch[4], P = pl.h[4] * pl.w[4], K = c->fc_classes;
+  int head(const float* x4, float* lg, long long* pr) const {
+    const int C = c->abl_ch[4], P = h[4] * w[4], K = c->fc_classes;
     if (split)
       hipLaunchKernelGGL(avgpool_kernel<true>, dim3((C + 255) / 256, n), dim3(256), 0, s, x4, P, C,
-                         1.f / c->act_scale, pl.pooled);
+                         1.f / c->act_scale, pooled);
     else
       hipLaunchKernelGGL(avgpool_kernel<false>, dim3((C + 255) / 256, n), dim3(256), 0, s, x4, P,
-                         C, 1.f, pl.pooled);
-    hipLaunchKernelGGL(fc_kernel, dim3((K + 3) / 4, n), dim3(256), 0, s, pl.pooled, c->fc_w,
-                       c->fc_b, C, K, logits);
-    if (preds)
-      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, logits, K, preds);
+                         C, 1.f, pooled);
+    hipLaunchKernelGGL(fc_kernel, dim3((K + 3) / 4, n), dim3(256), 0, s, pooled, c->fc_w,
+                       c->fc_b, C, K, lg);
+    if (pr) hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, lg, K, pr);
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   }
 
-  int hin = 0, win = 0;
-  float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-};
-
-// ---------------------------------------------------------------------------
-// AlexNet driver: torchvision's alexnet_seq in eval mode.  Levels 0..4 are
-// conv1..conv5; a level's tensor is relu(conv + bias) * mask, the conv run with the encoder's
-// bias + ReLU epilogue and the mask kernels above (no launch for a level without units).
-// Level 0 is fp32 in both modes (3 input channels), levels 1..4 are split at scale 1 in the
-// split mode.  Every level has a buffer of its own, so the sweep holds a level where it is.
-// ---------------------------------------------------------------------------
-struct AlexClsPlan {
-  int h[5], w[5];     // conv1..conv5 outputs
-  int hq[3], wq[3];   // pool1, pool2, pool5
-  size_t lvl_sz[5];
-  float *in4, *a[5], *q[2], *work, *flat, *f6, *f7, *logits;
-  long long* preds;
-};
-
-static void alex_cls_plan(const milan_ctx* c, int n, int H, int W, int sweep_units, int n_total,
-                          Arena& a, AlexClsPlan* pl) {
-  pl->h[0] = cls_out(H, 11, 4, 2); pl->w[0] = cls_out(W, 11, 4, 2);
-  pl->hq[0] = cls_out(pl->h[0], 3, 2, 0); pl->wq[0] = cls_out(pl->w[0], 3, 2, 0);
-  pl->h[1] = pl->hq[0]; pl->w[1] = pl->wq[0];
-  pl->hq[1] = cls_out(pl->h[1], 3, 2, 0); pl->wq[1] = cls_out(pl->w[1], 3, 2, 0);
-  for (int l = 2; l < 5; ++l) { pl->h[l] = pl->hq[1]; pl->w[l] = pl->wq[1]; }
-  pl->hq[2] = cls_out(pl->h[4], 3, 2, 0); pl->wq[2] = cls_out(pl->w[4], 3, 2, 0);
-  size_t lvl_max = 0;
-  for (int l = 0; l < 5; ++l) {
-    // (an image too small for the trunk is refused before anything is carved: see alex_geometry)
-    pl->lvl_sz[l] = (size_t)std::max(pl->h[l], 0) * std::max(pl->w[l], 0) * c->abl_ch[l];
-    lvl_max = std::max(lvl_max, pl->lvl_sz[l]);
-  }
-  const milan_ctx::AlexHead& hd = c->ahead;
-  pl->preds = sweep_units > 0 ? a.get<long long>((size_t)sweep_units * n_total) : nullptr;
-  pl->in4 = a.get<float>((size_t)n * H * W * 4);
-  for (int l = 0; l < 5; ++l) pl->a[l] = a.get<float>((size_t)n * pl->lvl_sz[l]);
-  for (int l = 0; l < 2; ++l)
-    pl->q[l] = a.get<float>((size_t)n * std::max(pl->hq[l], 0) * std::max(pl->wq[l], 0) *
-                            c->abl_ch[l]);
-  pl->flat = a.get<float>((size_t)n * hd.in[0]);
-  pl->f6 = a.get<float>((size_t)n * hd.out[0]);
-  pl->f7 = a.get<float>((size_t)n * hd.out[1]);
-  pl->logits = a.get<float>((size_t)n * hd.out[2]);
-  pl->work = sweep_units > 0 ? a.get<float>((size_t)n * lvl_max) : nullptr;
-}
-
-static size_t alex_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
-  if (n_images <= 0 || H < 1 || W < 1) return 0;
-  Arena a; a.dry = true;
-  const int sub = encoder_sub_batch_size();
-  AlexClsPlan pl;
-  alex_cls_plan(c, n_images < sub ? n_images : sub, H, W, sweep_units < 0 ? 0 : sweep_units,
-                n_images, a, &pl);
-  return a.off;
-}
-
-struct AlexWalker {
-  milan_ctx* c;
-  const AlexClsPlan& pl;
-  int n;
-  bool split;
-  hipStream_t s;
-  int hin = 0, win = 0;
-  float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-
-  int mask(int level, const float* x, float* y, int extra) const {
-    const int C = c->abl_ch[level];
-    const long px = (long)n * pl.h[level] * pl.w[level];
-    const float* m = c->abl_mask + c->abl_off[level];
-    if (split && level > 0) {
-      const long groups = px * (C / 8);
-      hipLaunchKernelGGL(channel_mask_split_kernel, dim3(grid_for(groups)), dim3(256), 0, s, x, y,
-                         groups, C / 8, m, extra);
-    } else {
-      const long total4 = px * (C / 4);
-      hipLaunchKernelGGL(channel_mask_f32_kernel, dim3(grid_for(total4)), dim3(256), 0, s,
-                         (const cf32x4_t*)x, (cf32x4_t*)y, total4, C / 4, (const cf32x4_t*)m,
-                         extra);
+  // The sweep's forward up to and including `level` starts from the images every time: levels
+  // >= 1 live in the ping-pong buffers the suffix overwrites, so they are copied into `hold`
+  // (the raw conv1 tensor has a buffer of its own).
+  int hold_level(const float* images, int, int level, const float** held) const {
+    MILAN_TRY(walk(-1, level, images, held));
+    if (level > 0) {
+      MILAN_CHECK_HIP(hipMemcpyAsync(hold, *held, sizeof(float) * n * lvl_sz[level],
+                                     hipMemcpyDeviceToDevice, s));
+      *held = hold;
     }
-    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
+};
+
+// AlexNet: torchvision's alexnet_seq in eval mode.  Levels 0..4 are
+// conv1..conv5; a level's tensor is relu(conv + bias) * mask, the conv run with the encoder's
+// bias + ReLU epilogue (no mask launch for a level without units).  Level 0 is fp32 in both
+// modes (3 input channels), levels 1..4 are split at scale 1 in the split mode.  Every level
+// has a buffer of its own, so the sweep holds a level where it is.
+struct AlexTrunk : Trunk {
+  int hq[3], wq[3];   // pool1, pool2, pool5
+  float *in4, *a[5], *q[2], *flat, *f6, *f7;
+
+  AlexTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
+      : Trunk{c, n, H, W, split, s, 1.f} {
+    h[0] = cls_out(H, 11, 4, 2); w[0] = cls_out(W, 11, 4, 2);
+    hq[0] = cls_out(h[0], 3, 2, 0); wq[0] = cls_out(w[0], 3, 2, 0);
+    h[1] = hq[0]; w[1] = wq[0];
+    hq[1] = cls_out(h[1], 3, 2, 0); wq[1] = cls_out(w[1], 3, 2, 0);
+    for (int l = 2; l < 5; ++l) { h[l] = hq[1]; w[l] = wq[1]; }
+    hq[2] = cls_out(h[4], 3, 2, 0); wq[2] = cls_out(w[4], 3, 2, 0);
+    // (an image too small for the trunk is refused before anything is used: check_geometry)
+    for (int l = 0; l < 5; ++l)
+      lvl_sz[l] = (size_t)std::max(h[l], 0) * std::max(w[l], 0) * c->abl_ch[l];
+  }
+
+  void carve(Arena& ar) {
+    const milan_ctx::AlexHead& hd = c->ahead;
+    in4 = ar.get<float>((size_t)n * hin * win * 4);
+    for (int l = 0; l < 5; ++l) a[l] = ar.get<float>((size_t)n * lvl_sz[l]);
+    for (int l = 0; l < 2; ++l)
+      q[l] = ar.get<float>((size_t)n * std::max(hq[l], 0) * std::max(wq[l], 0) * c->abl_ch[l]);
+    flat = ar.get<float>((size_t)n * hd.in[0]);
+    f6 = ar.get<float>((size_t)n * hd.out[0]);
+    f7 = ar.get<float>((size_t)n * hd.out[1]);
+  }
+  void carve_hold(Arena&, size_t) {}
+
+  // the smallest image leaves one pixel after pool5 (63 x 63)
+  int check_geometry() const {
+    // (the three pools need 3 pixels each way: C's division rounds a negative extent to zero)
+    MILAN_REQUIRE(h[0] >= 3 && w[0] >= 3 && h[1] >= 3 && w[1] >= 3 && h[4] >= 3 && w[4] >= 3,
+                  MILAN_ERR_SHAPE,
+                  "classify: image %dx%d is too small for AlexNet (63x63 at least)", hin, win);
     return 0;
   }
 
-  // the masked level tensor -> tap[level], fp32 NCHW; every level is post-ReLU, and the split
-  // levels are stored at scale 1
-  int emit(int level, const float* x) const {
-    const int C = c->abl_ch[level], P = pl.h[level] * pl.w[level];
-    const dim3 grid((P + TAP_P - 1) / TAP_P, (C + TAP_C - 1) / TAP_C, n);
-    if (split && level > 0)
-      hipLaunchKernelGGL(tap_nchw_kernel<true>, grid, dim3(256), 0, s, x, P, C, 1.f, tap[level]);
-    else
-      hipLaunchKernelGGL(tap_nchw_kernel<false>, grid, dim3(256), 0, s, x, P, C, 1.f,
-                         tap[level]);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-
-  // Walker::walk's contract: from level `from` (-1: `src` = the images; otherwise `src` is that
-  // level's tensor, masked) up to and including level `to`
+  // ResNetTrunk::walk's contract
   int walk(int from, int to, const float* src, const float** out) const {
     const float* x = src;
     int ho, wo;
     if (from < 0) {
-      MILAN_TRY(launch_raw_input(src, n, hin, win, false, pl.in4, c->status, s));
-      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[0], pl.in4, n, hin, win, pl.a[0],
-                                              EPI_BIAS_RELU, nullptr, c->zero, &ho, &wo, false),
-                            s));
-      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, pl.a[0], pl.a[0], -1));
-      x = pl.a[0];
+      MILAN_TRY(launch_raw_input(src, n, hin, win, false, in4, c->status, s));
+      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[0], in4, n, hin, win, a[0], EPI_BIAS_RELU,
+                                              nullptr, c->zero, &ho, &wo, false), s));
+      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, a[0], a[0], -1));
+      x = a[0];
       from = 0;
       if (tap[0]) MILAN_TRY(emit(0, x));
     }
     for (int l = from + 1; l <= to; ++l) {
-      int h = pl.h[l - 1], w = pl.w[l - 1];
+      int hh = h[l - 1], ww = w[l - 1];
       if (l <= 2) {
         // pool1 / pool2 (level 0 is fp32; the pool writes the format conv2 / conv3 read)
-        MILAN_TRY(launch_maxpool3s2(x, n, h, w, c->abl_ch[l - 1], pl.hq[l - 1], pl.wq[l - 1],
-                                    split, split && l == 2, pl.q[l - 1], c->status, s));
-        x = pl.q[l - 1];
-        h = pl.hq[l - 1]; w = pl.wq[l - 1];
+        MILAN_TRY(launch_maxpool3s2(x, n, hh, ww, c->abl_ch[l - 1], hq[l - 1], wq[l - 1], split,
+                                    split && l == 2, q[l - 1], c->status, s));
+        x = q[l - 1];
+        hh = hq[l - 1]; ww = wq[l - 1];
       }
-      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[l], x, n, h, w, pl.a[l], EPI_BIAS_RELU,
+      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[l], x, n, hh, ww, a[l], EPI_BIAS_RELU,
                                               nullptr, c->zero, &ho, &wo, split, false), s));
-      MILAN_REQUIRE(ho == pl.h[l] && wo == pl.w[l], MILAN_ERR_SHAPE,
+      MILAN_REQUIRE(ho == h[l] && wo == w[l], MILAN_ERR_SHAPE,
                     "internal: alexnet level %d geometry mismatch", l);
-      if (c->abl_count[l] > 0) MILAN_TRY(mask(l, pl.a[l], pl.a[l], -1));
-      x = pl.a[l];
+      if (c->abl_count[l] > 0) MILAN_TRY(mask(l, a[l], a[l], -1));
+      x = a[l];
       if (tap[l]) MILAN_TRY(emit(l, x));
     }
     *out = x;
@@ -846,106 +817,122 @@ struct AlexWalker {
 
   // pool5 + adaptive average pool + flatten, fc6 / fc7 / linear8 (+ argmax) of the masked
   // level-4 tensor; dropout is the identity in eval mode
-  int head(const float* x4, float* logits, long long* preds) const {
+  int head(const float* x4, float* lg, long long* pr) const {
     const milan_ctx::AlexHead& hd = c->ahead;
     const int C = c->abl_ch[4];
     const dim3 grid((36 * C + 255) / 256, n);
     if (split)
-      hipLaunchKernelGGL(alex_tail_kernel<true>, grid, dim3(256), 0, s, x4, pl.h[4], pl.w[4], C,
-                         pl.hq[2], pl.wq[2], 1.f, pl.flat);
+      hipLaunchKernelGGL(alex_tail_kernel<true>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
+                         wq[2], 1.f, flat);
     else
-      hipLaunchKernelGGL(alex_tail_kernel<false>, grid, dim3(256), 0, s, x4, pl.h[4], pl.w[4], C,
-                         pl.hq[2], pl.wq[2], 1.f, pl.flat);
+      hipLaunchKernelGGL(alex_tail_kernel<false>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
+                         wq[2], 1.f, flat);
     MILAN_CHECK_HIP(hipGetLastError());
-    MILAN_TRY(linear_run(pl.flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, pl.f6, s));
-    MILAN_TRY(linear_run(pl.f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, pl.f7, s));
-    MILAN_TRY(linear_run(pl.f7, hd.w[2], hd.b[2], n, hd.in[2], hd.out[2], false, logits, s));
-    if (preds) {
-      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, logits, hd.out[2], preds);
+    MILAN_TRY(linear_run(flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, f6, s));
+    MILAN_TRY(linear_run(f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, f7, s));
+    MILAN_TRY(linear_run(f7, hd.w[2], hd.b[2], n, hd.in[2], hd.out[2], false, lg, s));
+    if (pr) {
+      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, lg, hd.out[2], pr);
       MILAN_CHECK_HIP(hipGetLastError());
     }
     return 0;
   }
+
+  // The sweep's walk to `level` continues from the level held before it (`at`, -1: the
+  // images): the suffixes write levels above their own and the working tensor, never a held one.
+  int hold_level(const float* images, int at, int level, const float** held) const {
+    return walk(at, level, at < 0 ? images : *held, held);
+  }
 };
 
-// the smallest image leaves one pixel after pool5 (63 x 63)
-static int alex_geometry(const AlexClsPlan& pl, int H, int W) {
-  // (the three pools need 3 pixels each way: C's division rounds a negative extent to zero)
-  MILAN_REQUIRE(pl.h[0] >= 3 && pl.w[0] >= 3 && pl.h[1] >= 3 && pl.w[1] >= 3 && pl.h[4] >= 3 &&
-                    pl.w[4] >= 3,
-                MILAN_ERR_SHAPE, "classify: image %dx%d is too small for AlexNet (63x63 at least)",
-                H, W);
+template <class T>
+static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
+  Arena a; a.dry = true;
+  const int sub = encoder_sub_batch_size();
+  T t(c, n_images < sub ? n_images : sub, H, W, false, nullptr);
+  carve(t, sweep_units < 0 ? 0 : sweep_units, n_images, a);
+  return a.off;
+}
+
+size_t classify_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
+  if (n_images <= 0 || H < 1 || W < 1) return 0;
+  if (alex_trunk(c)) return workspace_dry<AlexTrunk>(c, n_images, H, W, sweep_units);
+  if (resnet_trunk(c)) return workspace_dry<ResNetTrunk>(c, n_images, H, W, sweep_units);
   return 0;
 }
 
-// milan_classify (taps == nullptr: walk to level 4, then the head) and milan_activations
-// (taps[l] != nullptr for the requested levels, `top` the highest: no head) on AlexNet
-static int alex_run(milan_ctx* c, const float* images, int n, int H, int W, bool split,
-                    float* logits, int64_t* predictions, float* const* taps, int top,
-                    Arena& ws, hipStream_t s) {
+// The pass loop: `n` images in slices of the encoder's sub-batch size, every pass on the same
+// scratch.  body(t, lo) runs on the pass's trunk `t`; `lo` is its first image.
+template <class T, class Body>
+static int for_each_pass(const milan_ctx* c, int n, int H, int W, bool split, int sweep_units,
+                         const char* what, const Arena& ws, hipStream_t s, Body body) {
   const int sub = encoder_sub_batch_size();
   for (int lo = 0; lo < n; lo += sub) {
     const int cnt = n - lo < sub ? n - lo : sub;
-    Arena a = ws;  // every pass reuses the same scratch
-    AlexClsPlan pl;
-    alex_cls_plan(c, cnt, H, W, 0, 0, a, &pl);
-    MILAN_TRY(alex_geometry(pl, H, W));
+    Arena a = ws;
+    T t(c, cnt, H, W, split, s);
+    carve(t, sweep_units, n, a);
+    MILAN_TRY(t.check_geometry());
     MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
-                  "classify: workspace too small (%zu needed, %zu given)", a.off, a.size);
-    MILAN_REQUIRE(cnt <= 65535, MILAN_ERR_ARG, "classify: sub-batch of %d images", cnt);
-    AlexWalker wk{c, pl, cnt, split, s};
-    wk.hin = H; wk.win = W;
-    const float* x;
-    if (taps) {
-      for (int l = 0; l < 5; ++l)
-        if (taps[l]) wk.tap[l] = taps[l] + (size_t)lo * pl.lvl_sz[l];
-      MILAN_TRY(wk.walk(-1, top, images + (size_t)lo * 3 * H * W, &x));
-      continue;
-    }
-    MILAN_TRY(wk.walk(-1, 4, images + (size_t)lo * 3 * H * W, &x));
-    float* lg = logits ? logits + (size_t)lo * c->ahead.out[2] : pl.logits;
-    MILAN_TRY(wk.head(x, lg, predictions ? (long long*)predictions + lo : nullptr));
+                  "%s: workspace too small (%zu needed, %zu given)", what, a.off, a.size);
+    // (the image index is a grid's y or z in the taps, the pools and the heads)
+    MILAN_REQUIRE(cnt <= 65535, MILAN_ERR_ARG, "%s: sub-batch of %d images", what, cnt);
+    MILAN_TRY(body(t, lo));
   }
   return 0;
 }
 
-static int alex_sweep(milan_ctx* c, const float* images, int n, int H, int W, bool split,
-                      const int32_t* levels, const int32_t* units, int count,
-                      const int64_t* targets, int32_t* correct, int64_t* predictions, Arena& ws,
-                      hipStream_t s) {
-  const int sub = encoder_sub_batch_size();
+// milan_classify (taps == nullptr: walk to level 4, then the head) and milan_activations
+// (taps[l] != nullptr for the requested levels, `top` the highest: each one converted to fp32
+// NCHW when it is produced; no head)
+template <class T>
+static int run(milan_ctx* c, const float* images, int n, int H, int W, bool split, float* logits,
+               int64_t* predictions, float* const* taps, int top, const char* what, Arena& ws,
+               hipStream_t s) {
+  return for_each_pass<T>(c, n, H, W, split, 0, what, ws, s, [&](T& t, int lo) -> int {
+    const float* from = images + (size_t)lo * 3 * H * W;
+    const float* x;
+    if (taps) {
+      for (int l = 0; l < 5; ++l)
+        if (taps[l]) t.tap[l] = taps[l] + (size_t)lo * t.lvl_sz[l];
+      return t.walk(-1, top, from, &x);
+    }
+    MILAN_TRY(t.walk(-1, 4, from, &x));
+    float* lg = logits ? logits + (size_t)lo * c->fc_classes : t.logits;
+    return t.head(x, lg, predictions ? (long long*)predictions + lo : nullptr);
+  });
+}
+
+// Units grouped by level, levels ascending: the forward up to and including a level runs once
+// per pass with the base set's masks and is held (T::hold_level); every unit is one masked copy
+// into the working tensor plus the suffix and the head.
+template <class T>
+static int sweep(milan_ctx* c, const float* images, int n, int H, int W, bool split,
+                 const int32_t* levels, const int32_t* units, int count, const int64_t* targets,
+                 int32_t* correct, int64_t* predictions, Arena& ws, hipStream_t s) {
   long long* preds_all = (long long*)predictions;
-  for (int lo = 0; lo < n; lo += sub) {
-    const int cnt = n - lo < sub ? n - lo : sub;
-    Arena a = ws;
-    AlexClsPlan pl;
-    alex_cls_plan(c, cnt, H, W, count, n, a, &pl);
-    MILAN_TRY(alex_geometry(pl, H, W));
-    MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
-                  "classify_sweep: workspace too small (%zu needed, %zu given)", a.off, a.size);
-    MILAN_REQUIRE(cnt <= 65535, MILAN_ERR_ARG, "classify_sweep: sub-batch of %d images", cnt);
-    if (preds_all == nullptr) preds_all = pl.preds;   // (the same address in every pass)
-    AlexWalker wk{c, pl, cnt, split, s};
-    wk.hin = H; wk.win = W;
-    // ascending levels: the walk to level L continues from the held level before it (the
-    // suffixes write levels above their own, and the working tensor, never a held one)
-    const float* held = images + (size_t)lo * 3 * H * W;
+  MILAN_TRY(for_each_pass<T>(c, n, H, W, split, count, "classify_sweep", ws, s,
+                             [&](T& t, int lo) -> int {
+    if (preds_all == nullptr) preds_all = t.preds;   // (the same address in every pass)
+    const float* from = images + (size_t)lo * 3 * H * W;
+    const float* held = nullptr;
     int at = -1;
     for (int level = 0; level < 5; ++level) {
       bool any = false;
       for (int j = 0; j < count && !any; ++j) any = levels[j] == level;
       if (!any) continue;
-      MILAN_TRY(wk.walk(at, level, held, &held));
+      MILAN_TRY(t.hold_level(from, at, level, &held));
       at = level;
       for (int j = 0; j < count; ++j) {
         if (levels[j] != level) continue;
-        MILAN_TRY(wk.mask(level, held, pl.work, units[j]));
+        MILAN_TRY(t.mask(level, held, t.work, units[j]));
         const float* x4;
-        MILAN_TRY(wk.walk(level, 4, pl.work, &x4));
-        MILAN_TRY(wk.head(x4, pl.logits, preds_all + (size_t)j * n + lo));
+        MILAN_TRY(t.walk(level, 4, t.work, &x4));
+        MILAN_TRY(t.head(x4, t.logits, preds_all + (size_t)j * n + lo));
       }
     }
-  }
+    return 0;
+  }));
   if (correct != nullptr) {
     hipLaunchKernelGGL(correct_count_kernel, dim3(count), dim3(256), 0, s, preds_all,
                        (const long long*)targets, n, correct);
@@ -983,17 +970,9 @@ int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* 
                                    hipMemcpyDeviceToDevice, s));
   }
   if (c->abl_mask == nullptr) {
-    int total = 0;
-    for (int l = 0; l < 5; ++l) {
-      c->abl_ch[l] = c->alex[l].cout;
-      c->abl_off[l] = total;
-      total += c->abl_ch[l];
-      c->abl_count[l] = 0;
-    }
-    MILAN_TRY(dev_alloc(c, (void**)&c->abl_mask, sizeof(float) * total));
-    hipLaunchKernelGGL(fill_ones_kernel, dim3((total + 255) / 256), dim3(256), 0, s, c->abl_mask,
-                       total);
-    MILAN_CHECK_HIP(hipGetLastError());
+    int channels[5];
+    for (int l = 0; l < 5; ++l) channels[l] = c->alex[l].cout;
+    MILAN_TRY(init_mask_table(c, channels, s));
   }
   // (the caller's tensors may go once this returns)
   MILAN_CHECK_HIP(hipStreamSynchronize(s));
@@ -1039,24 +1018,8 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
                  int64_t* predictions, Arena& ws, hipStream_t s) {
   bool split;
   MILAN_TRY(classify_checks(c, n, H, W, &split));
-  if (alex_trunk(c))
-    return alex_run(c, images, n, H, W, split, logits, predictions, nullptr, 4, ws, s);
-  const int sub = encoder_sub_batch_size();
-  for (int lo = 0; lo < n; lo += sub) {
-    const int cnt = n - lo < sub ? n - lo : sub;
-    Arena a = ws;  // every pass reuses the same scratch
-    ClsPlan pl;
-    cls_plan(c, cnt, H, W, 0, 0, a, &pl);
-    MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
-                  "classify: workspace too small (%zu needed, %zu given)", a.off, a.size);
-    Walker wk{c, pl, cnt, split, s};
-    wk.hin = H; wk.win = W;
-    const float* x4;
-    MILAN_TRY(wk.walk(-1, 4, images + (size_t)lo * 3 * H * W, &x4));
-    float* lg = logits ? logits + (size_t)lo * c->fc_classes : pl.logits;
-    MILAN_TRY(wk.head(x4, lg, predictions ? (long long*)predictions + lo : nullptr));
-  }
-  return 0;
+  auto go = alex_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
+  return go(c, images, n, H, W, split, logits, predictions, nullptr, 4, "classify", ws, s);
 }
 
 int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
@@ -1066,98 +1029,35 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
   MILAN_TRY(classify_checks(c, n, H, W, &split));
   MILAN_TRY(check_units(c, levels, units, count, "milan_classify_sweep"));
   if (count == 0) return 0;
-  if (alex_trunk(c))
-    return alex_sweep(c, images, n, H, W, split, levels, units, count, targets, correct,
-                      predictions, ws, s);
-  const int sub = encoder_sub_batch_size();
-  long long* preds_all = (long long*)predictions;
-  for (int lo = 0; lo < n; lo += sub) {
-    const int cnt = n - lo < sub ? n - lo : sub;
-    Arena a = ws;
-    ClsPlan pl;
-    cls_plan(c, cnt, H, W, count, n, a, &pl);
-    MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
-                  "classify_sweep: workspace too small (%zu needed, %zu given)", a.off, a.size);
-    if (preds_all == nullptr) preds_all = pl.preds;   // (the same address in every pass)
-    Walker wk{c, pl, cnt, split, s};
-    wk.hin = H; wk.win = W;
-    // units grouped by level: the forward up to and including the level runs once per pass with
-    // the base set's masks and is held; every unit is one masked copy plus the suffix
-    for (int level = 0; level < 5; ++level) {
-      bool any = false;
-      for (int j = 0; j < count && !any; ++j) any = levels[j] == level;
-      if (!any) continue;
-      const float* held;
-      MILAN_TRY(wk.walk(-1, level, images + (size_t)lo * 3 * H * W, &held));
-      if (level > 0) {
-        // (levels >= 1 live in the ping-pong buffers the suffix overwrites; the raw conv1
-        // tensor has a buffer of its own)
-        MILAN_CHECK_HIP(hipMemcpyAsync(pl.hold, held, sizeof(float) * cnt * pl.lvl_sz[level],
-                                       hipMemcpyDeviceToDevice, s));
-        held = pl.hold;
-      }
-      for (int j = 0; j < count; ++j) {
-        if (levels[j] != level) continue;
-        MILAN_TRY(wk.mask(level, held, pl.work, units[j]));
-        const float* x4;
-        MILAN_TRY(wk.walk(level, 4, pl.work, &x4));
-        MILAN_TRY(wk.head(x4, pl.logits, preds_all + (size_t)j * n + lo));
-      }
-    }
-  }
-  if (correct != nullptr) {
-    hipLaunchKernelGGL(correct_count_kernel, dim3(count), dim3(256), 0, s, preds_all,
-                       (const long long*)targets, n, correct);
-    MILAN_CHECK_HIP(hipGetLastError());
-  }
-  return 0;
+  auto go = alex_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
+  return go(c, images, n, H, W, split, levels, units, count, targets, correct, predictions, ws, s);
 }
 
 // milan_activations: the walk of classify_run, once per sub-batch up to the highest requested
-// level, each requested level converted to fp32 NCHW when it is produced; no head
-size_t activations_workspace(const milan_ctx* c, int n_images, int H, int W) {
-  return classify_workspace(c, n_images, H, W, 0);
-}
-
+// level; its scratch is classify_workspace(..., 0)
 int activations_run(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
                     int count, float* const* outputs, Arena& ws, hipStream_t s) {
   bool split;
   MILAN_TRY(classify_checks(c, n, H, W, &split, false));
-  int slot[5] = {-1, -1, -1, -1, -1}, top = -1;
+  float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int top = -1;
   for (int i = 0; i < count; ++i) {
     MILAN_REQUIRE(levels[i] >= 0 && levels[i] <= 4, MILAN_ERR_ARG,
                   "milan_activations: level %d is not one of 0..4 (%s)", levels[i],
                   level_names(c));
-    MILAN_REQUIRE(slot[levels[i]] < 0, MILAN_ERR_ARG,
+    MILAN_REQUIRE(taps[levels[i]] == nullptr, MILAN_ERR_ARG,
                   "milan_activations: level %d is requested twice", levels[i]);
     MILAN_REQUIRE(outputs[i] != nullptr, MILAN_ERR_ARG,
                   "milan_activations: outputs[%d] is null", i);
-    slot[levels[i]] = i;
+    taps[levels[i]] = outputs[i];
     top = std::max(top, (int)levels[i]);
   }
-  if (alex_trunk(c)) {
-    float* taps[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int l = 0; l < 5; ++l)
-      if (slot[l] >= 0) taps[l] = outputs[slot[l]];
-    return alex_run(c, images, n, H, W, split, nullptr, nullptr, taps, top, ws, s);
-  }
-  const int sub = encoder_sub_batch_size();
-  for (int lo = 0; lo < n; lo += sub) {
-    const int cnt = n - lo < sub ? n - lo : sub;
-    Arena a = ws;  // every pass reuses the same scratch
-    ClsPlan pl;
-    cls_plan(c, cnt, H, W, 0, 0, a, &pl);
-    MILAN_REQUIRE(a.off <= a.size, MILAN_ERR_WORKSPACE,
-                  "activations: workspace too small (%zu needed, %zu given)", a.off, a.size);
-    MILAN_REQUIRE(cnt <= 65535, MILAN_ERR_ARG, "activations: sub-batch of %d images", cnt);
-    Walker wk{c, pl, cnt, split, s};
-    wk.hin = H; wk.win = W;
-    for (int l = 0; l < 5; ++l)
-      if (slot[l] >= 0) wk.tap[l] = outputs[slot[l]] + (size_t)lo * pl.lvl_sz[l];
-    const float* x;
-    MILAN_TRY(wk.walk(-1, top, images + (size_t)lo * 3 * H * W, &x));
-  }
-  return 0;
+  // (the messages about the workspace and the sub-batch have named the call differently on
+  // the two trunks since they were written)
+  const bool alex = alex_trunk(c);
+  auto go = alex ? run<AlexTrunk> : run<ResNetTrunk>;
+  return go(c, images, n, H, W, split, nullptr, nullptr, taps, top,
+            alex ? "classify" : "activations", ws, s);
 }
 
 }  // namespace milan

@@ -672,7 +672,7 @@ int linear_run(const float* x, const float* packed, const float* bias, int M, in
 // the ResNet head's fc_kernel on caller-supplied operands (a measurement baseline)
 int linear_rowwise_run(const float* x, const float* W, const float* bias, int M, int K, int N,
                        float* y, hipStream_t s);
-size_t activations_workspace(const milan_ctx* c, int n, int H, int W);
+// (milan_activations' scratch is classify_workspace(c, n, H, W, 0))
 int activations_run(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
                     int count, float* const* outputs, Arena& ws, hipStream_t s);
 // decoder.hip

@@ -2376,7 +2376,9 @@ __global__ void maxpool3s2_split_kernel(const float* __restrict__ x, int n, int 
   report_saturation(status, sat);
 }
 
-// alexnet_run_batch's `maxpool`, for classify.hip's AlexNet walker
+// The trunk's 3x3 / stride 2 max-pool without padding (pool1, pool2), for alexnet_run_batch
+// below and for classify.hip's AlexNet walk: fp32 -> fp32, or with `split` fp32 / split
+// (`in_split`) -> split at scale 1; saturation is reported in `status`
 int launch_maxpool3s2(const float* x, int n, int H, int W, int C, int Ho, int Wo, bool split,
                       bool in_split, float* y, unsigned* status, hipStream_t s) {
   const long total = (long)n * Ho * Wo * (C / (split ? 8 : 4));
@@ -2487,32 +2489,15 @@ static int alexnet_run_batch(milan_ctx* c, const void* images, int image_dtype,
     col += C;
     return 0;
   };
-  auto maxpool = [&](int l, bool in_split) -> int {
-    const int C = pl.C[l];
-    const long total = (long)n * pl.hq[l] * pl.wq[l] * (C / (split ? 8 : 4));
-    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (!split)
-      hipLaunchKernelGGL(maxpool3s2_f32_kernel, dim3(blocks), dim3(256), 0, s,
-                         (const float4*)pl.a[l], n, pl.lv.h[l], pl.lv.w[l], C / 4,
-                         pl.hq[l], pl.wq[l], 0, (float4*)pl.q[l]);
-    else if (in_split)
-      hipLaunchKernelGGL(maxpool3s2_split_kernel<true>, dim3(blocks), dim3(256),
-                         0, s, pl.a[l], n, pl.lv.h[l], pl.lv.w[l], C, pl.hq[l],
-                         pl.wq[l], 0, pl.q[l], c->status);
-    else
-      hipLaunchKernelGGL(maxpool3s2_split_kernel<false>, dim3(blocks), dim3(256),
-                         0, s, pl.a[l], n, pl.lv.h[l], pl.lv.w[l], C, pl.hq[l],
-                         pl.wq[l], 0, pl.q[l], c->status);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  };
 
   int ho, wo;
   GemmArgs g0 = conv_args(c->alex[0], pl.in4, n, H, W, pl.a[0], EPI_BIAS_RELU,
                           nullptr, c->zero, &ho, &wo);
   MILAN_TRY(launch_gemm(g0, s));
   MILAN_TRY(pool(0, false));
-  MILAN_TRY(maxpool(0, false));
+  // (pool1 reads conv1's fp32 output; both pools write the format the next conv reads)
+  MILAN_TRY(launch_maxpool3s2(pl.a[0], n, pl.lv.h[0], pl.lv.w[0], pl.C[0], pl.hq[0], pl.wq[0],
+                              split, false, pl.q[0], c->status, s));
   const float* in = pl.q[0];
   int h = pl.hq[0], w = pl.wq[0];
   for (int l = 1; l < 5; ++l) {
@@ -2526,7 +2511,8 @@ static int alexnet_run_batch(milan_ctx* c, const void* images, int image_dtype,
     in = pl.a[l];
     h = ho; w = wo;
     if (l == 1) {
-      MILAN_TRY(maxpool(1, split));
+      MILAN_TRY(launch_maxpool3s2(pl.a[1], n, pl.lv.h[1], pl.lv.w[1], pl.C[1], pl.hq[1],
+                                  pl.wq[1], split, split, pl.q[1], c->status, s));
       in = pl.q[1];
       h = pl.hq[1]; w = pl.wq[1];
     }

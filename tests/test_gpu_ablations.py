@@ -7,6 +7,13 @@ the suite's fp32-GEMM-class bound against a float64 restatement (tests/ablref.py
 max|err| <= FEATURE_CLASS x max|want|.  A masked channel left at its value moves the logits
 by orders of magnitude more.
 """
+import ctypes
+import hashlib
+import os
+import pathlib
+import subprocess
+import sys
+
 import pytest
 import torch
 from torch.utils import data
@@ -17,6 +24,7 @@ from milan_amd import ablations, classifiers, hip, synthetic
 
 pytestmark = pytest.mark.gpu
 
+REPO = pathlib.Path(__file__).resolve().parent.parent
 PREFIX = 'encoder.encoder.model.'
 CONFIGS = ('resnet18', 'resnet50')
 PRECISIONS = ('f32', 'split_f16')
@@ -269,6 +277,98 @@ def test_sweep_is_one_classify_per_unit(gold, contexts, config, precision, geo, 
     assert torch.equal(predictions, want)
     assert torch.equal(correct.long(), (want == targets).sum(dim=1))
     assert len(torch.unique(want, dim=0)) > 1, 'every unit gives the same predictions'
+
+
+# ---- 4b. the sweep and classify over sub-batches ------------------------------------------------
+SUB_BASE = [(0, 1), (2, 5)]
+
+
+def correct_without_predictions(ctx, images, units, targets):
+    """milan_classify_sweep with `predictions` NULL: the prediction rows then live in the
+    workspace, carved at the same address in every pass.  `hip.Context.classify_sweep` always
+    passes a tensor, so this goes to the library directly."""
+    lib = hip.load_library()
+    images = images.to(ctx.device, torch.float32).contiguous()
+    targets = targets.to(ctx.device, torch.int64).contiguous()
+    n, _, h, w = images.shape
+    count = len(units)
+    levels = (ctypes.c_int32 * count)(*[level for level, _ in units])
+    ids = (ctypes.c_int32 * count)(*[unit for _, unit in units])
+    need = int(lib.milan_classify_workspace_bytes(ctx._h, n, h, w, count))
+    ws = torch.empty(need, dtype=torch.uint8, device=ctx.device)
+    correct = torch.full((count,), -1, dtype=torch.int32, device=ctx.device)
+    with torch.cuda.device(ctx.device):
+        code = lib.milan_classify_sweep(ctx._h, images.data_ptr(), n, h, w, levels, ids, count,
+                                        targets.data_ptr(), correct.data_ptr(), None,
+                                        ws.data_ptr(), ws.numel(), None)
+    assert code == 0, code
+    torch.cuda.synchronize()
+    return correct
+
+
+def sweep_that_discriminates(ctx, images, units, targets):
+    """`classify_sweep` on inputs that can tell a wrong result from a right one: the prediction
+    rows differ between units and between images and `correct` is not one number, so a pass
+    that read other images, a held level a suffix overwrote or a row written elsewhere changes
+    the result.  The same `correct` comes out with the rows kept in the workspace."""
+    predictions, correct = ctx.classify_sweep(images, units, targets)
+    assert predictions.shape == (len(units), len(images)) and correct.shape == (len(units),)
+    assert len(torch.unique(predictions, dim=0)) > 1, 'every unit gives the same predictions'
+    assert len(torch.unique(predictions, dim=1).t()) > 1, 'every image gets the same predictions'
+    assert len(torch.unique(correct)) > 1, 'every unit has the same count'
+    assert torch.equal(correct_without_predictions(ctx, images, units, targets), correct)
+    return predictions, correct
+
+
+def sub_batch_digest(ctx, tensors, meta, config):
+    """sha256 over classify's logits and predictions and the sweep's predictions and `correct`
+    for the first 7 images at 33x47, units on all five levels (level 0 is held where it is,
+    levels 1..4 in the sweep's copy), on top of a non-empty base set."""
+    images = tensors['images.33x47'][:7].cuda()
+    targets = tensors[f'{config}.33x47.targets'][:7].cuda()
+    channels = ablref.level_channels(config, meta['width'])
+    units = [(level, u) for u in (0, -1) for level in range(5)]
+    units = [(level, u % channels[level]) for level, u in units]
+    ctx.set_precision('f32')
+    ctx.set_ablation(SUB_BASE)
+    predictions, correct = sweep_that_discriminates(ctx, images, units, targets)
+    digest = hashlib.sha256()
+    for t in (ctx.classify(images), ctx.classify(images, return_logits=False), predictions,
+              correct):
+        digest.update(t.cpu().numpy().tobytes())
+    ctx.set_ablation([])
+    return digest.hexdigest()
+
+
+SUB_SCRIPT = r"""
+import sys
+sys.path[:0] = [{repo!r}, {pkg!r}, {tests!r}]
+import ablref
+import test_gpu_ablations as T
+from milan_amd import hip, synthetic
+tensors, meta = ablref.load_goldens()
+sd = {{T.PREFIX + k: v for k, v in ablref.state_dict({config!r}, tensors, meta).items()}}
+c = hip.Context(hip.make_dims(sd, 1, blocks=synthetic.RESNET_BLOCKS[{config!r}]), sd,
+                hip.require_device('cuda'))
+print('SHA', T.sub_batch_digest(c, tensors, meta, {config!r}))
+c.close()
+"""
+
+
+@pytest.mark.parametrize('config', CONFIGS)
+def test_sweep_and_classify_in_sub_batches(gold, contexts, config, tmp_path):
+    """MILAN_ENC_SUB is cached per process: one fresh child classifies and sweeps 7 images in
+    passes of 3 + 3 + 1; this process does so in one.  The same bits."""
+    tensors, meta = gold
+    want = sub_batch_digest(contexts[config], tensors, meta, config)
+    script = tmp_path / 'sub.py'
+    script.write_text(SUB_SCRIPT.format(repo=str(REPO), pkg=str(REPO / 'neuron-descriptions_amd'),
+                                        tests=str(REPO / 'tests'), config=config))
+    env = dict(os.environ, MILAN_ENC_SUB='3')
+    out = subprocess.run(['timeout', '-k', '10', '120', sys.executable, str(script)], env=env,
+                         capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert f'SHA {want}' in out.stdout, out.stdout
 
 
 @pytest.mark.parametrize('precision', ('f32', 'auto'))

@@ -27,6 +27,7 @@ import alexref
 from featclass import FEATURE_CLASS
 from milan_amd import ablations, classifiers, exemplars, hip, synthetic
 from oracle import exemplars_oracle as E
+from test_gpu_ablations import sweep_that_discriminates
 
 pytestmark = pytest.mark.gpu
 
@@ -319,6 +320,66 @@ def test_sub_batches(ctx, pictures, tmp_path):
                          capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-2000:]
     assert f'SHA {digest.hexdigest()}' in out.stdout, out.stdout
+
+
+# The golden model at the golden images predicts one class for every image under every unit of
+# such a sweep (float64: 70 times class 4), which no wrong pass could change.  This seed, the
+# goldens' sizes otherwise (width 8, hidden 72, 10 classes, 63x63), gives in float64 6 distinct
+# rows out of 10, 6 distinct columns out of 7, classes 1 / 2 / 4, rows changed by units of all
+# five levels, and a top-2 margin of at least 5e-3 x max|logit| (1000 x FEATURE_CLASS).
+SWEEP_SEED = 7
+
+
+def sweep_context():
+    return make_context(alexref.make_state_dict(SWEEP_SEED, 8, 72, 10))
+
+
+def sweep_digest(ctx):
+    """sha256 over the sweep's predictions and `correct` for 7 images at 63x63, units on
+    conv1..conv5, on top of a non-empty base set; the targets are the base set's predictions,
+    so `correct` counts the images a unit leaves alone."""
+    images = alexref.make_images(SWEEP_SEED, 7, (63, 63))
+    ch = alexref.channels(8)
+    units = [(level, u % ch[level]) for u in (0, -1) for level in range(5)]
+    ctx.set_precision('f32')
+    ctx.set_ablation([(0, 1), (2, 5)])
+    targets = ctx.classify(images, return_logits=False)
+    predictions, correct = sweep_that_discriminates(ctx, images, units, targets)
+    ctx.set_ablation([])
+    digest = hashlib.sha256()
+    for t in (targets, predictions, correct):
+        digest.update(t.cpu().numpy().tobytes())
+    return digest.hexdigest()
+
+
+SWEEP_SUB_SCRIPT = r"""
+import sys
+sys.path[:0] = [{repo!r}, {pkg!r}, {tests!r}]
+import test_gpu_alexnet as T
+c = T.sweep_context()
+print('SHA', T.sweep_digest(c))
+c.close()
+"""
+
+
+def test_sweep_in_sub_batches(tmp_path):
+    """test_sub_batches for classify_sweep: the child sweeps 7 images in passes of 3 + 3 + 1
+    (every pass reads its images, resumes from the levels it holds and writes its columns of
+    the prediction rows), this process in one."""
+    made = sweep_context()
+    try:
+        want = sweep_digest(made)
+    finally:
+        made.close()
+    script = tmp_path / 'sub.py'
+    script.write_text(SWEEP_SUB_SCRIPT.format(repo=str(REPO),
+                                              pkg=str(REPO / 'neuron-descriptions_amd'),
+                                              tests=str(REPO / 'tests')))
+    env = dict(os.environ, MILAN_ENC_SUB='3')
+    out = subprocess.run(['timeout', '-k', '10', '120', sys.executable, str(script)], env=env,
+                         capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert f'SHA {want}' in out.stdout, out.stdout
 
 
 def test_sweep_equals_the_loop(gold, ctx, pictures):

@@ -1100,6 +1100,63 @@ int milan_bert_score_pairs(const float* emb, const int32_t* offsets,
                            const int32_t* ref, int pairs, int n_sent, int width,
                            float* out, milan_stream stream);
 
+/* ---- Streaming attention and the DINO ViT (milan_amd.vits) -------------------------
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them
+ * (dlsym / hasattr(lib, "milan_vit_create")).
+ *
+ * milan_attention: softmax(q k^T / sqrt(head)) v per (sequence, head) for sequences
+ * of any length.
+ *   qkv: (seqs, tokens, 3 * width) fp32 DEVICE, 16-byte aligned: q | k | v, the
+ *     heads contiguous inside each (torch's reshape(B, N, 3, heads, head)).
+ *   out: (seqs, tokens, width) fp32 DEVICE.
+ *   head = width / heads must be a multiple of 16 up to 128; anything else is
+ *     MILAN_ERR_SHAPE and the message names it.  tokens >= 1.
+ * The scores never reach memory: K and V stream through LDS 32 keys at a time
+ * under an online softmax; both products are exact fp32 MFMA.  Needs no
+ * workspace.  Deterministic, and the bits of one (sequence, head) do not depend
+ * on the other sequences of the call.  Non-finite inputs are not specified.
+ * Does not synchronise. */
+int milan_attention(const float* qkv, float* out, int seqs, int tokens, int width,
+                    int heads, milan_stream stream);
+
+/* A pre-LN vision transformer as facebookresearch/dino builds it (cls token,
+ * learned positions, no distillation token, no head), weights under their DINO
+ * state-dict names (cls_token, pos_embed, patch_embed.proj.weight/bias,
+ * blocks.N.norm1/attn.qkv/attn.proj/norm2/mlp.fc1/mlp.fc2 .weight/.bias,
+ * norm.weight/bias), row-major fp32 as torch stores them.  create / set_weight /
+ * finalize_weights / destroy behave as their milan_clip_* namesakes.
+ * Exact fp32; every GEMM's split count depends on K alone, so the results for
+ * an image do not depend on the other images of the call. */
+typedef struct milan_vit_ctx milan_vit_ctx;
+typedef struct milan_vit_dims {
+  int32_t resolution; /* 224: input side, a multiple of patch            */
+  int32_t patch;      /* 8                                                */
+  int32_t width;      /* 384                                              */
+  int32_t layers;     /* 12                                               */
+  int32_t heads;      /* 6; width / heads a multiple of 16 up to 128      */
+  int32_t hidden;     /* 1536: columns of mlp.fc1                         */
+  float eps;          /* LayerNorm eps, 1e-6                              */
+} milan_vit_dims;
+
+int milan_vit_create(milan_vit_ctx** out, int device, const milan_vit_dims* dims);
+void milan_vit_destroy(milan_vit_ctx* ctx);
+int milan_vit_set_weight(milan_vit_ctx* ctx, const char* name, const float* data,
+                         const int64_t* shape, int ndim);
+int milan_vit_finalize_weights(milan_vit_ctx* ctx, milan_stream stream);
+
+/* One walk over n images (n, 3, resolution, resolution) fp32 DEVICE.
+ *   taps: HOST array of `layers` DEVICE pointers, or NULL.  A non-null taps[l]
+ *     receives the output of blocks.l.mlp.fc1, (n, tokens, hidden) fp32, bias
+ *     included, before the GELU; tokens = (resolution / patch)^2 + 1.
+ *   cls_out: NULL, or (n, width) fp32 DEVICE: the CLS row after the final norm.
+ *   Without cls_out the walk ends after fc1 of the deepest block asked for: no
+ *   GELU or fc2 of that block and no later block runs.  With it every block runs.
+ *   At least one output must be asked for.  Does not synchronise. */
+size_t milan_vit_workspace_bytes(const milan_vit_ctx* ctx, int n);
+int milan_vit_run(milan_vit_ctx* ctx, const float* images, int n, int resolution,
+                  float* const* taps, float* cls_out, void* workspace,
+                  size_t workspace_bytes, milan_stream stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

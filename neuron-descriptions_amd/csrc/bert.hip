@@ -14,7 +14,7 @@
 // Precision: exact fp32 tower; the pair kernel accumulates its cosines and its weighted sums
 // in float64 (a few thousand fused multiply-adds per pair, nothing beside the tower).
 // Determinism: fixed reduction orders, no float atomics; equal inputs give equal bits.
-#include "train_common.h"
+#include "tower_common.h"
 
 #include <string.h>
 #include <algorithm>
@@ -108,15 +108,16 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(
   ln_row([&](int j) { return we[j] + type[j] + pe[j]; }, W, eps, w, b, x + (long)r * W, lane);
 }
 
-// dst[r] = LayerNorm(src[r]); one wave per row.
+// dst[r] = LayerNorm(src[r * stride .. + W]); one wave per row.
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ src,
-                                                         float* __restrict__ dst, int rows,
-                                                         int W, const float* __restrict__ w,
+                                                         long stride, float* __restrict__ dst,
+                                                         int rows, int W,
+                                                         const float* __restrict__ w,
                                                          const float* __restrict__ b, float eps) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= rows) return;
-  const float* row = src + (long)r * W;
+  const float* row = src + (long)r * stride;
   ln_row([&](int j) { return row[j]; }, W, eps, w, b, dst + (long)r * W, lane);
 }
 
@@ -349,6 +350,24 @@ static const float* find(milan_bert_ctx* c, const std::string& name, size_t coun
 }
 
 }  // namespace bert
+
+namespace tower {
+int launch_layernorm_rows(const float* src, long stride, float* dst, int rows, int W,
+                          const float* w, const float* b, float eps, hipStream_t s) {
+  if (rows <= 0) return 0;
+  hipLaunchKernelGGL(bert::layernorm_kernel, dim3(bert::blocks_for(rows, 4)), dim3(256), 0, s,
+                     src, stride, dst, rows, W, w, b, eps);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+int launch_gelu_erf(float* x, long total, hipStream_t s) {
+  if (total <= 0) return 0;
+  hipLaunchKernelGGL(bert::gelu_erf_kernel, dim3(bert::blocks_for(total)), dim3(256), 0, s, x,
+                     total);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+}  // namespace tower
 }  // namespace milan
 
 using namespace milan;
@@ -506,18 +525,14 @@ int milan_bert_encode(milan_bert_ctx* c, const int64_t* ids, const int32_t* offs
     // x <- y Wo^T + bo + x, y <- LayerNorm(x)
     MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.ao_w, W), 1, view(x, W), view(x, W), b.ao_b,
                              nullptr, M, W, W, sc, s));
-    hipLaunchKernelGGL(layernorm_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, s, x, y, M, W,
-                       b.ln1_w, b.ln1_b, d.eps);
+    MILAN_TRY(tower::launch_layernorm_rows(x, W, y, M, W, b.ln1_w, b.ln1_b, d.eps, s));
     MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.in_w, W), 1, view(big, I), none, b.in_b,
                              nullptr, M, I, W, sc, s));
-    hipLaunchKernelGGL(gelu_erf_kernel, dim3(blocks_for((long)M * I)), dim3(256), 0, s, big,
-                       (long)M * I);
+    MILAN_TRY(tower::launch_gelu_erf(big, (long)M * I, s));
     // y <- big Wout^T + bout + y, x <- LayerNorm(y)
     MILAN_TRY(lmt::gemm_rows(view(big, I), 0, view(b.out_w, I), 1, view(y, W), view(y, W),
                              b.out_b, nullptr, M, W, I, sc, s));
-    hipLaunchKernelGGL(layernorm_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, s, y, x, M, W,
-                       b.ln2_w, b.ln2_b, d.eps);
-    MILAN_CHECK_HIP(hipGetLastError());
+    MILAN_TRY(tower::launch_layernorm_rows(y, W, x, M, W, b.ln2_w, b.ln2_b, d.eps, s));
   }
   hipLaunchKernelGGL(l2norm_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, s, x, out, M, W,
                      normalize ? 1 : 0);

@@ -15,7 +15,7 @@
 // one GEMM.  The text tower is causal, so the end-of-text row depends only on the positions
 // up to it: the caller passes `positions` = max(eot) + 1 and the tower runs over that many
 // positions instead of the full context.
-#include "train_common.h"
+#include "tower_common.h"
 
 #include <string.h>
 #include <algorithm>
@@ -438,6 +438,22 @@ static const float* find(milan_clip_ctx* c, const std::string& name, size_t coun
 }
 
 }  // namespace clip
+
+namespace tower {
+int launch_patch_gather(const float* images, float* A, long n, int R, int P,
+                        const float* renorm_mul_add, hipStream_t s) {
+  const int G = R / P;
+  const long total = n * G * G * 3 * P * P;
+  if (total <= 0) return 0;
+  float ma[6] = {1.f, 1.f, 1.f, 0.f, 0.f, 0.f};
+  if (renorm_mul_add) memcpy(ma, renorm_mul_add, sizeof(ma));  // HOST floats
+  hipLaunchKernelGGL(clip::patch_gather_kernel, dim3(clip::blocks_for(total)), dim3(256), 0, s,
+                     images, A, total, R, P, G, ma[0], ma[1], ma[2], ma[3], ma[4], ma[5],
+                     renorm_mul_add ? 1 : 0);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+}  // namespace tower
 }  // namespace milan
 
 using namespace milan;
@@ -596,11 +612,8 @@ int milan_clip_encode_images(milan_clip_ctx* c, const float* images, int n, int 
   float* cm = w + p.aux;
   float* cls_rows = cm + up64((size_t)np);
   float* emb = cls_rows + up64((size_t)seqs * std::max(W, E));
-  float ma[6] = {1.f, 1.f, 1.f, 0.f, 0.f, 0.f};
-  if (renorm_mul_add) memcpy(ma, renorm_mul_add, sizeof(ma));  // HOST floats
-  hipLaunchKernelGGL(patch_gather_kernel, dim3(blocks_for(np * kk)), dim3(256), 0, s, images,
-                     patches, np * kk, d.resolution, d.patch, G, ma[0], ma[1], ma[2], ma[3],
-                     ma[4], ma[5], renorm_mul_add ? 1 : 0);
+  MILAN_TRY(tower::launch_patch_gather(images, patches, n, d.resolution, d.patch, renorm_mul_add,
+                                       s));
   if (masks)
     hipLaunchKernelGGL(mask_downsample_kernel, dim3(blocks_for(np)), dim3(256), 0, s, masks, cm,
                        np, d.resolution, G);

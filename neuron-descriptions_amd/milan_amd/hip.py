@@ -99,6 +99,13 @@ class BertDims(ctypes.Structure):
 
 BERT_MAX_TOKENS = 64  # MILAN_BERT_MAX_TOKENS
 
+
+class VitDims(ctypes.Structure):
+    """struct milan_vit_dims."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'resolution', 'patch', 'width', 'layers', 'heads', 'hidden')] + [('eps', ctypes.c_float)]
+
+
 ABI_VERSION = 11  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
@@ -269,6 +276,16 @@ SIGNATURES = {
     'milan_conv2d_nhwc':
         (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I,
               _P]),
+    'milan_attention': (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    'milan_vit_create': (_I, [ctypes.POINTER(_P), _I,
+                              ctypes.POINTER(VitDims)]),
+    'milan_vit_destroy': (None, [_P]),
+    'milan_vit_set_weight':
+        (_I, [_P, ctypes.c_char_p, _P,
+              ctypes.POINTER(ctypes.c_int64), _I]),
+    'milan_vit_finalize_weights': (_I, [_P, _P]),
+    'milan_vit_workspace_bytes': (_SZ, [_P, _I]),
+    'milan_vit_run': (_I, [_P, _P, _I, _I, ctypes.POINTER(_P), _P, _P, _SZ, _P]),
 }
 
 # entry points added without a new ABI version: a library built before them
@@ -279,7 +296,9 @@ PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_classify_workspace_bytes', 'milan_classify',
           'milan_classify_sweep', 'milan_activations_workspace_bytes',
           'milan_activations', 'milan_set_alexnet_head', 'milan_linear_packed_bytes',
-          'milan_linear_pack', 'milan_linear', 'milan_linear_rowwise')
+          'milan_linear_pack', 'milan_linear', 'milan_linear_rowwise', 'milan_attention',
+          'milan_vit_create', 'milan_vit_destroy', 'milan_vit_set_weight',
+          'milan_vit_finalize_weights', 'milan_vit_workspace_bytes', 'milan_vit_run')
 
 _lib = None
 
@@ -1901,6 +1920,101 @@ class BertContext:
                 cand.data_ptr(), ref.data_ptr(), pairs, offsets.numel() - 1,
                 emb.shape[1], out.data_ptr(), _stream(self.device)))
         return out
+
+
+class VitContext:
+    """Owns one `milan_vit_ctx`: the weights of a DINO-style vision transformer on one GPU
+    and a workspace.  Every call computes in exact fp32 on torch's current stream and does
+    not synchronise."""
+
+    def __init__(self, dims: VitDims, state_dict: Dict[str, torch.Tensor],
+                 device: torch.device):
+        self.lib = load_library()
+        if not hasattr(self.lib, 'milan_vit_create'):
+            raise HipUnavailableError('this build of libmilan_hip has no milan_vit_create')
+        self.device = require_device(device)
+        self.dims = dims
+        self._h = _P()
+        with torch.cuda.device(self.device):
+            _check(self.lib.milan_vit_create(ctypes.byref(self._h), self.device.index,
+                                             ctypes.byref(dims)))
+            keep = []
+            for name, tensor in state_dict.items():
+                if not tensor.dtype.is_floating_point:
+                    continue
+                t = _dev(tensor.detach(), self.device, torch.float32)
+                keep.append(t)
+                shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
+                _check(self.lib.milan_vit_set_weight(self._h, name.encode(), t.data_ptr(),
+                                                     shape, t.dim()))
+            _check(self.lib.milan_vit_finalize_weights(self._h, _stream(self.device)))
+            del keep
+        self._ws: Optional[torch.Tensor] = None
+
+    def close(self) -> None:
+        if getattr(self, '_h', None):
+            self.lib.milan_vit_destroy(self._h)
+            self._h = None
+        self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    @property
+    def tokens(self) -> int:
+        return (self.dims.resolution // self.dims.patch)**2 + 1
+
+    def run(self, images: torch.Tensor, taps: Sequence[int] = (),
+            want_output: bool = False):
+        """images (n, 3, R, R) -> ({block: (n, tokens, hidden) output of blocks.<block>.mlp.fc1},
+        the (n, width) CLS row after the final norm or None).  The walk ends after fc1 of the
+        deepest block in `taps` unless `want_output`."""
+        d = self.dims
+        if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3]:
+            raise ValueError(f'images must be (n, 3, R, R), got {tuple(images.shape)}')
+        images = _dev(images.detach(), self.device, torch.float32)
+        n = images.shape[0]
+        taps = sorted(set(int(t) for t in taps))
+        if any(t < 0 or t >= d.layers for t in taps):
+            raise ValueError(f'taps {taps} outside the {d.layers} blocks')
+        if not taps and not want_output:
+            raise ValueError('neither a tap nor the output is asked for')
+        outs = {t: torch.empty((n, self.tokens, d.hidden), device=self.device) for t in taps}
+        cls = torch.empty((n, d.width), device=self.device) if want_output else None
+        if n == 0:
+            return outs, cls
+        pointers = (_P * d.layers)(*[_ptr(outs.get(l)) for l in range(d.layers)])
+        with torch.cuda.device(self.device):
+            need = int(self.lib.milan_vit_workspace_bytes(self._h, n))
+            if need == 0:
+                _check(ERR_ARG)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = None
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _check(self.lib.milan_vit_run(self._h, images.data_ptr(), n, images.shape[2],
+                                          pointers, _ptr(cls), self._ws.data_ptr(),
+                                          self._ws.numel(), _stream(self.device)))
+        return outs, cls
+
+
+def attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """softmax(q k^T / sqrt(head)) v per (sequence, head) by the streaming fp32-MFMA kernel
+    (milan_attention).  qkv (seqs, T, 3 * width) float32 on the GPU: q | k | v, the heads
+    contiguous inside each; returns (seqs, T, width).  Any T >= 1; head = width / heads a
+    multiple of 16 up to 128, anything else raises ValueError."""
+    device = require_device(qkv.device)
+    if qkv.dim() != 3 or qkv.shape[1] < 1 or qkv.shape[2] % 3 or heads < 1:
+        raise ValueError(f'qkv must be (seqs, T >= 1, 3 * width), got {tuple(qkv.shape)}')
+    qkv = _dev(qkv.detach(), device, torch.float32)
+    seqs, tokens, width = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    out = torch.empty((seqs, tokens, width), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _check(_need_export('milan_attention')(qkv.data_ptr(), out.data_ptr(), seqs, tokens,
+                                               width, int(heads), _stream(device)))
+    return out
 
 
 def profile_enable(enable: bool) -> None:

@@ -6,6 +6,8 @@
 // contraction goes through lmt::gemm_rows (train_common.h): the exact-fp32 MFMA GEMM of the
 // training path with its split count a function of K alone, so a sentence's embeddings do
 // not depend on the other sentences of the call.  Bias and residual adds are its epilogue.
+// LayerNorm, the erf GELU, the L2 norm, the attention kernel (a whole head in LDS, ragged
+// through `offsets`) and the weight store are the towers' shared parts (tower.hip).
 //
 // Ragged rows: the tokens of all sentences of a call are concatenated ([total][W]); the
 // offsets array says where each sentence starts.  No padding row exists anywhere: the GEMMs
@@ -20,11 +22,8 @@
 #include <algorithm>
 
 struct milan_bert_ctx {
-  int device = 0;
   milan_bert_dims d{};
-  bool finalized = false;
-  std::map<std::string, milan::Tensor> raw;
-  float* arena = nullptr;
+  milan::tower::Weights w;
   struct Layer {
     const float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b, *ao_w, *ao_b, *ln1_w, *ln1_b, *in_w, *in_b,
         *out_w, *out_b, *ln2_w, *ln2_b;
@@ -40,26 +39,12 @@ namespace bert {
 using lmt::Scratch;
 using lmt::View;
 using lmt::view;
+using namespace milan::tower;
 
 constexpr int MAX_TOKENS = MILAN_BERT_MAX_TOKENS;
-constexpr int ATT_THREADS = 256;
 constexpr int PAIR_THREADS = 256;
 constexpr int PAIR_KC = 32;                                          // columns per LDS chunk
 constexpr int PAIR_SLOTS = MAX_TOKENS * MAX_TOKENS / PAIR_THREADS;  // sim entries per thread
-constexpr size_t LDS_LIMIT = 64 * 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-static inline unsigned blocks_for(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
 // Sentence of token row r: the last s with offsets[s] <= r (offsets ascending, n + 1 entries).
 __device__ __forceinline__ int sentence_of(const int32_t* offsets, int n, int r) {
@@ -69,23 +54,6 @@ __device__ __forceinline__ int sentence_of(const int32_t* offsets, int n, int r)
     if (offsets[mid] <= r) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-// Two-pass LayerNorm of one row held by one wave (mean, then the centred second moment, as
-// torch's CPU kernel); `in(j)` gives element j.
-template <typename In>
-__device__ __forceinline__ void ln_row(In in, int W, float eps, const float* w, const float* b,
-                                       float* dst, int lane) {
-  float s = 0.f;
-  for (int j = lane; j < W; j += 64) s += in(j);
-  const float mean = wave_sum(s) / (float)W;
-  float q = 0.f;
-  for (int j = lane; j < W; j += 64) {
-    const float d = in(j) - mean;
-    q += d * d;
-  }
-  const float rstd = 1.f / sqrtf(wave_sum(q) / (float)W + eps);
-  for (int j = lane; j < W; j += 64) dst[j] = (in(j) - mean) * rstd * w[j] + b[j];
 }
 
 // x[r] = LayerNorm(word[ids[r]] + pos[position_offset + t] + type[0]), t = r - offsets[s].
@@ -106,107 +74,6 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(
   const float* we = word + id * W;
   const float* pe = pos + (long)p * W;
   ln_row([&](int j) { return we[j] + type[j] + pe[j]; }, W, eps, w, b, x + (long)r * W, lane);
-}
-
-// dst[r] = LayerNorm(src[r * stride .. + W]); one wave per row.
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ src,
-                                                         long stride, float* __restrict__ dst,
-                                                         int rows, int W,
-                                                         const float* __restrict__ w,
-                                                         const float* __restrict__ b, float eps) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= rows) return;
-  const float* row = src + (long)r * stride;
-  ln_row([&](int j) { return row[j]; }, W, eps, w, b, dst + (long)r * W, lane);
-}
-
-// x <- x * 0.5 * (1 + erf(x / sqrt(2)))
-__global__ void gelu_erf_kernel(float* __restrict__ x, long total) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const float v = x[i];
-  x[i] = v * 0.5f * (1.f + erff(v * 0.70710678118654752440f));
-}
-
-// Ragged bidirectional attention.  One workgroup per (sentence, head); the sentence's T =
-// offsets[s + 1] - offsets[s] tokens start at row offsets[s].  Q / sqrt(hd), K, V of the head
-// live in LDS (rows padded to hd + 1 floats: lanes that walk the keys hit distinct banks);
-// wave w owns query rows w, w + 4, ...: lanes walk the keys for the scores and the softmax,
-// then the head's columns for P V.
-// qkv: [total][3 W] (q | k | v, heads contiguous inside each), out: [total][W].
-__global__ __launch_bounds__(ATT_THREADS) void attention_kernel(
-    const float* __restrict__ qkv, const int32_t* __restrict__ offsets, float* __restrict__ out,
-    int W, int hd, int max_len) {
-  extern __shared__ float lds[];
-  const int s = blockIdx.x, head = blockIdx.y;
-  const int row0 = offsets[s];
-  int T = offsets[s + 1] - row0;
-  T = T < 0 ? 0 : (T > max_len ? max_len : T);  // memory safety only; the host validates
-  const int ldh = hd + 1;
-  float* Q = lds;
-  float* K = Q + (size_t)T * ldh;
-  float* V = K + (size_t)T * ldh;
-  float* P = V + (size_t)T * ldh;  // [4][T]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float* base = qkv + (size_t)row0 * 3 * W + (size_t)head * hd;
-  const float qs = sqrtf((float)hd);
-  for (int i = tid; i < T * hd; i += ATT_THREADS) {
-    const int t = i / hd, d = i % hd;
-    const float* p = base + (size_t)t * 3 * W + d;
-    Q[t * ldh + d] = p[0] / qs;
-    K[t * ldh + d] = p[W];
-    V[t * ldh + d] = p[2 * W];
-  }
-  __syncthreads();
-  float* Pw = P + (size_t)w * T;
-  for (int i = w; i < T; i += 4) {
-    const float* q = Q + i * ldh;
-    float mx = -INFINITY;
-    for (int j = lane; j < T; j += 64) {
-      const float* k = K + j * ldh;
-      float sc = 0.f;
-      for (int d = 0; d < hd; ++d) sc += q[d] * k[d];
-      Pw[j] = sc;
-      mx = fmaxf(mx, sc);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < T; j += 64) {
-      const float e = expf(Pw[j] - mx);
-      Pw[j] = e;
-      sum += e;
-    }
-    sum = wave_sum(sum);
-    for (int j = lane; j < T; j += 64) Pw[j] = Pw[j] / sum;
-    // (the lanes of one wave wrote Pw; the wave reads it back below)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    for (int d = lane; d < hd; d += 64) {
-      float o = 0.f;
-      for (int j = 0; j < T; ++j) o += Pw[j] * V[j * ldh + d];
-      out[((size_t)row0 + i) * W + (size_t)head * hd + d] = o;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
-}
-
-// y[r] = normalize ? x[r] / ||x[r]|| : x[r]   (one wave per row)
-__global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ x,
-                                                      float* __restrict__ y, int rows, int W,
-                                                      int normalize) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= rows) return;
-  const float* row = x + (long)r * W;
-  float nrm = 1.f;
-  if (normalize) {
-    float q = 0.f;
-    for (int j = lane; j < W; j += 64) q += row[j] * row[j];
-    nrm = sqrtf(wave_sum(q));
-  }
-  for (int j = lane; j < W; j += 64) y[(long)r * W + j] = row[j] / nrm;
 }
 
 // One workgroup per (candidate, reference) pair.  The two sentences' normalised rows go
@@ -302,10 +169,6 @@ __global__ __launch_bounds__(PAIR_THREADS) void score_pairs_kernel(
 }
 
 // ---- host side ------------------------------------------------------------------------------
-static size_t att_lds_bytes(int T, int hd) {
-  return sizeof(float) * (3 * (size_t)T * (hd + 1) + 4 * (size_t)T);
-}
-static size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 
 // Workspace of an encode over `total` token rows: x, y ([total][W]), big ([total][max(3 W,
 // I)]) and the GEMMs' split-K scratch; in floats, 64-float aligned.
@@ -314,7 +177,7 @@ struct Plan {
 };
 
 static int plan(const milan_bert_ctx* c, int n, int total, Plan* p) {
-  MILAN_REQUIRE(c && c->finalized, MILAN_ERR_STATE, "bert: weights are not finalized");
+  MILAN_REQUIRE(c && c->w.finalized, MILAN_ERR_STATE, "bert: weights are not finalized");
   const auto& d = c->d;
   MILAN_REQUIRE(n > 0 && total >= n, MILAN_ERR_ARG, "bert encode: %d sentences, %d tokens", n,
                 total);
@@ -334,40 +197,7 @@ static int plan(const milan_bert_ctx* c, int n, int total, Plan* p) {
   return 0;
 }
 
-static const float* find(milan_bert_ctx* c, const std::string& name, size_t count) {
-  auto it = c->raw.find(name);
-  if (it == c->raw.end()) {
-    set_error("bert: weight %s was not uploaded", name.c_str());
-    return nullptr;
-  }
-  size_t n = 1;
-  for (int64_t v : it->second.shape) n *= (size_t)v;
-  if (n != count) {
-    set_error("bert: weight %s has %zu elements, the dims need %zu", name.c_str(), n, count);
-    return nullptr;
-  }
-  return (const float*)it->second.dev;
-}
-
 }  // namespace bert
-
-namespace tower {
-int launch_layernorm_rows(const float* src, long stride, float* dst, int rows, int W,
-                          const float* w, const float* b, float eps, hipStream_t s) {
-  if (rows <= 0) return 0;
-  hipLaunchKernelGGL(bert::layernorm_kernel, dim3(bert::blocks_for(rows, 4)), dim3(256), 0, s,
-                     src, stride, dst, rows, W, w, b, eps);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-int launch_gelu_erf(float* x, long total, hipStream_t s) {
-  if (total <= 0) return 0;
-  hipLaunchKernelGGL(bert::gelu_erf_kernel, dim3(bert::blocks_for(total)), dim3(256), 0, s, x,
-                     total);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-}  // namespace tower
 }  // namespace milan
 
 using namespace milan;
@@ -389,45 +219,34 @@ int milan_bert_create(milan_bert_ctx** out, int device, const milan_bert_dims* d
                 "bert: position_offset %d leaves no position of %d", d.position_offset,
                 d.max_positions);
   const int hd = d.width / d.heads;
-  const size_t lds = att_lds_bytes(MAX_TOKENS, hd);
-  MILAN_REQUIRE(lds <= LDS_LIMIT, MILAN_ERR_SHAPE,
+  const size_t lds = lds_attention_bytes(MAX_TOKENS, hd);
+  MILAN_REQUIRE(lds_attention_fits(MAX_TOKENS, hd), MILAN_ERR_SHAPE,
                 "bert attention: %d tokens x head size %d (width %d / %d heads) need %zu bytes of "
                 "LDS, a workgroup has %zu",
                 MAX_TOKENS, hd, d.width, d.heads, lds, LDS_LIMIT);
   milan_bert_ctx* c = new milan_bert_ctx;
-  c->device = device;
+  c->w.device = device;
   c->d = d;
+  c->layers.assign(d.layers, {});
   *out = c;
   return 0;
 }
 
 void milan_bert_destroy(milan_bert_ctx* c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->arena) (void)hipFree(c->arena);
+  c->w.release();
   delete c;
 }
 
 int milan_bert_set_weight(milan_bert_ctx* c, const char* name, const float* data,
                           const int64_t* shape, int ndim) {
-  MILAN_REQUIRE(c && name && data && (shape || ndim == 0) && ndim >= 0 && ndim <= 8,
-                MILAN_ERR_ARG, "milan_bert_set_weight: bad argument");
-  MILAN_REQUIRE(!c->finalized, MILAN_ERR_STATE,
-                "milan_bert_set_weight after milan_bert_finalize_weights");
-  Tensor t;
-  t.shape.assign(shape, shape + ndim);
-  t.dev = data;
-  c->raw[name] = t;
-  return 0;
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "milan_bert_set_weight: bad argument");
+  return c->w.set("bert", name, data, shape, ndim);
 }
 
 int milan_bert_finalize_weights(milan_bert_ctx* c, milan_stream stream) {
   MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
-  MILAN_REQUIRE(!c->finalized, MILAN_ERR_STATE, "bert weights already finalized");
-  hipStream_t s = (hipStream_t)stream;
-  MILAN_CHECK_HIP(hipSetDevice(c->device));
   const auto& d = c->d;
-  struct Want { std::string name; size_t count; const float** dst; };
   std::vector<Want> wants;
   const size_t W = d.width, I = d.intermediate;
   wants.push_back({"embeddings.word_embeddings.weight", (size_t)d.vocab_size * W, &c->word});
@@ -435,7 +254,6 @@ int milan_bert_finalize_weights(milan_bert_ctx* c, milan_stream stream) {
   wants.push_back({"embeddings.token_type_embeddings.weight", (size_t)d.type_vocab * W, &c->type});
   wants.push_back({"embeddings.LayerNorm.weight", W, &c->eln_w});
   wants.push_back({"embeddings.LayerNorm.bias", W, &c->eln_b});
-  c->layers.assign(d.layers, {});
   for (int l = 0; l < d.layers; ++l) {
     const std::string p = "encoder.layer." + std::to_string(l) + ".";
     auto& b = c->layers[l];
@@ -456,23 +274,7 @@ int milan_bert_finalize_weights(milan_bert_ctx* c, milan_stream stream) {
     wants.push_back({p + "output.LayerNorm.weight", W, &b.ln2_w});
     wants.push_back({p + "output.LayerNorm.bias", W, &b.ln2_b});
   }
-  size_t total = 0;
-  for (auto& w : wants) {
-    if (!find(c, w.name, w.count)) return MILAN_ERR_STATE;
-    total += up64(w.count);
-  }
-  MILAN_CHECK_HIP(hipMalloc((void**)&c->arena, total * sizeof(float)));
-  size_t o = 0;
-  for (auto& w : wants) {
-    MILAN_CHECK_HIP(hipMemcpyAsync(c->arena + o, find(c, w.name, w.count),
-                                   w.count * sizeof(float), hipMemcpyDeviceToDevice, s));
-    *w.dst = c->arena + o;
-    o += up64(w.count);
-  }
-  MILAN_CHECK_HIP(hipStreamSynchronize(s));
-  c->raw.clear();
-  c->finalized = true;
-  return 0;
+  return c->w.finalize("bert", wants, (hipStream_t)stream);
 }
 
 size_t milan_bert_encode_workspace_bytes(const milan_bert_ctx* c, int n, int total) {
@@ -499,15 +301,16 @@ int milan_bert_encode(milan_bert_ctx* c, const int64_t* ids, const int32_t* offs
   MILAN_REQUIRE(ws_bytes >= p.total_floats * sizeof(float), MILAN_ERR_WORKSPACE,
                 "milan_bert_encode: workspace %zu < %zu bytes", ws_bytes,
                 p.total_floats * sizeof(float));
-  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  MILAN_CHECK_HIP(hipSetDevice(c->w.device));
   const hipStream_t s = (hipStream_t)stream;
   float* w = (float*)ws;
   const int W = d.width, I = d.intermediate, hd = W / d.heads, M = total;
   const Scratch sc{w + p.scratch, p.scratch_floats};
   const View none = view(nullptr, 0);
   float *x = w + p.x, *y = w + p.y, *big = w + p.big;
-  const size_t lds = att_lds_bytes(max_len, hd);
-  MILAN_TRY(ensure_lds_attr((const void*)attention_kernel, (int)lds));
+  LdsAttention att{};  // ragged, bidirectional, no mask edit
+  att.qkv = big; att.out = y; att.offsets = offsets; att.max_len = max_len; att.W = W;
+  att.hd = hd;
   hipLaunchKernelGGL(embed_ln_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, s, ids, offsets, n,
                      total, c->word, c->pos, c->type, c->eln_w, c->eln_b, x, W, d.vocab_size,
                      d.max_positions, d.position_offset, d.eps);
@@ -519,25 +322,20 @@ int milan_bert_encode(milan_bert_ctx* c, const int64_t* ids, const int32_t* offs
     for (int i = 0; i < 3; ++i)
       MILAN_TRY(lmt::gemm_rows(view(x, W), 0, view(qkv_w[i], W), 1, view(big + i * W, 3 * W),
                                none, qkv_b[i], nullptr, M, W, W, sc, s));
-    hipLaunchKernelGGL(attention_kernel, dim3((unsigned)n, d.heads), dim3(ATT_THREADS), lds, s,
-                       big, offsets, y, W, hd, max_len);
-    MILAN_CHECK_HIP(hipGetLastError());
+    MILAN_TRY(launch_lds_attention(att, n, d.heads, s));
     // x <- y Wo^T + bo + x, y <- LayerNorm(x)
     MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.ao_w, W), 1, view(x, W), view(x, W), b.ao_b,
                              nullptr, M, W, W, sc, s));
-    MILAN_TRY(tower::launch_layernorm_rows(x, W, y, M, W, b.ln1_w, b.ln1_b, d.eps, s));
+    MILAN_TRY(launch_layernorm_rows(x, W, y, M, W, b.ln1_w, b.ln1_b, d.eps, s));
     MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.in_w, W), 1, view(big, I), none, b.in_b,
                              nullptr, M, I, W, sc, s));
-    MILAN_TRY(tower::launch_gelu_erf(big, (long)M * I, s));
+    MILAN_TRY(launch_gelu_erf(big, (long)M * I, s));
     // y <- big Wout^T + bout + y, x <- LayerNorm(y)
     MILAN_TRY(lmt::gemm_rows(view(big, I), 0, view(b.out_w, I), 1, view(y, W), view(y, W),
                              b.out_b, nullptr, M, W, I, sc, s));
-    MILAN_TRY(tower::launch_layernorm_rows(y, W, x, M, W, b.ln2_w, b.ln2_b, d.eps, s));
+    MILAN_TRY(launch_layernorm_rows(y, W, x, M, W, b.ln2_w, b.ln2_b, d.eps, s));
   }
-  hipLaunchKernelGGL(l2norm_kernel, dim3(blocks_for(M, 4)), dim3(256), 0, s, x, out, M, W,
-                     normalize ? 1 : 0);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_l2norm(x, out, M, W, normalize ? 1 : 0, s);
 }
 
 int milan_bert_score_pairs(const float* emb, const int32_t* offsets, const float* weights,

@@ -6,7 +6,10 @@
 // layout, row-major as torch stores it.  No weight is transposed or packed: every
 // contraction goes through lmt::gemm (train_common.h), the strided exact-fp32 MFMA GEMM,
 // which reads x.W^T through a view.  Bias and residual adds are its epilogue (bias1 / d);
-// QuickGELU stays a row kernel, so no existing GEMM instantiation changes.
+// QuickGELU stays a row kernel, so no existing GEMM instantiation changes.  The plain
+// LayerNorm, the L2 norm, the patch gather, the attention kernel (a whole head in LDS, with
+// the causal flag and the CLS-row mask edit) and the weight store are the towers' shared
+// parts (tower.hip).
 //
 // Precision: exact fp32 whatever milan_set_precision says on the decoder's context.
 // Determinism: fixed reduction orders, no float atomics; equal inputs give equal bits.
@@ -21,11 +24,8 @@
 #include <algorithm>
 
 struct milan_clip_ctx {
-  int device = 0;
   milan_clip_dims d{};
-  bool finalized = false;
-  std::map<std::string, milan::Tensor> raw;
-  float* arena = nullptr;
+  milan::tower::Weights w;
   struct Block {
     const float *ln1_w, *ln1_b, *in_w, *in_b, *out_w, *out_b, *ln2_w, *ln2_b, *fc_w, *fc_b, *pj_w,
         *pj_b;
@@ -47,46 +47,9 @@ namespace clip {
 using lmt::Scratch;
 using lmt::View;
 using lmt::view;
+using namespace milan::tower;
 
 constexpr float LN_EPS = 1e-5f;
-constexpr int ATT_THREADS = 256;
-constexpr size_t LDS_LIMIT = 64 * 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-static inline unsigned blocks_for(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
-
-// ---- image front --------------------------------------------------------------------------
-// Renormalise (x * mul[c] + add[c], the reference's Renormalizer) and gather the stride-P
-// patches: A[(img * G + gy) * G + gx][(c * P + py) * P + px], the im2col of conv1.
-__global__ void patch_gather_kernel(const float* __restrict__ images, float* __restrict__ A,
-                                    long total, int R, int P, int G, float m0, float m1,
-                                    float m2, float a0, float a1, float a2, int renorm) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const int kk = 3 * P * P;
-  const int col = (int)(i % kk);
-  const long row = i / kk;
-  const int px = col % P, py = (col / P) % P, c = col / (P * P);
-  const int gx = (int)(row % G), gy = (int)((row / G) % G);
-  const long img = row / ((long)G * G);
-  float v = images[((img * 3 + c) * R + (gy * P + py)) * (long)R + gx * P + px];
-  if (renorm) {
-    const float mul = c == 0 ? m0 : (c == 1 ? m1 : m2);
-    const float add = c == 0 ? a0 : (c == 1 ? a1 : a2);
-    v = v * mul + add;
-  }
-  A[i] = v;
-}
 
 // Bilinear resize of the (n, 1, R, R) masks to the G x G patch grid, align_corners = False,
 // no antialiasing (torch's upsample_bilinear2d: src = max(0, (dst + .5) * scale - .5)).
@@ -109,16 +72,14 @@ __global__ void mask_downsample_kernel(const float* __restrict__ masks, float* _
            ly * (hx * m[(long)y1 * R + x0] + lx * m[(long)y1 * R + x1]);
 }
 
-// ---- LayerNorm rows -------------------------------------------------------------------------
+// ---- LayerNorm of gathered rows -------------------------------------------------------------
 // One wave per output row r.  Input row r is
-//   kind 0: src[r * stride]                                      (plain / strided rows)
 //   kind 1: (t == 0 ? cls : pe[(img * (T - 1) + t - 1)]) + pos[t] (image tokens + ln_pre;
 //           row r = (copy, img, t): every copy reads the same image)
 //   kind 2: src[(r * T + eot(r)) * W], eot(r) = min(argmax ids[r], T - 1)  (ln_final gather)
-// Two passes over the row (mean, then the centred second moment), as torch's CPU kernel.
-struct LnArgs {
+// (plain and strided rows: launch_layernorm_rows)
+struct GatherLnArgs {
   const float* src;
-  long stride;
   const float *cls, *pos;
   const int64_t* ids;
   int ctx_len;
@@ -129,12 +90,7 @@ struct LnArgs {
   int W;
 };
 
-__device__ __forceinline__ float ln_in(const LnArgs& a, const float* row, int t, int j) {
-  if (a.kind == 1) return (t == 0 ? a.cls[j] : row[j]) + a.pos[(long)t * a.W + j];
-  return row[j];
-}
-
-__global__ __launch_bounds__(256) void layernorm_kernel(LnArgs a) {
+__global__ __launch_bounds__(256) void gather_layernorm_kernel(GatherLnArgs a) {
   const long r = blockIdx.x * 4L + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= a.rows) return;
@@ -144,7 +100,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs a) {
     t = (int)(r % a.T);
     const long img = (r / a.T) % a.n_img;
     row = a.src + (img * (a.T - 1) + (t ? t - 1 : 0)) * (long)a.W;
-  } else if (a.kind == 2) {
+  } else {
     // first position of the largest id (torch.argmax), read over the whole context
     const int64_t* ids = a.ids + r * (long)a.ctx_len;
     int64_t best = ids[0];
@@ -156,21 +112,13 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs a) {
       }
     at = at < a.T ? at : a.T - 1;
     row = a.src + (r * a.T + at) * (long)a.W;
-  } else {
-    row = a.src + r * a.stride;
   }
-  float s = 0.f;
-  for (int j = lane; j < a.W; j += 64) s += ln_in(a, row, t, j);
-  const float mean = wave_sum(s) / (float)a.W;
-  float q = 0.f;
-  for (int j = lane; j < a.W; j += 64) {
-    const float d = ln_in(a, row, t, j) - mean;
-    q += d * d;
-  }
-  const float rstd = 1.f / sqrtf(wave_sum(q) / (float)a.W + LN_EPS);
-  float* dst = a.dst + r * (long)a.W;
-  for (int j = lane; j < a.W; j += 64)
-    dst[j] = (ln_in(a, row, t, j) - mean) * rstd * a.w[j] + a.b[j];
+  ln_row(
+      [=](int j) {
+        if (a.kind == 1) return (t == 0 ? a.cls[j] : row[j]) + a.pos[(long)t * a.W + j];
+        return row[j];
+      },
+      a.W, LN_EPS, a.w, a.b, a.dst + r * (long)a.W, lane);
 }
 
 // x[r][t][:] = token_embedding[ids[r][t]] + positional_embedding[t], t < T of ctx_len
@@ -194,87 +142,6 @@ __global__ void quick_gelu_kernel(float* __restrict__ x, long total) {
   if (i >= total) return;
   const float v = x[i];
   x[i] = v * (1.f / (1.f + expf(-1.702f * v)));
-}
-
-// ---- fused attention for short sequences ---------------------------------------------------
-// One workgroup per (sequence, head).  Q / sqrt(hd), K, V of the head live in LDS (rows
-// padded to hd + 1 floats); wave w owns query rows w, w + 4, ...: lanes walk the keys for
-// the scores and the softmax, then the head's columns for P V.
-//   causal:  keys j > i are excluded (the text tower's additive -inf mask);
-//   cls_mask: after the softmax, P[0][j] *= cls_mask[img][j - 1] for j >= 1, img = seq %
-//             n_img, for seq < n_masked only; not renormalised (rerankers.py:203-214).
-// qkv: [seq][T][3 W] (q | k | v, heads contiguous inside each), out: [seq][T][W].
-__global__ __launch_bounds__(ATT_THREADS) void attention_kernel(
-    const float* __restrict__ qkv, float* __restrict__ out, int T, int W, int hd, int causal,
-    const float* __restrict__ cls_mask, int n_img, int n_masked) {
-  extern __shared__ float lds[];
-  const int ldh = hd + 1;
-  float* Q = lds;
-  float* K = Q + (size_t)T * ldh;
-  float* V = K + (size_t)T * ldh;
-  float* P = V + (size_t)T * ldh;  // [4][T]
-  const int seq = blockIdx.x, head = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const float* base = qkv + (size_t)seq * T * 3 * W + (size_t)head * hd;
-  const float qs = sqrtf((float)hd);
-  for (int i = tid; i < T * hd; i += ATT_THREADS) {
-    const int t = i / hd, d = i % hd;
-    const float* p = base + (size_t)t * 3 * W + d;
-    Q[t * ldh + d] = p[0] / qs;
-    K[t * ldh + d] = p[W];
-    V[t * ldh + d] = p[2 * W];
-  }
-  __syncthreads();
-  const float* cm =
-      (cls_mask && seq < n_masked) ? cls_mask + (size_t)(seq % n_img) * (T - 1) : nullptr;
-  float* Pw = P + (size_t)w * T;
-  for (int i = w; i < T; i += 4) {
-    const int nk = causal ? i + 1 : T;
-    const float* q = Q + i * ldh;
-    float mx = -INFINITY;
-    for (int j = lane; j < nk; j += 64) {
-      const float* k = K + j * ldh;
-      float s = 0.f;
-      for (int d = 0; d < hd; ++d) s += q[d] * k[d];
-      Pw[j] = s;
-      mx = fmaxf(mx, s);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < nk; j += 64) {
-      const float e = expf(Pw[j] - mx);
-      Pw[j] = e;
-      sum += e;
-    }
-    sum = wave_sum(sum);
-    for (int j = lane; j < nk; j += 64) {
-      float p = Pw[j] / sum;
-      if (cm && i == 0 && j >= 1) p *= cm[j - 1];
-      Pw[j] = p;
-    }
-    // (the lanes of one wave wrote Pw; the wave reads it back below)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    for (int d = lane; d < hd; d += 64) {
-      float o = 0.f;
-      for (int j = 0; j < nk; ++j) o += Pw[j] * V[j * ldh + d];
-      out[((size_t)seq * T + i) * W + (size_t)head * hd + d] = o;
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
-}
-
-// x[r][:] /= ||x[r]||  (one wave per row)
-__global__ __launch_bounds__(256) void l2norm_kernel(const float* __restrict__ x,
-                                                      float* __restrict__ y, long rows, int E) {
-  const long r = blockIdx.x * 4L + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (r >= rows) return;
-  float q = 0.f;
-  for (int j = lane; j < E; j += 64) q += x[r * E + j] * x[r * E + j];
-  const float nrm = sqrtf(wave_sum(q));
-  for (int j = lane; j < E; j += 64) y[r * E + j] = x[r * E + j] / nrm;
 }
 
 // One wave per text row c of neuron n = neuron_of[c] (or c / candidates):
@@ -306,22 +173,11 @@ __global__ __launch_bounds__(256) void rerank_scores_kernel(
 }
 
 // ---- host side ------------------------------------------------------------------------------
-static size_t att_lds_bytes(int T, int hd) {
-  return sizeof(float) * (3 * (size_t)T * (hd + 1) + 4 * (size_t)T);
-}
-
-static int launch_ln(const LnArgs& a, hipStream_t s) {
+static int launch_gather_ln(const GatherLnArgs& a, hipStream_t s) {
   if (a.rows <= 0) return 0;
-  hipLaunchKernelGGL(layernorm_kernel, dim3(blocks_for(a.rows, 4)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(gather_layernorm_kernel, dim3(blocks_for(a.rows, 4)), dim3(256), 0, s, a);
   MILAN_CHECK_HIP(hipGetLastError());
   return 0;
-}
-static int ln_rows(const float* src, long stride, const float* w, const float* b, float* dst,
-                   long rows, int W, hipStream_t s) {
-  LnArgs a{};
-  a.src = src; a.stride = stride; a.kind = 0; a.w = w; a.b = b; a.dst = dst; a.rows = rows;
-  a.W = W;
-  return launch_ln(a, s);
 }
 
 // Workspace of a tower over `seqs` sequences of T tokens: x, y, big (max(3 W, 4 W) wide), the
@@ -329,7 +185,6 @@ static int ln_rows(const float* src, long stride, const float* w, const float* b
 struct Plan {
   size_t x, y, big, aux, scratch, scratch_floats, total_floats;
 };
-static size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 
 static size_t tower_scratch(long M, int W) {
   size_t s = 0;
@@ -344,26 +199,25 @@ static int run_tower(const milan_clip_ctx::Tower& tw, float* x, float* y, float*
                      uint64_t mask_layers, Scratch sc, hipStream_t s) {
   const int W = tw.width, hd = W / tw.heads;
   const long M = seqs * T;
-  const size_t lds = att_lds_bytes(T, hd);
-  MILAN_REQUIRE(lds <= LDS_LIMIT, MILAN_ERR_ARG,
+  MILAN_REQUIRE(lds_attention_fits(T, hd), MILAN_ERR_ARG,
                 "clip attention: %d tokens x head size %d need %zu bytes of LDS (limit %zu)", T,
-                hd, lds, LDS_LIMIT);
+                hd, lds_attention_bytes(T, hd), LDS_LIMIT);
   MILAN_REQUIRE(M < (1L << 31) / (4L * W), MILAN_ERR_ARG,
                 "clip: %ld tokens x width %d exceed the 2^31-element GEMM range", M, W);
-  MILAN_TRY(ensure_lds_attr((const void*)attention_kernel, (int)lds));
+  LdsAttention att{};  // uniform sequences of T tokens
+  att.qkv = big; att.out = y; att.T = T; att.max_len = T; att.W = W; att.hd = hd;
+  att.causal = causal; att.n_img = n_img; att.n_masked = n_masked;
   const View none = view(nullptr, 0);
   for (size_t l = 0; l < tw.blocks.size(); ++l) {
     const auto& b = tw.blocks[l];
-    MILAN_TRY(ln_rows(x, W, b.ln1_w, b.ln1_b, y, M, W, s));
+    MILAN_TRY(launch_layernorm_rows(x, W, y, (int)M, W, b.ln1_w, b.ln1_b, LN_EPS, s));
     MILAN_TRY(lmt::gemm(view(y, W), 0, view(b.in_w, W), 1, view(big, 3 * W), none, b.in_b,
                         nullptr, (int)M, 3 * W, W, sc, s));
-    const bool edit = cls_mask && l < 64 && ((mask_layers >> l) & 1);
-    hipLaunchKernelGGL(attention_kernel, dim3((unsigned)seqs, tw.heads), dim3(ATT_THREADS), lds,
-                       s, big, y, T, W, hd, causal, edit ? cls_mask : nullptr, n_img, n_masked);
-    MILAN_CHECK_HIP(hipGetLastError());
+    att.cls_mask = (cls_mask && l < 64 && ((mask_layers >> l) & 1)) ? cls_mask : nullptr;
+    MILAN_TRY(launch_lds_attention(att, seqs, tw.heads, s));
     MILAN_TRY(lmt::gemm(view(y, W), 0, view(b.out_w, W), 1, view(x, W), view(x, W), b.out_b,
                         nullptr, (int)M, W, W, sc, s));
-    MILAN_TRY(ln_rows(x, W, b.ln2_w, b.ln2_b, y, M, W, s));
+    MILAN_TRY(launch_layernorm_rows(x, W, y, (int)M, W, b.ln2_w, b.ln2_b, LN_EPS, s));
     MILAN_TRY(lmt::gemm(view(y, W), 0, view(b.fc_w, W), 1, view(big, 4 * W), none, b.fc_b,
                         nullptr, (int)M, 4 * W, W, sc, s));
     hipLaunchKernelGGL(quick_gelu_kernel, dim3(blocks_for(M * 4 * W)), dim3(256), 0, s, big,
@@ -376,7 +230,7 @@ static int run_tower(const milan_clip_ctx::Tower& tw, float* x, float* y, float*
 }
 
 static int image_plan(const milan_clip_ctx* c, int n, int copies, Plan* p) {
-  MILAN_REQUIRE(c && c->finalized, MILAN_ERR_STATE, "clip: weights are not finalized");
+  MILAN_REQUIRE(c && c->w.finalized, MILAN_ERR_STATE, "clip: weights are not finalized");
   MILAN_REQUIRE(n > 0 && (copies == 1 || copies == 2), MILAN_ERR_ARG,
                 "clip images: n %d, copies %d", n, copies);
   const auto& d = c->d;
@@ -401,7 +255,7 @@ static int image_plan(const milan_clip_ctx* c, int n, int copies, Plan* p) {
 }
 
 static int text_plan(const milan_clip_ctx* c, int rows, int positions, Plan* p) {
-  MILAN_REQUIRE(c && c->finalized, MILAN_ERR_STATE, "clip: weights are not finalized");
+  MILAN_REQUIRE(c && c->w.finalized, MILAN_ERR_STATE, "clip: weights are not finalized");
   const auto& d = c->d;
   MILAN_REQUIRE(rows > 0 && positions > 0 && positions <= d.context_length, MILAN_ERR_ARG,
                 "clip texts: rows %d, positions %d of context %d", rows, positions,
@@ -421,39 +275,7 @@ static int text_plan(const milan_clip_ctx* c, int rows, int positions, Plan* p) 
   p->total_floats = o;
   return 0;
 }
-
-static const float* find(milan_clip_ctx* c, const std::string& name, size_t count) {
-  auto it = c->raw.find(name);
-  if (it == c->raw.end()) {
-    set_error("clip: weight %s was not uploaded", name.c_str());
-    return nullptr;
-  }
-  size_t n = 1;
-  for (int64_t v : it->second.shape) n *= (size_t)v;
-  if (n != count) {
-    set_error("clip: weight %s has %zu elements, the dims need %zu", name.c_str(), n, count);
-    return nullptr;
-  }
-  return (const float*)it->second.dev;
-}
-
 }  // namespace clip
-
-namespace tower {
-int launch_patch_gather(const float* images, float* A, long n, int R, int P,
-                        const float* renorm_mul_add, hipStream_t s) {
-  const int G = R / P;
-  const long total = n * G * G * 3 * P * P;
-  if (total <= 0) return 0;
-  float ma[6] = {1.f, 1.f, 1.f, 0.f, 0.f, 0.f};
-  if (renorm_mul_add) memcpy(ma, renorm_mul_add, sizeof(ma));  // HOST floats
-  hipLaunchKernelGGL(clip::patch_gather_kernel, dim3(clip::blocks_for(total)), dim3(256), 0, s,
-                     images, A, total, R, P, G, ma[0], ma[1], ma[2], ma[3], ma[4], ma[5],
-                     renorm_mul_add ? 1 : 0);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-}  // namespace tower
 }  // namespace milan
 
 using namespace milan;
@@ -474,49 +296,42 @@ int milan_clip_create(milan_clip_ctx** out, int device, const milan_clip_dims* d
                     d.context_length > 0 && d.vocab_size > 0,
                 MILAN_ERR_SHAPE, "clip: layers, embed_dim, context_length, vocab_size must be > 0");
   const int G = d.resolution / d.patch;
-  const size_t lv = att_lds_bytes(G * G + 1, d.vision_width / d.vision_heads);
-  const size_t lt = att_lds_bytes(d.context_length, d.text_width / d.text_heads);
-  MILAN_REQUIRE(lv <= LDS_LIMIT && lt <= LDS_LIMIT, MILAN_ERR_SHAPE,
+  const int vhd = d.vision_width / d.vision_heads, thd = d.text_width / d.text_heads;
+  const size_t lv = lds_attention_bytes(G * G + 1, vhd);
+  const size_t lt = lds_attention_bytes(d.context_length, thd);
+  MILAN_REQUIRE(lds_attention_fits(G * G + 1, vhd) && lds_attention_fits(d.context_length, thd),
+                MILAN_ERR_SHAPE,
                 "clip attention: %d image tokens x head size %d (%zu bytes) or %d text tokens x "
                 "head size %d (%zu bytes) exceed %zu bytes of LDS",
-                G * G + 1, d.vision_width / d.vision_heads, lv, d.context_length,
-                d.text_width / d.text_heads, lt, LDS_LIMIT);
+                G * G + 1, vhd, lv, d.context_length, thd, lt, LDS_LIMIT);
   milan_clip_ctx* c = new milan_clip_ctx;
-  c->device = device;
+  c->w.device = device;
   c->d = d;
+  c->vis.width = d.vision_width; c->vis.heads = d.vision_heads;
+  c->txt.width = d.text_width; c->txt.heads = d.text_heads;
+  c->vis.blocks.assign(d.vision_layers, {});
+  c->txt.blocks.assign(d.text_layers, {});
   *out = c;
   return 0;
 }
 
 void milan_clip_destroy(milan_clip_ctx* c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->arena) (void)hipFree(c->arena);
+  c->w.release();
   delete c;
 }
 
 int milan_clip_set_weight(milan_clip_ctx* c, const char* name, const float* data,
                           const int64_t* shape, int ndim) {
-  MILAN_REQUIRE(c && name && data && (shape || ndim == 0) && ndim >= 0 && ndim <= 8,
-                MILAN_ERR_ARG, "milan_clip_set_weight: bad argument");
-  MILAN_REQUIRE(!c->finalized, MILAN_ERR_STATE,
-                "milan_clip_set_weight after milan_clip_finalize_weights");
-  Tensor t;
-  t.shape.assign(shape, shape + ndim);
-  t.dev = data;
-  c->raw[name] = t;
-  return 0;
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "milan_clip_set_weight: bad argument");
+  return c->w.set("clip", name, data, shape, ndim);
 }
 
 int milan_clip_finalize_weights(milan_clip_ctx* c, milan_stream stream) {
   MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
-  MILAN_REQUIRE(!c->finalized, MILAN_ERR_STATE, "clip weights already finalized");
-  hipStream_t s = (hipStream_t)stream;
-  MILAN_CHECK_HIP(hipSetDevice(c->device));
   const auto& d = c->d;
   const int G = d.resolution / d.patch, T = G * G + 1;
   // (name, element count, destination) of every tensor the towers read
-  struct Want { std::string name; size_t count; const float** dst; };
   std::vector<Want> wants;
   const size_t VW = d.vision_width, TW = d.text_width, E = d.embed_dim;
   wants.push_back({"visual.conv1.weight", VW * 3 * d.patch * d.patch, &c->conv1});
@@ -532,10 +347,6 @@ int milan_clip_finalize_weights(milan_clip_ctx* c, milan_stream stream) {
   wants.push_back({"ln_final.weight", TW, &c->ln_fin_w});
   wants.push_back({"ln_final.bias", TW, &c->ln_fin_b});
   wants.push_back({"text_projection", TW * E, &c->tproj});
-  c->vis.width = d.vision_width; c->vis.heads = d.vision_heads;
-  c->txt.width = d.text_width; c->txt.heads = d.text_heads;
-  c->vis.blocks.assign(d.vision_layers, {});
-  c->txt.blocks.assign(d.text_layers, {});
   for (int tower = 0; tower < 2; ++tower) {
     auto& tw = tower ? c->txt : c->vis;
     const size_t W = tw.width;
@@ -557,23 +368,7 @@ int milan_clip_finalize_weights(milan_clip_ctx* c, milan_stream stream) {
       wants.push_back({p + "mlp.c_proj.bias", W, &b.pj_b});
     }
   }
-  size_t total = 0;
-  for (auto& w : wants) {
-    if (!find(c, w.name, w.count)) return MILAN_ERR_STATE;
-    total += up64(w.count);
-  }
-  MILAN_CHECK_HIP(hipMalloc((void**)&c->arena, total * sizeof(float)));
-  size_t o = 0;
-  for (auto& w : wants) {
-    MILAN_CHECK_HIP(hipMemcpyAsync(c->arena + o, find(c, w.name, w.count),
-                                   w.count * sizeof(float), hipMemcpyDeviceToDevice, s));
-    *w.dst = c->arena + o;
-    o += up64(w.count);
-  }
-  MILAN_CHECK_HIP(hipStreamSynchronize(s));
-  c->raw.clear();
-  c->finalized = true;
-  return 0;
+  return c->w.finalize("clip", wants, (hipStream_t)stream);
 }
 
 size_t milan_clip_image_workspace_bytes(const milan_clip_ctx* c, int n, int both) {
@@ -599,7 +394,7 @@ int milan_clip_encode_images(milan_clip_ctx* c, const float* images, int n, int 
   MILAN_REQUIRE(ws_bytes >= p.total_floats * sizeof(float), MILAN_ERR_WORKSPACE,
                 "milan_clip_encode_images: workspace %zu < %zu bytes", ws_bytes,
                 p.total_floats * sizeof(float));
-  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  MILAN_CHECK_HIP(hipSetDevice(c->w.device));
   const hipStream_t s = (hipStream_t)stream;
   float* w = (float*)ws;
   const int G = d.resolution / d.patch, T = G * G + 1, W = d.vision_width, E = d.embed_dim;
@@ -612,7 +407,7 @@ int milan_clip_encode_images(milan_clip_ctx* c, const float* images, int n, int 
   float* cm = w + p.aux;
   float* cls_rows = cm + up64((size_t)np);
   float* emb = cls_rows + up64((size_t)seqs * std::max(W, E));
-  MILAN_TRY(tower::launch_patch_gather(images, patches, n, d.resolution, d.patch, renorm_mul_add,
+  MILAN_TRY(launch_patch_gather(images, patches, n, d.resolution, d.patch, renorm_mul_add,
                                        s));
   if (masks)
     hipLaunchKernelGGL(mask_downsample_kernel, dim3(blocks_for(np)), dim3(256), 0, s, masks, cm,
@@ -620,18 +415,17 @@ int milan_clip_encode_images(milan_clip_ctx* c, const float* images, int n, int 
   MILAN_CHECK_HIP(hipGetLastError());
   MILAN_TRY(lmt::gemm(view(patches, kk), 0, view(c->conv1, kk), 1, view(pe, W), none, nullptr,
                       nullptr, (int)np, W, kk, sc, s));
-  LnArgs a{};
+  GatherLnArgs a{};
   a.src = pe; a.cls = c->cls; a.pos = c->vpos; a.kind = 1; a.T = T; a.n_img = n;
   a.w = c->ln_pre_w; a.b = c->ln_pre_b; a.dst = w + p.x; a.rows = seqs * T; a.W = W;
-  MILAN_TRY(launch_ln(a, s));
+  MILAN_TRY(launch_gather_ln(a, s));
   MILAN_TRY(run_tower(c->vis, w + p.x, w + p.y, w + p.big, seqs, T, 0, masks ? cm : nullptr, n,
                       n, mask_layers, sc, s));
-  MILAN_TRY(ln_rows(w + p.x, (long)T * W, c->ln_post_w, c->ln_post_b, cls_rows, seqs, W, s));
+  MILAN_TRY(launch_layernorm_rows(w + p.x, (long)T * W, cls_rows, (int)seqs, W, c->ln_post_w,
+                                  c->ln_post_b, LN_EPS, s));
   MILAN_TRY(lmt::gemm(view(cls_rows, W), 0, view(c->vproj, E), 0, view(emb, E), none, nullptr,
                       nullptr, (int)seqs, E, W, sc, s));
-  hipLaunchKernelGGL(l2norm_kernel, dim3(blocks_for(seqs, 4)), dim3(256), 0, s, emb, out, seqs, E);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_l2norm(emb, out, (int)seqs, E, 1, s);
 }
 
 size_t milan_clip_text_workspace_bytes(const milan_clip_ctx* c, int rows, int positions) {
@@ -648,7 +442,7 @@ int milan_clip_encode_texts(milan_clip_ctx* c, const int64_t* tokens, int rows, 
   MILAN_REQUIRE(ws_bytes >= p.total_floats * sizeof(float), MILAN_ERR_WORKSPACE,
                 "milan_clip_encode_texts: workspace %zu < %zu bytes", ws_bytes,
                 p.total_floats * sizeof(float));
-  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  MILAN_CHECK_HIP(hipSetDevice(c->w.device));
   const hipStream_t s = (hipStream_t)stream;
   const auto& d = c->d;
   float* w = (float*)ws;
@@ -661,16 +455,13 @@ int milan_clip_encode_texts(milan_clip_ctx* c, const int64_t* tokens, int rows, 
                      c->tpos, w + p.x, M * W, T, d.context_length, W, d.vocab_size);
   MILAN_CHECK_HIP(hipGetLastError());
   MILAN_TRY(run_tower(c->txt, w + p.x, w + p.y, w + p.big, rows, T, 1, nullptr, 1, 0, 0, sc, s));
-  LnArgs a{};
+  GatherLnArgs a{};
   a.src = w + p.x; a.kind = 2; a.T = T; a.ids = tokens; a.ctx_len = d.context_length;
   a.w = c->ln_fin_w; a.b = c->ln_fin_b; a.dst = eot_rows; a.rows = rows; a.W = W;
-  MILAN_TRY(launch_ln(a, s));
+  MILAN_TRY(launch_gather_ln(a, s));
   MILAN_TRY(lmt::gemm(view(eot_rows, W), 0, view(c->tproj, E), 0, view(emb, E),
                       view(nullptr, 0), nullptr, nullptr, rows, E, W, sc, s));
-  hipLaunchKernelGGL(l2norm_kernel, dim3(blocks_for(rows, 4)), dim3(256), 0, s, emb, out,
-                     (long)rows, E);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
+  return launch_l2norm(emb, out, rows, E, 1, s);
 }
 
 int milan_clip_rerank_scores(const float* masked, const float* unmasked, const float* texts,

@@ -4,11 +4,11 @@
 // A context of its own (milan_vit_ctx): dims + one weight arena in DINO's state-dict layout,
 // row-major as torch stores it.  Every contraction goes through lmt::gemm_rows (split count a
 // function of K alone) and attention works per (sequence, head), so an image's taps do not
-// depend on the other images of the call.  LayerNorm, the erf GELU and the patch gather are
-// the kernels of bert.hip / clip.hip (tower_common.h).
+// depend on the other images of the call.  LayerNorm, the erf GELU, the patch gather and the
+// weight store are the towers' shared parts (tower.hip).
 //
-// Attention (attention_kernel): clip.hip and bert.hip hold Q, K, V of a whole head in LDS, which
-// ends near 64 tokens.  Here a workgroup owns 128 query rows of one (sequence, head), 32 per
+// Attention (attention_kernel): the towers' shared kernel holds Q, K, V of a whole head in LDS,
+// which ends near 64 tokens.  Here a workgroup owns 128 query rows of one (sequence, head), 32 per
 // wave, and streams K / V through LDS 32 keys at a time with the online softmax (running max
 // and sum per query row); the T x T scores exist only as one 32 x 32 accumulator tile per wave.
 // Both products run on the fp32 MFMA (v_mfma_f32_32x32x2_f32), transposed so that no operand
@@ -30,11 +30,8 @@
 #include <algorithm>
 
 struct milan_vit_ctx {
-  int device = 0;
   milan_vit_dims d{};
-  bool finalized = false;
-  std::map<std::string, milan::Tensor> raw;
-  float* arena = nullptr;
+  milan::tower::Weights w;
   struct Block {
     const float *ln1_w, *ln1_b, *qkv_w, *qkv_b, *proj_w, *proj_b, *ln2_w, *ln2_b, *fc1_w, *fc1_b,
         *fc2_w, *fc2_b;
@@ -50,6 +47,7 @@ namespace vit {
 using lmt::Scratch;
 using lmt::View;
 using lmt::view;
+using namespace milan::tower;
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
@@ -57,9 +55,6 @@ constexpr int ATT_THREADS = 256;
 constexpr int ATT_BM = 128;  // query rows per workgroup (32 per wave)
 constexpr int ATT_BN = 32;   // keys per LDS tile
 constexpr int ATT_MAX_HD = 128;
-
-static inline unsigned blocks_for(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
-static size_t up64(size_t v) { return (v + 63) / 64 * 64; }
 
 // LDS row strides in floats.  K rows are read 16 bytes per lane, lane = key: stride HD + 4
 // spreads 16 consecutive keys over all banks.  V rows are read 4 bytes per lane, the two lane
@@ -293,7 +288,7 @@ struct Plan {
 };
 
 static int plan(const milan_vit_ctx* c, int n, Plan* p) {
-  MILAN_REQUIRE(c && c->finalized, MILAN_ERR_STATE, "vit: weights are not finalized");
+  MILAN_REQUIRE(c && c->w.finalized, MILAN_ERR_STATE, "vit: weights are not finalized");
   MILAN_REQUIRE(n > 0, MILAN_ERR_ARG, "vit: %d images", n);
   const auto& d = c->d;
   const int G = d.resolution / d.patch, T = G * G + 1, W = d.width, H = d.hidden;
@@ -316,22 +311,6 @@ static int plan(const milan_vit_ctx* c, int n, Plan* p) {
   p->total_floats = o;
   return 0;
 }
-
-static const float* find(milan_vit_ctx* c, const std::string& name, size_t count) {
-  auto it = c->raw.find(name);
-  if (it == c->raw.end()) {
-    set_error("vit: weight %s was not uploaded", name.c_str());
-    return nullptr;
-  }
-  size_t n = 1;
-  for (int64_t v : it->second.shape) n *= (size_t)v;
-  if (n != count) {
-    set_error("vit: weight %s has %zu elements, the dims need %zu", name.c_str(), n, count);
-    return nullptr;
-  }
-  return (const float*)it->second.dev;
-}
-
 }  // namespace vit
 }  // namespace milan
 
@@ -358,40 +337,29 @@ int milan_vit_create(milan_vit_ctx** out, int device, const milan_vit_dims* dims
   const int G = d.resolution / d.patch;
   MILAN_TRY(check_attention_shape(1, G * G + 1, d.width, d.heads));
   milan_vit_ctx* c = new milan_vit_ctx;
-  c->device = device;
+  c->w.device = device;
   c->d = d;
+  c->blocks.assign(d.layers, {});
   *out = c;
   return 0;
 }
 
 void milan_vit_destroy(milan_vit_ctx* c) {
   if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->arena) (void)hipFree(c->arena);
+  c->w.release();
   delete c;
 }
 
 int milan_vit_set_weight(milan_vit_ctx* c, const char* name, const float* data,
                          const int64_t* shape, int ndim) {
-  MILAN_REQUIRE(c && name && data && (shape || ndim == 0) && ndim >= 0 && ndim <= 8,
-                MILAN_ERR_ARG, "milan_vit_set_weight: bad argument");
-  MILAN_REQUIRE(!c->finalized, MILAN_ERR_STATE,
-                "milan_vit_set_weight after milan_vit_finalize_weights");
-  Tensor t;
-  t.shape.assign(shape, shape + ndim);
-  t.dev = data;
-  c->raw[name] = t;
-  return 0;
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "milan_vit_set_weight: bad argument");
+  return c->w.set("vit", name, data, shape, ndim);
 }
 
 int milan_vit_finalize_weights(milan_vit_ctx* c, milan_stream stream) {
   MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
-  MILAN_REQUIRE(!c->finalized, MILAN_ERR_STATE, "vit weights already finalized");
-  hipStream_t s = (hipStream_t)stream;
-  MILAN_CHECK_HIP(hipSetDevice(c->device));
   const auto& d = c->d;
   const int G = d.resolution / d.patch, T = G * G + 1;
-  struct Want { std::string name; size_t count; const float** dst; };
   std::vector<Want> wants;
   const size_t W = d.width, H = d.hidden;
   wants.push_back({"patch_embed.proj.weight", W * 3 * d.patch * d.patch, &c->conv_w});
@@ -400,7 +368,6 @@ int milan_vit_finalize_weights(milan_vit_ctx* c, milan_stream stream) {
   wants.push_back({"pos_embed", (size_t)T * W, &c->pos});
   wants.push_back({"norm.weight", W, &c->norm_w});
   wants.push_back({"norm.bias", W, &c->norm_b});
-  c->blocks.assign(d.layers, {});
   for (int l = 0; l < d.layers; ++l) {
     const std::string p = "blocks." + std::to_string(l) + ".";
     auto& b = c->blocks[l];
@@ -417,23 +384,7 @@ int milan_vit_finalize_weights(milan_vit_ctx* c, milan_stream stream) {
     wants.push_back({p + "mlp.fc2.weight", W * H, &b.fc2_w});
     wants.push_back({p + "mlp.fc2.bias", W, &b.fc2_b});
   }
-  size_t total = 0;
-  for (auto& w : wants) {
-    if (!find(c, w.name, w.count)) return MILAN_ERR_STATE;
-    total += up64(w.count);
-  }
-  MILAN_CHECK_HIP(hipMalloc((void**)&c->arena, total * sizeof(float)));
-  size_t o = 0;
-  for (auto& w : wants) {
-    MILAN_CHECK_HIP(hipMemcpyAsync(c->arena + o, find(c, w.name, w.count),
-                                   w.count * sizeof(float), hipMemcpyDeviceToDevice, s));
-    *w.dst = c->arena + o;
-    o += up64(w.count);
-  }
-  MILAN_CHECK_HIP(hipStreamSynchronize(s));
-  c->raw.clear();
-  c->finalized = true;
-  return 0;
+  return c->w.finalize("vit", wants, (hipStream_t)stream);
 }
 
 size_t milan_vit_workspace_bytes(const milan_vit_ctx* c, int n) {
@@ -461,7 +412,7 @@ int milan_vit_run(milan_vit_ctx* c, const float* images, int n, int resolution,
   MILAN_REQUIRE(ws_bytes >= p.total_floats * sizeof(float), MILAN_ERR_WORKSPACE,
                 "milan_vit_run: workspace %zu < %zu bytes", ws_bytes,
                 p.total_floats * sizeof(float));
-  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  MILAN_CHECK_HIP(hipSetDevice(c->w.device));
   const hipStream_t s = (hipStream_t)stream;
   float* w = (float*)ws;
   const int G = d.resolution / d.patch, T = G * G + 1, W = d.width, H = d.hidden;
@@ -472,7 +423,7 @@ int milan_vit_run(milan_vit_ctx* c, const float* images, int n, int resolution,
   float *x = w + p.x, *y = w + p.y, *big = w + p.big;
   float* patches = big;
   float* pe = patches + up64((size_t)np * kk);
-  MILAN_TRY(tower::launch_patch_gather(images, patches, n, d.resolution, d.patch, nullptr, s));
+  MILAN_TRY(launch_patch_gather(images, patches, n, d.resolution, d.patch, nullptr, s));
   MILAN_TRY(lmt::gemm_rows(view(patches, kk), 0, view(c->conv_w, kk), 1, view(pe, W), none,
                            c->conv_b, nullptr, np, W, kk, sc, s));
   hipLaunchKernelGGL(embed_tokens_kernel, dim3(blocks_for((long)M * W)), dim3(256), 0, s, pe,
@@ -480,13 +431,13 @@ int milan_vit_run(milan_vit_ctx* c, const float* images, int n, int resolution,
   MILAN_CHECK_HIP(hipGetLastError());
   for (int l = 0; l <= last; ++l) {
     const auto& b = c->blocks[l];
-    MILAN_TRY(tower::launch_layernorm_rows(x, W, y, M, W, b.ln1_w, b.ln1_b, d.eps, s));
+    MILAN_TRY(launch_layernorm_rows(x, W, y, M, W, b.ln1_w, b.ln1_b, d.eps, s));
     MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.qkv_w, W), 1, view(big, 3 * W), none, b.qkv_b,
                              nullptr, M, 3 * W, W, sc, s));
     MILAN_TRY(launch_attention(big, y, n, T, W, d.heads, s));
     MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.proj_w, W), 1, view(x, W), view(x, W),
                              b.proj_b, nullptr, M, W, W, sc, s));
-    MILAN_TRY(tower::launch_layernorm_rows(x, W, y, M, W, b.ln2_w, b.ln2_b, d.eps, s));
+    MILAN_TRY(launch_layernorm_rows(x, W, y, M, W, b.ln2_w, b.ln2_b, d.eps, s));
     float* tap = taps ? taps[l] : nullptr;
     if (l == last && !cls_out) {  // the deepest tap: fc1 writes it, and the walk is over
       MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.fc1_w, W), 1, view(tap, H), none, b.fc1_b,
@@ -498,12 +449,12 @@ int milan_vit_run(milan_vit_ctx* c, const float* images, int n, int resolution,
     if (tap)
       MILAN_CHECK_HIP(hipMemcpyAsync(tap, big, (size_t)M * H * sizeof(float),
                                      hipMemcpyDeviceToDevice, s));
-    MILAN_TRY(tower::launch_gelu_erf(big, (long)M * H, s));
+    MILAN_TRY(launch_gelu_erf(big, (long)M * H, s));
     MILAN_TRY(lmt::gemm_rows(view(big, H), 0, view(b.fc2_w, H), 1, view(x, W), view(x, W),
                              b.fc2_b, nullptr, M, W, H, sc, s));
   }
   if (cls_out)
-    MILAN_TRY(tower::launch_layernorm_rows(x, (long)T * W, cls_out, n, W, c->norm_w, c->norm_b,
+    MILAN_TRY(launch_layernorm_rows(x, (long)T * W, cls_out, n, W, c->norm_w, c->norm_b,
                                            d.eps, s));
   return 0;
 }

@@ -1702,21 +1702,23 @@ class Context:
         return self._guarded('describe', run, check)
 
 
-class ClipContext:
-    """Owns one `milan_clip_ctx`: the weights of a ViT CLIP on one GPU and a
-    workspace.  Every call computes in exact fp32 on torch's current stream and
-    does not synchronise."""
+class _TowerContext:
+    """Owns one `milan_<prefix>_ctx` (the weights of one transformer tower model on one GPU)
+    and a grow-only workspace.  Subclasses set `_prefix` and add their calls."""
 
-    def __init__(self, dims: ClipDims, state_dict: Dict[str, torch.Tensor],
-                 device: torch.device):
+    _prefix = ''
+
+    def __init__(self, dims, state_dict: Dict[str, torch.Tensor], device: torch.device):
         self.lib = load_library()
+        if not hasattr(self.lib, f'milan_{self._prefix}_create'):
+            raise HipUnavailableError(
+                f'this build of libmilan_hip has no milan_{self._prefix}_create')
         self.device = require_device(device)
         self.dims = dims
         self._h = _P()
         with torch.cuda.device(self.device):
-            _check(self.lib.milan_clip_create(ctypes.byref(self._h),
-                                              self.device.index,
-                                              ctypes.byref(dims)))
+            _check(self._fn('create')(ctypes.byref(self._h), self.device.index,
+                                      ctypes.byref(dims)))
             keep = []
             for name, tensor in state_dict.items():
                 if not tensor.dtype.is_floating_point:
@@ -1724,17 +1726,18 @@ class ClipContext:
                 t = _dev(tensor.detach(), self.device, torch.float32)
                 keep.append(t)
                 shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
-                _check(self.lib.milan_clip_set_weight(self._h, name.encode(),
-                                                      t.data_ptr(), shape,
-                                                      t.dim()))
-            _check(self.lib.milan_clip_finalize_weights(self._h,
-                                                        _stream(self.device)))
+                _check(self._fn('set_weight')(self._h, name.encode(), t.data_ptr(), shape,
+                                              t.dim()))
+            _check(self._fn('finalize_weights')(self._h, _stream(self.device)))
             del keep
         self._ws: Optional[torch.Tensor] = None
 
+    def _fn(self, name: str):
+        return getattr(self.lib, f'milan_{self._prefix}_{name}')
+
     def close(self) -> None:
         if getattr(self, '_h', None):
-            self.lib.milan_clip_destroy(self._h)
+            self._fn('destroy')(self._h)
             self._h = None
         self._ws = None
 
@@ -1751,6 +1754,14 @@ class ClipContext:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
+
+
+class ClipContext(_TowerContext):
+    """Owns one `milan_clip_ctx`: the weights of a ViT CLIP on one GPU and a
+    workspace.  Every call computes in exact fp32 on torch's current stream and
+    does not synchronise."""
+
+    _prefix = 'clip'
 
     def encode_images(self, images: torch.Tensor,
                       masks: Optional[torch.Tensor] = None,
@@ -1820,55 +1831,12 @@ class ClipContext:
         return out
 
 
-class BertContext:
+class BertContext(_TowerContext):
     """Owns one `milan_bert_ctx`: the weights of a BERT-family encoder on one
     GPU and a workspace.  Every call computes in exact fp32 on torch's current
     stream and does not synchronise."""
 
-    def __init__(self, dims: BertDims, state_dict: Dict[str, torch.Tensor],
-                 device: torch.device):
-        self.lib = load_library()
-        self.device = require_device(device)
-        self.dims = dims
-        self._h = _P()
-        with torch.cuda.device(self.device):
-            _check(self.lib.milan_bert_create(ctypes.byref(self._h),
-                                              self.device.index,
-                                              ctypes.byref(dims)))
-            keep = []
-            for name, tensor in state_dict.items():
-                if not tensor.dtype.is_floating_point:
-                    continue
-                t = _dev(tensor.detach(), self.device, torch.float32)
-                keep.append(t)
-                shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
-                _check(self.lib.milan_bert_set_weight(self._h, name.encode(),
-                                                      t.data_ptr(), shape,
-                                                      t.dim()))
-            _check(self.lib.milan_bert_finalize_weights(self._h,
-                                                        _stream(self.device)))
-            del keep
-        self._ws: Optional[torch.Tensor] = None
-
-    def close(self) -> None:
-        if getattr(self, '_h', None):
-            self.lib.milan_bert_destroy(self._h)
-            self._h = None
-        self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter shutdown
-            pass
-
-    def _workspace(self, need: int) -> torch.Tensor:
-        if need == 0:
-            _check(ERR_ARG)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+    _prefix = 'bert'
 
     def encode(self, ids: torch.Tensor, offsets: torch.Tensor, max_len: int,
                normalize: bool = True,
@@ -1922,46 +1890,12 @@ class BertContext:
         return out
 
 
-class VitContext:
+class VitContext(_TowerContext):
     """Owns one `milan_vit_ctx`: the weights of a DINO-style vision transformer on one GPU
     and a workspace.  Every call computes in exact fp32 on torch's current stream and does
     not synchronise."""
 
-    def __init__(self, dims: VitDims, state_dict: Dict[str, torch.Tensor],
-                 device: torch.device):
-        self.lib = load_library()
-        if not hasattr(self.lib, 'milan_vit_create'):
-            raise HipUnavailableError('this build of libmilan_hip has no milan_vit_create')
-        self.device = require_device(device)
-        self.dims = dims
-        self._h = _P()
-        with torch.cuda.device(self.device):
-            _check(self.lib.milan_vit_create(ctypes.byref(self._h), self.device.index,
-                                             ctypes.byref(dims)))
-            keep = []
-            for name, tensor in state_dict.items():
-                if not tensor.dtype.is_floating_point:
-                    continue
-                t = _dev(tensor.detach(), self.device, torch.float32)
-                keep.append(t)
-                shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
-                _check(self.lib.milan_vit_set_weight(self._h, name.encode(), t.data_ptr(),
-                                                     shape, t.dim()))
-            _check(self.lib.milan_vit_finalize_weights(self._h, _stream(self.device)))
-            del keep
-        self._ws: Optional[torch.Tensor] = None
-
-    def close(self) -> None:
-        if getattr(self, '_h', None):
-            self.lib.milan_vit_destroy(self._h)
-            self._h = None
-        self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter shutdown
-            pass
+    _prefix = 'vit'
 
     @property
     def tokens(self) -> int:
@@ -1988,15 +1922,10 @@ class VitContext:
             return outs, cls
         pointers = (_P * d.layers)(*[_ptr(outs.get(l)) for l in range(d.layers)])
         with torch.cuda.device(self.device):
-            need = int(self.lib.milan_vit_workspace_bytes(self._h, n))
-            if need == 0:
-                _check(ERR_ARG)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._workspace(int(self.lib.milan_vit_workspace_bytes(self._h, n)))
             _check(self.lib.milan_vit_run(self._h, images.data_ptr(), n, images.shape[2],
-                                          pointers, _ptr(cls), self._ws.data_ptr(),
-                                          self._ws.numel(), _stream(self.device)))
+                                          pointers, _ptr(cls), ws.data_ptr(), ws.numel(),
+                                          _stream(self.device)))
         return outs, cls
 
 

@@ -1157,6 +1157,96 @@ int milan_vit_run(milan_vit_ctx* ctx, const float* images, int n, int resolution
                   float* const* taps, float* cls_out, void* workspace,
                   size_t workspace_bytes, milan_stream stream);
 
+/* ---- The attention block of a BigGAN generator ----------------------------------------
+ * MILAN_ABI_VERSION did not change with this entry point: probe for it
+ * (dlsym / hasattr(lib, "milan_sagan_attention")).
+ *
+ * milan_sagan_attention: the non-local block of SAGAN / BigGAN between its 1 x 1
+ * convs, for n images of height x width pixels with `channels` channels, dk =
+ * channels / 8, dv = channels / 2:
+ *     out_i = sum_j softmax_j(theta_i . phi_j) g_j        (no scale factor)
+ * over the height * width queries i and the height * width / 4 keys j of one image.
+ * Pixel-major (NHWC) throughout, so the 1 x 1 convs around it are plain GEMMs:
+ *   theta: fp32 DEVICE, 8-byte aligned; the dk query columns of pixel p of image b
+ *     start at theta + (b * height * width + p) * theta_stride.  theta_stride is
+ *     in floats, even and >= dk: dk for a dense (n, height * width, dk) tensor,
+ *     dk + dk + dv for the first columns of a fused theta | phi | g conv output.
+ *   phi_g: (n, height * width / 4, dk + dv) fp32 DEVICE, 16-byte aligned, dense:
+ *     per 2 x 2 max-pooled pixel the dk key columns, then the dv value columns.
+ *   out: (n, height * width, dv) fp32 DEVICE, 16-byte aligned, dense.
+ *   channels must be a multiple of 32 from 32 to 384 (dk = 4 .. 48, dv = 16 ..
+ *     192; BigGAN-128 / -256 have 192, BigGAN-512 has 384), height and width even
+ *     (the pooling): anything else is MILAN_ERR_SHAPE and the message names the
+ *     offending dimension.  n = 0 does nothing.
+ * The scores never reach memory: a workgroup owns 128 queries of one image and
+ * streams phi | g through LDS 32 keys at a time under an online softmax; both
+ * products are exact fp32 MFMA.  Needs no workspace.  Deterministic, and the bits
+ * of one image do not depend on the other images of the call.  Non-finite inputs
+ * are not specified.  Does not synchronise. */
+int milan_sagan_attention(const float* theta, int64_t theta_stride, const float* phi_g,
+                          float* out, int n, int height, int width, int channels,
+                          milan_stream stream);
+
+/* A BigGAN generator as ajbrock/BigGAN-PyTorch and pretorched build it (shared class
+ * embedding, class-conditional batch norm, optional hierarchical z, one SAGAN attention
+ * block), eval mode, weights under their pretorched state-dict names (shared.weight,
+ * linear.weight/bias, blocks.I.0.{conv1,conv2,conv_sc}.weight/bias,
+ * blocks.I.0.{bn1,bn2}.{gain,bias}.weight and .stored_mean/.stored_var,
+ * blocks.I.1.{theta,phi,g,o}.weight and .gamma, output_layer.0.gain/bias/stored_mean/
+ * stored_var, output_layer.2.weight/bias), row-major fp32 as torch stores them.
+ * Spectral norm is the caller's: upload weight / sv, the eval-mode weight (no u0 / sv0).
+ * create / set_weight / finalize_weights / destroy behave as their milan_vit_*
+ * namesakes; finalize_weights also packs the convolutions (theta | phi | g as one
+ * 1 x 1 conv, gamma folded into o, the 3-channel output conv padded to 4 rows).
+ * Exact fp32: every convolution runs on the implicit-GEMM MFMA tile chosen from the
+ * layer alone, the batch norms are folded at run time to one scale and shift per
+ * (sample, channel), the attention is milan_sagan_attention.  Deterministic; the
+ * results for a sample do not depend on the other samples of the call.  The shortcut
+ * of a block is conv_sc at the input side upsampled afterwards (a 1 x 1 conv commutes
+ * with nearest upsampling), so sums are not formed in torch's order. */
+typedef struct milan_gan_ctx milan_gan_ctx;
+typedef struct milan_gan_dims {
+  int32_t ch;              /* 96: channel multiplier, a multiple of 4                   */
+  int32_t dim_z;           /* 120: columns of z (hierarchical: a multiple of blocks + 1) */
+  int32_t shared_dim;      /* 128: columns of shared.weight                              */
+  int32_t n_classes;       /* 1000                                                       */
+  int32_t resolution;      /* 32, 64, 128, 256 or 512: selects the block table           */
+  int32_t bottom_width;    /* 4: side of the first feature map                           */
+  int32_t attn_resolution; /* 64: the block at this table resolution (8 << index) is
+                              followed by attention; 0: none.  Its channel count must be
+                              one milan_sagan_attention takes                            */
+  int32_t hier;            /* 1: z is split into blocks + 1 chunks; chunk 0 feeds linear,
+                              chunk i + 1 joins y as block i's condition                 */
+  float bn_eps;            /* the conditional batch norms' eps (1e-4 in BigGAN-256)     */
+  float out_bn_eps;        /* the output batch norm's eps (1e-5)                         */
+} milan_gan_dims;
+
+int milan_gan_create(milan_gan_ctx** out, int device, const milan_gan_dims* dims);
+void milan_gan_destroy(milan_gan_ctx* ctx);
+int milan_gan_set_weight(milan_gan_ctx* ctx, const char* name, const float* data,
+                         const int64_t* shape, int ndim);
+int milan_gan_finalize_weights(milan_gan_ctx* ctx, milan_stream stream);
+/* number of taps: one per block plus one for the attention block, in walk order
+ * (layer0, .., layerK, attnK, layerK+1, ..) */
+int milan_gan_taps(const milan_gan_ctx* ctx);
+
+/* One walk over n samples.
+ *   z: (n, dim_z) fp32 DEVICE.
+ *   classes: (n) int64 DEVICE class indices, or NULL; y: fp32 DEVICE or NULL: with
+ *     y_embedded the embedded classes (n, shared_dim), otherwise soft labels (n,
+ *     n_classes), which are multiplied by shared.weight.  Exactly one of classes and
+ *     y is given.  An index outside 0 .. n_classes - 1 is clamped: check it before.
+ *   taps: HOST array of milan_gan_taps() DEVICE pointers, or NULL.  A non-null
+ *     taps[j] receives the output h of that block, (n, C, H, W) fp32 NCHW.
+ *   images_out: NULL, or (n, 3, resolution, resolution) fp32 DEVICE, tanh included.
+ *   Without images_out the walk ends after the deepest tap asked for: no later block
+ *   runs.  At least one output must be asked for.  Does not synchronise. */
+size_t milan_gan_workspace_bytes(const milan_gan_ctx* ctx, int n);
+int milan_gan_run(milan_gan_ctx* ctx, const float* z, const int64_t* classes,
+                  const float* y, int y_embedded, int n, float* const* taps,
+                  float* images_out, void* workspace, size_t workspace_bytes,
+                  milan_stream stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

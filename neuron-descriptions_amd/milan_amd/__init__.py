@@ -5,7 +5,7 @@
     captions = decoder.predict(dataset, strategy='rerank', temperature=.2,
                                beam_size=50, device='cuda')
 """
-from milan_amd import ablations, classifiers, vits
+from milan_amd import ablations, classifiers, generators, vits
 from milan_amd.ablations import ImageClassifier
 from milan_amd.classifiers import ResNetClassifier
 from milan_amd.decoders import (STRATEGIES, STRATEGY_BEAM, STRATEGY_GREEDY,
@@ -19,7 +19,8 @@ from milan_amd.rerankers import (CLIPWithMasks, CLIPWithMasksReranker,
                                  RerankerOutput, reranker)
 
 __all__ = [
-    'ablations', 'classifiers', 'vits', 'ImageClassifier', 'ResNetClassifier',
+    'ablations', 'classifiers', 'generators', 'vits', 'ImageClassifier',
+    'ResNetClassifier',
     'Decoder', 'DecoderOutput', 'DecoderState', 'DecoderStep',
     'DecoderWithCLIP', 'CLIPWithMasks', 'CLIPWithMasksReranker',
     'RerankerOutput', 'reranker', 'Encoder',

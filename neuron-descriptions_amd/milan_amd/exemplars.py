@@ -907,16 +907,37 @@ def generative(model: nn.Module,
     if viz_dir is not None:
         viz_dir = pathlib.Path(viz_dir) / str(layer)
     model.to(device)
-    hook = _Retain(model, str(layer))
+    # A model that hands its layers out itself (a `generate(inputs, layer, images)` method plus
+    # `layers`, e.g. generators.SeqBigGAN) is asked: its native forward runs no torch
+    # sub-module, so a forward hook on one would never fire.  The hiddens-only pass asks for
+    # no images, which lets such a model stop at the layer.
+    asks = callable(getattr(model, 'generate', None)) and hasattr(model, 'layers')
+    hook = _Retain(model, None if asks else str(layer))
+
+    def ask(args, images):
+        inputs = transform_inputs(*map_location(args, device))
+        if not isinstance(inputs, tuple) or len(inputs) != 1:
+            raise ValueError('a model with `generate` takes one input, as a 1-tuple; '
+                             f'transform_inputs returned {type(inputs)}')
+        with torch.no_grad():
+            return model.generate(inputs[0], layer=str(layer), images=images)
 
     def run(*args):
+        if asks:
+            hiddens, images = ask(args, True)
+            return transform_hiddens(hiddens), transform_outputs(images)
         inputs = transform_inputs(*map_location(args, device))
         with torch.no_grad():
             images = _run_model(model, inputs)
         return transform_hiddens(hook.output), transform_outputs(images)
 
+    def hiddens_only(*args):
+        if asks:
+            return transform_hiddens(ask(args, False)[0])
+        return run(*args)[0]
+
     try:
-        return compute(lambda *a: run(*a)[0], run, dataset,
+        return compute(hiddens_only, run, dataset,
                        results_dir=results_dir, viz_dir=viz_dir, **kwargs)
     finally:
         hook.close()

@@ -106,6 +106,14 @@ class VitDims(ctypes.Structure):
         'resolution', 'patch', 'width', 'layers', 'heads', 'hidden')] + [('eps', ctypes.c_float)]
 
 
+class GanDims(ctypes.Structure):
+    """struct milan_gan_dims."""
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        'ch', 'dim_z', 'shared_dim', 'n_classes', 'resolution', 'bottom_width',
+        'attn_resolution', 'hier')] + [('bn_eps', ctypes.c_float),
+                                       ('out_bn_eps', ctypes.c_float)]
+
+
 ABI_VERSION = 11  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
@@ -286,6 +294,17 @@ SIGNATURES = {
     'milan_vit_finalize_weights': (_I, [_P, _P]),
     'milan_vit_workspace_bytes': (_SZ, [_P, _I]),
     'milan_vit_run': (_I, [_P, _P, _I, _I, ctypes.POINTER(_P), _P, _P, _SZ, _P]),
+    'milan_sagan_attention': (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _I, _I, _P]),
+    'milan_gan_create': (_I, [ctypes.POINTER(_P), _I,
+                              ctypes.POINTER(GanDims)]),
+    'milan_gan_destroy': (None, [_P]),
+    'milan_gan_set_weight':
+        (_I, [_P, ctypes.c_char_p, _P,
+              ctypes.POINTER(ctypes.c_int64), _I]),
+    'milan_gan_finalize_weights': (_I, [_P, _P]),
+    'milan_gan_taps': (_I, [_P]),
+    'milan_gan_workspace_bytes': (_SZ, [_P, _I]),
+    'milan_gan_run': (_I, [_P, _P, _P, _P, _I, _I, ctypes.POINTER(_P), _P, _P, _SZ, _P]),
 }
 
 # entry points added without a new ABI version: a library built before them
@@ -298,7 +317,10 @@ PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_activations', 'milan_set_alexnet_head', 'milan_linear_packed_bytes',
           'milan_linear_pack', 'milan_linear', 'milan_linear_rowwise', 'milan_attention',
           'milan_vit_create', 'milan_vit_destroy', 'milan_vit_set_weight',
-          'milan_vit_finalize_weights', 'milan_vit_workspace_bytes', 'milan_vit_run')
+          'milan_vit_finalize_weights', 'milan_vit_workspace_bytes', 'milan_vit_run',
+          'milan_sagan_attention', 'milan_gan_create', 'milan_gan_destroy',
+          'milan_gan_set_weight', 'milan_gan_finalize_weights', 'milan_gan_taps',
+          'milan_gan_workspace_bytes', 'milan_gan_run')
 
 _lib = None
 
@@ -1929,6 +1951,75 @@ class VitContext(_TowerContext):
         return outs, cls
 
 
+# channel multipliers (out) of a BigGAN generator's blocks per resolution; block i doubles the
+# side from bottom_width << i
+_GAN_OUT = {512: (16, 8, 8, 4, 2, 1, 1), 256: (16, 8, 8, 4, 2, 1), 128: (16, 8, 4, 2, 1),
+            64: (16, 8, 4, 2), 32: (4, 4, 4)}
+
+
+class GanContext(_TowerContext):
+    """Owns one `milan_gan_ctx`: the weights of a BigGAN generator on one GPU (spectral norm
+    already folded: `state_dict` holds weight / sv and no u0 / sv0) and a workspace.  Every
+    call computes in exact fp32 on torch's current stream and does not synchronise."""
+
+    _prefix = 'gan'
+
+    @property
+    def tap_shapes(self):
+        """[(channels, side)] of the taps in walk order: layer0, .., layerK, attnK, .."""
+        d, shapes = self.dims, []
+        for i, mult in enumerate(_GAN_OUT[d.resolution]):
+            shapes.append((d.ch * mult, d.bottom_width << (i + 1)))
+            if d.attn_resolution == 8 << i:
+                shapes.append(shapes[-1])
+        return shapes
+
+    def run(self, z: torch.Tensor, y: torch.Tensor, embedded: bool = False,
+            taps: Sequence[int] = (), want_images: bool = False):
+        """z (n, dim_z); y: class indices (n,) int64, soft labels (n, n_classes), or with
+        `embedded` the embedded classes (n, shared_dim) -> ({tap: (n, C, H, W) output of that
+        block}, the (n, 3, R, R) images or None).  The walk ends after the deepest block in
+        `taps` unless `want_images`."""
+        d = self.dims
+        if z.dim() != 2 or z.shape[1] != d.dim_z:
+            raise ValueError(f'z must be (n, {d.dim_z}), got {tuple(z.shape)}')
+        n = z.shape[0]
+        z = _dev(z.detach(), self.device, torch.float32)
+        classes = None
+        if y.dim() == 1 and not embedded:
+            if y.shape[0] != n or y.dtype.is_floating_point:
+                raise ValueError(f'y must be ({n},) class indices, got {tuple(y.shape)} '
+                                 f'{y.dtype}')
+            classes = _dev(y.detach(), self.device, torch.int64)
+            if n and bool(((classes < 0) | (classes >= d.n_classes)).any()):
+                raise IndexError(f'class index outside 0 .. {d.n_classes - 1}')
+            y = None
+        else:
+            columns = d.shared_dim if embedded else d.n_classes
+            if y.dim() != 2 or y.shape[0] != n or y.shape[1] != columns:
+                raise ValueError(f'y must be ({n}, {columns}), got {tuple(y.shape)}')
+            y = _dev(y.detach(), self.device, torch.float32)
+        shapes = self.tap_shapes
+        taps = sorted(set(int(t) for t in taps))
+        if any(t < 0 or t >= len(shapes) for t in taps):
+            raise ValueError(f'taps {taps} outside the {len(shapes)} taps')
+        if not taps and not want_images:
+            raise ValueError('neither a tap nor the images are asked for')
+        outs = {t: torch.empty((n, shapes[t][0], shapes[t][1], shapes[t][1]), device=self.device)
+                for t in taps}
+        images = (torch.empty((n, 3, d.resolution, d.resolution), device=self.device)
+                  if want_images else None)
+        if n == 0:
+            return outs, images
+        pointers = (_P * len(shapes))(*[_ptr(outs.get(t)) for t in range(len(shapes))])
+        with torch.cuda.device(self.device):
+            ws = self._workspace(int(self.lib.milan_gan_workspace_bytes(self._h, n)))
+            _check(self.lib.milan_gan_run(self._h, z.data_ptr(), _ptr(classes), _ptr(y),
+                                          int(embedded), n, pointers, _ptr(images),
+                                          ws.data_ptr(), ws.numel(), _stream(self.device)))
+        return outs, images
+
+
 def attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     """softmax(q k^T / sqrt(head)) v per (sequence, head) by the streaming fp32-MFMA kernel
     (milan_attention).  qkv (seqs, T, 3 * width) float32 on the GPU: q | k | v, the heads
@@ -1943,6 +2034,44 @@ def attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     with torch.cuda.device(device):
         _check(_need_export('milan_attention')(qkv.data_ptr(), out.data_ptr(), seqs, tokens,
                                                width, int(heads), _stream(device)))
+    return out
+
+
+def sagan_attention(theta: torch.Tensor, phi_g: torch.Tensor, height: int,
+                    width: int) -> torch.Tensor:
+    """The attention of a BigGAN / SAGAN non-local block by the streaming fp32-MFMA kernel
+    (milan_sagan_attention): out_i = sum_j softmax_j(theta_i . phi_j) g_j, no scale factor,
+    without the (height * width) x (height * width / 4) scores ever reaching memory.
+
+    Pixel-major, float32, on the GPU.  theta (n, height * width, dk): the queries; a column
+    slice of a wider tensor (the first dk columns of a fused theta | phi | g conv output) is
+    read in place.  phi_g (n, height * width / 4, dk + dv): the 2 x 2 max-pooled keys | values.
+    Returns (n, height * width, dv).  With C the block's channel count, dk = C / 8 and dv =
+    C / 2; C a multiple of 32 up to 384 and even height and width, anything else raises
+    ValueError."""
+    device = require_device(theta.device)
+    if theta.dim() != 3 or phi_g.dim() != 3 or phi_g.shape[0] != theta.shape[0]:
+        raise ValueError(f'theta must be (n, H W, dk) and phi_g (n, H W / 4, dk + dv), got '
+                         f'{tuple(theta.shape)} and {tuple(phi_g.shape)}')
+    n, dk = theta.shape[0], theta.shape[2]
+    channels = 8 * dk
+    if phi_g.shape[2] != 5 * dk:
+        raise ValueError(f'phi_g has {phi_g.shape[2]} columns: with dk = {dk} query columns '
+                         f'(C = {channels}) it needs dk + dv = {5 * dk}')
+    if theta.shape[1] != height * width or phi_g.shape[1] * 4 != theta.shape[1]:
+        raise ValueError(f'{theta.shape[1]} queries and {phi_g.shape[1]} keys are not '
+                         f'height x width = {height} x {width} and a quarter of it')
+    theta = theta.detach()
+    if (theta.dtype != torch.float32 or theta.stride(2) != 1 or n > 1 and
+            theta.stride(0) != theta.shape[1] * theta.stride(1) or theta.stride(1) % 2 or
+            theta.stride(1) < dk or theta.data_ptr() % 8):
+        theta = theta.to(torch.float32).contiguous()
+    phi_g = _dev(phi_g.detach(), device, torch.float32)
+    out = torch.empty((n, height * width, 4 * dk), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _check(_need_export('milan_sagan_attention')(
+            theta.data_ptr(), theta.stride(1), phi_g.data_ptr(), out.data_ptr(), n, int(height),
+            int(width), channels, _stream(device)))
     return out
 
 

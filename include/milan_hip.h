@@ -1238,9 +1238,14 @@ int milan_gan_taps(const milan_gan_ctx* ctx);
  *     y is given.  An index outside 0 .. n_classes - 1 is clamped: check it before.
  *   taps: HOST array of milan_gan_taps() DEVICE pointers, or NULL.  A non-null
  *     taps[j] receives the output h of that block, (n, C, H, W) fp32 NCHW.
- *   images_out: NULL, or (n, 3, resolution, resolution) fp32 DEVICE, tanh included.
+ *   images_out: NULL, or (n, 3, R, R) fp32 DEVICE, tanh included, with R =
+ *     bottom_width << blocks (every block doubles the side): `resolution` selects the
+ *     block table, and is R only at bottom_width 4.
  *   Without images_out the walk ends after the deepest tap asked for: no later block
- *   runs.  At least one output must be asked for.  Does not synchronise. */
+ *   runs.  At least one output must be asked for.  Does not synchronise.
+ *   n above 65535 (the launch grid's z) or n x the largest activation of a sample
+ *   >= 2^31 floats is MILAN_ERR_ARG ("split the batch"); milan_gan_workspace_bytes
+ *   then returns 0 with that message in milan_last_error, and nothing is launched. */
 size_t milan_gan_workspace_bytes(const milan_gan_ctx* ctx, int n);
 int milan_gan_run(milan_gan_ctx* ctx, const float* z, const int64_t* classes,
                   const float* y, int y_embedded, int n, float* const* taps,

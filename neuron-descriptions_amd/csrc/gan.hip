@@ -527,10 +527,15 @@ static int conv(const float* in, long n, int H, int W, int cin, long pix, const 
 struct Plan {
   size_t y, scale, shift, x0, x1, t, u, sc, total_floats;
 };
+constexpr int MAX_GRID_Z = 65535;
 
 static int plan(const milan_gan_ctx* c, int n, Plan* p) {
   MILAN_REQUIRE(c && c->w.finalized, MILAN_ERR_STATE, "gan: weights are not finalized");
   MILAN_REQUIRE(n > 0, MILAN_ERR_ARG, "gan: %d samples", n);
+  // fold_bn_kernel and nchw_kernel put the sample in gridDim.z
+  MILAN_REQUIRE(n <= MAX_GRID_Z, MILAN_ERR_ARG,
+                "gan: %d samples exceed the %d that a launch grid's z takes: split the batch", n,
+                MAX_GRID_Z);
   const auto& d = c->d;
   size_t x = 0, t = 0, u = 0, sc = 0;
   for (const auto& b : c->blocks) {

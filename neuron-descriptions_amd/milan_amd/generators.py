@@ -28,6 +28,7 @@ do; the running statistics are not updated (pretorched's `F.batch_norm` call doe
 Non-finite inputs are not specified.
 """
 import collections
+import math
 from typing import Any, Dict, List, Mapping, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
@@ -272,6 +273,12 @@ class Generator(nn.Module):
         return self.dim_z
 
     @property
+    def image_side(self) -> int:
+        """Side of the images: every block doubles bottom_width.  `resolution` names the
+        block table and is the side only at bottom_width 4."""
+        return self.bottom_width << len(self.blocks)
+
+    @property
     def attention_channels(self) -> int:
         """Channels of the attention block, 0 without one."""
         for block in self.blocks:
@@ -496,22 +503,28 @@ def biggan(resolution: int = 256, **kwargs: Any) -> Generator:
 
 
 def infer_config(state_dict: Mapping[str, torch.Tensor]) -> Dict[str, Any]:
-    """`Generator`'s structural arguments from a pretorched BigGAN state dict (bottom_width 4
-    assumed; BN_eps is not stored in a state dict and stays the caller's)."""
+    """`Generator`'s structural arguments from a pretorched BigGAN state dict (BN_eps is not
+    stored in a state dict and stays the caller's).  G_ch comes from the first block's input
+    channels and bottom_width from the rows of `linear` (G_ch * multiplier * bottom_width^2)."""
     try:
         n_classes, shared_dim = state_dict['shared.weight'].shape
         rows, z_in = state_dict['linear.weight'].shape
         cond = state_dict['blocks.0.0.bn1.gain.weight'].shape[1]
+        first = state_dict['blocks.0.0.conv1.weight'].shape[1]
     except KeyError as error:
         raise ValueError(f'not a BigGAN generator state dict: no {error}') from error
     blocks = len({k.split('.')[1] for k in state_dict if k.startswith('blocks.')})
     resolution = {len(v[0]): k for k, v in ARCH.items()}.get(blocks)
     if resolution is None:
         raise ValueError(f'{blocks} blocks match no BigGAN architecture')
-    ch = rows // 16 // ARCH[resolution][0][0]
+    ch = first // ARCH[resolution][0][0]
+    bottom_width = math.isqrt(rows // first)
+    if ch * ARCH[resolution][0][0] != first or first * bottom_width**2 != rows:
+        raise ValueError(f'linear has {rows} rows and the first block {first} input channels: '
+                         f'no G_ch and bottom_width give both at resolution {resolution}')
     hier = cond > shared_dim
     attn = [8 << int(k.split('.')[1]) for k in state_dict if k.endswith('.1.gamma')]
-    return dict(G_ch=ch, dim_z=z_in * (blocks + 1) if hier else z_in, bottom_width=4,
+    return dict(G_ch=ch, dim_z=z_in * (blocks + 1) if hier else z_in, bottom_width=bottom_width,
                 resolution=resolution, G_attn='_'.join(map(str, attn)) or '0',
                 n_classes=n_classes, shared_dim=shared_dim, hier=hier,
                 G_param='SN' if 'linear.u0' in state_dict else 'none')

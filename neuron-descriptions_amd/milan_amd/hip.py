@@ -1957,6 +1957,22 @@ _GAN_OUT = {512: (16, 8, 8, 4, 2, 1, 1), 256: (16, 8, 8, 4, 2, 1), 128: (16, 8, 
             64: (16, 8, 4, 2), 32: (4, 4, 4)}
 
 
+def gan_tap_shapes(dims: GanDims):
+    """[(channels, side)] of a generator's taps in walk order: layer0, .., layerK, attnK, .."""
+    shapes = []
+    for i, mult in enumerate(_GAN_OUT[dims.resolution]):
+        shapes.append((dims.ch * mult, dims.bottom_width << (i + 1)))
+        if dims.attn_resolution == 8 << i:
+            shapes.append(shapes[-1])
+    return shapes
+
+
+def gan_image_side(dims: GanDims) -> int:
+    """Side of a generator's images: every block doubles bottom_width.  `resolution` names the
+    block table; it is the side only at bottom_width 4."""
+    return dims.bottom_width << len(_GAN_OUT[dims.resolution])
+
+
 class GanContext(_TowerContext):
     """Owns one `milan_gan_ctx`: the weights of a BigGAN generator on one GPU (spectral norm
     already folded: `state_dict` holds weight / sv and no u0 / sv0) and a workspace.  Every
@@ -1967,19 +1983,19 @@ class GanContext(_TowerContext):
     @property
     def tap_shapes(self):
         """[(channels, side)] of the taps in walk order: layer0, .., layerK, attnK, .."""
-        d, shapes = self.dims, []
-        for i, mult in enumerate(_GAN_OUT[d.resolution]):
-            shapes.append((d.ch * mult, d.bottom_width << (i + 1)))
-            if d.attn_resolution == 8 << i:
-                shapes.append(shapes[-1])
-        return shapes
+        return gan_tap_shapes(self.dims)
+
+    @property
+    def image_side(self) -> int:
+        """R of the (n, 3, R, R) images."""
+        return gan_image_side(self.dims)
 
     def run(self, z: torch.Tensor, y: torch.Tensor, embedded: bool = False,
             taps: Sequence[int] = (), want_images: bool = False):
         """z (n, dim_z); y: class indices (n,) int64, soft labels (n, n_classes), or with
         `embedded` the embedded classes (n, shared_dim) -> ({tap: (n, C, H, W) output of that
-        block}, the (n, 3, R, R) images or None).  The walk ends after the deepest block in
-        `taps` unless `want_images`."""
+        block}, the (n, 3, R, R) images or None), R = `image_side` = bottom_width << blocks.
+        The walk ends after the deepest block in `taps` unless `want_images`."""
         d = self.dims
         if z.dim() != 2 or z.shape[1] != d.dim_z:
             raise ValueError(f'z must be (n, {d.dim_z}), got {tuple(z.shape)}')
@@ -2007,8 +2023,8 @@ class GanContext(_TowerContext):
             raise ValueError('neither a tap nor the images are asked for')
         outs = {t: torch.empty((n, shapes[t][0], shapes[t][1], shapes[t][1]), device=self.device)
                 for t in taps}
-        images = (torch.empty((n, 3, d.resolution, d.resolution), device=self.device)
-                  if want_images else None)
+        side = self.image_side
+        images = torch.empty((n, 3, side, side), device=self.device) if want_images else None
         if n == 0:
             return outs, images
         pointers = (_P * len(shapes))(*[_ptr(outs.get(t)) for t in range(len(shapes))])

@@ -21,12 +21,14 @@ The attention alone, pixel-major as milan_sagan_attention takes it: theta (n, H 
 phi_g (n, H W / 4, dk + dv) = phi | g.
 
 Runs in the dtype of its inputs: in float64 it is the oracle of tests/test_biggan_host.py,
-tests/test_gpu_sagan_attention.py and tests/test_gpu_biggan.py; in float32 on the CPU it
+tests/test_gpu_sagan_attention.py, tests/test_gpu_biggan.py and
+tests/test_gpu_biggan_shapes.py (SHAPE_CASES, at the end); in float32 on the CPU it
 defines the error an fp32 implementation is entitled to.  The bound is vitref.check's:
 max|got - want| <= max(4 x e32, FEATURE_CLASS x max|want|), e32 = the max error of the float32
 run against the float64 run of that same case.
 """
 import collections
+import functools
 import math
 
 import torch
@@ -182,6 +184,18 @@ def weights(dims, seed):
     return sd
 
 
+def tap_shapes(dims):
+    """[(channels, side)] per name of layer_names(dims): block i doubles bottom_width << i."""
+    shapes = []
+    for i, (_, cout, attn) in enumerate(blocks_of(dims)):
+        shapes += [(cout, dims['bottom_width'] << (i + 1))] * (2 if attn else 1)
+    return shapes
+
+
+def image_side(dims):
+    return dims['bottom_width'] << len(ARCH[dims['resolution']][0])
+
+
 def latents(dims, n, seed):
     """Seeded (z (n, dim_z) float64, hard y (n,) int64, soft y (n, n_classes) float64)."""
     g = torch.Generator().manual_seed(seed)
@@ -264,3 +278,38 @@ def forward(sd, z, y, dims):
     images = torch.tanh(F.conv2d(h, _w(sd, 'output_layer.2'), sd['output_layer.2.bias'],
                                  padding=1))
     return taps, images
+
+
+# ---- the architectures, bottom widths and batches off the golden's path ----------------------
+# name -> (dims, batch).  What each reaches in the native walk is listed in
+# tests/test_gpu_biggan_shapes.py; tests/test_biggan_host.py runs the eager modules on some.
+SHAPE_CASES = {
+    'r128': (make_dims(128, 16, 64, 30, 12, 7), 3),
+    'r256': (make_dims(256, 16, 128, 35, 9, 6), 1),
+    'r256flat': (make_dims(256, 4, 32, 21, 9, 6, hier=False), 2),
+    'r512': (make_dims(512, 8, 64, 24, 5, 3), 1),
+    'bw3': (make_dims(32, 8, 16, 32, 16, 10, bottom_width=3), 5),
+    'bw5': (make_dims(32, 8, 8, 32, 16, 10, bottom_width=5), 3),
+    'bw1': (make_dims(64, 16, 32, 10, 5, 1, bottom_width=1), 7),
+    'n80': (make_dims(32, 20, 0, 18, 7, 5, hier=False), 3),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def shape_case(name):
+    """(dims, float64 weights, (z, hard y, soft y)) of a SHAPE_CASES entry, seeded by its
+    position in the table."""
+    dims, batch = SHAPE_CASES[name]
+    index = list(SHAPE_CASES).index(name)
+    return dims, weights(dims, seed=700 + index), latents(dims, batch, seed=800 + index)
+
+
+@functools.lru_cache(maxsize=None)
+def shape_reference(name, soft=False):
+    """(float64 (taps, images), float32 (taps, images)) of a SHAPE_CASES entry for hard or soft
+    labels: computed once per process and left unchanged."""
+    dims, sd, (z, hard, soft_y) = shape_case(name)
+    with torch.no_grad():
+        want = forward(sd, z, soft_y if soft else hard, dims)
+        ref32 = forward(cast(sd, torch.float32), z.float(), soft_y.float() if soft else hard, dims)
+    return want, ref32

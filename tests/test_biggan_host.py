@@ -11,7 +11,7 @@ from torch import nn
 
 import bigganref
 from conftest import GOLDEN_DIR
-from milan_amd import exemplars, generators
+from milan_amd import exemplars, generators, hip
 
 CONFIGS = collections.OrderedDict(
     c32=bigganref.make_dims(32, 8, 16, 32, 16, 10, hier=True, bn_eps=1e-4),
@@ -152,6 +152,110 @@ def test_a_plain_conv_generator_has_no_sn_buffers():
     with torch.no_grad():  # both in float64: only the order of the sums differs
         got = g(z, hard, embed=True)
     assert float((got - want).abs().max()) < 1e-9
+
+
+# ---- the architectures and bottom widths that no golden covers -------------------------------
+def eager_of(name):
+    """The eager Generator of a bigganref.SHAPE_CASES entry in float32, loaded strictly."""
+    dims, sd, _ = bigganref.shape_case(name)
+    g = generators.from_state_dict(bigganref.cast(sd, torch.float32), BN_eps=dims['bn_eps'],
+                                   bottom_width=dims['bottom_width'])
+    assert (g.ch, g.bottom_width, g.resolution) == (dims['ch'], dims['bottom_width'],
+                                                    dims['resolution'])
+    return g
+
+
+@pytest.mark.parametrize('name', ['r128', 'r256flat', 'r512', 'bw3'])
+def test_the_eager_generator_matches_float64_off_the_golden(name):
+    """The Python ARCH rows for 128, 256 and 512 and a bottom width other than 4: the eager
+    modules against bigganref in float64, inside the bound of the native walk."""
+    dims, batch = bigganref.SHAPE_CASES[name]
+    _, _, (z, hard, _) = bigganref.shape_case(name)
+    (taps64, images64), (taps32, images32) = bigganref.shape_reference(name)
+    g = eager_of(name)
+    side = bigganref.image_side(dims)
+    with torch.no_grad():
+        images = g.forward_eager(z.float(), hard, embed=True)
+        assert images.shape == (batch, 3, side, side) and g.image_side == side
+        bigganref.check(f'host {name} forward_eager', images, images64, images32)
+        seq = generators.SeqBigGAN(g)
+        assert list(seq.layers) == bigganref.layer_names(dims)
+        inputs = generators.GInputs(z.float(), hard)
+        for layer in seq.layers:  # the hook-free eager path of generate, tap by tap
+            bag, _ = seq.generate(inputs, layer=layer, images=False)
+            bigganref.check(f'host {name} eager {layer}', bag.h, taps64[layer], taps32[layer])
+
+
+@pytest.mark.parametrize('bottom_width', [1, 3, 4, 5])
+@pytest.mark.parametrize('resolution', [32, 64, 128, 256, 512])
+def test_layer_names_tap_shapes_and_image_side(resolution, bottom_width):
+    """Shape arithmetic of the module, of the binding (what GanContext allocates) and of
+    bigganref agree: block i ends at side bottom_width << (i + 1), the images at
+    bottom_width << blocks, whatever `resolution` says."""
+    blocks = len(bigganref.ARCH[resolution][0])
+    for attn in [0] + [8 << i for i in range(blocks)]:
+        dims = bigganref.make_dims(resolution, 8, attn, 16, 8, 3, bottom_width=bottom_width)
+        g = generators.Generator(G_ch=8, dim_z=16, bottom_width=bottom_width,
+                                 resolution=resolution, G_attn=str(attn), n_classes=3,
+                                 shared_dim=8, hier=True, skip_init=True)
+        names, shapes = bigganref.layer_names(dims), bigganref.tap_shapes(dims)
+        assert list(g.layers) == names and len(shapes) == len(names) == blocks + bool(attn)
+        assert hip.gan_tap_shapes(g.dims()) == shapes
+        side = bigganref.image_side(dims)
+        assert hip.gan_image_side(g.dims()) == g.image_side == side == bottom_width << blocks
+        assert shapes[-1][1] == side and (side == resolution) == (bottom_width == 4)
+        if attn:  # 8 << k: after block k, with that block's shape
+            k = attn.bit_length() - 4
+            assert names[k + 1] == f'attn{k}' and shapes[k + 1] == shapes[k]
+
+
+def test_infer_config_reads_the_bottom_width():
+    for name in ('bw3', 'bw1', 'r128'):
+        dims, sd, _ = bigganref.shape_case(name)
+        config = generators.infer_config(sd)
+        assert (config['G_ch'], config['bottom_width']) == (dims['ch'], dims['bottom_width'])
+        assert config['resolution'] == dims['resolution'] and config['dim_z'] == dims['dim_z']
+    broken = dict(bigganref.shape_case('bw3')[1])
+    broken['linear.weight'] = broken['linear.weight'][:-1]
+    with pytest.raises(ValueError, match='no G_ch and bottom_width'):
+        generators.infer_config(broken)
+
+
+def _first_tap_outside(name, sd32, z32, hard):
+    """The first tap of the float32 reference on changed inputs that leaves bound(), or None."""
+    dims = bigganref.SHAPE_CASES[name][0]
+    (taps64, _), (taps32, _) = bigganref.shape_reference(name)
+    with torch.no_grad():
+        taps, _ = bigganref.forward(sd32, z32, hard, dims)
+    for layer, got in taps.items():
+        limit, _ = bigganref.bound(taps64[layer], taps32[layer])
+        err = float((got.double() - taps64[layer]).abs().max())
+        print(f'BIGGAN host mutation {layer}: max|err| {err:.3g}, bound {limit:.3g}')
+        if err > limit:
+            return layer
+    return None
+
+
+def test_the_bound_is_not_slack_on_r128():
+    """Three plausible mistakes of a walk, applied to the float32 reference itself, each leave
+    the bound on some tap, at the block where they first act; the reference unchanged does
+    not."""
+    name = 'r128'
+    dims, sd, (z, hard, _) = bigganref.shape_case(name)
+    sd32, z32 = bigganref.cast(sd, torch.float32), z.float()
+    assert _first_tap_outside(name, sd32, z32, hard) is None
+    # block i conditioned on z chunk i instead of i + 1: the chunks shifted by one
+    chunks = list(torch.split(z32, dims['chunk'], 1))
+    shifted = torch.cat([chunks[0]] + chunks[:-1], 1)
+    assert _first_tap_outside(name, sd32, shifted, hard) == 'layer0'
+    # the shortcut conv without its bias, in the last block only
+    no_bias = dict(sd32)
+    no_bias['blocks.4.0.conv_sc.bias'] = torch.zeros_like(sd32['blocks.4.0.conv_sc.bias'])
+    assert _first_tap_outside(name, no_bias, z32, hard) == 'layer4'
+    # gamma not applied: o + x instead of gamma * o + x
+    no_gamma = dict(sd32)
+    no_gamma['blocks.3.1.gamma'] = torch.ones_like(sd32['blocks.3.1.gamma'])
+    assert _first_tap_outside(name, no_gamma, z32, hard) == 'attn3'
 
 
 def test_unsupported_widths_decline_the_native_path_with_a_message(golden):

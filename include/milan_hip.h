@@ -69,8 +69,12 @@ enum {
   MILAN_TRUNK_BOTTLENECK = 0, /* taps conv1 + layer1..4, F = 61 * width      */
   MILAN_TRUNK_BASIC = 1,      /* same taps, expansion 1,   F = 16 * width      */
   MILAN_TRUNK_ALEXNET = 2,    /* taps features.0/3/6/8/10, F = 18 * width      */
-  MILAN_TRUNK_NONE = 3        /* decoder-only context (a foreign `Encoder`):
+  MILAN_TRUNK_NONE = 3,       /* decoder-only context (a foreign `Encoder`):
                                  any feature_size % 4 == 0, trunk_* ignored   */
+  MILAN_TRUNK_ALEXNET_PLACES = 4 /* the Places365 AlexNet: conv1..conv5 with grouped
+                                 convs, width / 32 x (96, 256, 384, 384, 256) channels,
+                                 F = 43 * width.  Classify / ablate / activations
+                                 only: the encoder entry points refuse it      */
 };
 typedef struct milan_dims {
   int32_t trunk_width;      /* 64 for the torchvision models                */
@@ -249,6 +253,35 @@ int milan_linear(const float* x, const float* packed, const float* bias, int row
                  int n_out, int relu, float* y, milan_stream stream);
 int milan_linear_rowwise(const float* x, const float* weight, const float* bias, int rows,
                          int n_in, int n_out, float* y, milan_stream stream);
+
+/* The same calls on the Places365 AlexNet (MILAN_TRUNK_ALEXNET_PLACES; the reference's
+ * src/deps/alexnet.py): conv1 11x11 / 4 / pad 0, pool 3/2 [, LRN], conv2 5x5 / pad 2 in 2 groups,
+ * pool 3/2 [, LRN], conv3 3x3 dense, conv4 and conv5 3x3 in 2 groups, pool 3/2, flatten in
+ * (C, h, w) order, fc6 / fc7 / fc8 with ReLU after the first two.  Channels are width / 32 x
+ * (96, 256, 384, 384, 256), width a multiple of 8.  The state dict's keys are
+ * `<prefix>conv1.weight` .. `<prefix>conv5.bias`; a conv's group count follows from its weight
+ * shape (cout, cin / groups, kh, kw), so dense weights (groups of 1) run as well.  A grouped
+ * conv is ONE launch with the group as a grid dimension (MILAN_GROUP_LAUNCH=0: one launch per
+ * group on offset pointers, the same bits).  A level whose per-group input width is not a
+ * multiple of 32 runs in fp32 in both precision modes.
+ *   Levels 0..4 are conv1..conv5 with the AlexNet semantics above: relu(conv + bias) x mask,
+ * before the pool and the LRN; a zero is handed out as +0.  The head is installed with
+ * milan_set_alexnet_head (its third layer is fc8 here).  milan_classify* needs an image that
+ * leaves 6 x 6 after pool5 (227 x 227, the reference's size, up to 258; MILAN_ERR_SHAPE
+ * otherwise: there is no adaptive pool); milan_activations needs no head and takes any image
+ * that leaves 3 x 3 before every pool it has to cross (35 x 35 reaches every level).  MILAN_PRECISION_F16 and the milan_encode* calls: MILAN_ERR_ARG.
+ *   milan_set_alexnet_lrn  the optional across-channel LRN after pool1 and pool2:
+ *     y = x / (1 + alpha * S / local_size)^beta, S = the sum of squares over the local_size
+ *     neighbouring channels, zero-padded (the divisor is always local_size).  local_size odd
+ *     and at most 17, 0 = off (the default); a context of another trunk kind or any other
+ *     size: MILAN_ERR_ARG.  beta == 0.75 is computed as sqrt(d) * sqrt(sqrt(d)), other values by powf.
+ *   milan_lrn  the LRN kernel alone on a DEVICE tensor (pixels, channels) with the channels of
+ *     a pixel contiguous, channels % 8 == 0, 16-byte aligned, x and y apart: fp32, or with
+ *     `split` != 0 split f16 groups at scale 1, in and out.  `status`: a device status word or NULL.
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them. */
+int milan_set_alexnet_lrn(milan_ctx* ctx, int local_size, float alpha, float beta);
+int milan_lrn(const float* x, long long pixels, int channels, int split, int local_size,
+              float alpha, float beta, float* y, unsigned* status, milan_stream stream);
 
 /* Decoder.init_state (src/milan/decoders.py:548-574).
  * features (n,k,F) -> h,c (n,hidden). */

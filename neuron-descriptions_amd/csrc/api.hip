@@ -134,7 +134,7 @@ int milan_create(milan_ctx** out, int device, const milan_dims* dims) {
   MILAN_REQUIRE(out && dims, MILAN_ERR_ARG, "milan_create: null argument");
   const milan_dims& d = *dims;
   MILAN_REQUIRE(d.trunk_kind >= MILAN_TRUNK_BOTTLENECK &&
-                    d.trunk_kind <= MILAN_TRUNK_NONE,
+                    d.trunk_kind <= MILAN_TRUNK_ALEXNET_PLACES,
                 MILAN_ERR_ARG, "unknown trunk_kind %d", d.trunk_kind);
   if (d.trunk_kind == MILAN_TRUNK_NONE) {
     // features come from a foreign Encoder: only the decoder's GEMM alignment
@@ -144,13 +144,15 @@ int milan_create(milan_ctx** out, int device, const milan_dims* dims) {
   } else {
     MILAN_REQUIRE(d.trunk_width > 0 && d.trunk_width % 4 == 0, MILAN_ERR_SHAPE,
                   "trunk_width %d must be a positive multiple of 4", d.trunk_width);
-    const int fmul = d.trunk_kind == MILAN_TRUNK_BOTTLENECK ? 61
-                     : d.trunk_kind == MILAN_TRUNK_BASIC    ? 16
-                                                            : 18;
+    const int fmul = d.trunk_kind == MILAN_TRUNK_BOTTLENECK       ? 61
+                     : d.trunk_kind == MILAN_TRUNK_BASIC          ? 16
+                     : d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES ? 43
+                                                                  : 18;
     MILAN_REQUIRE(d.feature_size == fmul * d.trunk_width, MILAN_ERR_SHAPE,
                   "feature_size %d != %d * trunk_width (pyramid of five taps, "
                   "trunk_kind %d)", d.feature_size, fmul, d.trunk_kind);
-    for (int i = 0; i < 4 && d.trunk_kind != MILAN_TRUNK_ALEXNET; ++i)
+    for (int i = 0; i < 4 && d.trunk_kind != MILAN_TRUNK_ALEXNET &&
+                    d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES; ++i)
       MILAN_REQUIRE(d.trunk_blocks[i] > 0, MILAN_ERR_SHAPE, "bad trunk_blocks");
   }
   MILAN_REQUIRE(d.hidden_size > 0 && d.hidden_size % 4 == 0 &&
@@ -396,6 +398,17 @@ int milan_set_alexnet_head(milan_ctx* c, const float* fc6_weight, const float* f
   const float* b[3] = {fc6_bias, fc7_bias, linear8_bias};
   const int out[3] = {fc6_out, fc7_out, linear8_out}, in[3] = {fc6_in, fc7_in, linear8_in};
   return classify_set_alexnet_head(c, w, b, out, in, (hipStream_t)stream);
+}
+
+int milan_set_alexnet_lrn(milan_ctx* c, int local_size, float alpha, float beta) {
+  MILAN_REQUIRE(c, MILAN_ERR_ARG, "milan_set_alexnet_lrn: null argument");
+  return classify_set_alexnet_lrn(c, local_size, alpha, beta);
+}
+
+int milan_lrn(const float* x, long long pixels, int channels, int split, int local_size,
+              float alpha, float beta, float* y, unsigned* status, milan_stream stream) {
+  return launch_lrn(x, pixels, channels, split != 0, local_size, alpha, beta, y, status,
+                    (hipStream_t)stream);
 }
 
 size_t milan_linear_packed_bytes(int n_out, int n_in) {

@@ -253,6 +253,109 @@ __global__ __launch_bounds__(256) void alex_tail_kernel(const float* __restrict_
   out[img * (size_t)C * 36 + (size_t)c * 36 + bin] = sum / (float)((r1 - r0) * (q1 - q0));
 }
 
+// Across-channel local response normalisation of the Places365 AlexNet, over an
+// NHWC tensor of `chunks` = pixels x C / 8 eight-channel pieces:
+//   y[c] = x[c] / (1 + alpha * S[c] / n)^beta,  S[c] = sum of x[j]^2, |j - c| <= half, 0 <= j < C
+// with n = 2 half + 1 whatever part of the window lies outside (torch's AvgPool3d with
+// count_include_pad).  A thread owns one piece and reads its two neighbours (half <= 8): two
+// 16-byte loads per piece, fp32 or split (hi x8 | lo x8) at scale 1, the channels of a pixel
+// contiguous.  Per value: squares by one multiplication, S from zero in ascending j by plain
+// additions, avg = S / n, d = fma(avg, alpha, 1), p = sqrt(d) * sqrt(sqrt(d)) for beta = 0.75
+// (correctly rounded steps) or powf(d, beta), y = x / p.  HALF > 0 fixes the window at compile
+// time; 0 reads `half` (<= 8).  x and y must not overlap.
+template <bool SPLIT, int HALF>
+__global__ __launch_bounds__(256) void lrn_kernel(const float* __restrict__ x, long chunks, int C8,
+                                                  int half, float alpha, float beta,
+                                                  float* __restrict__ y,
+                                                  unsigned* __restrict__ status) {
+  const float n = (float)(2 * (HALF > 0 ? HALF : half) + 1);
+  const bool b34 = beta == 0.75f;
+  float sat = 0.f;
+  for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < chunks;
+       q += (long)gridDim.x * blockDim.x) {
+    const int k = (int)(q % C8);
+    float v[24];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int kk = k - 1 + t;
+      if (kk >= 0 && kk < C8) {
+        const float* px = x + (q + (t - 1)) * 8;
+        const cf32x4_t a = *reinterpret_cast<const cf32x4_t*>(px);
+        const cf32x4_t b = *reinterpret_cast<const cf32x4_t*>(px + 4);
+        if constexpr (SPLIT) {
+          join8_exact(a, b, v + t * 8);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { v[t * 8 + e] = a[e]; v[t * 8 + 4 + e] = b[e]; }
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[t * 8 + e] = 0.f;
+      }
+    }
+    float sq[24];
+#pragma unroll
+    for (int i = 0; i < 24; ++i) sq[i] = __fmul_rn(v[i], v[i]);
+    float out[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float S = 0.f;
+      if constexpr (HALF > 0) {
+#pragma unroll
+        for (int j = -HALF; j <= HALF; ++j) S = __fadd_rn(S, sq[8 + e + j]);
+      } else {
+#pragma unroll
+        for (int j = -8; j <= 8; ++j)
+          S = __fadd_rn(S, (j >= -half && j <= half) ? sq[8 + e + j] : 0.f);
+      }
+      const float d = __fmaf_rn(__fdiv_rn(S, n), alpha, 1.f);
+      const float p = b34 ? __fmul_rn(__fsqrt_rn(d), __fsqrt_rn(__fsqrt_rn(d))) : powf(d, beta);
+      out[e] = __fdiv_rn(v[8 + e], p);
+    }
+    float* dst = y + q * 8;
+    if constexpr (SPLIT) {
+      cf32x4_t hi4, lo4;
+      split8_rne(out, &hi4, &lo4, &sat);
+      *reinterpret_cast<cf32x4_t*>(dst) = hi4;
+      *reinterpret_cast<cf32x4_t*>(dst + 4) = lo4;
+    } else {
+      const cf32x4_t o0 = {out[0], out[1], out[2], out[3]}, o1 = {out[4], out[5], out[6], out[7]};
+      *reinterpret_cast<cf32x4_t*>(dst) = o0;
+      *reinterpret_cast<cf32x4_t*>(dst + 4) = o1;
+    }
+  }
+  if constexpr (SPLIT) report_saturation(status, sat);
+}
+
+int launch_lrn(const float* x, long long pixels, int C, bool split, int local_size, float alpha,
+               float beta, float* y, unsigned* status, hipStream_t s) {
+  MILAN_REQUIRE(x && y && pixels >= 1 && C >= 8 && C % 8 == 0, MILAN_ERR_ARG,
+                "lrn: need a tensor of >= 1 pixels and a multiple of 8 channels (got %lld x %d)",
+                pixels, C);
+  MILAN_REQUIRE(local_size >= 1 && local_size % 2 == 1 && local_size <= 17, MILAN_ERR_ARG,
+                "lrn: local_size %d is not an odd number in 1..17", local_size);
+  const size_t bytes = (size_t)pixels * C * sizeof(float);
+  MILAN_REQUIRE((const char*)x + bytes <= (const char*)y || (const char*)y + bytes <= (const char*)x,
+                MILAN_ERR_ARG, "lrn: input and output overlap");
+  MILAN_REQUIRE((((uintptr_t)x | (uintptr_t)y) & 15) == 0, MILAN_ERR_ARG,
+                "lrn: tensors must be 16-byte aligned");
+  const long chunks = (long)pixels * (C / 8);
+  const long b = (chunks + 255) / 256;
+  const dim3 grid((int)(b < 16384 ? b : 16384));
+  const int half = local_size / 2;
+#define MILAN_LRN(SPLIT, HALF)                                                                 \
+  hipLaunchKernelGGL((lrn_kernel<SPLIT, HALF>), grid, dim3(256), 0, s, x, chunks, C / 8, half, \
+                     alpha, beta, y, status)
+  if (split) {
+    if (half == 2) MILAN_LRN(true, 2); else if (half == 1) MILAN_LRN(true, 1); else MILAN_LRN(true, 0);
+  } else {
+    if (half == 2) MILAN_LRN(false, 2); else if (half == 1) MILAN_LRN(false, 1); else MILAN_LRN(false, 0);
+  }
+#undef MILAN_LRN
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // Linear layer y (M, N) = act(x (M, K) W^T + bias) on v_mfma_f32_32x32x2_f32: exact fp32, and
 // per output a k-ordered fmaf chain.  The summation order of an output depends on K alone:
 //   - K is padded with zeros to Kp (a multiple of 8) and cut into chunks of 256;
@@ -438,9 +541,15 @@ static bool resnet_trunk(const milan_ctx* c) {
 static bool alex_trunk(const milan_ctx* c) {
   return c->d.trunk_kind == MILAN_TRUNK_ALEXNET && c->ahead.installed;
 }
-static bool classifier_trunk(const milan_ctx* c) { return resnet_trunk(c) || alex_trunk(c); }
+// the Places365 AlexNet taps and ablates without a head; classifying needs one
+static bool places_trunk(const milan_ctx* c) {
+  return c->d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES;
+}
+static bool classifier_trunk(const milan_ctx* c) {
+  return resnet_trunk(c) || alex_trunk(c) || places_trunk(c);
+}
 static const char* level_names(const milan_ctx* c) {
-  return alex_trunk(c) ? "conv1..conv5" : "conv1, layer1..layer4";
+  return alex_trunk(c) || places_trunk(c) ? "conv1..conv5" : "conv1, layer1..layer4";
 }
 static int level_channels(const milan_ctx* c, int level) {
   const int wd = c->d.trunk_width;
@@ -467,6 +576,11 @@ static int init_mask_table(milan_ctx* c, const int* channels, hipStream_t s) {
 // called from milan_finalize_weights after encoder_finalize: keeps fc.weight / fc.bias when the
 // state dict has them (a context without them runs everything but the classify calls)
 int classify_finalize(milan_ctx* c, hipStream_t s) {
+  if (places_trunk(c) && c->stem.w != nullptr) {
+    int channels[5];
+    for (int l = 0; l < 5; ++l) channels[l] = c->alex[l].cout;
+    return init_mask_table(c, channels, s);
+  }
   if (!resnet_trunk(c) || c->stem.w == nullptr) return 0;
   int channels[5];
   for (int l = 0; l < 5; ++l) channels[l] = level_channels(c, l);
@@ -508,8 +622,8 @@ static int check_units(const milan_ctx* c, const int32_t* levels, const int32_t*
 int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* units, int count,
                           hipStream_t s) {
   MILAN_REQUIRE(classifier_trunk(c), MILAN_ERR_ARG,
-                "unit ablation needs a ResNet trunk, or an AlexNet trunk whose head "
-                "milan_set_alexnet_head has installed");
+                "unit ablation needs a ResNet trunk, a Places365 AlexNet trunk, or an AlexNet "
+                "trunk whose head milan_set_alexnet_head has installed");
   MILAN_REQUIRE(c->abl_mask != nullptr, MILAN_ERR_STATE, "encoder weights were not uploaded");
   MILAN_TRY(check_units(c, levels, units, count, "milan_set_ablation"));
   const int total = c->abl_off[4] + c->abl_ch[4];
@@ -556,6 +670,9 @@ struct Trunk {
   long long* preds = nullptr;
   float *logits = nullptr, *work = nullptr;
   float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // whether a level's tensor is in split format (a trunk's constructor fills it: level 0 is
+  // fp32 everywhere, the Places trunk has fp32 levels above it too)
+  bool fmt[5] = {false, false, false, false, false};
 
   // level tensor `x` -> `y` (x == y: in place), times the context's mask of that level and with
   // unit `extra` (>= 0) zeroed too
@@ -563,7 +680,7 @@ struct Trunk {
     const int C = c->abl_ch[level];
     const long px = (long)n * h[level] * w[level];
     const float* m = c->abl_mask + c->abl_off[level];
-    if (split && level > 0) {
+    if (fmt[level]) {
       const long groups = px * (C / 8);
       hipLaunchKernelGGL(channel_mask_split_kernel, dim3(grid_for(groups)), dim3(256), 0, s, x, y,
                          groups, C / 8, m, extra);
@@ -582,7 +699,7 @@ struct Trunk {
   int emit(int level, const float* x) const {
     const int C = c->abl_ch[level], P = h[level] * w[level];
     const dim3 grid((P + TAP_P - 1) / TAP_P, (C + TAP_C - 1) / TAP_C, n);
-    if (split && level > 0)
+    if (fmt[level])
       hipLaunchKernelGGL(tap_nchw_kernel<true>, grid, dim3(256), 0, s, x, P, C, split_tap_scale,
                          tap[level]);
     else
@@ -622,6 +739,7 @@ struct ResNetTrunk : Trunk {
       w[l] = cls_out(w[l - 1], 3, 2, 1);
     }
     for (int l = 0; l < 5; ++l) lvl_sz[l] = (size_t)h[l] * w[l] * level_channels(c, l);
+    for (int l = 1; l < 5; ++l) fmt[l] = split;
   }
 
   void carve(Arena& a) {
@@ -758,6 +876,7 @@ struct AlexTrunk : Trunk {
     // (an image too small for the trunk is refused before anything is used: check_geometry)
     for (int l = 0; l < 5; ++l)
       lvl_sz[l] = (size_t)std::max(h[l], 0) * std::max(w[l], 0) * c->abl_ch[l];
+    for (int l = 1; l < 5; ++l) fmt[l] = split;
   }
 
   void carve(Arena& ar) {
@@ -845,6 +964,147 @@ struct AlexTrunk : Trunk {
   }
 };
 
+// The Places365 AlexNet (the reference's src/deps/alexnet.py in eval mode): conv1
+// 11x11 / 4 without padding, conv2 / conv4 / conv5 grouped (ConvW::groups: one launch each, the
+// group a grid dimension), an optional LRN after pool1 and pool2, no adaptive pool.  Levels and
+// their semantics are AlexTrunk's.  Formats in the split mode: conv l runs on the split kernels
+// when its weights have a split copy (per-group input width a multiple of 32: sp[l]), in fp32
+// otherwise, as level 0 does in every mode; a level's tensor is in the format its reader takes --
+// the pools convert fp32 to split on the way, conv3 writes fp32 when conv4 is an fp32 level.
+struct PlacesTrunk : Trunk {
+  int hq[3], wq[3];   // pool1, pool2, pool5
+  bool sp[5];         // conv l reads (and multiplies) split operands
+  float *in4, *a[5], *q[2], *qn[2], *flat, *f6, *f7;
+
+  PlacesTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
+      : Trunk{c, n, H, W, split, s, 1.f} {
+    h[0] = cls_out(H, 11, 4, 0); w[0] = cls_out(W, 11, 4, 0);
+    hq[0] = cls_out(h[0], 3, 2, 0); wq[0] = cls_out(w[0], 3, 2, 0);
+    h[1] = hq[0]; w[1] = wq[0];
+    hq[1] = cls_out(h[1], 3, 2, 0); wq[1] = cls_out(w[1], 3, 2, 0);
+    for (int l = 2; l < 5; ++l) { h[l] = hq[1]; w[l] = wq[1]; }
+    hq[2] = cls_out(h[4], 3, 2, 0); wq[2] = cls_out(w[4], 3, 2, 0);
+    for (int l = 0; l < 5; ++l)
+      lvl_sz[l] = (size_t)std::max(h[l], 0) * std::max(w[l], 0) * c->abl_ch[l];
+    sp[0] = false;
+    for (int l = 1; l < 5; ++l) sp[l] = split && c->alex[l].ws != nullptr;
+    // (no pool between conv3, conv4 and conv5: an fp32 level cannot hand on split values)
+    for (int l = 3; l < 5; ++l) sp[l] = sp[l] && sp[l - 1];
+    fmt[1] = sp[1];
+    fmt[2] = sp[3];
+    fmt[3] = sp[4];
+    fmt[4] = sp[4];
+  }
+
+  void carve(Arena& ar) {
+    const milan_ctx::AlexHead& hd = c->ahead;
+    in4 = ar.get<float>((size_t)n * hin * win * 4);
+    for (int l = 0; l < 5; ++l) a[l] = ar.get<float>((size_t)n * lvl_sz[l]);
+    for (int l = 0; l < 2; ++l) {
+      const size_t sz = (size_t)n * std::max(hq[l], 0) * std::max(wq[l], 0) * c->abl_ch[l];
+      q[l] = ar.get<float>(sz);
+      qn[l] = c->lrn.size > 0 ? ar.get<float>(sz) : nullptr;
+    }
+    flat = ar.get<float>((size_t)n * hd.in[0]);
+    f6 = ar.get<float>((size_t)n * hd.out[0]);
+    f7 = ar.get<float>((size_t)n * hd.out[1]);
+  }
+  void carve_hold(Arena&, size_t) {}
+
+  // conv1 needs an 11 x 11 image; a pool needs 3 pixels each way, which walk() asks for when it
+  // has to cross one (19 x 19 reaches conv2, 35 x 35 every level); a classify call needs 6 x 6
+  // after pool5 (classify_checks)
+  int check_geometry() const {
+    // (the unpadded conv1: C's division rounds the extent of a smaller image up to 1)
+    MILAN_REQUIRE(hin >= 11 && win >= 11 && h[0] >= 1 && w[0] >= 1, MILAN_ERR_SHAPE,
+                  "classify: image %dx%d is too small for the Places365 AlexNet's 11x11 conv1",
+                  hin, win);
+    return 0;
+  }
+
+  // ResNetTrunk::walk's contract
+  int walk(int from, int to, const float* src, const float** out) const {
+    const float* x = src;
+    int ho, wo;
+    if (from < 0) {
+      MILAN_TRY(launch_raw_input(src, n, hin, win, false, in4, c->status, s));
+      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[0], in4, n, hin, win, a[0], EPI_BIAS_RELU,
+                                              nullptr, c->zero, &ho, &wo, false), s));
+      MILAN_REQUIRE(ho == h[0] && wo == w[0], MILAN_ERR_SHAPE,
+                    "internal: places level 0 geometry mismatch");
+      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, a[0], a[0], -1));
+      x = a[0];
+      from = 0;
+      if (tap[0]) MILAN_TRY(emit(0, x));
+    }
+    for (int l = from + 1; l <= to; ++l) {
+      int hh = h[l - 1], ww = w[l - 1];
+      if (l <= 2) {
+        // pool1 / pool2 write the format conv2 / conv3 read, the LRN keeps it
+        const int C = c->abl_ch[l - 1];
+        MILAN_REQUIRE(hh >= 3 && ww >= 3, MILAN_ERR_SHAPE,
+                      "classify: image %dx%d is too small for the Places365 AlexNet: pool%d needs "
+                      "3x3 pixels and gets %dx%d (19x19 reaches conv2, 35x35 every level)",
+                      hin, win, l, hh, ww);
+        MILAN_REQUIRE(sp[l] || !fmt[l - 1], MILAN_ERR_STATE,
+                      "internal: places level %d would need a split -> fp32 pool", l);
+        MILAN_TRY(launch_maxpool3s2(x, n, hh, ww, C, hq[l - 1], wq[l - 1], sp[l], fmt[l - 1],
+                                    q[l - 1], c->status, s));
+        x = q[l - 1];
+        hh = hq[l - 1]; ww = wq[l - 1];
+        if (c->lrn.size > 0) {
+          MILAN_TRY(launch_lrn(x, (long long)n * hh * ww, C, sp[l], c->lrn.size, c->lrn.alpha,
+                               c->lrn.beta, qn[l - 1], c->status, s));
+          x = qn[l - 1];
+        }
+      }
+      GemmArgs g = encoder_conv_args(c->alex[l], x, n, hh, ww, a[l], EPI_BIAS_RELU, nullptr,
+                                     c->zero, &ho, &wo, sp[l], false);
+      if (sp[l] && !fmt[l]) g.out_split = 0;   // the next level is an fp32 one
+      MILAN_REQUIRE(sp[l] || !fmt[l], MILAN_ERR_STATE,
+                    "internal: places level %d is fp32 and would have to write split", l);
+      MILAN_TRY(launch_gemm(g, s));
+      MILAN_REQUIRE(ho == h[l] && wo == w[l], MILAN_ERR_SHAPE,
+                    "internal: places level %d geometry mismatch", l);
+      if (c->abl_count[l] > 0) MILAN_TRY(mask(l, a[l], a[l], -1));
+      x = a[l];
+      if (tap[l]) MILAN_TRY(emit(l, x));
+    }
+    *out = x;
+    return 0;
+  }
+
+  // pool5 + flatten in (C, h, w) order (alex_tail_kernel with 6 x 6 pooled pixels: every bin of
+  // its average is one pixel, divided by 1), fc6 / fc7 / fc8 (+ argmax)
+  int head(const float* x4, float* lg, long long* pr) const {
+    const milan_ctx::AlexHead& hd = c->ahead;
+    const int C = c->abl_ch[4];
+    MILAN_REQUIRE(hq[2] == 6 && wq[2] == 6 && hd.installed, MILAN_ERR_STATE,
+                  "internal: places head without 6 x 6 features or fc layers");
+    const dim3 grid((36 * C + 255) / 256, n);
+    if (fmt[4])
+      hipLaunchKernelGGL(alex_tail_kernel<true>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
+                         wq[2], 1.f, flat);
+    else
+      hipLaunchKernelGGL(alex_tail_kernel<false>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
+                         wq[2], 1.f, flat);
+    MILAN_CHECK_HIP(hipGetLastError());
+    MILAN_TRY(linear_run(flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, f6, s));
+    MILAN_TRY(linear_run(f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, f7, s));
+    MILAN_TRY(linear_run(f7, hd.w[2], hd.b[2], n, hd.in[2], hd.out[2], false, lg, s));
+    if (pr) {
+      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, lg, hd.out[2], pr);
+      MILAN_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+  }
+
+  // every level has a buffer of its own: AlexTrunk's rule
+  int hold_level(const float* images, int at, int level, const float** held) const {
+    return walk(at, level, at < 0 ? images : *held, held);
+  }
+};
+
 template <class T>
 static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
   Arena a; a.dry = true;
@@ -856,6 +1116,7 @@ static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int 
 
 size_t classify_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
   if (n_images <= 0 || H < 1 || W < 1) return 0;
+  if (places_trunk(c)) return workspace_dry<PlacesTrunk>(c, n_images, H, W, sweep_units);
   if (alex_trunk(c)) return workspace_dry<AlexTrunk>(c, n_images, H, W, sweep_units);
   if (resnet_trunk(c)) return workspace_dry<ResNetTrunk>(c, n_images, H, W, sweep_units);
   return 0;
@@ -945,7 +1206,7 @@ static int sweep(milan_ctx* c, const float* images, int n, int H, int W, bool sp
 // library-owned memory; switches the classify family on for this AlexNet context
 int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
                               const int* out, const int* in, hipStream_t s) {
-  MILAN_REQUIRE(c->d.trunk_kind == MILAN_TRUNK_ALEXNET, MILAN_ERR_ARG,
+  MILAN_REQUIRE(c->d.trunk_kind == MILAN_TRUNK_ALEXNET || places_trunk(c), MILAN_ERR_ARG,
                 "milan_set_alexnet_head: the context's trunk is not AlexNet");
   MILAN_REQUIRE(c->stem.w != nullptr, MILAN_ERR_STATE, "encoder weights were not uploaded");
   const int c5 = c->alex[4].cout;
@@ -982,6 +1243,20 @@ int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* 
   return 0;
 }
 
+// milan_set_alexnet_lrn: the Places trunk's optional LRN after pool1 and pool2 (0: off)
+int classify_set_alexnet_lrn(milan_ctx* c, int local_size, float alpha, float beta) {
+  MILAN_REQUIRE(places_trunk(c), MILAN_ERR_ARG,
+                "milan_set_alexnet_lrn: the context's trunk is not the Places365 AlexNet");
+  MILAN_REQUIRE(local_size == 0 || (local_size >= 1 && local_size % 2 == 1 && local_size <= 17),
+                MILAN_ERR_ARG,
+                "milan_set_alexnet_lrn: local_size %d is neither 0 (off) nor an odd number in 1..17",
+                local_size);
+  c->lrn.size = local_size;
+  c->lrn.alpha = alpha;
+  c->lrn.beta = beta;
+  return 0;
+}
+
 int linear_rowwise_run(const float* x, const float* W, const float* bias, int M, int K, int N,
                        float* y, hipStream_t s) {
   MILAN_REQUIRE(x && W && y && M >= 1 && M <= 65535 && K >= 1 && N >= 1, MILAN_ERR_ARG,
@@ -994,17 +1269,32 @@ int linear_rowwise_run(const float* x, const float* W, const float* bias, int M,
 // `head`: the call runs avgpool + fc (milan_activations stops before them and does not)
 static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool head = true) {
   MILAN_REQUIRE(classifier_trunk(c), MILAN_ERR_ARG,
-                "classification needs a ResNet trunk, or an AlexNet trunk whose head "
-                "milan_set_alexnet_head has installed (the Places365 AlexNet is not built)");
+                "classification needs a ResNet trunk, a Places365 AlexNet trunk, or an AlexNet "
+                "trunk whose head milan_set_alexnet_head has installed");
   MILAN_REQUIRE(c->stem.w != nullptr && c->abl_mask != nullptr, MILAN_ERR_STATE,
                 "encoder weights were not uploaded");
-  MILAN_REQUIRE(!head || alex_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
+  MILAN_REQUIRE(!head || !places_trunk(c) || c->ahead.installed, MILAN_ERR_STATE,
+                "this Places365 AlexNet context has no head: milan_set_alexnet_head installs "
+                "fc6 / fc7 / fc8");
+  MILAN_REQUIRE(!head || alex_trunk(c) || places_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
                 "this context was created without fc.weight: it has no classifier head");
   MILAN_REQUIRE(!c->trunk_f16, MILAN_ERR_ARG,
                 "classification runs in the f32 and split_f16 modes, not in the fast f16 mode");
   MILAN_REQUIRE(n > 0 && H >= 1 && W >= 1, MILAN_ERR_SHAPE,
                 "classify: need n>0 and H,W>=1 (got n=%d H=%d W=%d)", n, H, W);
+  if (places_trunk(c) && head) {
+    // fc6 reads C5 x 6 x 6 features and there is no adaptive pool in front of it
+    const int h0 = cls_out(H, 11, 4, 0), w0 = cls_out(W, 11, 4, 0);
+    const int h5 = cls_out(cls_out(cls_out(h0, 3, 2, 0), 3, 2, 0), 3, 2, 0);
+    const int w5 = cls_out(cls_out(cls_out(w0, 3, 2, 0), 3, 2, 0), 3, 2, 0);
+    MILAN_REQUIRE(h0 >= 3 && w0 >= 3 && h5 == 6 && w5 == 6, MILAN_ERR_SHAPE,
+                  "classify: image %dx%d does not leave 6x6 after pool5 of the Places365 AlexNet "
+                  "(227x227 does; fc6 reads %d features)", H, W, c->ahead.in[0]);
+  }
   bool sp = c->precision == MILAN_PRECISION_SPLIT_F16 && c->d.trunk_width % 8 == 0;
+  // (Places: conv3 is dense and reads a multiple of 64 channels; the grouped levels decide for
+  // themselves, PlacesTrunk::sp)
+  if (places_trunk(c)) sp = sp && c->alex[2].ws != nullptr;
   // (AlexNet: conv1 has 3 input channels and stays fp32, as in alexnet_run_batch)
   for (int l = 1; l < 5 && sp && alex_trunk(c); ++l) sp = c->alex[l].ws != nullptr;
   for (int li = 0; li < 4 && sp; ++li)
@@ -1018,7 +1308,7 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
                  int64_t* predictions, Arena& ws, hipStream_t s) {
   bool split;
   MILAN_TRY(classify_checks(c, n, H, W, &split));
-  auto go = alex_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
+  auto go = places_trunk(c) ? run<PlacesTrunk> : alex_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
   return go(c, images, n, H, W, split, logits, predictions, nullptr, 4, "classify", ws, s);
 }
 
@@ -1029,7 +1319,8 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
   MILAN_TRY(classify_checks(c, n, H, W, &split));
   MILAN_TRY(check_units(c, levels, units, count, "milan_classify_sweep"));
   if (count == 0) return 0;
-  auto go = alex_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
+  auto go = places_trunk(c) ? sweep<PlacesTrunk>
+            : alex_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
   return go(c, images, n, H, W, split, levels, units, count, targets, correct, predictions, ws, s);
 }
 
@@ -1054,8 +1345,8 @@ int activations_run(milan_ctx* c, const float* images, int n, int H, int W, cons
   }
   // (the messages about the workspace and the sub-batch have named the call differently on
   // the two trunks since they were written)
-  const bool alex = alex_trunk(c);
-  auto go = alex ? run<AlexTrunk> : run<ResNetTrunk>;
+  const bool alex = alex_trunk(c) || places_trunk(c);
+  auto go = places_trunk(c) ? run<PlacesTrunk> : alex ? run<AlexTrunk> : run<ResNetTrunk>;
   return go(c, images, n, H, W, split, nullptr, nullptr, taps, top,
             alex ? "classify" : "activations", ws, s);
 }

@@ -152,8 +152,29 @@ struct GemmArgs {
   // sets tap_ncls = -1 to keep a launch on the linear order (test hook).
   int tap_ncls;
   int tap_cls[MILAN_TAP_CLASSES][5];  // y0, ny, x0, nx, mask
+  // Grouped convolution: `groups` > 1 runs that many independent products of
+  // the SAME geometry in one launch, the group a grid dimension (blockIdx.y).  Every field
+  // above describes ONE group (N, Cin, K, Kp are per-group; ldc and a_pix_stride the full
+  // rows); group q reads A + q * a_grp, W (Wt) + q * w_grp, bias + q * bias_grp, aux +
+  // q * aux_grp and writes C + q * c_grp (floats).  A grouped kernel shifts its copy of the
+  // arguments at entry (shift_group) and runs unchanged; groups <= 1 is the plain launch.
+  int groups;
+  long a_grp, w_grp, bias_grp, c_grp, aux_grp;
 };
 static_assert(sizeof(GemmArgs) % 4 == 0, "GemmArgs is reloaded word by word");
+
+// group `q` of a grouped launch as a plain launch on offset pointers: what a grouped kernel
+// does to its arguments at entry, and what the per-group baseline (MILAN_GROUP_LAUNCH=0)
+// launches one by one
+__host__ __device__ inline void shift_group(GemmArgs& g, int q) {
+  g.A += (long)q * g.a_grp;
+  g.W += (long)q * g.w_grp;
+  if (g.Wt) g.Wt += (long)q * g.w_grp;
+  if (g.bias) g.bias += (long)q * g.bias_grp;
+  if (g.aux) g.aux += (long)q * g.aux_grp;
+  g.C += (long)q * g.c_grp;
+  g.groups = 1;
+}
 
 enum OutMode : int { OUT_SCALAR = 0, OUT_VEC4 = 1, OUT_SPLIT8 = 2, OUT_F16 = 3 };
 
@@ -367,6 +388,10 @@ struct ConvW {
   float* wft = nullptr;     // ... `wf` in (64-channel slice, tap, channel) order
   int cout = 0, cin = 0, kh = 0, kw = 0, stride = 1, pad = 0, K = 0, Kp = 0;
   int cin_real = 0;  // channels before padding to a multiple of 4
+  // grouped conv: cout is the full width; cin, cin_real, K and Kp are those of ONE group (cin =
+  // the weight's second extent, K = kh * kw * cin; an input pixel has cin * groups channels);
+  // w, ws, wst hold the groups' rows back to back ([cout][Kp])
+  int groups = 1;
 };
 struct Bottleneck {
   ConvW c1, c2, c3, down;
@@ -610,6 +635,8 @@ struct milan_ctx {
     float* b[3] = {nullptr, nullptr, nullptr};
     int out[3] = {0, 0, 0}, in[3] = {0, 0, 0};
   } ahead;
+  // the Places365 AlexNet's optional LRN after pool1 and pool2 (milan_set_alexnet_lrn; 0: off)
+  struct AlexLrn { int size = 0; float alpha = 1e-4f, beta = 0.75f; } lrn;
 };
 
 namespace milan {
@@ -664,6 +691,11 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
                    int64_t* predictions, Arena& ws, hipStream_t s);
 int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
                               const int* out, const int* in, hipStream_t s);
+int classify_set_alexnet_lrn(milan_ctx* c, int local_size, float alpha, float beta);
+// across-channel LRN over (pixels, C) with a pixel's channels contiguous, fp32 or split at
+// scale 1 in and out (classify.hip, lrn_kernel); x and y must not overlap
+int launch_lrn(const float* x, long long pixels, int C, bool split, int local_size, float alpha,
+               float beta, float* y, unsigned* status, hipStream_t s);
 // y (M, N) = act(x (M, K) W^T + bias) on the fp32 MFMA; `packed` from linear_pack
 size_t linear_packed_floats(int N, int K);
 int linear_pack(const float* W, int N, int K, float* packed, hipStream_t s);

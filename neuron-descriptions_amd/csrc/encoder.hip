@@ -141,7 +141,7 @@ static int make_f16_weight(milan_ctx* c, ConvW* w, hipStream_t s) {
 
 static int pack_conv(milan_ctx* c, const std::string& conv,
                      const std::string& bn, int stride, int pad, ConvW* out,
-                     hipStream_t s, bool split_without_bn = false) {
+                     hipStream_t s, bool split_without_bn = false, int groups = 1) {
   const Tensor* w = find(c, conv + ".weight");
   MILAN_REQUIRE(w && w->shape.size() == 4, MILAN_ERR_STATE,
                 "missing conv weight %s.weight", conv.c_str());
@@ -156,6 +156,15 @@ static int pack_conv(milan_ctx* c, const std::string& conv,
                   "%s channels != %s out channels", bn.c_str(), conv.c_str());
     g = tg->dev; b = tb->dev; m = tm->dev; v = tv->dev;
   }
+  // A grouped conv's weight is (cout, cin / groups, kh, kw): its rows are packed exactly like
+  // a dense conv's of cin / groups channels -- K and Kp per group, the groups' rows back to
+  // back -- and so are the split and slice-major copies below (ConvW::groups)
+  MILAN_REQUIRE(groups >= 1 && w->shape[0] % groups == 0 &&
+                    (groups == 1 || w->shape[1] % 4 == 0),
+                MILAN_ERR_SHAPE, "%s.weight: %ld x %ld channels do not split into %d groups of "
+                "a multiple of 4 input channels", conv.c_str(), (long)w->shape[0],
+                (long)w->shape[1], groups);
+  out->groups = groups;
   out->cout = (int)w->shape[0];
   out->cin = ((int)w->shape[1] + 3) / 4 * 4;
   out->cin_real = (int)w->shape[1];
@@ -327,6 +336,32 @@ int encoder_finalize(milan_ctx* c, hipStream_t s) {
                     MILAN_ERR_SHAPE,
                     "features.%d: %d channels, expected %d (with a bias)", idx[i],
                     c->alex[i].cout, mult[i] * c->d.trunk_width);
+    }
+    c->stem = c->alex[0];  // "encoder weights present" marker
+  } else if (kind == MILAN_TRUNK_ALEXNET_PLACES) {
+    // the Places365 AlexNet: conv1 unpadded, conv2 / conv4 / conv5 in two groups
+    // unless the weights say otherwise (split_groups=False: dense weights, groups of 1)
+    if (!find(c, p + "conv1.weight")) return 0;
+    static const int stride[5] = {4, 1, 1, 1, 1}, pad[5] = {0, 2, 1, 1, 1};
+    static const int mult[5] = {3, 8, 12, 12, 8};
+    MILAN_REQUIRE(c->d.trunk_width % 8 == 0, MILAN_ERR_SHAPE,
+                  "the Places365 AlexNet needs a width that is a multiple of 8 (got %d)",
+                  c->d.trunk_width);
+    int cin_full = 3;
+    for (int i = 0; i < 5; ++i) {
+      const std::string name = p + "conv" + std::to_string(i + 1);
+      const Tensor* w = find(c, name + ".weight");
+      MILAN_REQUIRE(w && w->shape.size() == 4 && w->shape[1] >= 1 &&
+                        cin_full % (int)w->shape[1] == 0,
+                    MILAN_ERR_SHAPE, "conv%d.weight is missing or does not divide %d input "
+                    "channels into groups", i + 1, cin_full);
+      const int groups = cin_full / (int)w->shape[1];
+      MILAN_TRY(pack_conv(c, name, "", stride[i], pad[i], &c->alex[i], s, i > 0, groups));
+      MILAN_REQUIRE(c->alex[i].cout == mult[i] * c->d.trunk_width &&
+                        c->alex[i].bias != nullptr,
+                    MILAN_ERR_SHAPE, "conv%d: %d channels, expected %d (with a bias)", i + 1,
+                    c->alex[i].cout, mult[i] * c->d.trunk_width);
+      cin_full = c->alex[i].cout;
     }
     c->stem = c->alex[0];  // "encoder weights present" marker
   } else {
@@ -1324,7 +1359,8 @@ size_t encoder_workspace(const milan_ctx* c, int n_images, int H, int W) {
   Arena a; a.dry = true;
   const int sub = encoder_sub_batch();
   const int n = n_images < sub ? n_images : sub;
-  if (c->d.trunk_kind == MILAN_TRUNK_NONE) return 0;
+  if (c->d.trunk_kind == MILAN_TRUNK_NONE || c->d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES)
+    return 0;
   if (c->d.trunk_kind == MILAN_TRUNK_ALEXNET) {
     alexnet_workspace_dry(c, n, H, W, a);
     return a.off;
@@ -1350,6 +1386,16 @@ static GemmArgs conv_args(const ConvW& cw, const float* in, int n, int H, int W,
   g.a_img_stride = (long)H * W * cw.cin;
   g.epilogue = epi; g.zero = zero;
   g.flop_k = cw.kh * cw.kw * cw.cin_real;
+  if (cw.groups > 1) {
+    // one group's product, the full rows as strides (GemmArgs::groups)
+    const int ng = cw.cout / cw.groups;
+    g.N = ng;
+    g.a_pix_stride = (long)cw.cin * cw.groups;
+    g.a_img_stride = (long)H * W * cw.cin * cw.groups;
+    g.groups = cw.groups;
+    g.a_grp = cw.cin; g.w_grp = (long)ng * cw.Kp;
+    g.bias_grp = ng; g.c_grp = ng; g.aux_grp = ng;
+  }
   if (split) {
     g.W = cw.ws; g.a_split = 1; g.out_split = 1; g.aux_split = aux != nullptr;
     g.acc_scale = cw.ws_inv;
@@ -1408,8 +1454,9 @@ int encoder_run(milan_ctx* c, const void* images, int image_dtype,
 int encoder_run_spatial(milan_ctx* c, const void* images, int image_dtype,
                         const void* masks, int mask_dtype, int n, int H, int W,
                         float* out, Arena& ws, hipStream_t s) {
-  MILAN_REQUIRE(c->d.trunk_kind != MILAN_TRUNK_ALEXNET, MILAN_ERR_ARG,
-                "spatial encoding needs a ResNet trunk");
+  MILAN_REQUIRE(c->d.trunk_kind != MILAN_TRUNK_ALEXNET &&
+                    c->d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES,
+                MILAN_ERR_ARG, "spatial encoding needs a ResNet trunk");
   Arena dry; dry.dry = true;
   EncPlan pl;
   plan(c, 1, H, W, dry, &pl);
@@ -1436,6 +1483,9 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
                              int W, float* features, Arena& ws, hipStream_t s,
                              float* spatial_out) {
   const bool spatial = spatial_out != nullptr;
+  MILAN_REQUIRE(c->d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES, MILAN_ERR_ARG,
+                "the Places365 AlexNet trunk has no encoder config: it classifies, ablates and "
+                "taps activations only");
   MILAN_REQUIRE(!spatial || c->d.trunk_kind != MILAN_TRUNK_ALEXNET, MILAN_ERR_ARG,
                 "spatial encoding needs a ResNet trunk");
   MILAN_REQUIRE(c->stem.w != nullptr, MILAN_ERR_STATE,

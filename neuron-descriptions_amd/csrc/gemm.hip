@@ -610,9 +610,13 @@ __device__ __forceinline__ int live_tiles_m(GemmArgs& g, int tiles_m, int BM) {
   return (g.M + BM - 1) / BM;
 }
 
-template <int BM, int BN, int STAGES, bool CIN32, bool SPLIT>
+// GROUPED (GemmArgs::groups): blockIdx.y is the group; the arguments are shifted to it at
+// entry and the kernel runs unchanged.  A compile-time flag: the plain instantiations keep
+// the code they had.
+template <int BM, int BN, int STAGES, bool CIN32, bool SPLIT, bool GROUPED = false>
 __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 2) void igemm_kernel(
     GemmArgs g, int tiles_m, int tiles_n) {
+  if constexpr (GROUPED) shift_group(g, (int)blockIdx.y);
   constexpr int BK = 32;
   constexpr int WM = 64, WN = 64;
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -1478,7 +1482,7 @@ __global__ __launch_bounds__(512, 2) void igemm_split16_linp_kernel(GemmArgs g,
 // VALU and VMEM traffic inside a loop whose waits count VMEM operations).
 // (DENSE_M: M stays the launch's dense row count -- the epilogue of a row-list tile bounds
 // its output rows by it, the list's length is read separately)
-template <bool DENSE_M = false>
+template <bool DENSE_M = false, bool GROUPED = false>
 __device__ __forceinline__ GemmArgs reload_gemm_args() {
   typedef const int __attribute__((address_space(4)))* KArgWords;
   KArgWords kw = (KArgWords)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1488,6 +1492,7 @@ __device__ __forceinline__ GemmArgs reload_gemm_args() {
 #pragma unroll
   for (unsigned i = 0; i < sizeof(GemmArgs) / 4; ++i) words[i] = kw[i];
   __builtin_memcpy(&g, words, sizeof(GemmArgs));
+  if constexpr (GROUPED) shift_group(g, (int)blockIdx.y);
   if constexpr (!DENSE_M)
     g.M = live_rows(g.m_live, g.m_live_mul, g.M);   // (GemmArgs::m_live: row count on the device)
   return g;
@@ -1846,11 +1851,11 @@ __device__ __forceinline__ bool tap_tile(const GemmArgs& g, int tiles_m, int til
 // residual) through the row table.  A TAPI list tile is given the whole-image class: all taps
 // with the per-row mask -- the products that are skipped elsewhere are +-0.  One tile per
 // workgroup (the row table lives in A slot 0).
-template <int BNW, bool F16 = false, bool TAPI = false, bool LIST = false>
+template <int BNW, bool F16 = false, bool TAPI = false, bool LIST = false, bool GROUPED = false>
 __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int tid, bool prefetched,
                                                   bool has_next, int ntile_m, int ntile_n,
                                                   TapTile tt = TapTile{}) {
-  const GemmArgs g = reload_gemm_args();
+  const GemmArgs g = reload_gemm_args<false, GROUPED>();
   constexpr int BM = 256, BN = 256, BKP = 32, TM = BNW == 256 ? 4 : 2, TN = 2;
   static_assert(BNW == 256 || BNW == 128, "ping-pong tile: 256 or 128 columns");
   constexpr int SLOTF = BM * BKP;  // floats per 32 KB slot
@@ -2221,7 +2226,7 @@ __device__ __forceinline__ void split16_pp32_tile(int tile_m, int tile_n, int ti
     issue_w(N, I0{}, true);
     issue_a(N, I1{}, true);
   }
-  const GemmArgs ge = reload_gemm_args<LIST>();  // the epilogue's arguments, loaded here
+  const GemmArgs ge = reload_gemm_args<LIST, GROUPED>();  // the epilogue's arguments, loaded here
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -2317,6 +2322,33 @@ __global__ __launch_bounds__(512, 2) void igemm_split16_pp32t_kernel(GemmArgs g,
   split16_pp32_tile<BNW, false, true>(tt.j, tt.tile_n, tid, false, false, tt.j, tt.tile_n, tt);
 }
 
+// Grouped convs (GemmArgs::groups) on the 128-column tile: blockIdx.y is the group, the tile
+// reloads its arguments shifted to it.  One tile per workgroup.  Kernels of their own names:
+// the plain forms above keep their code objects (and their pins in tools/check_isa.py).
+__global__ __launch_bounds__(512, 2) void igemm_grouped_pp32n_kernel(GemmArgs g, int tiles_m,
+                                                                     int tiles_n) {
+  tiles_m = live_tiles_m(g, tiles_m, 256);
+  const int T = tiles_m * tiles_n;
+  const int q = blockIdx.x;
+  if (q >= T) return;
+  const int tile = xcd_tile(q, T);
+  const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  split16_pp32_tile<128, false, false, false, true>(tile_m, tile_n, tid, false, false, tile_m,
+                                                    tile_n);
+}
+__global__ __launch_bounds__(512, 2) void igemm_grouped_pp32t_kernel(GemmArgs g, int tiles_m,
+                                                                     int tiles_n) {
+  tiles_m = live_tiles_m(g, tiles_m, 256);
+  TapTile tt;
+  if (!tap_tile(g, tiles_m, tiles_n, &tt)) return;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  split16_pp32_tile<128, false, true, false, true>(tt.j, tt.tile_n, tid, false, false, tt.j,
+                                                   tt.tile_n, tt);
+}
+
 // row-list launches (GemmArgs::row_list): 256-column tiles over 256 listed rows each, one tile
 // per workgroup; TAPI: a k x k conv in (slice, tap, channel) order, all taps, per-row mask
 template <bool TAPI>
@@ -2380,9 +2412,10 @@ __global__ __launch_bounds__(512, 2) void igemm_split16_pp_kernel(GemmArgs g, in
 
 // The same pipeline with 64 x 64 wave tiles (4 waves per 256 x 64 block, two
 // blocks per CU): the N = 64 layers of layer1.
-template <int BM, int BN, int STAGES>
+template <int BM, int BN, int STAGES, bool GROUPED = false>
 __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, 2) void igemm_split16_tm2_kernel(
     GemmArgs g, int tiles_m, int tiles_n) {
+  if constexpr (GROUPED) shift_group(g, (int)blockIdx.y);
   tiles_m = live_tiles_m(g, tiles_m, BM);
   if ((int)blockIdx.x >= tiles_m * tiles_n) return;
   const int tile = xcd_tile(blockIdx.x, tiles_m * tiles_n);
@@ -2713,6 +2746,27 @@ static int launch_cfg(const GemmArgs& g, hipStream_t s) {
   return 0;
 }
 
+// set by the launchers that have a grouped form (GemmArgs::groups > 1): launch_gemm() fails a
+// grouped launch that the dispatch sent anywhere else (it would run group 0 alone)
+static thread_local bool t_group_taken = false;
+
+// the general fp32 kernel with the group as grid.y
+template <int BM, int BN, int STAGES, bool CIN32>
+static int launch_cfg_grouped(const GemmArgs& g, hipStream_t s) {
+  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
+  constexpr int NT = (BM / 64) * (BN / 64) * 64;
+  size_t lds = size_t(STAGES) * (BM + BN) * 32 * sizeof(float);
+  const size_t stage_bytes = size_t(NT / 64) * 32 * 68 * sizeof(float);
+  if (lds < stage_bytes) lds = stage_bytes;
+  auto kern = igemm_kernel<BM, BN, STAGES, CIN32, false, true>;
+  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
+  t_group_taken = true;
+  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, g.groups), dim3(NT), lds, s, g, tiles_m,
+                     tiles_n);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---- live kernel timing (bench.py's roofline leg) ---------------------------
 // While profiling is enabled, HIP events are recorded on the launch stream
 // right before/after every GEMM launch and around every stage region
@@ -2927,6 +2981,15 @@ static int launch_split16_tm2(const GemmArgs& g, hipStream_t s) {
   size_t lds = size_t(STAGES) * (BM + BN) * 16 * sizeof(float);
   const size_t stage_bytes = size_t(NT / 64) * 32 * 68 * sizeof(float);
   if (lds < stage_bytes) lds = stage_bytes;
+  if (g.groups > 1) {
+    auto gkern = igemm_split16_tm2_kernel<BM, BN, STAGES, true>;
+    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(gkern), (int)lds));
+    t_group_taken = true;
+    hipLaunchKernelGGL(gkern, dim3(tiles_m * tiles_n, g.groups), dim3(NT), lds, s, g, tiles_m,
+                       tiles_n);
+    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   auto kern = igemm_split16_tm2_kernel<BM, BN, STAGES>;
   MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(NT), lds, s, g, tiles_m,
@@ -3033,6 +3096,30 @@ static int launch_split16_pp32(const GemmArgs& g, hipStream_t s) {
     MILAN_CHECK_HIP(hipGetLastError());
     return 0;
   }
+  if (g.groups > 1) {
+    // grouped convs: the 128-column tile only (the per-group widths of the Places AlexNet),
+    // one tile per workgroup, the group as grid.y; the k order is the plain launch's
+    MILAN_REQUIRE(BNW == 128, MILAN_ERR_STATE,
+                  "gemm: internal: a grouped launch reached the 256-column tile (N=%d per group)",
+                  g.N);
+    t_group_taken = true;
+    GemmArgs t = g;
+    const bool tapi = tap_inner_wanted(g);
+    int grid = tiles_m * tiles_n;
+    if (tapi) {
+      // (shift_group moves Wt with W: the kernel reads W)
+      t.W = g.Wt;
+      t.Wt = nullptr;
+      t.tap_inner = 1;
+      grid = tap_classes(t, tiles_m, tiles_n);
+    }
+    profile_tag_kernel(MILAN_KERNEL_PP32_128);
+    auto kern = tapi ? igemm_grouped_pp32t_kernel : igemm_grouped_pp32n_kernel;
+    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid, g.groups), dim3(512), lds, s, t, tiles_m, tiles_n);
+    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   if (tap_inner_wanted(g)) {
     GemmArgs t = g;
     t.W = g.Wt;
@@ -3118,13 +3205,18 @@ static bool pp_eligible(const GemmArgs& g) {
   return a_span < 0x7fffffffL && a2_span < 0x7fffffffL && w_span < 0x7fffffffL;
 }
 
+// MILAN_PP128=0: the round-3 lockstep 256 x 128 kernel instead of the pair-staged tile (A/B timing)
+static bool pp128_on() {
+  static int pp128 = -1;
+  if (pp128 < 0) { const char* e = getenv("MILAN_PP128"); pp128 = e ? atoi(e) : 1; }
+  return pp128 != 0;
+}
+
 template <int BM, int BN, int STAGES>
 static int launch_split16(const GemmArgs& g, hipStream_t s) {
   if constexpr (BM == 256 && BN == 128 && STAGES == 3) {
     // MILAN_PP128=0: the round-3 lockstep 256 x 128 kernel (same bits; A/B timing)
-    static int pp128 = -1;
-    if (pp128 < 0) { const char* e = getenv("MILAN_PP128"); pp128 = e ? atoi(e) : 1; }
-    if (pp128 && !g.chunk_major && pp_eligible(g) && g.Cin % 32 == 0 &&
+    if (pp128_on() && !g.chunk_major && pp_eligible(g) && g.Cin % 32 == 0 &&
         (!g.A2 || g.K1 % 32 == 0) && ((long)g.H + g.pad) < 32768 && ((long)g.Wd + g.pad) < 32768)
       return launch_split16_pp32<128>(g, s);
   }
@@ -3263,6 +3355,25 @@ bool row_list_supported(const GemmArgs& g) {
   return true;
 }
 
+// A launch whose group strides are set is a grouped conv or ONE group of it (shift_group
+// leaves the strides in place): the dispatch gives both the same kernel.
+static bool group_part(const GemmArgs& g) { return g.groups > 1 || g.c_grp != 0; }
+
+// Whether the dispatch below sends `g` (groups > 1) to a kernel with a grouped form: the general
+// fp32 kernel, the 64-column split tile of the k x k convs and the 128-column pair-staged tile.
+// Everything else -- a forced tile, MILAN_PP128=0, the 1x1 convs with N <= 64, a layer beyond the
+// pair-staged tile's 32-bit offsets -- runs as one plain launch per group.
+static bool groups_supported(const GemmArgs& g) {
+  if (g.tile_hint != 0 || env_tile_hint() != 0 || env_tile_override(g.N, g.K) != 0) return false;
+  if (!g.a_split) return true;
+  if (g.f16 || g.A2 || g.chunk_major || g.Cin % 32 != 0) return false;
+#if MILAN_EXPERIMENTS
+  if (conv3x3_enabled() || (getenv("MILAN_SCHED") && atoi(getenv("MILAN_SCHED")))) return false;
+#endif
+  if (g.N <= 64) return g.KH * g.KW > 1;
+  return pp128_on() && pp_eligible(g) && (long)g.H + g.pad < 32768 && (long)g.Wd + g.pad < 32768;
+}
+
 static int launch_gemm_impl(GemmArgs g, hipStream_t s) {
   const bool cin32 = (g.Cin % 32 == 0);
   if (g.status == nullptr) g.status = status_word();
@@ -3393,6 +3504,9 @@ static int launch_gemm_impl(GemmArgs g, hipStream_t s) {
 #endif
     // 256x256 tile, 5-deep ring = all 160 KB of LDS, four k-tiles in flight (round 3,
     // same-box A/B against the 4-deep ring: +0.5 % end to end, same bits)
+    // (a grouped conv, or one group of it, stays on the 128-column tile at every width: the
+    // tile that has a grouped form, so that both forms of the launch give the same bits)
+    if (group_part(g)) return launch_split16<256, 128, 3>(g, s);
     if (g.N % 256 == 0) return launch_split16<256, 256, 5>(g, s);
     {
       // wide outputs that are not a multiple of 256 (the vocabulary GEMMs, N =
@@ -3405,6 +3519,14 @@ static int launch_gemm_impl(GemmArgs g, hipStream_t s) {
         return launch_split16<256, 256, 5>(g, s);
     }
     return launch_split16<256, 128, 3>(g, s);
+  }
+  if (g.groups > 1) {
+    // grouped fp32: the tiles of the plain dispatch below, the group as grid.y
+    if (g.N <= 64)
+      return cin32 ? launch_cfg_grouped<256, 64, 2, true>(g, s)
+                   : launch_cfg_grouped<256, 64, 2, false>(g, s);
+    return cin32 ? launch_cfg_grouped<128, 128, 2, true>(g, s)
+                 : launch_cfg_grouped<128, 128, 2, false>(g, s);
   }
   if (g.N <= 64) {
     return cin32 ? launch_cfg<256, 64, 2, true, false>(g, s)
@@ -3432,6 +3554,31 @@ int launch_gemm(const GemmArgs& g, hipStream_t s) {
                 MILAN_ERR_SHAPE,
                 "gemm: Cin=%d / strides must be multiples of 4 floats and "
                 "operands 16-byte aligned", g.Cin);
+  if (g.groups > 1) {
+    MILAN_REQUIRE(!g.row_list && !g.m_live && !g.A2 && !g.f16 && g.epilogue != EPI_LSE &&
+                      g.epilogue != EPI_LSTM && g.groups <= 65535,
+                  MILAN_ERR_SHAPE, "gemm: a grouped launch is a plain conv (groups=%d)", g.groups);
+    // MILAN_GROUP_LAUNCH=0: the baseline, one plain launch per group on offset pointers (the
+    // same kernel per group as the grouped launch runs: the dispatch reads per-group sizes)
+    static int one = -1;
+    if (one < 0) { const char* e = getenv("MILAN_GROUP_LAUNCH"); one = e ? atoi(e) : 1; }
+    // ... which is also how a launch without a grouped kernel runs, decided before anything starts
+    if (!one || !groups_supported(g)) {
+      for (int q = 0; q < g.groups; ++q) {
+        GemmArgs t = g;
+        shift_group(t, q);
+        MILAN_TRY(launch_gemm_checked(t, s));
+      }
+      return 0;
+    }
+    t_group_taken = false;
+    const int r = launch_gemm_checked(g, s);
+    MILAN_REQUIRE(r != 0 || t_group_taken, MILAN_ERR_STATE,
+                  "gemm: a grouped launch was dispatched to a kernel without a grouped form "
+                  "(N=%d Cin=%d %dx%d per group: groups_supported() no longer matches the "
+                  "dispatch)", g.N, g.Cin, g.KH, g.KW);
+    return r;
+  }
   if (g.row_list != nullptr) {
     // row_list_supported() restates the dispatch below; should the two ever part, the launch
     // must not run on some other kernel unnoticed

@@ -5,8 +5,12 @@ offers.  `AlexNetClassifier` has the module tree of the reference's `alexnet_seq
 (`src/deps/ext/torchvision/models.py`: `conv1 .. conv5`, `fc6`, `fc7`, `linear8`), so a
 checkpoint that experiment saved loads with `load_state_dict` and
 `ImageClassifier.fit(layers=['fc6', 'fc7', 'linear8'])` finds its layers; it is edited and
-tapped at `conv1 .. conv5`.  The Places365 AlexNet of `src/deps/alexnet.py` (grouped convs,
-an unpadded conv1, `fc8`) is a different network and is not built.
+tapped at `conv1 .. conv5`.
+
+`PlacesAlexNetClassifier` and `OldResNet152` are the two Places365 networks of the reference's
+model zoo (`src/deps/alexnet.py`, `src/deps/resnet152.py`): the first is a network of its own
+(grouped convs, an unpadded conv1, an optional LRN, `fc8`), the second the v1.5 bottleneck
+ResNet-152 under Torch7-converted key and layer names.
 
 `ResNetClassifier` is the CNN the reference's experiments dissect and edit
 (`experiments/analyze.py`, `experiments/edit.py`: a torchvision ResNet handed to
@@ -25,8 +29,11 @@ tree and key names (`conv1.weight`, `bn1.*`, `layerL.B.convK.weight`, `downsampl
 """
 from typing import Dict, Optional, Sequence, Tuple
 
+import re
+
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 from milan_amd import hip, synthetic
 
@@ -317,3 +324,209 @@ class AlexNetClassifier(NativeClassifier):
             sd[f'encoder.encoder.model.features.{index}.bias'] = module.bias
         head = [t for fc in (self.fc6, self.fc7, self.linear8) for t in (fc.weight, fc.bias)]
         return hip.Context(hip.make_dims(sd, 1), sd, device, alexnet_head=head)
+
+
+class LRN(nn.Module):
+    """Across-channel local response normalisation as the Places365 AlexNet defines it:
+    y = x / (1 + alpha * mean)^beta, `mean` the average of x^2 over the `local_size`
+    neighbouring channels with zeros beyond both ends (the divisor is always `local_size`).
+    The torch module takes any odd size; the native kernel behind `PlacesAlexNetClassifier`
+    (`hip.Context.set_alexnet_lrn`) takes odd sizes up to 17."""
+
+    def __init__(self, local_size: int = 5, alpha: float = 1e-4, beta: float = 0.75):
+        super().__init__()
+        if local_size < 1 or local_size % 2 == 0:
+            raise ValueError(f'local_size must be odd, got {local_size}')
+        self.local_size, self.alpha, self.beta = int(local_size), float(alpha), float(beta)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        half = self.local_size // 2
+        squares = F.pad(x * x, (0, 0, 0, 0, half, half))
+        total = sum(squares[:, j:j + x.shape[1]] for j in range(self.local_size))
+        return x / (total / self.local_size * self.alpha + 1.0)**self.beta
+
+    def extra_repr(self) -> str:
+        return f'local_size={self.local_size}, alpha={self.alpha}, beta={self.beta}'
+
+
+class PlacesAlexNetClassifier(NativeClassifier):
+    """The Places365 AlexNet of the reference (`src/deps/alexnet.py`) with a native eval-mode
+    forward.
+
+    Named children, in order: conv1, relu1, pool1, [lrn1,] conv2, relu2, pool2, [lrn2,]
+    conv3, relu3, conv4, relu4, conv5, relu5, pool5, flatten, fc6, relu6, [dropout6,] fc7,
+    relu7, [dropout7,] fc8 -- the reference's, so its `state_dict` loads with
+    `load_state_dict`.  Channels are `width` / 32 x (96, 256, 384, 384, 256), `width` a
+    multiple of 8 (the reference: 32); conv2, conv4 and conv5 have two groups unless
+    `split_groups` is off.  conv1 has no padding and there is no adaptive pool: the forward
+    needs images that leave 6 x 6 after pool5 (227 x 227); `activations` takes any image of
+    35 x 35 or more.  Edited and tapped at `layers` = conv1 .. conv5 with
+    `AlexNetClassifier`'s semantics: relu(conv + bias) x mask, before the pool and the LRN.
+    `precision` as for `ResNetClassifier`.
+    """
+
+    layers: Tuple[str, ...] = ALEXNET_LAYERS
+
+    def __init__(self,
+                 num_classes: int = 365,
+                 width: int = 32,
+                 hidden: int = 4096,
+                 include_lrn: bool = False,
+                 split_groups: bool = True,
+                 include_dropout: bool = False,
+                 precision: str = 'auto'):
+        super().__init__()
+        if precision not in ('auto', 'split_f16', 'f32'):
+            raise ValueError(f'unknown precision: {precision}')
+        if width < 8 or width % 8:
+            raise ValueError(f'width must be a multiple of 8, got {width}')
+        self.width = int(width)
+        self.hidden = int(hidden)
+        self.num_classes = int(num_classes)
+        self.include_lrn = bool(include_lrn)
+        self.precision = precision
+        ch = [c * self.width for c in synthetic.PLACES_ALEXNET_CHANNELS]
+        groups = synthetic.PLACES_ALEXNET_GROUPS if split_groups else (1, 1, 1, 1, 1)
+        self.conv1 = nn.Conv2d(3, ch[0], 11, 4, groups=groups[0])
+        self.relu1 = nn.ReLU(inplace=True)
+        self.pool1 = nn.MaxPool2d(3, 2)
+        if include_lrn:
+            self.lrn1 = LRN(5, 1e-4, 0.75)
+        self.conv2 = nn.Conv2d(ch[0], ch[1], 5, padding=2, groups=groups[1])
+        self.relu2 = nn.ReLU(inplace=True)
+        self.pool2 = nn.MaxPool2d(3, 2)
+        if include_lrn:
+            self.lrn2 = LRN(5, 1e-4, 0.75)
+        self.conv3 = nn.Conv2d(ch[1], ch[2], 3, padding=1, groups=groups[2])
+        self.relu3 = nn.ReLU(inplace=True)
+        self.conv4 = nn.Conv2d(ch[2], ch[3], 3, padding=1, groups=groups[3])
+        self.relu4 = nn.ReLU(inplace=True)
+        self.conv5 = nn.Conv2d(ch[3], ch[4], 3, padding=1, groups=groups[4])
+        self.relu5 = nn.ReLU(inplace=True)
+        self.pool5 = nn.MaxPool2d(3, 2)
+        self.flatten = nn.Flatten()
+        self.fc6 = nn.Linear(ch[4] * 36, self.hidden)
+        self.relu6 = nn.ReLU(inplace=True)
+        if include_dropout:
+            self.dropout6 = nn.Dropout()
+        self.fc7 = nn.Linear(self.hidden, self.hidden)
+        self.relu7 = nn.ReLU(inplace=True)
+        if include_dropout:
+            self.dropout7 = nn.Dropout()
+        self.fc8 = nn.Linear(self.hidden, self.num_classes)
+        self._init_native()
+
+    def forward_eager(self, images: torch.Tensor) -> torch.Tensor:
+        """The reference's `nn.Sequential` forward: the named children in order."""
+        x = images
+        for module in self.children():
+            x = module(x)
+        return x
+
+    def _make_context(self, device: torch.device) -> hip.Context:
+        sd = {}
+        for conv in self.layers:
+            module = getattr(self, conv)
+            sd[f'encoder.encoder.model.{conv}.weight'] = module.weight
+            sd[f'encoder.encoder.model.{conv}.bias'] = module.bias
+        head = [t for fc in (self.fc6, self.fc7, self.fc8) for t in (fc.weight, fc.bias)]
+        ctx = hip.Context(hip.make_dims(sd, 1), sd, device, alexnet_head=head)
+        if self.include_lrn:
+            ctx.set_alexnet_lrn(self.lrn1.local_size, self.lrn1.alpha, self.lrn1.beta)
+        return ctx
+
+
+# the reference's `OldResNet152` is an `nn.Sequential` converted from Torch7: children 0 / 1
+# are conv1 / bn1, 4..7 the four stages, 10.1 the Linear layer; inside a block `0.0.N` is the
+# residual branch (conv, bn, relu three times over) and `0.1.N` the downsample branch
+_OLD_BRANCH = {'0': 'conv1', '1': 'bn1', '3': 'conv2', '4': 'bn2', '6': 'conv3', '7': 'bn3'}
+_OLD_KEY = re.compile(r'^([4-7])\.(\d+)\.0\.([01])\.(\d+)\.(\w+)$')
+OLD_RESNET152_LAYERS = {'0': 'conv1', '4': 'layer1', '5': 'layer2', '6': 'layer3',
+                        '7': 'layer4'}
+
+
+def rekey_old_resnet152(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A state dict of the reference's `OldResNet152` (`0.weight`, `4.0.0.0.0.weight`,
+    `10.1.weight`, ...) under torchvision's key names (`conv1.weight`,
+    `layer1.0.conv1.weight`, `fc.weight`, ...), in the same order.  Keys that already are
+    torchvision's pass through; anything else is a KeyError."""
+    out = {}
+    for key, value in state_dict.items():
+        head, _, tail = key.partition('.')
+        match = _OLD_KEY.match(key)
+        if head in ('0', '1') and tail and '.' not in tail:
+            new = f"{'conv1' if head == '0' else 'bn1'}.{tail}"
+        elif key.startswith('10.1.') and key.count('.') == 2:
+            new = 'fc.' + key[5:]
+        elif match:
+            stage, block, branch, index, leaf = match.groups()
+            if branch == '0':
+                if index not in _OLD_BRANCH:
+                    raise KeyError(f'not a key of OldResNet152: {key}')
+                module = _OLD_BRANCH[index]
+            else:
+                if index not in ('0', '1'):
+                    raise KeyError(f'not a key of OldResNet152: {key}')
+                module = f'downsample.{index}'
+            new = f'layer{int(stage) - 3}.{block}.{module}.{leaf}'
+        elif head in ('conv1', 'bn1', 'fc') or head.startswith('layer'):
+            new = key
+        else:
+            raise KeyError(f'not a key of OldResNet152: {key}')
+        if new in out:
+            raise KeyError(f'two keys map to {new}')
+        out[new] = value
+    return out
+
+
+class OldResNet152(ResNetClassifier):
+    """The Places365 ResNet-152 of the reference (`src/deps/resnet152.py`): arithmetically the
+    v1.5 bottleneck ResNet-152, so it is a `ResNetClassifier('resnet152')` that also
+
+      - loads a state dict in the reference class's Torch7-style keys (`rekey_old_resnet152`;
+        `num_batches_tracked` may be there or not),
+      - answers to the reference's layer names 0, 4, 5, 6, 7 (ints or strings) as aliases of
+        conv1, layer1 .. layer4 in `activations`, so `exemplars.discriminative(model, dataset,
+        layer=5)` runs natively and writes to `.../5/`,
+      - pools with the reference's fixed `AvgPool2d(7)`: the forward takes images that leave
+        7 x 7 after layer4 (224 x 224) and nothing else.
+    """
+
+    layer_aliases = OLD_RESNET152_LAYERS
+
+    def __init__(self, num_classes: int = 365, width: int = 64, precision: str = 'auto'):
+        super().__init__('resnet152', num_classes=num_classes, width=width, precision=precision)
+        self.avgpool = nn.AvgPool2d(7, 1)
+        self.layers = LAYERS + tuple(self.layer_aliases)
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        state_dict = rekey_old_resnet152(state_dict)
+        own = self.state_dict()
+        # (a checkpoint converted from Torch7 has no num_batches_tracked; a later one does)
+        for key, value in own.items():
+            if key.endswith('num_batches_tracked') and key not in state_dict:
+                state_dict[key] = value
+        return super().load_state_dict(state_dict, strict=strict)
+
+    def _canonical(self, name) -> str:
+        return self.layer_aliases.get(str(name), name)
+
+    def forward(self, images: torch.Tensor) -> torch.Tensor:
+        if self.runs_natively(images):
+            h, w = images.shape[-2:]
+            for _ in range(5):
+                h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            if (h, w) != (7, 7):
+                raise ValueError(f'OldResNet152 pools with a fixed AvgPool2d(7): images of '
+                                 f'{tuple(images.shape[-2:])} leave {h} x {w} after layer4, '
+                                 'not 7 x 7 (224 x 224 images do)')
+        return super().forward(images)
+
+    def activations(self, images: torch.Tensor, layers) -> Dict[str, torch.Tensor]:
+        names = [layers] if isinstance(layers, (str, int)) else list(layers)
+        for name in names:
+            if not isinstance(name, (str, int)) or (isinstance(name, int) and
+                                                    str(name) not in self.layer_aliases):
+                raise KeyError(f'layer not found: {name}')
+        got = super().activations(images, [self._canonical(name) for name in names])
+        return {name: got[self._canonical(name)] for name in names}

@@ -16,6 +16,8 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
+from milan_amd import synthetic
+
 # MILAN_LIB=<path>: load another build of the library (A/B timing of compiler options)
 LIB_PATH = pathlib.Path(os.environ.get('MILAN_LIB') or
                        pathlib.Path(__file__).resolve().parent / 'lib' / 'libmilan_hip.so')
@@ -118,7 +120,11 @@ ABI_VERSION = 11  # MILAN_ABI_VERSION this binding was written against
 
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
 TRUNK_BOTTLENECK, TRUNK_BASIC, TRUNK_ALEXNET, TRUNK_NONE = 0, 1, 2, 3
-_FEATURE_MULT = {TRUNK_BOTTLENECK: 61, TRUNK_BASIC: 16, TRUNK_ALEXNET: 18}
+TRUNK_ALEXNET_PLACES = 4  # the Places365 AlexNet: classify / ablate / activations only
+_FEATURE_MULT = {TRUNK_BOTTLENECK: 61, TRUNK_BASIC: 16, TRUNK_ALEXNET: 18,
+                 TRUNK_ALEXNET_PLACES: 43}
+# channels of conv1..conv5 per unit of `trunk_width` (the reference's net has width 32)
+PLACES_ALEXNET_CHANNELS = synthetic.PLACES_ALEXNET_CHANNELS
 
 
 _P = ctypes.c_void_p
@@ -170,6 +176,8 @@ SIGNATURES = {
     'milan_activations': (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
     'milan_set_alexnet_head':
         (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P]),
+    'milan_set_alexnet_lrn': (_I, [_P, _I, _F, _F]),
+    'milan_lrn': (_I, [_P, ctypes.c_longlong, _I, _I, _I, _F, _F, _P, _P, _P]),
     'milan_linear_packed_bytes': (_SZ, [_I, _I]),
     'milan_linear_pack': (_I, [_P, _I, _I, _P, _P]),
     'milan_linear': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
@@ -314,7 +322,8 @@ PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_get_beam_path', 'milan_set_ablation',
           'milan_classify_workspace_bytes', 'milan_classify',
           'milan_classify_sweep', 'milan_activations_workspace_bytes',
-          'milan_activations', 'milan_set_alexnet_head', 'milan_linear_packed_bytes',
+          'milan_activations', 'milan_set_alexnet_head', 'milan_set_alexnet_lrn', 'milan_lrn',
+          'milan_linear_packed_bytes',
           'milan_linear_pack', 'milan_linear', 'milan_linear_rowwise', 'milan_attention',
           'milan_vit_create', 'milan_vit_destroy', 'milan_vit_set_weight',
           'milan_vit_finalize_weights', 'milan_vit_workspace_bytes', 'milan_vit_run',
@@ -931,9 +940,17 @@ class Context:
     @property
     def ablation_levels(self) -> Tuple[str, ...]:
         """The names of levels 0..4 on this context's trunk."""
-        if self.dims.trunk_kind == TRUNK_ALEXNET:
+        if self.dims.trunk_kind in (TRUNK_ALEXNET, TRUNK_ALEXNET_PLACES):
             return self.ALEXNET_LEVELS
         return self.ABLATION_LEVELS
+
+    def set_alexnet_lrn(self, local_size: int = 5, alpha: float = 1e-4,
+                        beta: float = 0.75) -> None:
+        """Switch the Places365 AlexNet's across-channel LRN after pool1 and pool2 on
+        (`local_size` odd, at most 17: the kernel reads one 8-channel neighbour each side) or off (0): y = x / (1 + alpha * S / local_size) ** beta, S the sum
+        of squares over the `local_size` neighbouring channels, zero-padded."""
+        fn = self._need('milan_set_alexnet_lrn')
+        _check(fn(self._h, int(local_size), float(alpha), float(beta)))
 
     def set_alexnet_head(self, fc6_weight, fc6_bias, fc7_weight, fc7_bias, linear8_weight,
                          linear8_bias) -> None:
@@ -1084,12 +1101,16 @@ class Context:
             if not 0 <= level <= 4:  # (the library reports it; the shape is a placeholder)
                 outs.append(torch.empty(1, dtype=torch.float32, device=self.device))
                 continue
-            if self.dims.trunk_kind == TRUNK_ALEXNET:
-                # conv1 11x11/4 pad 2; pool1, pool2 3x3/2 before conv2, conv3; the rest keep
-                hl, wl = (h + 4 - 11) // 4 + 1, (w + 4 - 11) // 4 + 1
+            if self.dims.trunk_kind in (TRUNK_ALEXNET, TRUNK_ALEXNET_PLACES):
+                # conv1 11x11/4 pad 2 (Places: pad 0); pool1, pool2 3x3/2 before conv2, conv3;
+                # the rest keep
+                places = self.dims.trunk_kind == TRUNK_ALEXNET_PLACES
+                pad = 0 if places else 4
+                hl, wl = (h + pad - 11) // 4 + 1, (w + pad - 11) // 4 + 1
                 for _ in range(min(level, 2)):
                     hl, wl = (hl - 3) // 2 + 1, (wl - 3) // 2 + 1
-                ch = self.dims.trunk_width * (1, 3, 6, 4, 4)[level]
+                mult = PLACES_ALEXNET_CHANNELS if places else (1, 3, 6, 4, 4)
+                ch = self.dims.trunk_width * mult[level]
                 outs.append(torch.empty(n, ch, max(hl, 1), max(wl, 1), dtype=torch.float32,
                                         device=self.device))
                 continue
@@ -2301,6 +2322,23 @@ def linear_rowwise(x: torch.Tensor, weight: torch.Tensor,
     return y
 
 
+def lrn(x: torch.Tensor, local_size: int, alpha: float, beta: float,
+        split: bool = False) -> torch.Tensor:
+    """The across-channel LRN kernel alone on a device tensor (pixels, channels) with a
+    pixel's channels contiguous: fp32, or with `split` the split-f16 groups at scale 1 (a
+    float32 tensor of the same shape that holds them), in and out."""
+    device = require_device(x.device)
+    x = _dev(x.detach(), device, torch.float32)
+    if x.dim() != 2:
+        raise ValueError(f'lrn takes (pixels, channels), got {tuple(x.shape)}')
+    y = torch.empty_like(x)
+    with torch.cuda.device(device):
+        _check(_need_export('milan_lrn')(x.data_ptr(), x.shape[0], x.shape[1], int(split),
+                                         int(local_size), float(alpha), float(beta),
+                                         y.data_ptr(), None, _stream(device)))
+    return y
+
+
 def make_dims(state_dict: Dict[str, torch.Tensor],
               n_vocab_tokens: int,
               blocks: Sequence[int] = (3, 4, 23, 3)) -> Dims:
@@ -2311,6 +2349,11 @@ def make_dims(state_dict: Dict[str, torch.Tensor],
     width = kind = None
     if pre + 'features.0.weight' in sd:  # 'alexnet' config
         kind, width = TRUNK_ALEXNET, sd[pre + 'features.0.weight'].shape[0]
+    elif pre + 'conv5.weight' in sd:  # the Places365 AlexNet (conv1..conv5 by name)
+        kind = TRUNK_ALEXNET_PLACES
+        if sd[pre + 'conv1.weight'].shape[0] % 3:
+            raise ValueError('conv1 of the Places365 AlexNet has 3 x width channels')
+        width = sd[pre + 'conv1.weight'].shape[0] // 3
     elif pre + 'conv1.weight' in sd:
         width = sd[pre + 'conv1.weight'].shape[0]
         kind = (TRUNK_BOTTLENECK if pre + 'layer1.0.conv3.weight' in sd else

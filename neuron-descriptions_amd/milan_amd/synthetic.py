@@ -154,6 +154,33 @@ def alexnet_state_dict(seed: int = 0,
     return sd
 
 
+PLACES_ALEXNET_CHANNELS = (3, 8, 12, 12, 8)  # x width (32): 96, 256, 384, 384, 256
+PLACES_ALEXNET_GROUPS = (1, 2, 1, 2, 2)
+
+
+def places_alexnet_state_dict(seed: int = 0,
+                              width: int = 32,
+                              hidden: int = 4096,
+                              classes: int = 365,
+                              split_groups: bool = True) -> Dict[str, torch.Tensor]:
+    """Synthetic state dict of the Places365 AlexNet (the reference's `src/deps/alexnet.py`:
+    `conv1 .. conv5`, `fc6`, `fc7`, `fc8`; conv2 / conv4 / conv5 in two groups unless
+    `split_groups` is off).  Channels are `width` x (3, 8, 12, 12, 8).  He-scaled convs with
+    biases, so that activations keep their scale through the trunk."""
+    g = _gen(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    ch = [3] + [c * width for c in PLACES_ALEXNET_CHANNELS]
+    for i, k in enumerate((11, 5, 3, 3, 3)):
+        groups = PLACES_ALEXNET_GROUPS[i] if split_groups else 1
+        sd[f'conv{i + 1}.weight'] = _conv(g, ch[i + 1], ch[i] // groups, k)
+        sd[f'conv{i + 1}.bias'] = 0.1 * torch.randn(ch[i + 1], generator=g)
+    for name, cin, cout in (('fc6', ch[5] * 36, hidden), ('fc7', hidden, hidden),
+                            ('fc8', hidden, classes)):
+        sd[f'{name}.weight'] = torch.randn(cout, cin, generator=g) * (2.0 / cin)**0.5
+        sd[f'{name}.bias'] = 0.1 * torch.randn(cout, generator=g)
+    return sd
+
+
 def _linear(g: torch.Generator, sd: Dict[str, torch.Tensor], name: str,
             out_f: int, in_f: int, scale: float = 1.0) -> None:
     bound = scale / in_f**0.5

@@ -59,6 +59,9 @@ PINNED = {
     'igemm_f16_pp32_kernelILi128ELb0': {'mfma': 192, 'lds_dma': 84, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 52, 'scratch': 0, 'vmcnt': [0, 4], 'scratch_in_loops': 0, 'hazards': 0},
     'igemm_split16_pp32t_kernelILi256': {'mfma': 576, 'lds_dma': 112, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 52, 'scratch': 0, 'vmcnt': [0, 4], 'scratch_in_loops': 0, 'hazards': 0},
     'igemm_split16_pp32t_kernelILi128': {'mfma': 288, 'lds_dma': 84, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 52, 'scratch': 0, 'vmcnt': [0, 4], 'scratch_in_loops': 0, 'hazards': 0},
+    # grouped convs (GemmArgs::groups): the 128-column tile with the group as grid.y
+    'igemm_grouped_pp32n_kernel': {'mfma': 288, 'lds_dma': 84, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 52, 'scratch': 0, 'vmcnt': [0, 4], 'scratch_in_loops': 0, 'hazards': 0},
+    'igemm_grouped_pp32t_kernel': {'mfma': 288, 'lds_dma': 84, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 52, 'scratch': 0, 'vmcnt': [0, 4], 'scratch_in_loops': 0, 'hazards': 0},
     # the row-list forms of the 256-column tile (GemmArgs::row_list): linear / two-source, tap-inner
     'igemm_split16_pp32l_kernelILb0': {'mfma': 576, 'lds_dma': 112, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 52, 'scratch': 0, 'vmcnt': [0, 4], 'scratch_in_loops': 0, 'hazards': 0},
     'igemm_split16_pp32l_kernelILb1': {'mfma': 576, 'lds_dma': 112, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 52, 'scratch': 0, 'vmcnt': [0, 4], 'scratch_in_loops': 0, 'hazards': 0},

@@ -545,11 +545,11 @@ static bool alex_trunk(const milan_ctx* c) {
 static bool places_trunk(const milan_ctx* c) {
   return c->d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES;
 }
-static bool classifier_trunk(const milan_ctx* c) {
-  return resnet_trunk(c) || alex_trunk(c) || places_trunk(c);
-}
+// either of them: AlexTrunk walks it
+static bool alexnet_trunk(const milan_ctx* c) { return alex_trunk(c) || places_trunk(c); }
+static bool classifier_trunk(const milan_ctx* c) { return resnet_trunk(c) || alexnet_trunk(c); }
 static const char* level_names(const milan_ctx* c) {
-  return alex_trunk(c) || places_trunk(c) ? "conv1..conv5" : "conv1, layer1..layer4";
+  return alexnet_trunk(c) ? "conv1..conv5" : "conv1, layer1..layer4";
 }
 static int level_channels(const milan_ctx* c, int level) {
   const int wd = c->d.trunk_width;
@@ -643,8 +643,9 @@ int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* un
 
 // ---------------------------------------------------------------------------
 // driver: one pass loop, one sweep loop and one workspace dry run, written over
-// a trunk.  A trunk (ResNetTrunk, AlexTrunk) is one pass's plan and walker: it derives from
-// Trunk, fills h / w / lvl_sz and split_tap_scale when it is made, and supplies
+// a trunk.  A trunk (ResNetTrunk; AlexTrunk, which walks both AlexNets) is one pass's plan and
+// walker: it derives from Trunk, fills h / w / lvl_sz and split_tap_scale when it is made, and
+// supplies
 //   carve(a)           its own buffers out of the arena, in its own order
 //   carve_hold(a, f)   the sweep's room of `f` floats for a held level, if it needs one
 //   check_geometry()   what it asks of the image extent
@@ -652,8 +653,6 @@ int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* un
 //   head(x4, logits, preds)     from the masked level-4 tensor to logits (+ argmax)
 //   hold_level(images, at, level, &held)   the sweep's step to the next level with units
 // ---------------------------------------------------------------------------
-static int cls_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
-
 static int grid_for(long items) {
   const long b = (items + 255) / 256;
   return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
@@ -671,7 +670,7 @@ struct Trunk {
   float *logits = nullptr, *work = nullptr;
   float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // whether a level's tensor is in split format (a trunk's constructor fills it: level 0 is
-  // fp32 everywhere, the Places trunk has fp32 levels above it too)
+  // fp32 everywhere, the Places365 AlexNet has fp32 levels above it too)
   bool fmt[5] = {false, false, false, false, false};
 
   // level tensor `x` -> `y` (x == y: in place), times the context's mask of that level and with
@@ -733,10 +732,10 @@ struct ResNetTrunk : Trunk {
 
   ResNetTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
       : Trunk{c, n, H, W, split, s, 1.f / c->act_scale} {
-    h[0] = cls_out(H, 7, 2, 3); w[0] = cls_out(W, 7, 2, 3);
+    h[0] = conv_out(H, 7, 2, 3); w[0] = conv_out(W, 7, 2, 3);
     for (int l = 1; l < 5; ++l) {
-      h[l] = cls_out(h[l - 1], 3, 2, 1);
-      w[l] = cls_out(w[l - 1], 3, 2, 1);
+      h[l] = conv_out(h[l - 1], 3, 2, 1);
+      w[l] = conv_out(w[l - 1], 3, 2, 1);
     }
     for (int l = 0; l < 5; ++l) lvl_sz[l] = (size_t)h[l] * w[l] * level_channels(c, l);
     for (int l = 1; l < 5; ++l) fmt[l] = split;
@@ -856,134 +855,31 @@ struct ResNetTrunk : Trunk {
   }
 };
 
-// AlexNet: torchvision's alexnet_seq in eval mode.  Levels 0..4 are
-// conv1..conv5; a level's tensor is relu(conv + bias) * mask, the conv run with the encoder's
-// bias + ReLU epilogue (no mask launch for a level without units).  Level 0 is fp32 in both
-// modes (3 input channels), levels 1..4 are split at scale 1 in the split mode.  Every level
-// has a buffer of its own, so the sweep holds a level where it is.
+// The two AlexNets in eval mode: torchvision's alexnet_seq and the Places365 one
+// (the reference's src/deps/alexnet.py).  Levels 0..4 are conv1..conv5; a level's
+// tensor is relu(conv + bias) * mask, the conv run with the encoder's bias + ReLU epilogue (no
+// mask launch for a level without units).  Every level has a buffer of its own, so the sweep
+// holds a level where it is.  The convs' shapes, paddings and groups are in c->alex (AlexSpec,
+// DESIGN 4.28): the Places net has conv1 without padding and conv2 / conv4 / conv5 grouped
+// (ConvW::groups: one launch each, the group a grid dimension).  Here it differs in an optional
+// LRN after pool1 and pool2 (c->lrn, which only it can set), in what it asks of the image
+// (check_geometry, walk) and in having no adaptive pool in front of fc6 (head).
+// Formats in the split mode: conv l runs on the split kernels when its weights have a split
+// copy (sp[l]), in fp32 otherwise, as level 0 (3 input channels) does in every mode; a level's
+// tensor is in the format its reader takes -- the pools convert fp32 to split on the way, conv3
+// writes fp32 when conv4 is an fp32 level.  torchvision's convs all have a split copy when
+// `split` is on (classify_checks): its levels 1..4 are split at scale 1.  The Places net's
+// grouped convs have one when their per-group input width is a multiple of 32.
 struct AlexTrunk : Trunk {
-  int hq[3], wq[3];   // pool1, pool2, pool5
-  float *in4, *a[5], *q[2], *flat, *f6, *f7;
-
-  AlexTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
-      : Trunk{c, n, H, W, split, s, 1.f} {
-    h[0] = cls_out(H, 11, 4, 2); w[0] = cls_out(W, 11, 4, 2);
-    hq[0] = cls_out(h[0], 3, 2, 0); wq[0] = cls_out(w[0], 3, 2, 0);
-    h[1] = hq[0]; w[1] = wq[0];
-    hq[1] = cls_out(h[1], 3, 2, 0); wq[1] = cls_out(w[1], 3, 2, 0);
-    for (int l = 2; l < 5; ++l) { h[l] = hq[1]; w[l] = wq[1]; }
-    hq[2] = cls_out(h[4], 3, 2, 0); wq[2] = cls_out(w[4], 3, 2, 0);
-    // (an image too small for the trunk is refused before anything is used: check_geometry)
-    for (int l = 0; l < 5; ++l)
-      lvl_sz[l] = (size_t)std::max(h[l], 0) * std::max(w[l], 0) * c->abl_ch[l];
-    for (int l = 1; l < 5; ++l) fmt[l] = split;
-  }
-
-  void carve(Arena& ar) {
-    const milan_ctx::AlexHead& hd = c->ahead;
-    in4 = ar.get<float>((size_t)n * hin * win * 4);
-    for (int l = 0; l < 5; ++l) a[l] = ar.get<float>((size_t)n * lvl_sz[l]);
-    for (int l = 0; l < 2; ++l)
-      q[l] = ar.get<float>((size_t)n * std::max(hq[l], 0) * std::max(wq[l], 0) * c->abl_ch[l]);
-    flat = ar.get<float>((size_t)n * hd.in[0]);
-    f6 = ar.get<float>((size_t)n * hd.out[0]);
-    f7 = ar.get<float>((size_t)n * hd.out[1]);
-  }
-  void carve_hold(Arena&, size_t) {}
-
-  // the smallest image leaves one pixel after pool5 (63 x 63)
-  int check_geometry() const {
-    // (the three pools need 3 pixels each way: C's division rounds a negative extent to zero)
-    MILAN_REQUIRE(h[0] >= 3 && w[0] >= 3 && h[1] >= 3 && w[1] >= 3 && h[4] >= 3 && w[4] >= 3,
-                  MILAN_ERR_SHAPE,
-                  "classify: image %dx%d is too small for AlexNet (63x63 at least)", hin, win);
-    return 0;
-  }
-
-  // ResNetTrunk::walk's contract
-  int walk(int from, int to, const float* src, const float** out) const {
-    const float* x = src;
-    int ho, wo;
-    if (from < 0) {
-      MILAN_TRY(launch_raw_input(src, n, hin, win, false, in4, c->status, s));
-      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[0], in4, n, hin, win, a[0], EPI_BIAS_RELU,
-                                              nullptr, c->zero, &ho, &wo, false), s));
-      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, a[0], a[0], -1));
-      x = a[0];
-      from = 0;
-      if (tap[0]) MILAN_TRY(emit(0, x));
-    }
-    for (int l = from + 1; l <= to; ++l) {
-      int hh = h[l - 1], ww = w[l - 1];
-      if (l <= 2) {
-        // pool1 / pool2 (level 0 is fp32; the pool writes the format conv2 / conv3 read)
-        MILAN_TRY(launch_maxpool3s2(x, n, hh, ww, c->abl_ch[l - 1], hq[l - 1], wq[l - 1], split,
-                                    split && l == 2, q[l - 1], c->status, s));
-        x = q[l - 1];
-        hh = hq[l - 1]; ww = wq[l - 1];
-      }
-      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[l], x, n, hh, ww, a[l], EPI_BIAS_RELU,
-                                              nullptr, c->zero, &ho, &wo, split, false), s));
-      MILAN_REQUIRE(ho == h[l] && wo == w[l], MILAN_ERR_SHAPE,
-                    "internal: alexnet level %d geometry mismatch", l);
-      if (c->abl_count[l] > 0) MILAN_TRY(mask(l, a[l], a[l], -1));
-      x = a[l];
-      if (tap[l]) MILAN_TRY(emit(l, x));
-    }
-    *out = x;
-    return 0;
-  }
-
-  // pool5 + adaptive average pool + flatten, fc6 / fc7 / linear8 (+ argmax) of the masked
-  // level-4 tensor; dropout is the identity in eval mode
-  int head(const float* x4, float* lg, long long* pr) const {
-    const milan_ctx::AlexHead& hd = c->ahead;
-    const int C = c->abl_ch[4];
-    const dim3 grid((36 * C + 255) / 256, n);
-    if (split)
-      hipLaunchKernelGGL(alex_tail_kernel<true>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
-                         wq[2], 1.f, flat);
-    else
-      hipLaunchKernelGGL(alex_tail_kernel<false>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
-                         wq[2], 1.f, flat);
-    MILAN_CHECK_HIP(hipGetLastError());
-    MILAN_TRY(linear_run(flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, f6, s));
-    MILAN_TRY(linear_run(f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, f7, s));
-    MILAN_TRY(linear_run(f7, hd.w[2], hd.b[2], n, hd.in[2], hd.out[2], false, lg, s));
-    if (pr) {
-      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, lg, hd.out[2], pr);
-      MILAN_CHECK_HIP(hipGetLastError());
-    }
-    return 0;
-  }
-
-  // The sweep's walk to `level` continues from the level held before it (`at`, -1: the
-  // images): the suffixes write levels above their own and the working tensor, never a held one.
-  int hold_level(const float* images, int at, int level, const float** held) const {
-    return walk(at, level, at < 0 ? images : *held, held);
-  }
-};
-
-// The Places365 AlexNet (the reference's src/deps/alexnet.py in eval mode): conv1
-// 11x11 / 4 without padding, conv2 / conv4 / conv5 grouped (ConvW::groups: one launch each, the
-// group a grid dimension), an optional LRN after pool1 and pool2, no adaptive pool.  Levels and
-// their semantics are AlexTrunk's.  Formats in the split mode: conv l runs on the split kernels
-// when its weights have a split copy (per-group input width a multiple of 32: sp[l]), in fp32
-// otherwise, as level 0 does in every mode; a level's tensor is in the format its reader takes --
-// the pools convert fp32 to split on the way, conv3 writes fp32 when conv4 is an fp32 level.
-struct PlacesTrunk : Trunk {
+  const bool places;  // the Places365 net
   int hq[3], wq[3];   // pool1, pool2, pool5
   bool sp[5];         // conv l reads (and multiplies) split operands
   float *in4, *a[5], *q[2], *qn[2], *flat, *f6, *f7;
 
-  PlacesTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
-      : Trunk{c, n, H, W, split, s, 1.f} {
-    h[0] = cls_out(H, 11, 4, 0); w[0] = cls_out(W, 11, 4, 0);
-    hq[0] = cls_out(h[0], 3, 2, 0); wq[0] = cls_out(w[0], 3, 2, 0);
-    h[1] = hq[0]; w[1] = wq[0];
-    hq[1] = cls_out(h[1], 3, 2, 0); wq[1] = cls_out(w[1], 3, 2, 0);
-    for (int l = 2; l < 5; ++l) { h[l] = hq[1]; w[l] = wq[1]; }
-    hq[2] = cls_out(h[4], 3, 2, 0); wq[2] = cls_out(w[4], 3, 2, 0);
+  AlexTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
+      : Trunk{c, n, H, W, split, s, 1.f}, places(places_trunk(c)) {
+    alex_geometry(c, H, W, h, w, hq, wq);
+    // (an image too small for the trunk is refused before anything is used: check_geometry)
     for (int l = 0; l < 5; ++l)
       lvl_sz[l] = (size_t)std::max(h[l], 0) * std::max(w[l], 0) * c->abl_ch[l];
     sp[0] = false;
@@ -1011,14 +907,20 @@ struct PlacesTrunk : Trunk {
   }
   void carve_hold(Arena&, size_t) {}
 
-  // conv1 needs an 11 x 11 image; a pool needs 3 pixels each way, which walk() asks for when it
-  // has to cross one (19 x 19 reaches conv2, 35 x 35 every level); a classify call needs 6 x 6
-  // after pool5 (classify_checks)
+  // torchvision: the smallest image leaves one pixel after pool5 (63 x 63).  Places: conv1 needs
+  // an 11 x 11 image; a pool needs 3 pixels each way, which walk() asks for when it has to cross
+  // one (19 x 19 reaches conv2, 35 x 35 every level); a classify call needs 6 x 6 after pool5
+  // (classify_checks)
   int check_geometry() const {
     // (the unpadded conv1: C's division rounds the extent of a smaller image up to 1)
-    MILAN_REQUIRE(hin >= 11 && win >= 11 && h[0] >= 1 && w[0] >= 1, MILAN_ERR_SHAPE,
+    MILAN_REQUIRE(!places || (hin >= 11 && win >= 11 && h[0] >= 1 && w[0] >= 1), MILAN_ERR_SHAPE,
                   "classify: image %dx%d is too small for the Places365 AlexNet's 11x11 conv1",
                   hin, win);
+    // (the three pools need 3 pixels each way: C's division rounds a negative extent to zero)
+    MILAN_REQUIRE(places ||
+                      (h[0] >= 3 && w[0] >= 3 && h[1] >= 3 && w[1] >= 3 && h[4] >= 3 && w[4] >= 3),
+                  MILAN_ERR_SHAPE,
+                  "classify: image %dx%d is too small for AlexNet (63x63 at least)", hin, win);
     return 0;
   }
 
@@ -1030,8 +932,6 @@ struct PlacesTrunk : Trunk {
       MILAN_TRY(launch_raw_input(src, n, hin, win, false, in4, c->status, s));
       MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[0], in4, n, hin, win, a[0], EPI_BIAS_RELU,
                                               nullptr, c->zero, &ho, &wo, false), s));
-      MILAN_REQUIRE(ho == h[0] && wo == w[0], MILAN_ERR_SHAPE,
-                    "internal: places level 0 geometry mismatch");
       if (c->abl_count[0] > 0) MILAN_TRY(mask(0, a[0], a[0], -1));
       x = a[0];
       from = 0;
@@ -1042,12 +942,13 @@ struct PlacesTrunk : Trunk {
       if (l <= 2) {
         // pool1 / pool2 write the format conv2 / conv3 read, the LRN keeps it
         const int C = c->abl_ch[l - 1];
+        // (torchvision's net has asked for all three pools in check_geometry)
         MILAN_REQUIRE(hh >= 3 && ww >= 3, MILAN_ERR_SHAPE,
                       "classify: image %dx%d is too small for the Places365 AlexNet: pool%d needs "
                       "3x3 pixels and gets %dx%d (19x19 reaches conv2, 35x35 every level)",
                       hin, win, l, hh, ww);
         MILAN_REQUIRE(sp[l] || !fmt[l - 1], MILAN_ERR_STATE,
-                      "internal: places level %d would need a split -> fp32 pool", l);
+                      "internal: alexnet level %d would need a split -> fp32 pool", l);
         MILAN_TRY(launch_maxpool3s2(x, n, hh, ww, C, hq[l - 1], wq[l - 1], sp[l], fmt[l - 1],
                                     q[l - 1], c->status, s));
         x = q[l - 1];
@@ -1058,14 +959,13 @@ struct PlacesTrunk : Trunk {
           x = qn[l - 1];
         }
       }
+      // (ho x wo is h[l] x w[l]: alex_geometry reads the same ConvW)
       GemmArgs g = encoder_conv_args(c->alex[l], x, n, hh, ww, a[l], EPI_BIAS_RELU, nullptr,
                                      c->zero, &ho, &wo, sp[l], false);
       if (sp[l] && !fmt[l]) g.out_split = 0;   // the next level is an fp32 one
       MILAN_REQUIRE(sp[l] || !fmt[l], MILAN_ERR_STATE,
-                    "internal: places level %d is fp32 and would have to write split", l);
+                    "internal: alexnet level %d is fp32 and would have to write split", l);
       MILAN_TRY(launch_gemm(g, s));
-      MILAN_REQUIRE(ho == h[l] && wo == w[l], MILAN_ERR_SHAPE,
-                    "internal: places level %d geometry mismatch", l);
       if (c->abl_count[l] > 0) MILAN_TRY(mask(l, a[l], a[l], -1));
       x = a[l];
       if (tap[l]) MILAN_TRY(emit(l, x));
@@ -1074,12 +974,14 @@ struct PlacesTrunk : Trunk {
     return 0;
   }
 
-  // pool5 + flatten in (C, h, w) order (alex_tail_kernel with 6 x 6 pooled pixels: every bin of
-  // its average is one pixel, divided by 1), fc6 / fc7 / fc8 (+ argmax)
+  // pool5 + adaptive average pool + flatten in (C, h, w) order, fc6 / fc7 / linear8 (+ argmax)
+  // of the masked level-4 tensor; dropout is the identity in eval mode.  The Places net has no
+  // adaptive pool: with the 6 x 6 pooled pixels it requires, every bin of alex_tail_kernel's
+  // average is one pixel, divided by 1.
   int head(const float* x4, float* lg, long long* pr) const {
     const milan_ctx::AlexHead& hd = c->ahead;
     const int C = c->abl_ch[4];
-    MILAN_REQUIRE(hq[2] == 6 && wq[2] == 6 && hd.installed, MILAN_ERR_STATE,
+    MILAN_REQUIRE(!places || (hq[2] == 6 && wq[2] == 6 && hd.installed), MILAN_ERR_STATE,
                   "internal: places head without 6 x 6 features or fc layers");
     const dim3 grid((36 * C + 255) / 256, n);
     if (fmt[4])
@@ -1099,7 +1001,8 @@ struct PlacesTrunk : Trunk {
     return 0;
   }
 
-  // every level has a buffer of its own: AlexTrunk's rule
+  // The sweep's walk to `level` continues from the level held before it (`at`, -1: the
+  // images): the suffixes write levels above their own and the working tensor, never a held one.
   int hold_level(const float* images, int at, int level, const float** held) const {
     return walk(at, level, at < 0 ? images : *held, held);
   }
@@ -1116,8 +1019,7 @@ static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int 
 
 size_t classify_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
   if (n_images <= 0 || H < 1 || W < 1) return 0;
-  if (places_trunk(c)) return workspace_dry<PlacesTrunk>(c, n_images, H, W, sweep_units);
-  if (alex_trunk(c)) return workspace_dry<AlexTrunk>(c, n_images, H, W, sweep_units);
+  if (alexnet_trunk(c)) return workspace_dry<AlexTrunk>(c, n_images, H, W, sweep_units);
   if (resnet_trunk(c)) return workspace_dry<ResNetTrunk>(c, n_images, H, W, sweep_units);
   return 0;
 }
@@ -1276,7 +1178,7 @@ static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool 
   MILAN_REQUIRE(!head || !places_trunk(c) || c->ahead.installed, MILAN_ERR_STATE,
                 "this Places365 AlexNet context has no head: milan_set_alexnet_head installs "
                 "fc6 / fc7 / fc8");
-  MILAN_REQUIRE(!head || alex_trunk(c) || places_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
+  MILAN_REQUIRE(!head || alexnet_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
                 "this context was created without fc.weight: it has no classifier head");
   MILAN_REQUIRE(!c->trunk_f16, MILAN_ERR_ARG,
                 "classification runs in the f32 and split_f16 modes, not in the fast f16 mode");
@@ -1284,16 +1186,15 @@ static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool 
                 "classify: need n>0 and H,W>=1 (got n=%d H=%d W=%d)", n, H, W);
   if (places_trunk(c) && head) {
     // fc6 reads C5 x 6 x 6 features and there is no adaptive pool in front of it
-    const int h0 = cls_out(H, 11, 4, 0), w0 = cls_out(W, 11, 4, 0);
-    const int h5 = cls_out(cls_out(cls_out(h0, 3, 2, 0), 3, 2, 0), 3, 2, 0);
-    const int w5 = cls_out(cls_out(cls_out(w0, 3, 2, 0), 3, 2, 0), 3, 2, 0);
-    MILAN_REQUIRE(h0 >= 3 && w0 >= 3 && h5 == 6 && w5 == 6, MILAN_ERR_SHAPE,
+    int h[5], w[5], hq[3], wq[3];
+    alex_geometry(c, H, W, h, w, hq, wq);
+    MILAN_REQUIRE(h[0] >= 3 && w[0] >= 3 && hq[2] == 6 && wq[2] == 6, MILAN_ERR_SHAPE,
                   "classify: image %dx%d does not leave 6x6 after pool5 of the Places365 AlexNet "
                   "(227x227 does; fc6 reads %d features)", H, W, c->ahead.in[0]);
   }
   bool sp = c->precision == MILAN_PRECISION_SPLIT_F16 && c->d.trunk_width % 8 == 0;
   // (Places: conv3 is dense and reads a multiple of 64 channels; the grouped levels decide for
-  // themselves, PlacesTrunk::sp)
+  // themselves, AlexTrunk::sp)
   if (places_trunk(c)) sp = sp && c->alex[2].ws != nullptr;
   // (AlexNet: conv1 has 3 input channels and stays fp32, as in alexnet_run_batch)
   for (int l = 1; l < 5 && sp && alex_trunk(c); ++l) sp = c->alex[l].ws != nullptr;
@@ -1308,7 +1209,7 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
                  int64_t* predictions, Arena& ws, hipStream_t s) {
   bool split;
   MILAN_TRY(classify_checks(c, n, H, W, &split));
-  auto go = places_trunk(c) ? run<PlacesTrunk> : alex_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
+  auto go = alexnet_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
   return go(c, images, n, H, W, split, logits, predictions, nullptr, 4, "classify", ws, s);
 }
 
@@ -1319,8 +1220,7 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
   MILAN_TRY(classify_checks(c, n, H, W, &split));
   MILAN_TRY(check_units(c, levels, units, count, "milan_classify_sweep"));
   if (count == 0) return 0;
-  auto go = places_trunk(c) ? sweep<PlacesTrunk>
-            : alex_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
+  auto go = alexnet_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
   return go(c, images, n, H, W, split, levels, units, count, targets, correct, predictions, ws, s);
 }
 
@@ -1345,8 +1245,8 @@ int activations_run(milan_ctx* c, const float* images, int n, int H, int W, cons
   }
   // (the messages about the workspace and the sub-batch have named the call differently on
   // the two trunks since they were written)
-  const bool alex = alex_trunk(c) || places_trunk(c);
-  auto go = places_trunk(c) ? run<PlacesTrunk> : alex ? run<AlexTrunk> : run<ResNetTrunk>;
+  const bool alex = alexnet_trunk(c);
+  auto go = alex ? run<AlexTrunk> : run<ResNetTrunk>;
   return go(c, images, n, H, W, split, nullptr, nullptr, taps, top,
             alex ? "classify" : "activations", ws, s);
 }

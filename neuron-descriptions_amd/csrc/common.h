@@ -640,6 +640,43 @@ struct milan_ctx {
 };
 
 namespace milan {
+// ---- the two AlexNets ------------------------------------------
+// What torchvision's AlexNet (MILAN_TRUNK_ALEXNET) and the Places365 one
+// (MILAN_TRUNK_ALEXNET_PLACES) differ in when encoder_finalize packs conv1..conv5 into
+// milan_ctx::alex; whatever runs them afterwards (alexnet_plan, AlexTrunk) reads alex[l].
+struct AlexSpec {
+  const char* key[5];  // conv l in the state dict, under the trunk's prefix
+  int stride[5], pad[5];
+  int mult[5];         // channels of conv l per unit of dims.trunk_width
+  bool weight_groups;  // conv l's groups = its input's channels / its weight's second extent
+  bool width8;         // dims.trunk_width has to be a multiple of 8
+};
+inline const AlexSpec& alex_spec(int trunk_kind) {
+  static const AlexSpec spec[2] = {
+      {{"features.0", "features.3", "features.6", "features.8", "features.10"},
+       {4, 1, 1, 1, 1}, {2, 2, 1, 1, 1}, {1, 3, 6, 4, 4}, false, false},
+      {{"conv1", "conv2", "conv3", "conv4", "conv5"},
+       {4, 1, 1, 1, 1}, {0, 2, 1, 1, 1}, {3, 8, 12, 12, 8}, true, true}};
+  return spec[trunk_kind == MILAN_TRUNK_ALEXNET_PLACES];
+}
+
+inline int conv_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
+
+// Extents of conv1..conv5 (h, w) and of pool1, pool2, pool5 (hq, wq: 3 x 3 / 2 without padding,
+// after conv1, conv2 and conv5) of an H x W image, from the packed convs.  C's division
+// truncates: an image too small for a level leaves an extent below the 3 (1) pixels the next
+// pool (conv) needs, which the callers refuse.
+inline void alex_geometry(const milan_ctx* c, int H, int W, int* h, int* w, int* hq, int* wq) {
+  for (int l = 0, q = 0; l < 5; ++l) {
+    const ConvW& cw = c->alex[l];
+    H = h[l] = conv_out(H, cw.kh, cw.stride, cw.pad);
+    W = w[l] = conv_out(W, cw.kw, cw.stride, cw.pad);
+    if (l == 2 || l == 3) continue;
+    H = hq[q] = conv_out(H, 3, 2, 0);
+    W = wq[q++] = conv_out(W, 3, 2, 0);
+  }
+}
+
 int dev_alloc(milan_ctx* c, void** p, size_t bytes);
 // api.hip: split-f16 copy of a packed [n][kp] fp32 weight; picks a power-of-two
 // scale from max|w| (host sync) and returns its inverse.

@@ -322,45 +322,33 @@ int encoder_finalize(milan_ctx* c, hipStream_t s) {
   const std::string p = "encoder.encoder.model.";
   const int kind = c->d.trunk_kind;
   if (kind == MILAN_TRUNK_NONE) return 0;  // decoder-only context
-  if (kind == MILAN_TRUNK_ALEXNET) {
-    if (!find(c, p + "features.0.weight")) return 0;  // decoder-only context
-    // torchvision AlexNet.features: conv indices, strides, paddings
-    static const int idx[5] = {0, 3, 6, 8, 10};
-    static const int stride[5] = {4, 1, 1, 1, 1}, pad[5] = {2, 2, 1, 1, 1};
-    static const int mult[5] = {1, 3, 6, 4, 4};
-    for (int i = 0; i < 5; ++i) {
-      MILAN_TRY(pack_conv(c, p + "features." + std::to_string(idx[i]), "",
-                          stride[i], pad[i], &c->alex[i], s, i > 0));
-      MILAN_REQUIRE(c->alex[i].cout == mult[i] * c->d.trunk_width &&
-                        c->alex[i].bias != nullptr,
-                    MILAN_ERR_SHAPE,
-                    "features.%d: %d channels, expected %d (with a bias)", idx[i],
-                    c->alex[i].cout, mult[i] * c->d.trunk_width);
-    }
-    c->stem = c->alex[0];  // "encoder weights present" marker
-  } else if (kind == MILAN_TRUNK_ALEXNET_PLACES) {
-    // the Places365 AlexNet: conv1 unpadded, conv2 / conv4 / conv5 in two groups
-    // unless the weights say otherwise (split_groups=False: dense weights, groups of 1)
-    if (!find(c, p + "conv1.weight")) return 0;
-    static const int stride[5] = {4, 1, 1, 1, 1}, pad[5] = {0, 2, 1, 1, 1};
-    static const int mult[5] = {3, 8, 12, 12, 8};
-    MILAN_REQUIRE(c->d.trunk_width % 8 == 0, MILAN_ERR_SHAPE,
+  if (kind == MILAN_TRUNK_ALEXNET || kind == MILAN_TRUNK_ALEXNET_PLACES) {
+    // torchvision's AlexNet.features, or the Places365 AlexNet: conv1 unpadded,
+    // conv2 / conv4 / conv5 in two groups unless the weights say otherwise
+    // (split_groups=False: dense weights, groups of 1)
+    const AlexSpec& spec = alex_spec(kind);
+    if (!find(c, p + spec.key[0] + ".weight")) return 0;  // decoder-only context
+    MILAN_REQUIRE(!spec.width8 || c->d.trunk_width % 8 == 0, MILAN_ERR_SHAPE,
                   "the Places365 AlexNet needs a width that is a multiple of 8 (got %d)",
                   c->d.trunk_width);
     int cin_full = 3;
     for (int i = 0; i < 5; ++i) {
-      const std::string name = p + "conv" + std::to_string(i + 1);
-      const Tensor* w = find(c, name + ".weight");
-      MILAN_REQUIRE(w && w->shape.size() == 4 && w->shape[1] >= 1 &&
-                        cin_full % (int)w->shape[1] == 0,
-                    MILAN_ERR_SHAPE, "conv%d.weight is missing or does not divide %d input "
-                    "channels into groups", i + 1, cin_full);
-      const int groups = cin_full / (int)w->shape[1];
-      MILAN_TRY(pack_conv(c, name, "", stride[i], pad[i], &c->alex[i], s, i > 0, groups));
-      MILAN_REQUIRE(c->alex[i].cout == mult[i] * c->d.trunk_width &&
+      const std::string name = p + spec.key[i];
+      int groups = 1;
+      if (spec.weight_groups) {
+        const Tensor* w = find(c, name + ".weight");
+        MILAN_REQUIRE(w && w->shape.size() == 4 && w->shape[1] >= 1 &&
+                          cin_full % (int)w->shape[1] == 0,
+                      MILAN_ERR_SHAPE, "%s.weight is missing or does not divide %d input "
+                      "channels into groups", spec.key[i], cin_full);
+        groups = cin_full / (int)w->shape[1];
+      }
+      MILAN_TRY(pack_conv(c, name, "", spec.stride[i], spec.pad[i], &c->alex[i], s, i > 0,
+                          groups));
+      MILAN_REQUIRE(c->alex[i].cout == spec.mult[i] * c->d.trunk_width &&
                         c->alex[i].bias != nullptr,
-                    MILAN_ERR_SHAPE, "conv%d: %d channels, expected %d (with a bias)", i + 1,
-                    c->alex[i].cout, mult[i] * c->d.trunk_width);
+                    MILAN_ERR_SHAPE, "%s: %d channels, expected %d (with a bias)", spec.key[i],
+                    c->alex[i].cout, spec.mult[i] * c->d.trunk_width);
       cin_full = c->alex[i].cout;
     }
     c->stem = c->alex[0];  // "encoder weights present" marker
@@ -1268,8 +1256,6 @@ struct EncPlan {
   int *tail_loc3, *tail_cnt3, *tail_off3, *tail_rows3, *tail_U3;
   unsigned char* tail_s3;
 };
-
-static int conv_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
 
 static int plan(const milan_ctx* c, int n, int H, int W, Arena& a, EncPlan* pl) {
   const int wd = c->d.trunk_width;
@@ -2448,7 +2434,7 @@ int launch_maxpool3s2(const float* x, int n, int H, int W, int C, int Ho, int Wo
 
 struct AlexPlan {
   Levels lv;
-  int hq[2], wq[2];        // max-pooled sizes after conv1 / conv2
+  int hq[3], wq[3];        // max-pooled sizes after conv1 / conv2 (/ conv5: not used here)
   int C[5];
   float *in4, *a[5], *q[2];
   int *list_idx, *list_n;
@@ -2457,18 +2443,12 @@ struct AlexPlan {
 
 static void alexnet_plan(const milan_ctx* c, int n, int H, int W, Arena& ar,
                          AlexPlan* pl) {
-  static const int mult[5] = {1, 3, 6, 4, 4};
-  const int wd = c->d.trunk_width;
   Levels& lv = pl->lv;
-  lv.h[0] = conv_out(H, 11, 4, 2); lv.w[0] = conv_out(W, 11, 4, 2);
-  pl->hq[0] = conv_out(lv.h[0], 3, 2, 0); pl->wq[0] = conv_out(lv.w[0], 3, 2, 0);
-  lv.h[1] = pl->hq[0]; lv.w[1] = pl->wq[0];          // 5x5 pad 2 keeps the size
-  pl->hq[1] = conv_out(lv.h[1], 3, 2, 0); pl->wq[1] = conv_out(lv.w[1], 3, 2, 0);
-  for (int l = 2; l < 5; ++l) { lv.h[l] = pl->hq[1]; lv.w[l] = pl->wq[1]; }
+  alex_geometry(c, H, W, lv.h, lv.w, pl->hq, pl->wq);
   long off = 0;
   for (int l = 0; l < 5; ++l) { lv.off[l] = off; off += (long)lv.h[l] * lv.w[l]; }
   lv.per_image = off;
-  for (int l = 0; l < 5; ++l) pl->C[l] = mult[l] * wd;
+  for (int l = 0; l < 5; ++l) pl->C[l] = c->alex[l].cout;
   pl->in4 = ar.get<float>((size_t)n * H * W * 4);
   for (int l = 0; l < 5; ++l)
     pl->a[l] = ar.get<float>((size_t)n * lv.h[l] * lv.w[l] * pl->C[l]);
@@ -2551,11 +2531,10 @@ static int alexnet_run_batch(milan_ctx* c, const void* images, int image_dtype,
   const float* in = pl.q[0];
   int h = pl.hq[0], w = pl.wq[0];
   for (int l = 1; l < 5; ++l) {
-    // (the AlexNet path keeps activation scale 1: its taps are pooled as stored)
+    // (the AlexNet path keeps activation scale 1: its taps are pooled as stored; ho x wo is
+    // the plan's extent of the level: alex_geometry reads the same ConvW)
     GemmArgs g = conv_args(c->alex[l], in, n, h, w, pl.a[l], EPI_BIAS_RELU,
                            nullptr, c->zero, &ho, &wo, split, false);
-    MILAN_REQUIRE(ho == pl.lv.h[l] && wo == pl.lv.w[l], MILAN_ERR_SHAPE,
-                  "internal: alexnet level %d geometry mismatch", l);
     MILAN_TRY(launch_gemm(g, s));
     MILAN_TRY(pool(l, split));
     in = pl.a[l];

@@ -127,6 +127,28 @@ _FEATURE_MULT = {TRUNK_BOTTLENECK: 61, TRUNK_BASIC: 16, TRUNK_ALEXNET: 18,
 PLACES_ALEXNET_CHANNELS = synthetic.PLACES_ALEXNET_CHANNELS
 
 
+def level_shapes(kind: int, width: int, h: int, w: int):
+    """[(C, h, w)] of the tensors of levels 0..4 (`Context.activations`) that a trunk of
+    `kind` and `width` makes of an h x w image."""
+    if kind in (TRUNK_ALEXNET, TRUNK_ALEXNET_PLACES):
+        # conv1 11x11/4 pad 2 (Places: pad 0); pool1, pool2 3x3/2 before conv2, conv3; the
+        # rest keep.  (The library refuses an image too small for a level: at least 1 then.)
+        places = kind == TRUNK_ALEXNET_PLACES
+        mult = PLACES_ALEXNET_CHANNELS if places else synthetic.ALEXNET_CHANNELS
+        pad = 0 if places else 2
+        extents = [((h + 2 * pad - 11) // 4 + 1, (w + 2 * pad - 11) // 4 + 1)]
+        for _ in range(2):
+            extents.append(tuple((x - 3) // 2 + 1 for x in extents[-1]))
+        extents += extents[-1:] * 2
+        return [(width * m, max(hl, 1), max(wl, 1)) for m, (hl, wl) in zip(mult, extents)]
+    # conv1 7x7/2 pad 3, then the maxpool and every later stage 3x3/2 pad 1
+    extents = [((h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1)]
+    for _ in range(4):
+        extents.append(tuple((x + 2 - 3) // 2 + 1 for x in extents[-1]))
+    wide = width if kind == TRUNK_BASIC else width * 4
+    return [(c, hl, wl) for c, (hl, wl) in zip([width] + [wide << l for l in range(4)], extents)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
@@ -1094,32 +1116,10 @@ class Context:
             idx.append(int(level))
         ws = self._classify_ws(
             n, h, w, need=int(self._need('milan_activations_workspace_bytes')(self._h, n, h, w)))
-        # level extents: conv1 7x7/2 pad 3, then the maxpool and every later stage 3x3/2 pad 1
-        basic = self.dims.trunk_kind == TRUNK_BASIC
-        outs = []
-        for level in idx:
-            if not 0 <= level <= 4:  # (the library reports it; the shape is a placeholder)
-                outs.append(torch.empty(1, dtype=torch.float32, device=self.device))
-                continue
-            if self.dims.trunk_kind in (TRUNK_ALEXNET, TRUNK_ALEXNET_PLACES):
-                # conv1 11x11/4 pad 2 (Places: pad 0); pool1, pool2 3x3/2 before conv2, conv3;
-                # the rest keep
-                places = self.dims.trunk_kind == TRUNK_ALEXNET_PLACES
-                pad = 0 if places else 4
-                hl, wl = (h + pad - 11) // 4 + 1, (w + pad - 11) // 4 + 1
-                for _ in range(min(level, 2)):
-                    hl, wl = (hl - 3) // 2 + 1, (wl - 3) // 2 + 1
-                mult = PLACES_ALEXNET_CHANNELS if places else (1, 3, 6, 4, 4)
-                ch = self.dims.trunk_width * mult[level]
-                outs.append(torch.empty(n, ch, max(hl, 1), max(wl, 1), dtype=torch.float32,
-                                        device=self.device))
-                continue
-            hl, wl = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
-            for _ in range(level):
-                hl, wl = (hl + 2 - 3) // 2 + 1, (wl + 2 - 3) // 2 + 1
-            width = self.dims.trunk_width
-            ch = width if level == 0 else (width if basic else width * 4) << (level - 1)
-            outs.append(torch.empty(n, ch, hl, wl, dtype=torch.float32, device=self.device))
+        shapes = level_shapes(self.dims.trunk_kind, self.dims.trunk_width, h, w)
+        # (a level out of range: the library reports it; the shape is a placeholder)
+        outs = [torch.empty((n,) + shapes[level] if 0 <= level <= 4 else 1, dtype=torch.float32,
+                            device=self.device) for level in idx]
         c_levels = (ctypes.c_int32 * len(idx))(*idx)
         c_outs = (ctypes.c_void_p * len(idx))(*[o.data_ptr() for o in outs])
 

@@ -1,7 +1,8 @@
 """Host tests of classifiers.AlexNetClassifier under milan_amd.ablations: the torch path (CPU)
 against the reference's goldens (tests/golden/reference_goldens_alexnet.*, made by the
 reference's own src/utils/ablations.py over an `alexnet_seq`-shaped stand-in) and against the
-restatement tests/alexref.py."""
+restatement tests/alexref.py; and `hip.level_shapes` of the three trunk families against the
+shapes forward hooks see on the eager modules."""
 import collections
 
 import pytest
@@ -11,7 +12,7 @@ from torch.utils import data
 
 import alexref
 from featclass import FEATURE_CLASS
-from milan_amd import ablations, classifiers
+from milan_amd import ablations, classifiers, hip
 
 SMALL = ((63, 63), (95, 127))   # (the two large geometries run on the GPU)
 
@@ -179,3 +180,34 @@ def test_unit_scores_on_cpu_is_the_loop(gold):
     scores = classifier.unit_scores(dataset, units, batch_size=5, display_progress_as=None)
     assert scores == [classifier.accuracy(dataset, batch_size=5, ablate=[unit],
                                           display_progress_as=None) for unit in units]
+
+
+LEVEL_SHAPE_CASES = (
+    (lambda: classifiers.AlexNetClassifier(4, 8, 8), hip.TRUNK_ALEXNET, ((63, 63), (95, 127))),
+    (lambda: classifiers.PlacesAlexNetClassifier(4, 8, 8), hip.TRUNK_ALEXNET_PLACES,
+     ((35, 38), (99, 131), (227, 227))),
+    (lambda: classifiers.ResNetClassifier('resnet18', 4, 8), hip.TRUNK_BASIC, ((33, 47),)),
+    (lambda: classifiers.ResNetClassifier('resnet50', 4, 8), hip.TRUNK_BOTTLENECK, ((33, 47),)),
+)
+
+
+@pytest.mark.parametrize('make,kind,geometries', LEVEL_SHAPE_CASES,
+                         ids=('alexnet', 'places', 'resnet18', 'resnet50'))
+def test_level_shapes_are_what_forward_hooks_see(make, kind, geometries):
+    """`hip.level_shapes` (the tensors `Context.activations` allocates) against the eager
+    modules of the three trunk families at width 8."""
+    model = make().eval()
+    seen = []
+    for layer in model.layers:
+        getattr(model, layer).register_forward_hook(
+            lambda module, inputs, output: seen.append(tuple(output.shape[1:])))
+    for h, w in geometries:
+        del seen[:]
+        x = torch.zeros(1, 3, h, w)
+        with torch.no_grad():
+            # (the trunk alone: the Places365 net's fc6 takes 227 x 227 only)
+            for name, module in model.named_children():
+                x = module(x)
+                if name == model.layers[-1]:
+                    break
+        assert hip.level_shapes(kind, 8, h, w) == seen, (h, w)

@@ -3,9 +3,9 @@
 //
 // A context of its own (milan_bert_ctx): dims + one weight arena in the HuggingFace
 // state-dict layout, row-major as torch stores it, nothing transposed or packed.  Every
-// contraction goes through lmt::gemm_rows (train_common.h): the exact-fp32 MFMA GEMM of the
-// training path with its split count a function of K alone, so a sentence's embeddings do
-// not depend on the other sentences of the call.  Bias and residual adds are its epilogue.
+// contraction goes through tgemm::gemm_rows (tgemm.h): the strided exact-fp32 MFMA GEMM
+// with its split count a function of K alone, so a sentence's embeddings do not depend on
+// the other sentences of the call.  Bias and residual adds are its epilogue.
 // LayerNorm, the erf GELU, the L2 norm, the attention kernel (a whole head in LDS, ragged
 // through `offsets`) and the weight store are the towers' shared parts (tower.hip).
 //
@@ -36,9 +36,9 @@ struct milan_bert_ctx {
 namespace milan {
 namespace bert {
 
-using lmt::Scratch;
-using lmt::View;
-using lmt::view;
+using tgemm::Scratch;
+using tgemm::View;
+using tgemm::view;
 using namespace milan::tower;
 
 constexpr int MAX_TOKENS = MILAN_BERT_MAX_TOKENS;
@@ -189,9 +189,9 @@ static int plan(const milan_bert_ctx* c, int n, int total, Plan* p) {
   p->x = o; o += up64((size_t)total * W);
   p->y = o; o += up64((size_t)total * W);
   p->big = o; o += up64((size_t)total * wide);
-  p->scratch_floats = std::max({lmt::rows_scratch_floats(total, W, W),
-                                lmt::rows_scratch_floats(total, I, W),
-                                lmt::rows_scratch_floats(total, W, I)});
+  p->scratch_floats = std::max({tgemm::rows_scratch_floats(total, W, W),
+                                tgemm::rows_scratch_floats(total, I, W),
+                                tgemm::rows_scratch_floats(total, W, I)});
   p->scratch = o; o += up64(p->scratch_floats);
   p->total_floats = o;
   return 0;
@@ -320,18 +320,18 @@ int milan_bert_encode(milan_bert_ctx* c, const int64_t* ids, const int32_t* offs
     const float* qkv_w[3] = {b.q_w, b.k_w, b.v_w};
     const float* qkv_b[3] = {b.q_b, b.k_b, b.v_b};
     for (int i = 0; i < 3; ++i)
-      MILAN_TRY(lmt::gemm_rows(view(x, W), 0, view(qkv_w[i], W), 1, view(big + i * W, 3 * W),
+      MILAN_TRY(tgemm::gemm_rows(view(x, W), 0, view(qkv_w[i], W), 1, view(big + i * W, 3 * W),
                                none, qkv_b[i], nullptr, M, W, W, sc, s));
     MILAN_TRY(launch_lds_attention(att, n, d.heads, s));
     // x <- y Wo^T + bo + x, y <- LayerNorm(x)
-    MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.ao_w, W), 1, view(x, W), view(x, W), b.ao_b,
+    MILAN_TRY(tgemm::gemm_rows(view(y, W), 0, view(b.ao_w, W), 1, view(x, W), view(x, W), b.ao_b,
                              nullptr, M, W, W, sc, s));
     MILAN_TRY(launch_layernorm_rows(x, W, y, M, W, b.ln1_w, b.ln1_b, d.eps, s));
-    MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.in_w, W), 1, view(big, I), none, b.in_b,
+    MILAN_TRY(tgemm::gemm_rows(view(y, W), 0, view(b.in_w, W), 1, view(big, I), none, b.in_b,
                              nullptr, M, I, W, sc, s));
     MILAN_TRY(launch_gelu_erf(big, (long)M * I, s));
     // y <- big Wout^T + bout + y, x <- LayerNorm(y)
-    MILAN_TRY(lmt::gemm_rows(view(big, I), 0, view(b.out_w, I), 1, view(y, W), view(y, W),
+    MILAN_TRY(tgemm::gemm_rows(view(big, I), 0, view(b.out_w, I), 1, view(y, W), view(y, W),
                              b.out_b, nullptr, M, W, I, sc, s));
     MILAN_TRY(launch_layernorm_rows(y, W, x, M, W, b.ln2_w, b.ln2_b, d.eps, s));
   }

@@ -4,7 +4,7 @@
 //
 // A context of its own (milan_clip_ctx): dims + one weight arena in OpenAI's state-dict
 // layout, row-major as torch stores it.  No weight is transposed or packed: every
-// contraction goes through lmt::gemm (train_common.h), the strided exact-fp32 MFMA GEMM,
+// contraction goes through tgemm::gemm (tgemm.h), the strided exact-fp32 MFMA GEMM,
 // which reads x.W^T through a view.  Bias and residual adds are its epilogue (bias1 / d);
 // QuickGELU stays a row kernel, so no existing GEMM instantiation changes.  The plain
 // LayerNorm, the L2 norm, the patch gather, the attention kernel (a whole head in LDS, with
@@ -44,9 +44,9 @@ struct milan_clip_ctx {
 namespace milan {
 namespace clip {
 
-using lmt::Scratch;
-using lmt::View;
-using lmt::view;
+using tgemm::Scratch;
+using tgemm::View;
+using tgemm::view;
 using namespace milan::tower;
 
 constexpr float LN_EPS = 1e-5f;
@@ -189,7 +189,7 @@ struct Plan {
 static size_t tower_scratch(long M, int W) {
   size_t s = 0;
   const int shapes[4][2] = {{3 * W, W}, {W, W}, {4 * W, W}, {W, 4 * W}};
-  for (auto& sh : shapes) s = std::max(s, lmt::split_scratch_floats((int)M, sh[0], sh[1]));
+  for (auto& sh : shapes) s = std::max(s, tgemm::split_scratch_floats((int)M, sh[0], sh[1]));
   return s;
 }
 
@@ -211,18 +211,18 @@ static int run_tower(const milan_clip_ctx::Tower& tw, float* x, float* y, float*
   for (size_t l = 0; l < tw.blocks.size(); ++l) {
     const auto& b = tw.blocks[l];
     MILAN_TRY(launch_layernorm_rows(x, W, y, (int)M, W, b.ln1_w, b.ln1_b, LN_EPS, s));
-    MILAN_TRY(lmt::gemm(view(y, W), 0, view(b.in_w, W), 1, view(big, 3 * W), none, b.in_b,
+    MILAN_TRY(tgemm::gemm(view(y, W), 0, view(b.in_w, W), 1, view(big, 3 * W), none, b.in_b,
                         nullptr, (int)M, 3 * W, W, sc, s));
     att.cls_mask = (cls_mask && l < 64 && ((mask_layers >> l) & 1)) ? cls_mask : nullptr;
     MILAN_TRY(launch_lds_attention(att, seqs, tw.heads, s));
-    MILAN_TRY(lmt::gemm(view(y, W), 0, view(b.out_w, W), 1, view(x, W), view(x, W), b.out_b,
+    MILAN_TRY(tgemm::gemm(view(y, W), 0, view(b.out_w, W), 1, view(x, W), view(x, W), b.out_b,
                         nullptr, (int)M, W, W, sc, s));
     MILAN_TRY(launch_layernorm_rows(x, W, y, (int)M, W, b.ln2_w, b.ln2_b, LN_EPS, s));
-    MILAN_TRY(lmt::gemm(view(y, W), 0, view(b.fc_w, W), 1, view(big, 4 * W), none, b.fc_b,
+    MILAN_TRY(tgemm::gemm(view(y, W), 0, view(b.fc_w, W), 1, view(big, 4 * W), none, b.fc_b,
                         nullptr, (int)M, 4 * W, W, sc, s));
     hipLaunchKernelGGL(quick_gelu_kernel, dim3(blocks_for(M * 4 * W)), dim3(256), 0, s, big,
                        M * 4 * W);
-    MILAN_TRY(lmt::gemm(view(big, 4 * W), 0, view(b.pj_w, 4 * W), 1, view(x, W), view(x, W),
+    MILAN_TRY(tgemm::gemm(view(big, 4 * W), 0, view(b.pj_w, 4 * W), 1, view(x, W), view(x, W),
                         b.pj_b, nullptr, (int)M, W, 4 * W, sc, s));
   }
   MILAN_CHECK_HIP(hipGetLastError());
@@ -247,8 +247,8 @@ static int image_plan(const milan_clip_ctx* c, int n, int copies, Plan* p) {
   p->big = o; o += std::max(up64((size_t)M * 4 * W), front);
   p->aux = o; o += up64((size_t)n * G * G) + 2 * up64((size_t)seqs * std::max(W, d.embed_dim));
   p->scratch_floats = std::max({tower_scratch(M, W),
-                                lmt::split_scratch_floats(n * G * G, W, kk),
-                                lmt::split_scratch_floats((int)seqs, d.embed_dim, W)});
+                                tgemm::split_scratch_floats(n * G * G, W, kk),
+                                tgemm::split_scratch_floats((int)seqs, d.embed_dim, W)});
   p->scratch = o; o += up64(p->scratch_floats);
   p->total_floats = o;
   return 0;
@@ -270,7 +270,7 @@ static int text_plan(const milan_clip_ctx* c, int rows, int positions, Plan* p) 
   p->big = o; o += up64((size_t)M * 4 * W);
   p->aux = o; o += 2 * up64((size_t)rows * std::max(W, d.embed_dim));
   p->scratch_floats =
-      std::max(tower_scratch(M, W), lmt::split_scratch_floats(rows, d.embed_dim, W));
+      std::max(tower_scratch(M, W), tgemm::split_scratch_floats(rows, d.embed_dim, W));
   p->scratch = o; o += up64(p->scratch_floats);
   p->total_floats = o;
   return 0;
@@ -413,7 +413,7 @@ int milan_clip_encode_images(milan_clip_ctx* c, const float* images, int n, int 
     hipLaunchKernelGGL(mask_downsample_kernel, dim3(blocks_for(np)), dim3(256), 0, s, masks, cm,
                        np, d.resolution, G);
   MILAN_CHECK_HIP(hipGetLastError());
-  MILAN_TRY(lmt::gemm(view(patches, kk), 0, view(c->conv1, kk), 1, view(pe, W), none, nullptr,
+  MILAN_TRY(tgemm::gemm(view(patches, kk), 0, view(c->conv1, kk), 1, view(pe, W), none, nullptr,
                       nullptr, (int)np, W, kk, sc, s));
   GatherLnArgs a{};
   a.src = pe; a.cls = c->cls; a.pos = c->vpos; a.kind = 1; a.T = T; a.n_img = n;
@@ -423,7 +423,7 @@ int milan_clip_encode_images(milan_clip_ctx* c, const float* images, int n, int 
                       n, mask_layers, sc, s));
   MILAN_TRY(launch_layernorm_rows(w + p.x, (long)T * W, cls_rows, (int)seqs, W, c->ln_post_w,
                                   c->ln_post_b, LN_EPS, s));
-  MILAN_TRY(lmt::gemm(view(cls_rows, W), 0, view(c->vproj, E), 0, view(emb, E), none, nullptr,
+  MILAN_TRY(tgemm::gemm(view(cls_rows, W), 0, view(c->vproj, E), 0, view(emb, E), none, nullptr,
                       nullptr, (int)seqs, E, W, sc, s));
   return launch_l2norm(emb, out, (int)seqs, E, 1, s);
 }
@@ -459,7 +459,7 @@ int milan_clip_encode_texts(milan_clip_ctx* c, const int64_t* tokens, int rows, 
   a.src = w + p.x; a.kind = 2; a.T = T; a.ids = tokens; a.ctx_len = d.context_length;
   a.w = c->ln_fin_w; a.b = c->ln_fin_b; a.dst = eot_rows; a.rows = rows; a.W = W;
   MILAN_TRY(launch_gather_ln(a, s));
-  MILAN_TRY(lmt::gemm(view(eot_rows, W), 0, view(c->tproj, E), 0, view(emb, E),
+  MILAN_TRY(tgemm::gemm(view(eot_rows, W), 0, view(c->tproj, E), 0, view(emb, E),
                       view(nullptr, 0), nullptr, nullptr, rows, E, W, sc, s));
   return launch_l2norm(emb, out, rows, E, 1, s);
 }

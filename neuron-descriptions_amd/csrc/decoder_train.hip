@@ -12,8 +12,10 @@
 //   loss = NLL(ignore pad) mean + w * mean_{row, k} (1 - sum_t alpha_{t,k})^2
 //
 // As in lm_train.hip: exact fp32 MFMA whatever milan_set_precision says, raw torch-layout
-// parameters read on every call through the strided GEMM of train_common.h, fixed
-// reduction orders and no float atomics (equal inputs and seed give equal bits).
+// parameters read on every call through the strided GEMM of tgemm.h, fixed reduction orders
+// and no float atomics (equal inputs and seed give equal bits).  The embedding gather and
+// gradient, the dropout, the LSTM cell, the log-softmax and the output layer are the LM
+// trainer's (train_common.h); the attention and the init_h / init_c kernels are defined here.
 //
 // Layout.  Hoisted before the time loop: the feature mean and the
 // init_h / init_c GEMMs, the attention keys W_k f + b_k of all rows * k features, and the
@@ -29,36 +31,9 @@
 
 namespace milan {
 namespace dect {
-
-using lmt::colsum;
-using lmt::gemm;
-using lmt::Scratch;
-using lmt::split_scratch_floats;
-using lmt::View;
-using lmt::view;
+using namespace train;
 
 constexpr int kMaxK = 64;  // features per row (the attention kernels keep k scores in LDS)
-// the decoder's dropout mask tag: the top byte of the hashed key, above every LM layer
-constexpr uint64_t kDropoutTag = 0xDC;
-
-// keep <=> (mix64(seed ^ mix64(0xDC << 56 | row << 32 | t << 16 | unit)) >> 40) >= thr
-__device__ __forceinline__ bool keep(uint64_t seed, int row, int t, int unit, uint32_t thr) {
-  const uint64_t key = kDropoutTag << 56 | (uint64_t)row << 32 | (uint64_t)t << 16 |
-                       (uint64_t)unit;
-  return (uint32_t)(lmt::mix64(seed ^ lmt::mix64(key)) >> 40) >= thr;
-}
-
-__device__ __forceinline__ int clamp_id(int64_t id, int V) {
-  return id < 0 ? 0 : (id >= V ? V - 1 : (int)id);
-}
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-static unsigned blocks_for(long n) { return (unsigned)((n + 255) / 256); }
 
 // Teacher-forced inputs: in[b][0] = start, in[b][t] = targets[b][t - 1].
 __global__ void inputs_kernel(const int64_t* __restrict__ tgt, int64_t* __restrict__ in, int rows,
@@ -67,15 +42,6 @@ __global__ void inputs_kernel(const int64_t* __restrict__ tgt, int64_t* __restri
   if (i >= (long)rows * L) return;
   const int t = (int)(i % L);
   in[i] = t ? tgt[i - 1] : (int64_t)start;
-}
-
-// X[n][e] = embedding[in[n]][e] for e < E (row stride E + F: the context columns follow)
-__global__ void embed_kernel(const int64_t* __restrict__ ids, const float* __restrict__ emb,
-                             float* __restrict__ X, int N, int E, int F, int V) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= (long)N * E) return;
-  const int n = (int)(i / E), e = (int)(i % E);
-  X[(long)n * (E + F) + e] = emb[(long)clamp_id(ids[n], V) * E + e];
 }
 
 // pooled[b][f] = (sum over k of feat[b][k][f], in k order) / k
@@ -150,49 +116,6 @@ __global__ __launch_bounds__(256) void attend_fwd_kernel(
   }
 }
 
-// One LSTM cell step t (torch gate order i, f, g, o).  G: pre-activations of step t in,
-// activated gates out [rows * L][4H]; C, Hs: [rows][L + 1][H], slot t in, slot t + 1 out.
-__global__ void cell_fwd_kernel(float* __restrict__ G, float* __restrict__ C,
-                                float* __restrict__ Hs, int rows, int L, int H, int t) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= (long)rows * H) return;
-  const int b = (int)(i / H), j = (int)(i % H);
-  float* g = G + ((long)b * L + t) * 4 * H;
-  const float ig = sigm(g[j]), fg = sigm(g[H + j]), gg = tanhf(g[2 * H + j]),
-              og = sigm(g[3 * H + j]);
-  const long o = ((long)b * (L + 1) + t) * H + j;
-  const float c = fg * C[o] + ig * gg;
-  g[j] = ig;
-  g[H + j] = fg;
-  g[2 * H + j] = gg;
-  g[3 * H + j] = og;
-  C[o + H] = c;
-  Hs[o + H] = og * tanhf(c);
-}
-
-// HD[b][t][j] = dropout(h_{t+1})  (mask * scale)
-__global__ void dropout_fwd_kernel(const float* __restrict__ Hs, float* __restrict__ HD, int rows,
-                                   int L, int H, uint64_t seed, uint32_t thr, float scale) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= (long)rows * L * H) return;
-  const int j = (int)(i % H);
-  const long bt = i / H;
-  const int t = (int)(bt % L), b = (int)(bt / L);
-  const float h = Hs[((long)b * (L + 1) + t + 1) * H + j];
-  HD[i] = keep(seed, b, t, j, thr) ? h * scale : 0.f;
-}
-
-// dY[b][t][j] *= mask * scale (the same mask as dropout_fwd_kernel)
-__global__ void dropout_bwd_kernel(float* __restrict__ dY, int rows, int L, int H, uint64_t seed,
-                                   uint32_t thr, float scale) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= (long)rows * L * H) return;
-  const int j = (int)(i % H);
-  const long bt = i / H;
-  const int t = (int)(bt % L), b = (int)(bt / L);
-  dY[i] = keep(seed, b, t, j, thr) ? dY[i] * scale : 0.f;
-}
-
 // S[b][j] = sum over t (in order) of alpha[b][t][j]
 __global__ void attn_sum_kernel(const float* __restrict__ ALPHA, float* __restrict__ S, int rows,
                                 int L, int k) {
@@ -217,30 +140,6 @@ __global__ __launch_bounds__(256) void reg_reduce_kernel(const float* __restrict
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
-}
-
-// Backward of cell step t.  dY: dL/dh_{t+1} from the output layer [rows * L][H]; dhrec:
-// dL/dh_{t+1} through step t + 1 (absent at t = L - 1); dc: dL/dc_{t+1} in (absent at
-// t = L - 1), dL/dc_t out.  G: activated gates in, d(pre-activation) out.
-__global__ void cell_bwd_kernel(const float* __restrict__ dY, const float* __restrict__ dhrec,
-                                float* __restrict__ G, const float* __restrict__ C,
-                                float* __restrict__ dc, int rows, int L, int H, int t) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= (long)rows * H) return;
-  const int b = (int)(i / H), j = (int)(i % H);
-  const bool last = t == L - 1;
-  float* g = G + ((long)b * L + t) * 4 * H;
-  const float ig = g[j], fg = g[H + j], gg = g[2 * H + j], og = g[3 * H + j];
-  const long o = ((long)b * (L + 1) + t) * H + j;
-  const float cp = C[o], c = C[o + H];
-  const float d_h = dY[((long)b * L + t) * H + j] + (last ? 0.f : dhrec[i]);
-  const float tc = tanhf(c);
-  const float dcur = d_h * og * (1.f - tc * tc) + (last ? 0.f : dc[i]);
-  dc[i] = dcur * fg;
-  g[j] = dcur * gg * ig * (1.f - ig);
-  g[H + j] = dcur * cp * fg * (1.f - fg);
-  g[2 * H + j] = dcur * ig * (1.f - gg * gg);
-  g[3 * H + j] = d_h * tc * og * (1.f - og);
 }
 
 // Attention backward of step t, one workgroup per row b.  dZ: dL/dz of the step [rows][F].
@@ -348,38 +247,6 @@ __global__ __launch_bounds__(256) void attend_bwd_up_kernel(
   }
 }
 
-// out[n][v] = logits[n][v] - lse[n]: the log-probabilities of every position
-__global__ void log_softmax_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
-                                   float* __restrict__ out, int N, int V) {
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= (long)N * V) return;
-  out[i] = logits[i] - lse[i / V];
-}
-
-// Log-softmax backward from an upstream gradient G [N][V] (null: zero), one workgroup per
-// row: logits[n][v] <- G[n][v] - exp(logits[n][v] - lse[n]) * sum_v G[n][v], in place.  The
-// row sum is taken in a fixed order (per-thread strided sums, lanes by xor butterfly, the 4
-// waves in order).
-__global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float* __restrict__ G,
-                                                              float* __restrict__ logits,
-                                                              const float* __restrict__ lse,
-                                                              int V) {
-  __shared__ float red[4];
-  const int n = blockIdx.x;
-  float* x = logits + (long)n * V;
-  const float* g = G ? G + (long)n * V : nullptr;
-  float s = 0.f;
-  if (g)
-    for (int v = threadIdx.x; v < V; v += blockDim.x) s += g[v];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const float sum = red[0] + red[1] + red[2] + red[3];
-  const float l = lse[n];
-  for (int v = threadIdx.x; v < V; v += blockDim.x)
-    x[v] = g ? g[v] - expf(x[v] - l) * sum : 0.f;
-}
-
 // The context and mean-pool shares of the feature gradient, added to the key share that dF
 // [rows][k][F] holds: dF[b][j][f] = (dF[b][j][f] + sum over t (increasing) of
 // alpha[b][t][j] * dctx[b][t][f]) + dpool[b][f] / k.
@@ -446,44 +313,37 @@ static int make_plan(const milan_ctx* c, int rows, int k, int L, Plan* p) {
   p->L = L;
   const int N = p->N = rows * L, H = p->H, E = p->E, V = p->V, A = p->A, F = p->F;
   const long BK = (long)rows * k;
-  size_t off = 0;
-  auto take = [&](size_t floats) {
-    const size_t at = off;
-    off += (floats + 63) / 64 * 64;
-    return at;
-  };
-  p->ids = take((size_t)N * 2);  // int64
-  p->pooled = take((size_t)rows * F);
-  p->kh = take((size_t)BK * A);
-  p->x = take((size_t)N * (E + F));
-  p->g = take((size_t)N * 4 * H);
-  p->cst = take((size_t)rows * (L + 1) * H);
-  p->hs = take((size_t)rows * (L + 1) * H);
-  p->hd = take((size_t)N * H);
-  p->q = take((size_t)N * A);
-  p->gt = take((size_t)N * F);
-  p->ctx = take((size_t)N * F);
-  p->alpha = take((size_t)N * k);
-  p->u = take((size_t)N * k * A);
-  p->s = take((size_t)BK);
-  p->logits = take((size_t)N * V);
-  p->lse = take(N);
-  p->term = take(N);
-  p->valid = take(N);
-  p->dy = take((size_t)N * H);
-  p->dhrec = take((size_t)rows * H);
-  p->dc = take((size_t)rows * H);
-  p->dz = take((size_t)rows * F);
-  p->dgp = take((size_t)N * F);
-  p->ds = take((size_t)N * k);
-  p->dq = take((size_t)N * A);
-  p->dkh = take((size_t)BK * A);
-  p->dxe = take((size_t)N * E);
-  p->dph = take((size_t)rows * H);
-  p->dpc = take((size_t)rows * H);
-  size_t sc = 0;
-  auto need = [&](size_t f) { sc = f > sc ? f : sc; };
-  auto cs = [&](long R, long cols) { need((size_t)lmt::colsum_chunks((int)R) * cols); };
+  Layout w;
+  p->ids = w.take((size_t)N * 2);  // int64
+  p->pooled = w.take((size_t)rows * F);
+  p->kh = w.take((size_t)BK * A);
+  p->x = w.take((size_t)N * (E + F));
+  p->g = w.take((size_t)N * 4 * H);
+  p->cst = w.take((size_t)rows * (L + 1) * H);
+  p->hs = w.take((size_t)rows * (L + 1) * H);
+  p->hd = w.take((size_t)N * H);
+  p->q = w.take((size_t)N * A);
+  p->gt = w.take((size_t)N * F);
+  p->ctx = w.take((size_t)N * F);
+  p->alpha = w.take((size_t)N * k);
+  p->u = w.take((size_t)N * k * A);
+  p->s = w.take((size_t)BK);
+  p->logits = w.take((size_t)N * V);
+  p->lse = w.take(N);
+  p->term = w.take(N);
+  p->valid = w.take(N);
+  p->dy = w.take((size_t)N * H);
+  p->dhrec = w.take((size_t)rows * H);
+  p->dc = w.take((size_t)rows * H);
+  p->dz = w.take((size_t)rows * F);
+  p->dgp = w.take((size_t)N * F);
+  p->ds = w.take((size_t)N * k);
+  p->dq = w.take((size_t)N * A);
+  p->dkh = w.take((size_t)BK * A);
+  p->dxe = w.take((size_t)N * E);
+  p->dph = w.take((size_t)rows * H);
+  p->dpc = w.take((size_t)rows * H);
+  auto cs = [&](long R, long cols) { w.need((size_t)colsum_chunks((int)R) * cols); };
   cs(N, V);
   cs(N, 4 * H);
   cs(N, A);
@@ -497,18 +357,18 @@ static int make_plan(const milan_ctx* c, int rows, int k, int L, Plan* p) {
       {rows, 4 * H, F}, {rows, 4 * H, H}, {N, V, H},  {V, H, N},        {N, H, V},
       {rows, F, 4 * H}, {rows, H, A}, {rows, H, 4 * H}, {4 * H, E + F, N}, {4 * H, H, N}, {A, H, N},
       {F, H, N},     {A, F, (int)BK}, {1, A, KK},     {N, E, 4 * H},    {H, F, rows}};
-  for (const auto& s : shapes) need(split_scratch_floats(s[0], s[1], s[2]));
-  p->scratch = take(sc);
-  p->scratch_floats = sc;
-  p->total = off * sizeof(float);
-  p->terms = take(4);
-  p->dctx = take((size_t)N * F);
-  p->dpool = take((size_t)rows * F);
+  for (const auto& s : shapes) w.need(split_scratch_floats(s[0], s[1], s[2]));
+  p->scratch = w.take(w.scratch);
+  p->scratch_floats = w.scratch;
+  p->total = w.off * sizeof(float);
+  p->terms = w.take(4);
+  p->dctx = w.take((size_t)N * F);
+  p->dpool = w.take((size_t)rows * F);
   const size_t gk = split_scratch_floats((int)BK, F, A), gp = split_scratch_floats(rows, F, H);
   const size_t gsc = gk > gp ? gk : gp;  // dKh . W_k, then dph . W_init_h + dpc . W_init_c
-  p->gscratch = take(gsc);
+  p->gscratch = w.take(gsc);
   p->gscratch_floats = gsc;
-  p->grad_total = off * sizeof(float);
+  p->grad_total = w.off * sizeof(float);
   return 0;
 }
 
@@ -528,8 +388,6 @@ static int check_params(const void* const* params, int n, const char* what) {
   return 0;
 }
 
-static uint32_t drop_threshold(float p) { return (uint32_t)((double)p * 16777216.0); }
-
 // Forward, loss terms [nll sum, valid count, sum (1 - S)^2].  thr > 0: dropout on h.
 static int forward(const Plan& p, const float* const* w, float* ws, const float* feat,
                    const int64_t* targets, uint32_t thr, float scale, uint64_t seed, float* loss,
@@ -544,8 +402,7 @@ static int forward(const Plan& p, const float* const* w, float* ws, const float*
         *GT = ws + p.gt, *Kh = ws + p.kh;
   hipLaunchKernelGGL(inputs_kernel, dim3(blocks_for(N)), dim3(256), 0, s, targets, ids, rows, L,
                      p.start);
-  hipLaunchKernelGGL(embed_kernel, dim3(blocks_for((long)N * E)), dim3(256), 0, s, ids,
-                     w[P_EMB], X, N, E, F, V);
+  launch_embed(ids, w[P_EMB], X, N, E, E + F, V, s);  // (the context columns follow)
   hipLaunchKernelGGL(pool_kernel, dim3(blocks_for((long)rows * F)), dim3(256), 0, s, feat,
                      ws + p.pooled, rows, k, F);
   MILAN_CHECK_HIP(hipGetLastError());
@@ -576,21 +433,17 @@ static int forward(const Plan& p, const float* const* w, float* ws, const float*
                    view(w[P_W_IH] + E, E + F), 1, gt, gt, nullptr, nullptr, rows, 4 * H, F, sc,
                    s));
     MILAN_TRY(gemm(ht, 0, view(w[P_W_HH], H), 1, gt, gt, nullptr, nullptr, rows, 4 * H, H, sc, s));
-    hipLaunchKernelGGL(cell_fwd_kernel, dim3(blocks_for((long)rows * H)), dim3(256), 0, s, G, C,
-                       Hs, rows, L, H, t);
+    // c_t, h_t: slot t of C, Hs [rows][L + 1][H] in, slot t + 1 out
+    launch_cell_fwd(G, C + (size_t)t * H, C + (size_t)(t + 1) * H, (long)(L + 1) * H, Hs, rows, L,
+                    H, t, s);
   }
   // logits of every position from (dropped-out) h_{t+1}
   View hout = view(Hs + H, H, L, (long)(L + 1) * H);
   if (thr) {
-    hipLaunchKernelGGL(dropout_fwd_kernel, dim3(blocks_for((long)N * H)), dim3(256), 0, s, Hs,
-                       ws + p.hd, rows, L, H, seed, thr, scale);
+    launch_dropout_fwd(Hs, ws + p.hd, rows, L, H, kDecoderDropoutTag, seed, thr, scale, s);
     hout = view(ws + p.hd, H);
   }
-  MILAN_TRY(gemm(hout, 0, view(w[P_OUT_W], H), 1, view(ws + p.logits, V), none, w[P_OUT_B],
-                 nullptr, N, V, H, sc, s));
-  lmt::launch_nll_rows(ws + p.logits, targets, N, V, p.pad, ws + p.lse, ws + p.term,
-                       ws + p.valid, s);
-  lmt::launch_loss_reduce(ws + p.term, ws + p.valid, N, loss, s);
+  MILAN_TRY(output_forward(out_layer(p, ws), hout, w[P_OUT_W], w[P_OUT_B], targets, loss, sc, s));
   hipLaunchKernelGGL(attn_sum_kernel, dim3(blocks_for(BK)), dim3(256), 0, s, ws + p.alpha,
                      ws + p.s, rows, L, k);
   hipLaunchKernelGGL(reg_reduce_kernel, dim3(1), dim3(256), 0, s, ws + p.s, (long)BK, loss + 2);
@@ -621,22 +474,17 @@ static int backward(const Plan& p, const float* const* w, float* const* gr, floa
   float *X = ws + p.x, *G = ws + p.g, *Hs = ws + p.hs, *dY = ws + p.dy, *dh = ws + p.dhrec,
         *dc = ws + p.dc, *dZ = ws + p.dz, *DGP = ws + p.dgp, *DQ = ws + p.dq, *DS = ws + p.ds,
         *dKh = ws + p.dkh;
-  float* dlog = ws + p.logits;
-  if (!up) lmt::launch_dlogits(dlog, targets, ws + p.lse, ws + p.valid, loss, N, V, s);
   const View hout = thr ? view(ws + p.hd, H) : view(Hs + H, H, L, (long)(L + 1) * H);
-  // output layer: dW_out = dlogits^T . h_out, db_out = sum dlogits, dY = dlogits . W_out
-  MILAN_TRY(gemm(view(dlog, V), 1, hout, 0, view(gr[P_OUT_W], H), none, nullptr, nullptr, V, H,
-                 N, sc, s));
-  MILAN_TRY(colsum(dlog, N, V, gr[P_OUT_B], nullptr, sc, s));
-  MILAN_TRY(gemm(view(dlog, V), 0, view(w[P_OUT_W], H), 0, view(dY, H), none, nullptr, nullptr,
-                 N, H, V, sc, s));
-  if (thr)
-    hipLaunchKernelGGL(dropout_bwd_kernel, dim3(blocks_for((long)N * H)), dim3(256), 0, s, dY,
-                       rows, L, H, seed, thr, scale);
+  // (loss is null exactly when up is given: the logits buffer then holds dlogits)
+  MILAN_TRY(output_backward(out_layer(p, ws), hout, w[P_OUT_W], targets, loss, gr[P_OUT_W],
+                            gr[P_OUT_B], dY, sc, s));
+  if (thr) launch_dropout_bwd(dY, rows, L, H, kDecoderDropoutTag, seed, thr, scale, s);
   const float reg = 2.f * reg_weight / (float)BK;
+  const float* C = ws + p.cst;
   for (int t = L - 1; t >= 0; --t) {
-    hipLaunchKernelGGL(cell_bwd_kernel, dim3(blocks_for((long)rows * H)), dim3(256), 0, s, dY, dh,
-                       G, ws + p.cst, dc, rows, L, H, t);
+    // dL/dh_{t+1} = dY[:, t] + dh through step t + 1 (absent at t = L - 1)
+    launch_cell_bwd(dY + (size_t)t * H, (long)L * H, dh, G, C + (size_t)(t + 1) * H,
+                    C + (size_t)t * H, (long)(L + 1) * H, dc, rows, L, H, t, s);
     const View dgt = view(G + (size_t)t * 4 * H, (long)L * 4 * H);
     // dz = dG_t . W_ih[:, E:]
     MILAN_TRY(gemm(dgt, 0, view(w[P_W_IH] + E, E + F), 0, view(dZ, F), none, nullptr, nullptr,
@@ -682,7 +530,7 @@ static int backward(const Plan& p, const float* const* w, float* const* gr, floa
   // embedding: dX_emb = dG . W_ih[:, :E], summed by token id (no padding row)
   MILAN_TRY(gemm(view(G, 4 * H), 0, view(w[P_W_IH], E + F), 0, view(ws + p.dxe, E), none,
                  nullptr, nullptr, N, E, 4 * H, sc, s));
-  lmt::launch_embed_grad(ids, ws + p.dxe, N, E, V, -1, gr[P_EMB], s);
+  launch_embed_grad(ids, ws + p.dxe, N, E, V, -1, gr[P_EMB], s);
   // init_h / init_c from dh_0 / dc_0
   hipLaunchKernelGGL(init_bwd_kernel, dim3(blocks_for((long)rows * H)), dim3(256), 0, s, Hs,
                      ws + p.cst, dh, dc, ws + p.dph, ws + p.dpc, rows, L, H);
@@ -740,7 +588,7 @@ int milan_decoder_train_step(milan_ctx* c, const float* const* params, float* co
   MILAN_TRY(check_params((const void* const*)params, n_params, "parameter"));
   MILAN_TRY(check_params((const void* const*)grads, n_params, "gradient"));
   const uint32_t thr = drop_threshold(dropout);
-  const float scale = dropout > 0.f ? 1.f / (1.f - dropout) : 1.f;
+  const float scale = drop_scale(dropout);
   const hipStream_t s = (hipStream_t)stream;
   MILAN_TRY(forward(p, params, (float*)ws, features, targets, thr, scale, seed, loss_terms, s));
   return backward(p, params, grads, (float*)ws, features, targets, thr, scale, seed,
@@ -768,12 +616,11 @@ int milan_decoder_forward_train(milan_ctx* c, const float* const* params, int n_
                 "milan_decoder_forward_train: workspace %zu < %zu bytes", ws_bytes, p.grad_total);
   MILAN_TRY(check_params((const void* const*)params, n_params, "parameter"));
   const uint32_t thr = drop_threshold(dropout);
-  const float scale = dropout > 0.f ? 1.f / (1.f - dropout) : 1.f;
+  const float scale = drop_scale(dropout);
   const hipStream_t s = (hipStream_t)stream;
   float* w = (float*)ws;
   MILAN_TRY(forward(p, params, w, features, targets, thr, scale, seed, w + p.terms, s));
-  hipLaunchKernelGGL(log_softmax_kernel, dim3(blocks_for((long)p.N * p.V)), dim3(256), 0, s,
-                     w + p.logits, w + p.lse, logprobs_out, p.N, p.V);
+  launch_logprobs(w + p.logits, w + p.lse, logprobs_out, p.N, p.V, s);
   MILAN_CHECK_HIP(hipGetLastError());
   MILAN_CHECK_HIP(hipMemcpyAsync(attentions_out, w + p.alpha, (size_t)p.N * k * sizeof(float),
                                  hipMemcpyDeviceToDevice, s));
@@ -795,12 +642,11 @@ int milan_decoder_backward(milan_ctx* c, const float* const* params, float* cons
   MILAN_TRY(check_params((const void* const*)params, n_params, "parameter"));
   MILAN_TRY(check_params((const void* const*)grads, n_params, "gradient"));
   const uint32_t thr = drop_threshold(dropout);
-  const float scale = dropout > 0.f ? 1.f / (1.f - dropout) : 1.f;
+  const float scale = drop_scale(dropout);
   const hipStream_t s = (hipStream_t)stream;
   float* w = (float*)ws;
   // dlogits into the logits buffer, where backward() expects them
-  hipLaunchKernelGGL(log_softmax_bwd_kernel, dim3(p.N), dim3(256), 0, s, dlogprobs, w + p.logits,
-                     w + p.lse, p.V);
+  launch_log_softmax_bwd(dlogprobs, nullptr, nullptr, w + p.logits, w + p.lse, p.N, p.V, s);
   MILAN_CHECK_HIP(hipGetLastError());
   const Upstream up{dattentions, dfeatures ? w + p.dctx : nullptr};
   MILAN_TRY(backward(p, params, grads, w, features, targets, thr, scale, seed, 0.f, nullptr, &up,

@@ -1,24 +1,18 @@
 // What the transformer towers share (clip.hip, bert.hip, vit.hip): the wave reductions and
 // the LayerNorm row as device inlines, the row kernels and the LDS attention kernel behind
 // host launchers, and the weight store of a tower context.  Kernels and the store are defined
-// once, in tower.hip.  Each tower keeps its own block walk and workspace plan.
+// once, in tower.hip.  Each tower keeps its own block walk and workspace plan.  The towers'
+// contraction is the strided exact-fp32 GEMM of tgemm.h; the wave reductions are wave.h's.
 #pragma once
-#include "train_common.h"
+#include "tgemm.h"
+#include "wave.h"
 
 namespace milan {
 namespace tower {
 
 // ---- device inlines ---------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+using wave::wave_max;
+using wave::wave_sum;
 
 // Two-pass LayerNorm of one row held by one wave (mean, then the centred second moment, as
 // torch's CPU kernel); `in(j)` gives element j.

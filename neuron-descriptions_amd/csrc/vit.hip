@@ -2,10 +2,10 @@
 // taps on blocks.N.mlp.fc1, and the streaming attention it needs.
 //
 // A context of its own (milan_vit_ctx): dims + one weight arena in DINO's state-dict layout,
-// row-major as torch stores it.  Every contraction goes through lmt::gemm_rows (split count a
-// function of K alone) and attention works per (sequence, head), so an image's taps do not
-// depend on the other images of the call.  LayerNorm, the erf GELU, the patch gather and the
-// weight store are the towers' shared parts (tower.hip).
+// row-major as torch stores it.  Every contraction goes through tgemm::gemm_rows (tgemm.h;
+// split count a function of K alone) and attention works per (sequence, head), so an image's
+// taps do not depend on the other images of the call.  LayerNorm, the erf GELU, the patch
+// gather and the weight store are the towers' shared parts (tower.hip).
 //
 // Attention (attention_kernel): the towers' shared kernel holds Q, K, V of a whole head in LDS,
 // which ends near 64 tokens.  Here a workgroup owns 128 query rows of one (sequence, head), 32 per
@@ -44,9 +44,9 @@ struct milan_vit_ctx {
 namespace milan {
 namespace vit {
 
-using lmt::Scratch;
-using lmt::View;
-using lmt::view;
+using tgemm::Scratch;
+using tgemm::View;
+using tgemm::view;
 using namespace milan::tower;
 
 typedef float v16f __attribute__((ext_vector_type(16)));
@@ -302,11 +302,11 @@ static int plan(const milan_vit_ctx* c, int n, Plan* p) {
   p->y = o; o += up64((size_t)M * W);
   const size_t front = up64((size_t)np * kk) + up64((size_t)np * W);
   p->big = o; o += std::max(up64((size_t)M * wide), front);
-  p->scratch_floats = std::max({lmt::rows_scratch_floats((int)np, W, kk),
-                                lmt::rows_scratch_floats((int)M, 3 * W, W),
-                                lmt::rows_scratch_floats((int)M, W, W),
-                                lmt::rows_scratch_floats((int)M, H, W),
-                                lmt::rows_scratch_floats((int)M, W, H)});
+  p->scratch_floats = std::max({tgemm::rows_scratch_floats((int)np, W, kk),
+                                tgemm::rows_scratch_floats((int)M, 3 * W, W),
+                                tgemm::rows_scratch_floats((int)M, W, W),
+                                tgemm::rows_scratch_floats((int)M, H, W),
+                                tgemm::rows_scratch_floats((int)M, W, H)});
   p->scratch = o; o += up64(p->scratch_floats);
   p->total_floats = o;
   return 0;
@@ -424,7 +424,7 @@ int milan_vit_run(milan_vit_ctx* c, const float* images, int n, int resolution,
   float* patches = big;
   float* pe = patches + up64((size_t)np * kk);
   MILAN_TRY(launch_patch_gather(images, patches, n, d.resolution, d.patch, nullptr, s));
-  MILAN_TRY(lmt::gemm_rows(view(patches, kk), 0, view(c->conv_w, kk), 1, view(pe, W), none,
+  MILAN_TRY(tgemm::gemm_rows(view(patches, kk), 0, view(c->conv_w, kk), 1, view(pe, W), none,
                            c->conv_b, nullptr, np, W, kk, sc, s));
   hipLaunchKernelGGL(embed_tokens_kernel, dim3(blocks_for((long)M * W)), dim3(256), 0, s, pe,
                      c->cls, c->pos, x, (long)M * W, T, W);
@@ -432,25 +432,25 @@ int milan_vit_run(milan_vit_ctx* c, const float* images, int n, int resolution,
   for (int l = 0; l <= last; ++l) {
     const auto& b = c->blocks[l];
     MILAN_TRY(launch_layernorm_rows(x, W, y, M, W, b.ln1_w, b.ln1_b, d.eps, s));
-    MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.qkv_w, W), 1, view(big, 3 * W), none, b.qkv_b,
+    MILAN_TRY(tgemm::gemm_rows(view(y, W), 0, view(b.qkv_w, W), 1, view(big, 3 * W), none, b.qkv_b,
                              nullptr, M, 3 * W, W, sc, s));
     MILAN_TRY(launch_attention(big, y, n, T, W, d.heads, s));
-    MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.proj_w, W), 1, view(x, W), view(x, W),
+    MILAN_TRY(tgemm::gemm_rows(view(y, W), 0, view(b.proj_w, W), 1, view(x, W), view(x, W),
                              b.proj_b, nullptr, M, W, W, sc, s));
     MILAN_TRY(launch_layernorm_rows(x, W, y, M, W, b.ln2_w, b.ln2_b, d.eps, s));
     float* tap = taps ? taps[l] : nullptr;
     if (l == last && !cls_out) {  // the deepest tap: fc1 writes it, and the walk is over
-      MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.fc1_w, W), 1, view(tap, H), none, b.fc1_b,
+      MILAN_TRY(tgemm::gemm_rows(view(y, W), 0, view(b.fc1_w, W), 1, view(tap, H), none, b.fc1_b,
                                nullptr, M, H, W, sc, s));
       break;
     }
-    MILAN_TRY(lmt::gemm_rows(view(y, W), 0, view(b.fc1_w, W), 1, view(big, H), none, b.fc1_b,
+    MILAN_TRY(tgemm::gemm_rows(view(y, W), 0, view(b.fc1_w, W), 1, view(big, H), none, b.fc1_b,
                              nullptr, M, H, W, sc, s));
     if (tap)
       MILAN_CHECK_HIP(hipMemcpyAsync(tap, big, (size_t)M * H * sizeof(float),
                                      hipMemcpyDeviceToDevice, s));
     MILAN_TRY(launch_gelu_erf(big, (long)M * H, s));
-    MILAN_TRY(lmt::gemm_rows(view(big, H), 0, view(b.fc2_w, H), 1, view(x, W), view(x, W),
+    MILAN_TRY(tgemm::gemm_rows(view(big, H), 0, view(b.fc2_w, H), 1, view(x, W), view(x, W),
                              b.fc2_b, nullptr, M, W, H, sc, s));
   }
   if (cls_out)

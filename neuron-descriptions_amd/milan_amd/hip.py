@@ -1333,28 +1333,44 @@ class Context:
 
         return self._guarded('lm_logprobs', run, check, decoder=True)
 
-    # -- LanguageModel training (include/milan_hip.h, milan_lm_train_step) --
-    def _lm_train_call(self, params, inputs, targets):
-        rows, length = inputs.shape
-        if targets.shape != inputs.shape:
-            raise ValueError(f'targets {tuple(targets.shape)} != inputs '
-                             f'{tuple(inputs.shape)}')
+    # -- what the LM and decoder training calls share --
+    def _f32_ptrs(self, tensors, expected, what, like=None):
+        """`tensors` (`what`: 'LM parameters', 'gradients', ...) as an array
+        of pointers, once there are `expected` of them and each is contiguous
+        float32 on this device (and shaped as its partner in `like`, when
+        given)."""
+        if len(tensors) != expected:
+            raise ValueError(f'{len(tensors)} {what}, expected {expected}')
+        for i, t in enumerate(tensors):
+            if (t.device != self.device or t.dtype != torch.float32
+                    or not t.is_contiguous()
+                    or (like is not None and t.shape != like[i].shape)):
+                raise ValueError(
+                    f'{what} must be contiguous float32 on {self.device}' +
+                    ('' if like is None else ', shaped like the parameters'))
+        return (_P * len(tensors))(*[t.data_ptr() for t in tensors])
+
+    def _grad_ptrs(self, params, grads):
+        return self._f32_ptrs(grads, len(params), 'gradients', like=params)
+
+    def _check_ids(self, name, ids):
         v = self.dims.vocab_size
-        for name, ids in (('inputs', inputs), ('targets', targets)):
-            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= v):
-                raise ValueError(f'{name} hold ids outside [0, {v})')
-        if len(params) != 3 + 4 * self.dims.lm_layers:
-            raise ValueError(f'{len(params)} parameters, expected '
-                             f'{3 + 4 * self.dims.lm_layers}')
-        for p in params:
-            if (p.device != self.device or p.dtype != torch.float32
-                    or not p.is_contiguous()):
-                raise ValueError('LM parameters must be contiguous float32 on '
-                                 f'{self.device}')
-        inputs = _dev(inputs, self.device, torch.long)
-        targets = _dev(targets, self.device, torch.long)
-        need = int(self.lib.milan_lm_train_workspace_bytes(self._h, rows,
-                                                           length))
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= v):
+            raise ValueError(f'{name} hold ids outside [0, {v})')
+
+    def _check_upstream(self, wanted):
+        """`wanted`: (upstream gradient or None, the shape it must have)."""
+        for t, shape in wanted:
+            if t is not None and (tuple(t.shape) != shape
+                                  or t.device != self.device
+                                  or t.dtype != torch.float32
+                                  or not t.is_contiguous()):
+                raise ValueError(f'gradient {tuple(t.shape)} must be a '
+                                 f'contiguous float32 {shape} on {self.device}')
+
+    def _train_workspace(self, need):
+        """The context's training workspace, grown to `need` bytes (0: the
+        library refused the shape)."""
         if need == 0:
             _check(ERR_SHAPE)
         ws = getattr(self, '_train_ws', None)
@@ -1362,7 +1378,23 @@ class Context:
             self._train_ws = None
             ws = self._train_ws = torch.empty(need, dtype=torch.uint8,
                                               device=self.device)
-        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
+        return ws
+
+    # -- LanguageModel training (include/milan_hip.h, milan_lm_train_step) --
+    def _lm_train_call(self, params, inputs, targets):
+        rows, length = inputs.shape
+        if targets.shape != inputs.shape:
+            raise ValueError(f'targets {tuple(targets.shape)} != inputs '
+                             f'{tuple(inputs.shape)}')
+        self._check_ids('inputs', inputs)
+        self._check_ids('targets', targets)
+        ptrs = self._f32_ptrs(params, 3 + 4 * self.dims.lm_layers,
+                              'LM parameters')
+        inputs = _dev(inputs, self.device, torch.long)
+        targets = _dev(targets, self.device, torch.long)
+        ws = self._train_workspace(
+            int(self.lib.milan_lm_train_workspace_bytes(self._h, rows,
+                                                        length)))
         loss = torch.empty(2, device=self.device)
         return inputs, targets, ptrs, ws, loss
 
@@ -1390,15 +1422,7 @@ class Context:
         and shapes as `params`).  Does not synchronise."""
         inputs, targets, ptrs, ws, loss = self._lm_train_call(
             params, inputs, targets)
-        for p, g in zip(params, grads):
-            if (g.shape != p.shape or g.device != self.device
-                    or g.dtype != torch.float32 or not g.is_contiguous()):
-                raise ValueError('gradients must be contiguous float32 '
-                                 'tensors shaped like the parameters')
-        if len(grads) != len(params):
-            raise ValueError(f'{len(grads)} gradients for {len(params)} '
-                             'parameters')
-        gptrs = (_P * len(grads))(*[g.data_ptr() for g in grads])
+        gptrs = self._grad_ptrs(params, grads)
         with torch.cuda.device(self.device):
             _check(
                 self.lib.milan_lm_train_step(
@@ -1422,20 +1446,11 @@ class Context:
         if targets is not None and targets.shape != inputs.shape:
             raise ValueError(f'targets {tuple(targets.shape)} != inputs '
                              f'{tuple(inputs.shape)}')
-        v = self.dims.vocab_size
         for name, ids in (('inputs', inputs), ('targets', targets)):
-            if not check_ids or ids is None or not ids.numel():
-                continue  # (the backward takes what its forward checked)
-            if int(ids.min()) < 0 or int(ids.max()) >= v:
-                raise ValueError(f'{name} hold ids outside [0, {v})')
-        if len(params) != 3 + 4 * self.dims.lm_layers:
-            raise ValueError(f'{len(params)} parameters, expected '
-                             f'{3 + 4 * self.dims.lm_layers}')
-        for p in params:
-            if (p.device != self.device or p.dtype != torch.float32
-                    or not p.is_contiguous()):
-                raise ValueError('LM parameters must be contiguous float32 on '
-                                 f'{self.device}')
+            if check_ids and ids is not None:
+                self._check_ids(name, ids)  # (the backward takes its forward's)
+        ptrs = self._f32_ptrs(params, 3 + 4 * self.dims.lm_layers,
+                              'LM parameters')
         inputs = _dev(inputs, self.device, torch.long)
         if targets is not None:
             targets = _dev(targets, self.device, torch.long)
@@ -1443,7 +1458,6 @@ class Context:
             self._h, inputs.shape[0], inputs.shape[1]))
         if need == 0:
             _check(ERR_SHAPE)
-        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
         return inputs, targets, ptrs, need
 
     def lm_forward_train(self, params, inputs: torch.Tensor,
@@ -1495,19 +1509,13 @@ class Context:
         inputs, targets, ptrs, need = self._lm_grad_args(params, inputs,
                                                          targets, False)
         rows, length = inputs.shape
-        shapes = ((dlogprobs, (rows, length, self.dims.vocab_size)),
-                  (dpicked, (rows, length)))
-        for t, shape in shapes:
-            if t is not None and (tuple(t.shape) != shape
-                                  or t.device != self.device
-                                  or t.dtype != torch.float32
-                                  or not t.is_contiguous()):
-                raise ValueError(f'gradient {tuple(t.shape)} must be a '
-                                 f'contiguous float32 {shape} on {self.device}')
+        self._check_upstream(
+            ((dlogprobs, (rows, length, self.dims.vocab_size)),
+             (dpicked, (rows, length))))
         if ws.numel() < need:
             raise ValueError('workspace does not come from lm_forward_train '
                              'at these dims')
-        gptrs = self._decoder_grads(params, grads)
+        gptrs = self._grad_ptrs(params, grads)
         with torch.cuda.device(self.device):
             _check(
                 self.lib.milan_lm_backward(
@@ -1532,47 +1540,20 @@ class Context:
         if f != self.dims.feature_size:
             raise ValueError(f'feature size {f} != the decoder\'s '
                              f'{self.dims.feature_size}')
-        v = self.dims.vocab_size
-        if targets.numel() and (int(targets.min()) < 0 or
-                                int(targets.max()) >= v):
-            raise ValueError(f'targets hold ids outside [0, {v})')
-        if len(params) != self.DECODER_TRAIN_PARAMS:
-            raise ValueError(f'{len(params)} parameters, expected '
-                             f'{self.DECODER_TRAIN_PARAMS}')
-        for p in params:
-            if (p.device != self.device or p.dtype != torch.float32
-                    or not p.is_contiguous()):
-                raise ValueError('decoder parameters must be contiguous '
-                                 f'float32 on {self.device}')
+        self._check_ids('targets', targets)
+        ptrs = self._f32_ptrs(params, self.DECODER_TRAIN_PARAMS,
+                              'decoder parameters')
         features = _dev(features, self.device, torch.float32)
         targets = _dev(targets, self.device, torch.long)
-        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
         return features, targets, ptrs
-
-    def _decoder_grads(self, params, grads):
-        if len(grads) != len(params):
-            raise ValueError(f'{len(grads)} gradients for {len(params)} '
-                             'parameters')
-        for p, g in zip(params, grads):
-            if (g.shape != p.shape or g.device != self.device
-                    or g.dtype != torch.float32 or not g.is_contiguous()):
-                raise ValueError('gradients must be contiguous float32 '
-                                 'tensors shaped like the parameters')
-        return (_P * len(grads))(*[g.data_ptr() for g in grads])
 
     def _decoder_train_call(self, params, features, targets):
         features, targets, ptrs = self._decoder_args(params, features,
                                                      targets)
         rows, k, _ = features.shape
-        need = int(self.lib.milan_decoder_train_workspace_bytes(
-            self._h, rows, k, targets.shape[1]))
-        if need == 0:
-            _check(ERR_SHAPE)
-        ws = getattr(self, '_train_ws', None)
-        if ws is None or ws.numel() < need:
-            self._train_ws = None
-            ws = self._train_ws = torch.empty(need, dtype=torch.uint8,
-                                              device=self.device)
+        ws = self._train_workspace(
+            int(self.lib.milan_decoder_train_workspace_bytes(
+                self._h, rows, k, targets.shape[1])))
         loss = torch.empty(3, device=self.device)
         return features, targets, ptrs, ws, loss
 
@@ -1604,7 +1585,7 @@ class Context:
         `params`).  Does not synchronise."""
         features, targets, ptrs, ws, loss = self._decoder_train_call(
             params, features, targets)
-        gptrs = self._decoder_grads(params, grads)
+        gptrs = self._grad_ptrs(params, grads)
         with torch.cuda.device(self.device):
             _check(
                 self.lib.milan_decoder_train_step(
@@ -1657,27 +1638,19 @@ class Context:
         feature gradient into `dfeatures` (None: not computed).  Consumes
         `ws`: a second backward from the same workspace is wrong.  Does not
         synchronise."""
-        if len(params) != self.DECODER_TRAIN_PARAMS:
-            raise ValueError(f'{len(params)} parameters, expected '
-                             f'{self.DECODER_TRAIN_PARAMS}')
+        ptrs = self._f32_ptrs(params, self.DECODER_TRAIN_PARAMS,
+                              'decoder parameters')
         rows, k, f = features.shape
         length = targets.shape[1]
-        shapes = ((dlogprobs, (rows, length, self.dims.vocab_size)),
-                  (dattentions, (rows, length, k)), (dfeatures, (rows, k, f)))
-        for t, shape in shapes:
-            if t is not None and (tuple(t.shape) != shape
-                                  or t.device != self.device
-                                  or t.dtype != torch.float32
-                                  or not t.is_contiguous()):
-                raise ValueError(f'gradient {tuple(t.shape)} must be a '
-                                 f'contiguous float32 {shape} on {self.device}')
+        self._check_upstream(
+            ((dlogprobs, (rows, length, self.dims.vocab_size)),
+             (dattentions, (rows, length, k)), (dfeatures, (rows, k, f))))
         need = int(self.lib.milan_decoder_grad_workspace_bytes(
             self._h, rows, k, length))
         if need == 0 or ws.numel() < need:
             raise ValueError('workspace does not come from decoder_forward_train '
                              'at these dims')
-        ptrs = (_P * len(params))(*[p.data_ptr() for p in params])
-        gptrs = self._decoder_grads(params, grads)
+        gptrs = self._grad_ptrs(params, grads)
         with torch.cuda.device(self.device):
             _check(
                 self.lib.milan_decoder_backward(

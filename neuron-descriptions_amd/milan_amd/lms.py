@@ -41,12 +41,12 @@ from torch.utils import data
 from milan_amd import hip, lang, params, training
 
 
-def dropout_mask(seed: int, layer: int, rows: int, length: int, units: int,
-                 p: float) -> torch.Tensor:
-    """Host restatement of the training kernels' dropout mask on the output of
-    LSTM layer `layer`: (rows, length, units) bool, True = kept (kept values
-    are scaled by 1 / (1 - p)).  A pure function of (seed, layer, row, t,
-    unit); see milan_lm_train_step in include/milan_hip.h."""
+def tagged_dropout_mask(seed: int, tag: int, rows: int, length: int,
+                        units: int, p: float) -> torch.Tensor:
+    """Host restatement of the training kernels' dropout mask (`keep` in
+    csrc/train_common.h): (rows, length, units) bool, True = kept (kept values
+    are scaled by 1 / (1 - p)).  A pure function of (seed, tag, row, t, unit);
+    the tag tells the LM's layers and the decoder apart."""
     m64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
     def mix64(z):
@@ -61,24 +61,30 @@ def dropout_mask(seed: int, layer: int, rows: int, length: int, units: int,
     b = np.arange(rows, dtype=np.uint64)[:, None, None]
     t = np.arange(length, dtype=np.uint64)[None, :, None]
     j = np.arange(units, dtype=np.uint64)[None, None, :]
-    key = ((np.uint64(layer) << np.uint64(56)) | (b << np.uint64(32)) |
+    key = ((np.uint64(tag) << np.uint64(56)) | (b << np.uint64(32)) |
            (t << np.uint64(16)) | j)
     z = mix64(np.uint64(seed & 0xFFFFFFFFFFFFFFFF) ^ mix64(key))
     threshold = int(float(np.float32(p)) * 16777216.0)
     return torch.from_numpy((z >> np.uint64(40)) >= np.uint64(threshold))
 
 
-
 DECODER_DROPOUT_TAG = 0xDC  # the decoder's mask, never one of the LM's layers
+
+
+def dropout_mask(seed: int, layer: int, rows: int, length: int, units: int,
+                 p: float) -> torch.Tensor:
+    """The mask on the output of LSTM layer `layer` of the LM (tag = layer);
+    see milan_lm_train_step in include/milan_hip.h."""
+    return tagged_dropout_mask(seed, layer, rows, length, units, p)
 
 
 def decoder_dropout_mask(seed: int, rows: int, length: int, units: int,
                          p: float) -> torch.Tensor:
-    """Host restatement of the decoder training kernel's dropout mask on h
-    before the output Linear: (rows, length, units) bool, True = kept.  The
-    LM's hash with the tag 0xDC in place of the layer; see
+    """The mask on the decoder's h before the output Linear (tag 0xDC); see
     milan_decoder_train_step in include/milan_hip.h."""
-    return dropout_mask(seed, DECODER_DROPOUT_TAG, rows, length, units, p)
+    return tagged_dropout_mask(seed, DECODER_DROPOUT_TAG, rows, length, units,
+                               p)
+
 
 class _SequenceDataset(data.Dataset):
     """The annotations of a dataset, one sample per sequence (a sample's

@@ -12,7 +12,7 @@ reduced-precision matmul mode for the latter).  tests/test_train_ref_host.py
 pins them to the reference's own autograd on the CPU.
 
 Also here: the split planner of the shared GEMM and the column-sum chunking,
-restated from lm_train.hip, and the (M, N, K) of every GEMM each training call
+restated from tgemm.hip, and the (M, N, K) of every GEMM each training call
 runs, so that the tests can say which branches a shape reaches.
 """
 import contextlib
@@ -137,8 +137,8 @@ def fp32_reference():
 
 
 # ---- the branches a shape reaches ------------------------------------------------
-# Restated from neuron-descriptions_amd/csrc/lm_train.hip: plan_splits (:151-162) and
-# colsum_chunks (:359-362), with the tile sizes BM = BN = 64, BK = 32 (:42).  The two
+# Restated from neuron-descriptions_amd/csrc/tgemm.hip: plan_splits (:134-145) and
+# colsum_chunks (:233-236), with the tile sizes BM = BN = 64, BK = 32 (:25).  The two
 # must move together: if the planner changes there, change it here, or the edge
 # table of test_gpu_train_fuzz.py no longer provably reaches the branches it names.
 BM = BN = 64

@@ -71,10 +71,14 @@ enum {
   MILAN_TRUNK_ALEXNET = 2,    /* taps features.0/3/6/8/10, F = 18 * width      */
   MILAN_TRUNK_NONE = 3,       /* decoder-only context (a foreign `Encoder`):
                                  any feature_size % 4 == 0, trunk_* ignored   */
-  MILAN_TRUNK_ALEXNET_PLACES = 4 /* the Places365 AlexNet: conv1..conv5 with grouped
+  MILAN_TRUNK_ALEXNET_PLACES = 4, /* the Places365 AlexNet: conv1..conv5 with grouped
                                  convs, width / 32 x (96, 256, 384, 384, 256) channels,
                                  F = 43 * width.  Classify / ablate / activations
                                  only: the encoder entry points refuse it      */
+  MILAN_TRUNK_VGG = 5         /* torchvision's VGG-11/13/16/19 without batch norm: five
+                                 blocks of 3x3 convs, width x (1, 2, 4, 8, 8) channels,
+                                 F = 23 * width; the block structure follows from the
+                                 uploaded keys.  Classify / ablate / activations only   */
 };
 typedef struct milan_dims {
   int32_t trunk_width;      /* 64 for the torchvision models                */
@@ -282,6 +286,40 @@ int milan_linear_rowwise(const float* x, const float* weight, const float* bias,
 int milan_set_alexnet_lrn(milan_ctx* ctx, int local_size, float alpha, float beta);
 int milan_lrn(const float* x, long long pixels, int channels, int split, int local_size,
               float alpha, float beta, float* y, unsigned* status, milan_stream stream);
+
+/* The same calls on torchvision's VGG-11 / 13 / 16 / 19 without batch norm (MILAN_TRUNK_VGG):
+ * five blocks of 3x3 / pad 1 / stride 1 convs with bias and ReLU, a 2x2 / 2 max-pool after each
+ * block, AdaptiveAvgPool2d((7, 7)), flatten in (C, h, w) order and three Linear layers with ReLU
+ * after the first two (dropout is the identity).  milan_dims::trunk_blocks has four entries and
+ * a VGG five blocks, so the structure follows from the uploaded keys: `<prefix>vgg.B.J.weight` /
+ * `.bias` with block B = 1..5 and conv J = 0..3, contiguous from 0, one to four convs per
+ * block (the caller renames torchvision's `features.N`).  Block B has width x min(2^(B-1), 8)
+ * output channels, width a multiple of 8; anything else is MILAN_ERR_SHAPE at
+ * milan_finalize_weights.
+ *   Levels 0..4 are the last conv of blocks 1..5 (the reference's LAYERS.VGG11 .. VGG19) with
+ * the AlexNet semantics above: relu(conv + bias) x mask, which is what the pool reads and what
+ * milan_activations hands out; a zero is handed out as +0.  Every extent is floor(x / 2) per
+ * pool: reaching level l needs H, W >= 2^l, a classify call H, W >= 32 (MILAN_ERR_SHAPE before
+ * anything is launched).  In MILAN_PRECISION_SPLIT_F16 a conv multiplies split operands when its
+ * input width is a multiple of 32 and its input was written in split format (by a pool, by the
+ * first conv's kernel or by a split conv); the others run in exact fp32.  The tail and the
+ * Linear layers are exact fp32 in both modes, each adaptive-pool bin summed from zero in
+ * row-major order and divided by its count.  A headless context taps and ablates; classifying
+ * without a head is MILAN_ERR_STATE.  MILAN_PRECISION_F16 and the milan_encode* calls:
+ * MILAN_ERR_ARG.
+ *   milan_set_vgg_head  milan_set_alexnet_head's contract for classifier.0 / .3 / .6; fc0_in
+ *     must be C5 x 49.  On a context of another kind, and milan_set_alexnet_head on this one:
+ *     MILAN_ERR_ARG.
+ *   milan_vgg_trace  what the walks of the context's last classify / classify_sweep /
+ *     activations call did, per conv slot 4 (B - 1) + J (HOST arrays of 20 entries):
+ *     launches[slot] = how often the conv was launched, split[slot] = 1 when its last launch
+ *     multiplied split operands.  Either may be NULL.
+ * MILAN_ABI_VERSION did not change with these entry points: probe for them. */
+int milan_set_vgg_head(milan_ctx* ctx, const float* fc0_weight, const float* fc0_bias,
+                       int fc0_out, int fc0_in, const float* fc3_weight, const float* fc3_bias,
+                       int fc3_out, int fc3_in, const float* fc6_weight, const float* fc6_bias,
+                       int fc6_out, int fc6_in, milan_stream stream);
+int milan_vgg_trace(const milan_ctx* ctx, int32_t* launches, int32_t* split);
 
 /* Decoder.init_state (src/milan/decoders.py:548-574).
  * features (n,k,F) -> h,c (n,hidden). */

@@ -134,7 +134,7 @@ int milan_create(milan_ctx** out, int device, const milan_dims* dims) {
   MILAN_REQUIRE(out && dims, MILAN_ERR_ARG, "milan_create: null argument");
   const milan_dims& d = *dims;
   MILAN_REQUIRE(d.trunk_kind >= MILAN_TRUNK_BOTTLENECK &&
-                    d.trunk_kind <= MILAN_TRUNK_ALEXNET_PLACES,
+                    d.trunk_kind <= MILAN_TRUNK_VGG,
                 MILAN_ERR_ARG, "unknown trunk_kind %d", d.trunk_kind);
   if (d.trunk_kind == MILAN_TRUNK_NONE) {
     // features come from a foreign Encoder: only the decoder's GEMM alignment
@@ -147,12 +147,14 @@ int milan_create(milan_ctx** out, int device, const milan_dims* dims) {
     const int fmul = d.trunk_kind == MILAN_TRUNK_BOTTLENECK       ? 61
                      : d.trunk_kind == MILAN_TRUNK_BASIC          ? 16
                      : d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES ? 43
+                     : d.trunk_kind == MILAN_TRUNK_VGG            ? 23
                                                                   : 18;
     MILAN_REQUIRE(d.feature_size == fmul * d.trunk_width, MILAN_ERR_SHAPE,
                   "feature_size %d != %d * trunk_width (pyramid of five taps, "
                   "trunk_kind %d)", d.feature_size, fmul, d.trunk_kind);
     for (int i = 0; i < 4 && d.trunk_kind != MILAN_TRUNK_ALEXNET &&
-                    d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES; ++i)
+                    d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES &&
+                    d.trunk_kind != MILAN_TRUNK_VGG; ++i)
       MILAN_REQUIRE(d.trunk_blocks[i] > 0, MILAN_ERR_SHAPE, "bad trunk_blocks");
   }
   MILAN_REQUIRE(d.hidden_size > 0 && d.hidden_size % 4 == 0 &&
@@ -398,6 +400,30 @@ int milan_set_alexnet_head(milan_ctx* c, const float* fc6_weight, const float* f
   const float* b[3] = {fc6_bias, fc7_bias, linear8_bias};
   const int out[3] = {fc6_out, fc7_out, linear8_out}, in[3] = {fc6_in, fc7_in, linear8_in};
   return classify_set_alexnet_head(c, w, b, out, in, (hipStream_t)stream);
+}
+
+int milan_set_vgg_head(milan_ctx* c, const float* fc0_weight, const float* fc0_bias, int fc0_out,
+                       int fc0_in, const float* fc3_weight, const float* fc3_bias, int fc3_out,
+                       int fc3_in, const float* fc6_weight, const float* fc6_bias, int fc6_out,
+                       int fc6_in, milan_stream stream) {
+  MILAN_REQUIRE(c && fc0_weight && fc0_bias && fc3_weight && fc3_bias && fc6_weight && fc6_bias,
+                MILAN_ERR_ARG, "milan_set_vgg_head: null argument");
+  MILAN_REQUIRE(c->finalized, MILAN_ERR_STATE, "weights not finalized");
+  MILAN_CHECK_HIP(hipSetDevice(c->device));
+  const float* w[3] = {fc0_weight, fc3_weight, fc6_weight};
+  const float* b[3] = {fc0_bias, fc3_bias, fc6_bias};
+  const int out[3] = {fc0_out, fc3_out, fc6_out}, in[3] = {fc0_in, fc3_in, fc6_in};
+  return classify_set_vgg_head(c, w, b, out, in, (hipStream_t)stream);
+}
+
+int milan_vgg_trace(const milan_ctx* c, int32_t* launches, int32_t* split) {
+  MILAN_REQUIRE(c && c->d.trunk_kind == MILAN_TRUNK_VGG, MILAN_ERR_ARG,
+                "milan_vgg_trace: the context's trunk is not a VGG");
+  for (int i = 0; i < 20; ++i) {
+    if (launches) launches[i] = c->vgg_launches[i];
+    if (split) split[i] = c->vgg_split[i];
+  }
+  return 0;
 }
 
 int milan_set_alexnet_lrn(milan_ctx* c, int local_size, float alpha, float beta) {

@@ -28,6 +28,12 @@ typedef float cf32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned cu32x4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 cf16x8_t __attribute__((ext_vector_type(8)));
 
+// workgroups of 256 threads for a grid-stride loop over `items`
+static int grid_for(long items) {
+  const long b = (items + 255) / 256;
+  return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
+}
+
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
@@ -251,6 +257,269 @@ __global__ __launch_bounds__(256) void alex_tail_kernel(const float* __restrict_
       sum += best;
     }
   out[img * (size_t)C * 36 + (size_t)c * 36 + bin] = sum / (float)((r1 - r0) * (q1 - q0));
+}
+
+// ---------------------------------------------------------------------------
+// VGG: the first conv, the 2x2 pool and the tail of the trunk
+// ---------------------------------------------------------------------------
+// conv1_1's weight (cout, 3, 3, 3) OIHW -> (27, cout), row k = (kh * 3 + kw) * 3 + c
+__global__ void vgg_pack_first_kernel(const float* __restrict__ w, int cout,
+                                      float* __restrict__ out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 27 * cout) return;
+  const int o = idx % cout, k = idx / cout;
+  const int c = k % 3, t = k / 3;   // t = kh * 3 + kw
+  out[idx] = w[(o * 3 + c) * 9 + t];
+}
+
+int vgg_pack_first(const float* w_oihw, int cout, float* w27, hipStream_t s) {
+  hipLaunchKernelGGL(vgg_pack_first_kernel, dim3((27 * cout + 255) / 256), dim3(256), 0, s,
+                     w_oihw, cout, w27);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// conv1_1 (3 -> C channels, 3x3, pad 1, stride 1) + bias + ReLU straight from the fp32 NCHW
+// image (n, 3, H, W) to NHWC (n, H, W, C): fp32, or OUT_SPLIT split groups [hi x8 | lo x8] at
+// scale 1.  A workgroup owns one output row of one image (grid = n H); a thread owns the
+// 8-channel piece g of two horizontally adjacent pixels, pieces fastest: consecutive lanes write
+// consecutive 32 bytes (two 16-byte stores per pixel) and read the same or neighbouring image
+// words, the 3 x 4 x 3 input words of a pair once each.  The 27 x C weights and the bias sit
+// in LDS (28 C floats); a lane reads its 8 weights of a tap as two 16-byte pieces, lanes of one
+// piece the same address, and uses them for both pixels.  Per output: acc from zero, acc =
+// fma(x, w, acc) over the taps in (kh, kw, c) ascending order -- a tap in the padding enters
+// with x = 0, which leaves acc as it is; two channels share one packed fma, every lane of it a
+// correctly rounded fma of its own -- then acc + bias, then max(., 0).  Neither the grid nor
+// the batch enters, nor which pixel of its pair an output is.
+// (The loop over kernel rows stays rolled: unrolled, the compiler issues all 54 weight reads of
+// a piece up front, 272 VGPRs and one wave per SIMD, and the loads' latency shows; rolled it is
+// 58 VGPRs.)
+typedef float cf32x2_t __attribute__((ext_vector_type(2)));
+template <bool OUT_SPLIT>
+__global__ __launch_bounds__(256) void vgg_first_kernel(const float* __restrict__ img, int H,
+                                                        int W, int C,
+                                                        const float* __restrict__ w27,
+                                                        const float* __restrict__ bias,
+                                                        float* __restrict__ y,
+                                                        unsigned* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) float vgg_w[];   // [27][C] | bias [C]
+  for (int i = threadIdx.x; i < 27 * C; i += blockDim.x) vgg_w[i] = w27[i];
+  for (int i = threadIdx.x; i < C; i += blockDim.x) vgg_w[27 * C + i] = bias[i];
+  __syncthreads();
+  const int C8 = C >> 3, items = ((W + 1) >> 1) * C8;
+  const size_t plane = (size_t)H * W;
+  const size_t row = blockIdx.x;   // image * H + y0
+  const int y0 = (int)(row % H);
+  const float* src = img + (row / H) * 3 * plane;
+  float* out_row = y + row * (size_t)W * C;
+  float sat = 0.f;
+  for (int i = threadIdx.x; i < items; i += blockDim.x) {
+    const int g = i % C8, x0 = 2 * (i / C8);
+    cf32x2_t acc[2][4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[p][e] = cf32x2_t{0.f, 0.f};
+#pragma unroll 1
+    for (int kh = 0; kh < 3; ++kh) {
+      const int iy = y0 + kh - 1;
+      const bool row_in = iy >= 0 && iy < H;
+      const float* line = src + (size_t)(row_in ? iy : y0) * W;
+      // columns x0 - 1 .. x0 + 2 of the three channels: clamped addresses, zeros outside
+      float v[3][4];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const int ix = x0 - 1 + d;
+        const bool in = row_in && ix >= 0 && ix < W;
+        const int ixc = ix < 0 ? 0 : (ix < W ? ix : W - 1);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const float t = line[ch * plane + ixc];
+          v[ch][d] = in ? t : 0.f;
+        }
+      }
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const float* wk = vgg_w + ((kh * 3 + kw) * 3 + ch) * C + g * 8;
+          const cf32x4_t w0 = *reinterpret_cast<const cf32x4_t*>(wk);
+          const cf32x4_t w1 = *reinterpret_cast<const cf32x4_t*>(wk + 4);
+          const cf32x2_t wp[4] = {{w0[0], w0[1]}, {w0[2], w0[3]}, {w1[0], w1[1]}, {w1[2], w1[3]}};
+#pragma unroll
+          for (int p = 0; p < 2; ++p) {
+            const cf32x2_t xx = {v[ch][kw + p], v[ch][kw + p]};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[p][e] = __builtin_elementwise_fma(xx, wp[e], acc[p][e]);
+          }
+        }
+    }
+    const float* bk = vgg_w + 27 * C + g * 8;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (x0 + p >= W) break;   // (the second pixel of the last pair of an odd row)
+      float r[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) r[e] = __fadd_rn(acc[p][e >> 1][e & 1], bk[e]);
+      float* dst = out_row + (size_t)(x0 + p) * C + g * 8;
+      if constexpr (OUT_SPLIT) {
+        cf32x4_t hi4, lo4;
+        split8_relu_rne(r, &hi4, &lo4, &sat);
+        *reinterpret_cast<cf32x4_t*>(dst) = hi4;
+        *reinterpret_cast<cf32x4_t*>(dst + 4) = lo4;
+      } else {
+        cf32x4_t o0, o1;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o0[e] = r[e] > 0.f ? r[e] : 0.f;
+          o1[e] = r[4 + e] > 0.f ? r[4 + e] : 0.f;
+        }
+        *reinterpret_cast<cf32x4_t*>(dst) = o0;
+        *reinterpret_cast<cf32x4_t*>(dst + 4) = o1;
+      }
+    }
+  }
+  if constexpr (OUT_SPLIT) report_saturation(status, sat);
+}
+
+// 2x2 / stride 2 max-pool without padding over NHWC, (n, H, W, C) -> (n, Ho, Wo, C) with
+// Ho = floor(H / 2), Wo = floor(W / 2): an odd last row or column is dropped, every window is
+// whole.  A thread owns one output pixel's piece of 8 channels: two 16-byte loads per input
+// pixel, two 16-byte stores.  fp32 -> fp32, fp32 -> split and split -> split at scale 1 (a
+// split value is float(hi) + float(lo)); the maximum starts at -inf and fmaxf drops a NaN, as
+// in the 3x3 / 2 pool of the AlexNets; saturation of the conversion goes to `status`.
+template <bool IN_SPLIT, bool OUT_SPLIT>
+__global__ __launch_bounds__(256) void maxpool2s2_kernel(const float* __restrict__ x, int H,
+                                                         int W, int C8, int Ho, int Wo,
+                                                         long total, float* __restrict__ y,
+                                                         unsigned* __restrict__ status) {
+  float sat = 0.f;
+  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
+       idx += (long)gridDim.x * blockDim.x) {
+    const int c8 = (int)(idx % C8);
+    long t = idx / C8;
+    const int wo = (int)(t % Wo); t /= Wo;
+    const int ho = (int)(t % Ho);
+    const size_t img = (size_t)(t / Ho);
+    float best[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) best[e] = -INFINITY;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const float* p =
+            x + (((img * H + (size_t)(2 * ho + dy)) * W + (size_t)(2 * wo + dx)) * C8 + c8) * 8;
+        const cf32x4_t a = *reinterpret_cast<const cf32x4_t*>(p);
+        const cf32x4_t b = *reinterpret_cast<const cf32x4_t*>(p + 4);
+        float v[8];
+        if constexpr (IN_SPLIT) {
+          join8_exact(a, b, v);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) best[e] = fmaxf(best[e], v[e]);
+      }
+    float* d = y + idx * 8;
+    if constexpr (OUT_SPLIT) {
+      cf32x4_t hi4, lo4;
+      split8_rne(best, &hi4, &lo4, &sat);
+      *reinterpret_cast<cf32x4_t*>(d) = hi4;
+      *reinterpret_cast<cf32x4_t*>(d + 4) = lo4;
+    } else {
+      const cf32x4_t o0 = {best[0], best[1], best[2], best[3]};
+      const cf32x4_t o1 = {best[4], best[5], best[6], best[7]};
+      *reinterpret_cast<cf32x4_t*>(d) = o0;
+      *reinterpret_cast<cf32x4_t*>(d + 4) = o1;
+    }
+  }
+  if constexpr (OUT_SPLIT) report_saturation(status, sat);
+}
+
+// pool5 (2x2 / 2) + AdaptiveAvgPool2d((7, 7)) + flatten of the masked level-4 tensor
+// (n, H, W, C), fp32 or split at scale 1 -> fp32 (n, C * 49), column c * 49 + i * 7 + j.
+// (Hp, Wp) = (floor(H / 2), floor(W / 2)) is pool5's extent; bin (i, j) covers pooled rows
+// floor(i Hp / 7) .. ceil((i + 1) Hp / 7) - 1 and the columns likewise (torch's rule: a 1 x 1
+// extent is replicated, a 7 x 7 one handed through), added from zero in ascending (row,
+// column) order, then one division by the bin's size.  A thread per (image, bin, channel),
+// channels fastest.  grid (ceil(49 C / 256), n).
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void vgg_tail_kernel(const float* __restrict__ x, int H, int W,
+                                                       int C, int Hp, int Wp,
+                                                       float* __restrict__ out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 49 * C) return;
+  const int c = idx % C, bin = idx / C, bi = bin / 7, bj = bin % 7;
+  const size_t img = blockIdx.y;
+  const float* src = x + img * (size_t)H * W * C;
+  const int r0 = (bi * Hp) / 7, r1 = ((bi + 1) * Hp + 6) / 7;
+  const int q0 = (bj * Wp) / 7, q1 = ((bj + 1) * Wp + 6) / 7;
+  float sum = 0.f;
+  for (int r = r0; r < r1; ++r)
+    for (int q = q0; q < q1; ++q) {
+      float best = -INFINITY;
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const float* px = src + ((size_t)(2 * r + dy) * W + (2 * q + dx)) * C;
+          float v;
+          if constexpr (SPLIT) {
+            const _Float16* g = reinterpret_cast<const _Float16*>(px + (c >> 3) * 8);
+            v = (float)g[c & 7] + (float)g[8 + (c & 7)];
+          } else {
+            v = px[c];
+          }
+          best = fmaxf(best, v);
+        }
+      sum = __fadd_rn(sum, best);
+    }
+  out[img * (size_t)C * 49 + (size_t)c * 49 + bin] =
+      __fdiv_rn(sum, (float)((r1 - r0) * (q1 - q0)));
+}
+
+static int launch_vgg_first(const float* images, int n, int H, int W, int C, const float* w27,
+                     const float* bias, bool out_split, float* y, unsigned* status,
+                     hipStream_t s) {
+  MILAN_REQUIRE(images && w27 && bias && y && n >= 1 && H >= 1 && W >= 1 && C >= 8 &&
+                    C % 8 == 0 && C <= 512,
+                MILAN_ERR_ARG, "vgg first conv: bad argument (C = %d)", C);
+  // (a workgroup per output row: the grid's x extent takes 2^31 - 1 of them)
+  MILAN_REQUIRE((long)n * H <= 0x7fffffffL, MILAN_ERR_ARG, "vgg first conv: %d x %d rows", n, H);
+  const dim3 grid((unsigned)((long)n * H));
+  const size_t lds = sizeof(float) * 28 * (size_t)C;
+  if (out_split)
+    hipLaunchKernelGGL(vgg_first_kernel<true>, grid, dim3(256), lds, s, images, H, W, C, w27,
+                       bias, y, status);
+  else
+    hipLaunchKernelGGL(vgg_first_kernel<false>, grid, dim3(256), lds, s, images, H, W, C, w27,
+                       bias, y, status);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+static int launch_maxpool2s2(const float* x, int n, int H, int W, int C, bool in_split, bool out_split,
+                      float* y, unsigned* status, hipStream_t s) {
+  const int Ho = H / 2, Wo = W / 2;
+  MILAN_REQUIRE(x && y && n >= 1 && Ho >= 1 && Wo >= 1 && C >= 8 && C % 8 == 0, MILAN_ERR_ARG,
+                "maxpool 2x2: bad argument (%d x %d x %d)", H, W, C);
+  MILAN_REQUIRE(out_split || !in_split, MILAN_ERR_STATE,
+                "internal: there is no split -> fp32 2x2 pool");
+  const long total = (long)n * Ho * Wo * (C / 8);
+  const dim3 grid(grid_for(total));
+  if (!out_split)
+    hipLaunchKernelGGL((maxpool2s2_kernel<false, false>), grid, dim3(256), 0, s, x, H, W, C / 8,
+                       Ho, Wo, total, y, status);
+  else if (in_split)
+    hipLaunchKernelGGL((maxpool2s2_kernel<true, true>), grid, dim3(256), 0, s, x, H, W, C / 8, Ho,
+                       Wo, total, y, status);
+  else
+    hipLaunchKernelGGL((maxpool2s2_kernel<false, true>), grid, dim3(256), 0, s, x, H, W, C / 8,
+                       Ho, Wo, total, y, status);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 // Across-channel local response normalisation of the Places365 AlexNet, over an
@@ -547,8 +816,13 @@ static bool places_trunk(const milan_ctx* c) {
 }
 // either of them: AlexTrunk walks it
 static bool alexnet_trunk(const milan_ctx* c) { return alex_trunk(c) || places_trunk(c); }
-static bool classifier_trunk(const milan_ctx* c) { return resnet_trunk(c) || alexnet_trunk(c); }
+// VGG: like the Places net it taps and ablates without a head; VggTrunk walks it
+static bool vgg_trunk(const milan_ctx* c) { return c->d.trunk_kind == MILAN_TRUNK_VGG; }
+static bool classifier_trunk(const milan_ctx* c) {
+  return resnet_trunk(c) || alexnet_trunk(c) || vgg_trunk(c);
+}
 static const char* level_names(const milan_ctx* c) {
+  if (vgg_trunk(c)) return "the last conv of blocks 1..5";
   return alexnet_trunk(c) ? "conv1..conv5" : "conv1, layer1..layer4";
 }
 static int level_channels(const milan_ctx* c, int level) {
@@ -576,6 +850,15 @@ static int init_mask_table(milan_ctx* c, const int* channels, hipStream_t s) {
 // called from milan_finalize_weights after encoder_finalize: keeps fc.weight / fc.bias when the
 // state dict has them (a context without them runs everything but the classify calls)
 int classify_finalize(milan_ctx* c, hipStream_t s) {
+  if (vgg_trunk(c)) {
+    if (c->stem.w == nullptr) return 0;
+    // (vgg_first_kernel keeps 28 x width floats in LDS)
+    MILAN_REQUIRE(c->d.trunk_width <= 512, MILAN_ERR_SHAPE,
+                  "the VGG trunk takes widths up to 512 (got %d)", c->d.trunk_width);
+    int channels[5];
+    for (int l = 0; l < 5; ++l) channels[l] = c->vgg[l][0].cout;
+    return init_mask_table(c, channels, s);
+  }
   if (places_trunk(c) && c->stem.w != nullptr) {
     int channels[5];
     for (int l = 0; l < 5; ++l) channels[l] = c->alex[l].cout;
@@ -643,8 +926,8 @@ int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* un
 
 // ---------------------------------------------------------------------------
 // driver: one pass loop, one sweep loop and one workspace dry run, written over
-// a trunk.  A trunk (ResNetTrunk; AlexTrunk, which walks both AlexNets) is one pass's plan and
-// walker: it derives from Trunk, fills h / w / lvl_sz and split_tap_scale when it is made, and
+// a trunk.  A trunk (ResNetTrunk; AlexTrunk, which walks both AlexNets; VggTrunk) is one
+// pass's plan and walker: it derives from Trunk, fills h / w / lvl_sz and split_tap_scale when it is made, and
 // supplies
 //   carve(a)           its own buffers out of the arena, in its own order
 //   carve_hold(a, f)   the sweep's room of `f` floats for a held level, if it needs one
@@ -653,11 +936,6 @@ int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* un
 //   head(x4, logits, preds)     from the masked level-4 tensor to logits (+ argmax)
 //   hold_level(images, at, level, &held)   the sweep's step to the next level with units
 // ---------------------------------------------------------------------------
-static int grid_for(long items) {
-  const long b = (items + 255) / 256;
-  return (int)(b < 1 ? 1 : (b < 16384 ? b : 16384));
-}
-
 struct Trunk {
   const milan_ctx* c;
   int n, hin, win;        // the pass's images and their extent
@@ -670,7 +948,8 @@ struct Trunk {
   float *logits = nullptr, *work = nullptr;
   float* tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // whether a level's tensor is in split format (a trunk's constructor fills it: level 0 is
-  // fp32 everywhere, the Places365 AlexNet has fp32 levels above it too)
+  // fp32 on the ResNets and the AlexNets, the Places365 AlexNet and the narrow VGGs have fp32
+  // levels above it too)
   bool fmt[5] = {false, false, false, false, false};
 
   // level tensor `x` -> `y` (x == y: in place), times the context's mask of that level and with
@@ -1008,6 +1287,140 @@ struct AlexTrunk : Trunk {
   }
 };
 
+// torchvision's VGG-11 / 13 / 16 / 19 without batch norm in eval mode: five blocks
+// of 3x3 / pad 1 convs (c->vgg, as the uploaded keys gave them), a 2x2 / 2 pool after each.
+// Level l is the output of the last conv of block l + 1 with AlexTrunk's semantics: relu(conv +
+// bias) x mask, the conv run with the encoder's bias + ReLU epilogue.  The five levels have a
+// buffer each (the sweep holds them where they are); the convs inside a block and the pools
+// write two scratch buffers in turn.  walk() runs, for each block it crosses, the pool and then
+// the block's convs; conv1_1 reads the image itself (vgg_first_kernel).
+// Formats in the split mode, conv by conv in network order: conv i multiplies split operands
+// (rd[i]) when its weights have a split copy (cin % 32 == 0) and its input was written in
+// split format -- by the pool in front of it, which converts on the way, by vgg_first_kernel,
+// or by a split conv.  A conv writes the format it reads (of[i] = rd[i]); vgg_first_kernel
+// writes the one the next conv can take.  Channel widths never shrink along a VGG, so a split
+// tensor never has to feed an fp32 conv: walk() asserts that and there is no conversion back.
+// Split activations sit at scale 1, as on the AlexNets.
+struct VggTrunk : Trunk {
+  int nconv = 0;
+  int cb[20], cj[20];       // block and place in its block of conv i (network order)
+  int first[5];             // block b's first conv
+  bool rd[20], of[20];      // conv i reads split operands / writes split format
+  float *lv[5], *sc[2], *flat, *f6, *f7;
+
+  VggTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
+      : Trunk{c, n, H, W, split, s, 1.f} {
+    h[0] = H; w[0] = W;
+    for (int l = 1; l < 5; ++l) { h[l] = h[l - 1] / 2; w[l] = w[l - 1] / 2; }
+    for (int l = 0; l < 5; ++l) lvl_sz[l] = (size_t)h[l] * w[l] * c->abl_ch[l];
+    for (int b = 0; b < 5; ++b) {
+      first[b] = nconv;
+      for (int j = 0; j < c->vgg_n[b]; ++j) { cb[nconv] = b; cj[nconv] = j; ++nconv; }
+    }
+    auto want = [&](int i) { return split && c->vgg[cb[i]][cj[i]].ws != nullptr; };
+    rd[0] = false;
+    of[0] = nconv > 1 && want(1);
+    for (int i = 1; i < nconv; ++i) {
+      rd[i] = want(i) && (cj[i] == 0 || of[i - 1]);
+      of[i] = rd[i];
+    }
+    for (int b = 0; b < 5 && nconv > 0; ++b) fmt[b] = of[first[b] + c->vgg_n[b] - 1];
+  }
+
+  void carve(Arena& ar) {
+    const milan_ctx::AlexHead& hd = c->ahead;
+    for (int l = 0; l < 5; ++l) lv[l] = ar.get<float>((size_t)n * lvl_sz[l]);
+    // (a pool's output is no larger than the level behind it, a conv's inside block b as large)
+    const size_t sc_sz = *std::max_element(lvl_sz, lvl_sz + 5);
+    for (int k = 0; k < 2; ++k) sc[k] = ar.get<float>((size_t)n * sc_sz);
+    flat = ar.get<float>((size_t)n * hd.in[0]);
+    f6 = ar.get<float>((size_t)n * hd.out[0]);
+    f7 = ar.get<float>((size_t)n * hd.out[1]);
+  }
+  void carve_hold(Arena&, size_t) {}
+  // (what a call asks of the image depends on the level it walks to: walk())
+  int check_geometry() const { return 0; }
+
+  void trace(int i, bool split_operands) const {
+    ++c->vgg_launches[cb[i] * 4 + cj[i]];
+    c->vgg_split[cb[i] * 4 + cj[i]] = split_operands;
+  }
+
+  // ResNetTrunk::walk's contract
+  int walk(int from, int to, const float* src, const float** out) const {
+    // every pool halves (floor): level l needs 2^l pixels each way.  Nothing has been launched.
+    MILAN_REQUIRE(to < 0 || (h[to] >= 1 && w[to] >= 1), MILAN_ERR_SHAPE,
+                  "classify: image %dx%d is too small for VGG level %d (%dx%d at least)", hin,
+                  win, to, 1 << (to < 0 ? 0 : to), 1 << (to < 0 ? 0 : to));
+    const float* x = src;
+    bool xs = from >= 0 && fmt[from];   // the format of x
+    for (int b = from + 1; b <= to; ++b) {
+      const int hh = h[b], ww = w[b], i0 = first[b], nb = c->vgg_n[b];
+      int j = 0;
+      if (b == 0) {
+        float* dst = nb == 1 ? lv[0] : sc[0];
+        MILAN_TRY(launch_vgg_first(src, n, hin, win, c->abl_ch[0], c->vgg_w27, c->vgg[0][0].bias,
+                                   of[0], dst, c->status, s));
+        trace(0, false);
+        x = dst; xs = of[0];
+        j = 1;
+      } else {
+        MILAN_REQUIRE(rd[i0] || !xs, MILAN_ERR_STATE,
+                      "internal: vgg block %d is fp32 behind a split level", b + 1);
+        MILAN_TRY(launch_maxpool2s2(x, n, h[b - 1], w[b - 1], c->abl_ch[b - 1], xs, rd[i0], sc[0],
+                                    c->status, s));
+        x = sc[0]; xs = rd[i0];
+      }
+      for (; j < nb; ++j) {
+        const int i = i0 + j;
+        // (the scratch buffer the input is not in)
+        float* dst = j == nb - 1 ? lv[b] : (x == sc[0] ? sc[1] : sc[0]);
+        MILAN_REQUIRE(rd[i] == xs, MILAN_ERR_STATE,
+                      "internal: vgg conv %d.%d would read a tensor of the other format", b + 1, j);
+        int ho, wo;
+        MILAN_TRY(launch_gemm(encoder_conv_args(c->vgg[b][j], x, n, hh, ww, dst, EPI_BIAS_RELU,
+                                                nullptr, c->zero, &ho, &wo, rd[i], false), s));
+        trace(i, rd[i]);
+        x = dst; xs = of[i];
+      }
+      if (c->abl_count[b] > 0) MILAN_TRY(mask(b, lv[b], lv[b], -1));
+      if (tap[b]) MILAN_TRY(emit(b, x));
+    }
+    *out = x;
+    return 0;
+  }
+
+  // pool5 + adaptive average pool + flatten in (C, h, w) order, classifier.0 / .3 / .6 (+ argmax)
+  // of the masked level-4 tensor; dropout is the identity in eval mode
+  int head(const float* x4, float* lg, long long* pr) const {
+    const milan_ctx::AlexHead& hd = c->ahead;
+    const int C = c->abl_ch[4];
+    MILAN_REQUIRE(hd.installed && h[4] >= 2 && w[4] >= 2, MILAN_ERR_STATE,
+                  "internal: vgg head without fc layers or without a pixel after pool5");
+    const dim3 grid((49 * C + 255) / 256, n);
+    if (fmt[4])
+      hipLaunchKernelGGL(vgg_tail_kernel<true>, grid, dim3(256), 0, s, x4, h[4], w[4], C,
+                         h[4] / 2, w[4] / 2, flat);
+    else
+      hipLaunchKernelGGL(vgg_tail_kernel<false>, grid, dim3(256), 0, s, x4, h[4], w[4], C,
+                         h[4] / 2, w[4] / 2, flat);
+    MILAN_CHECK_HIP(hipGetLastError());
+    MILAN_TRY(linear_run(flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, f6, s));
+    MILAN_TRY(linear_run(f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, f7, s));
+    MILAN_TRY(linear_run(f7, hd.w[2], hd.b[2], n, hd.in[2], hd.out[2], false, lg, s));
+    if (pr) {
+      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, lg, hd.out[2], pr);
+      MILAN_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+  }
+
+  // AlexTrunk::hold_level: every level has a buffer of its own
+  int hold_level(const float* images, int at, int level, const float** held) const {
+    return walk(at, level, at < 0 ? images : *held, held);
+  }
+};
+
 template <class T>
 static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
   Arena a; a.dry = true;
@@ -1019,6 +1432,7 @@ static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int 
 
 size_t classify_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
   if (n_images <= 0 || H < 1 || W < 1) return 0;
+  if (vgg_trunk(c)) return workspace_dry<VggTrunk>(c, n_images, H, W, sweep_units);
   if (alexnet_trunk(c)) return workspace_dry<AlexTrunk>(c, n_images, H, W, sweep_units);
   if (resnet_trunk(c)) return workspace_dry<ResNetTrunk>(c, n_images, H, W, sweep_units);
   return 0;
@@ -1104,6 +1518,10 @@ static int sweep(milan_ctx* c, const float* images, int n, int H, int W, bool sp
   return 0;
 }
 
+static int install_head(milan_ctx* c, const char* what, const float* const* w,
+                        const float* const* b, const int* out, const int* in,
+                        const int* channels, hipStream_t s);
+
 // milan_set_alexnet_head: fc6 / fc7 / linear8 (device fp32, row-major (out, in)) packed into
 // library-owned memory; switches the classify family on for this AlexNet context
 int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
@@ -1118,11 +1536,38 @@ int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* 
                 "milan_set_alexnet_head: fc6 (%d, %d), fc7 (%d, %d), linear8 (%d, %d) do not "
                 "chain from %d x 36 features",
                 out[0], in[0], out[1], in[1], out[2], in[2], c5);
+  int channels[5];
+  for (int l = 0; l < 5; ++l) channels[l] = c->alex[l].cout;
+  return install_head(c, "milan_set_alexnet_head", w, b, out, in, channels, s);
+}
+
+// milan_set_vgg_head: classifier.0 / .3 / .6 into the same storage
+int classify_set_vgg_head(milan_ctx* c, const float* const* w, const float* const* b,
+                          const int* out, const int* in, hipStream_t s) {
+  MILAN_REQUIRE(vgg_trunk(c), MILAN_ERR_ARG,
+                "milan_set_vgg_head: the context's trunk is not a VGG");
+  MILAN_REQUIRE(c->stem.w != nullptr, MILAN_ERR_STATE, "encoder weights were not uploaded");
+  const int c5 = c->vgg[4][0].cout;
+  MILAN_REQUIRE(out[0] >= 1 && out[1] >= 1 && out[2] >= 1 && in[0] == c5 * 49 &&
+                    in[1] == out[0] && in[2] == out[1],
+                MILAN_ERR_SHAPE,
+                "milan_set_vgg_head: classifier.0 (%d, %d), .3 (%d, %d), .6 (%d, %d) do not "
+                "chain from %d x 49 features",
+                out[0], in[0], out[1], in[1], out[2], in[2], c5);
+  int channels[5];
+  for (int l = 0; l < 5; ++l) channels[l] = c->vgg[l][0].cout;
+  return install_head(c, "milan_set_vgg_head", w, b, out, in, channels, s);
+}
+
+// the three Linear layers packed into library-owned memory (`what`: the calling entry point)
+static int install_head(milan_ctx* c, const char* what, const float* const* w,
+                        const float* const* b, const int* out, const int* in,
+                        const int* channels, hipStream_t s) {
   milan_ctx::AlexHead& hd = c->ahead;
   for (int i = 0; i < 3; ++i) {
     // (a second call with the same widths reuses the first one's memory)
     MILAN_REQUIRE(hd.w[i] == nullptr || (hd.out[i] == out[i] && hd.in[i] == in[i]),
-                  MILAN_ERR_STATE, "milan_set_alexnet_head: a head of other widths is installed");
+                  MILAN_ERR_STATE, "%s: a head of other widths is installed", what);
     if (hd.w[i] == nullptr) {
       MILAN_TRY(dev_alloc(c, (void**)&hd.w[i], sizeof(float) * linear_packed_floats(out[i], in[i])));
       MILAN_TRY(dev_alloc(c, (void**)&hd.b[i], sizeof(float) * (size_t)out[i]));
@@ -1132,11 +1577,7 @@ int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* 
     MILAN_CHECK_HIP(hipMemcpyAsync(hd.b[i], b[i], sizeof(float) * (size_t)out[i],
                                    hipMemcpyDeviceToDevice, s));
   }
-  if (c->abl_mask == nullptr) {
-    int channels[5];
-    for (int l = 0; l < 5; ++l) channels[l] = c->alex[l].cout;
-    MILAN_TRY(init_mask_table(c, channels, s));
-  }
+  if (c->abl_mask == nullptr) MILAN_TRY(init_mask_table(c, channels, s));
   // (the caller's tensors may go once this returns)
   MILAN_CHECK_HIP(hipStreamSynchronize(s));
   c->fc_classes = out[2];
@@ -1168,6 +1609,11 @@ int linear_rowwise_run(const float* x, const float* W, const float* bias, int M,
   return 0;
 }
 
+// milan_vgg_trace counts from the start of a classify-family call
+static void vgg_trace_reset(const milan_ctx* c) {
+  for (int i = 0; i < 20; ++i) c->vgg_launches[i] = c->vgg_split[i] = 0;
+}
+
 // `head`: the call runs avgpool + fc (milan_activations stops before them and does not)
 static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool head = true) {
   MILAN_REQUIRE(classifier_trunk(c), MILAN_ERR_ARG,
@@ -1178,7 +1624,10 @@ static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool 
   MILAN_REQUIRE(!head || !places_trunk(c) || c->ahead.installed, MILAN_ERR_STATE,
                 "this Places365 AlexNet context has no head: milan_set_alexnet_head installs "
                 "fc6 / fc7 / fc8");
-  MILAN_REQUIRE(!head || alexnet_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
+  MILAN_REQUIRE(!head || !vgg_trunk(c) || c->ahead.installed, MILAN_ERR_STATE,
+                "this VGG context has no head: milan_set_vgg_head installs classifier.0 / .3 / "
+                ".6");
+  MILAN_REQUIRE(!head || alexnet_trunk(c) || vgg_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
                 "this context was created without fc.weight: it has no classifier head");
   MILAN_REQUIRE(!c->trunk_f16, MILAN_ERR_ARG,
                 "classification runs in the f32 and split_f16 modes, not in the fast f16 mode");
@@ -1192,6 +1641,10 @@ static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool 
                   "classify: image %dx%d does not leave 6x6 after pool5 of the Places365 AlexNet "
                   "(227x227 does; fc6 reads %d features)", H, W, c->ahead.in[0]);
   }
+  // (VGG: pool5 has to leave a pixel for the adaptive pool)
+  MILAN_REQUIRE(!head || !vgg_trunk(c) || (H >= 32 && W >= 32), MILAN_ERR_SHAPE,
+                "classify: image %dx%d is too small for VGG (32x32 at least: five 2x2 pools)", H,
+                W);
   bool sp = c->precision == MILAN_PRECISION_SPLIT_F16 && c->d.trunk_width % 8 == 0;
   // (Places: conv3 is dense and reads a multiple of 64 channels; the grouped levels decide for
   // themselves, AlexTrunk::sp)
@@ -1209,7 +1662,8 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
                  int64_t* predictions, Arena& ws, hipStream_t s) {
   bool split;
   MILAN_TRY(classify_checks(c, n, H, W, &split));
-  auto go = alexnet_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
+  vgg_trace_reset(c);
+  auto go = vgg_trunk(c) ? run<VggTrunk> : alexnet_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
   return go(c, images, n, H, W, split, logits, predictions, nullptr, 4, "classify", ws, s);
 }
 
@@ -1220,7 +1674,9 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
   MILAN_TRY(classify_checks(c, n, H, W, &split));
   MILAN_TRY(check_units(c, levels, units, count, "milan_classify_sweep"));
   if (count == 0) return 0;
-  auto go = alexnet_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
+  vgg_trace_reset(c);
+  auto go = vgg_trunk(c) ? sweep<VggTrunk>
+                         : alexnet_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
   return go(c, images, n, H, W, split, levels, units, count, targets, correct, predictions, ws, s);
 }
 
@@ -1236,6 +1692,11 @@ int activations_run(milan_ctx* c, const float* images, int n, int H, int W, cons
     MILAN_REQUIRE(levels[i] >= 0 && levels[i] <= 4, MILAN_ERR_ARG,
                   "milan_activations: level %d is not one of 0..4 (%s)", levels[i],
                   level_names(c));
+    // (VggTrunk::walk's check, ahead of the one for an output that such a level leaves empty)
+    MILAN_REQUIRE(!vgg_trunk(c) || ((H >> levels[i]) >= 1 && (W >> levels[i]) >= 1),
+                  MILAN_ERR_SHAPE,
+                  "classify: image %dx%d is too small for VGG level %d (%dx%d at least)", H, W,
+                  levels[i], 1 << levels[i], 1 << levels[i]);
     MILAN_REQUIRE(taps[levels[i]] == nullptr, MILAN_ERR_ARG,
                   "milan_activations: level %d is requested twice", levels[i]);
     MILAN_REQUIRE(outputs[i] != nullptr, MILAN_ERR_ARG,
@@ -1246,7 +1707,8 @@ int activations_run(milan_ctx* c, const float* images, int n, int H, int W, cons
   // (the messages about the workspace and the sub-batch have named the call differently on
   // the two trunks since they were written)
   const bool alex = alexnet_trunk(c);
-  auto go = alex ? run<AlexTrunk> : run<ResNetTrunk>;
+  vgg_trace_reset(c);
+  auto go = vgg_trunk(c) ? run<VggTrunk> : alex ? run<AlexTrunk> : run<ResNetTrunk>;
   return go(c, images, n, H, W, split, nullptr, nullptr, taps, top,
             alex ? "classify" : "activations", ws, s);
 }

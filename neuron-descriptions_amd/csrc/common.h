@@ -637,6 +637,15 @@ struct milan_ctx {
   } ahead;
   // the Places365 AlexNet's optional LRN after pool1 and pool2 (milan_set_alexnet_lrn; 0: off)
   struct AlexLrn { int size = 0; float alpha = 1e-4f, beta = 0.75f; } lrn;
+  // VGG (MILAN_TRUNK_VGG): block b's convs vgg[b][0 .. vgg_n[b] - 1], as the
+  // uploaded keys `vgg.B.J` gave them; conv1_1 once more as vgg_w27, (27 taps in (kh, kw, c)
+  // order) x cout fp32, for vgg_first_kernel.  Its head lives in `ahead` (milan_set_vgg_head).
+  milan::ConvW vgg[5][4];
+  int vgg_n[5] = {0, 0, 0, 0, 0};
+  float* vgg_w27 = nullptr;
+  // what the walks of the last classify-family call launched (milan_vgg_trace): slot 4 b + j
+  mutable int vgg_launches[20] = {};
+  mutable int vgg_split[20] = {};
 };
 
 namespace milan {
@@ -729,6 +738,11 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
 int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
                               const int* out, const int* in, hipStream_t s);
 int classify_set_alexnet_lrn(milan_ctx* c, int local_size, float alpha, float beta);
+// milan_set_vgg_head: classify_set_alexnet_head's storage and packing for classifier.0 / 3 / 6
+int classify_set_vgg_head(milan_ctx* c, const float* const* w, const float* const* b,
+                          const int* out, const int* in, hipStream_t s);
+// conv1_1's OIHW weight (cout, 3, 3, 3) -> (27, cout), k = (kh * 3 + kw) * 3 + c (classify.hip)
+int vgg_pack_first(const float* w_oihw, int cout, float* w27, hipStream_t s);
 // across-channel LRN over (pixels, C) with a pixel's channels contiguous, fp32 or split at
 // scale 1 in and out (classify.hip, lrn_kernel); x and y must not overlap
 int launch_lrn(const float* x, long long pixels, int C, bool split, int local_size, float alpha,

@@ -13,6 +13,7 @@
 #include <optional>
 #include <vector>
 
+#include <cstdio>
 #include <cstdlib>
 
 namespace milan {
@@ -352,6 +353,56 @@ int encoder_finalize(milan_ctx* c, hipStream_t s) {
       cin_full = c->alex[i].cout;
     }
     c->stem = c->alex[0];  // "encoder weights present" marker
+  } else if (kind == MILAN_TRUNK_VGG) {
+    // torchvision's VGG without batch norm: the blocks follow from the keys
+    // `vgg.B.J` -- B = 1..5, J contiguous from 0, at most four convs per block
+    if (!find(c, p + "vgg.1.0.weight")) return 0;  // decoder-only context
+    const int wd = c->d.trunk_width;
+    MILAN_REQUIRE(wd % 8 == 0, MILAN_ERR_SHAPE,
+                  "the VGG trunk needs a width that is a multiple of 8 (got %d)", wd);
+    const size_t plen = p.size() + 4;  // "<prefix>vgg."
+    for (const auto& kv : c->raw) {
+      const std::string& key = kv.first;
+      if (key.compare(0, plen, p + "vgg.") != 0) continue;
+      int b = 0, j = 0, used = 0;
+      const bool ok = sscanf(key.c_str() + plen, "%d.%d.%n", &b, &j, &used) == 2 && used > 0 &&
+                      (key.compare(plen + used, std::string::npos, "weight") == 0 ||
+                       key.compare(plen + used, std::string::npos, "bias") == 0);
+      MILAN_REQUIRE(ok && b >= 1 && b <= 5 && j >= 0 && j <= 3, MILAN_ERR_SHAPE,
+                    "%s is not a VGG key: vgg.B.J.weight / .bias with B in 1..5 and J in 0..3",
+                    key.c_str() + p.size());
+      // (a gap in J: the conv in front of this one has to be there)
+      MILAN_REQUIRE(j == 0 || find(c, p + "vgg." + std::to_string(b) + "." +
+                                          std::to_string(j - 1) + ".weight"),
+                    MILAN_ERR_SHAPE, "VGG block %d has conv %d but no conv %d: the convs of a "
+                    "block are numbered from 0 without a gap", b, j, j - 1);
+    }
+    int cin = 3;
+    for (int b = 0; b < 5; ++b) {
+      const int cout = wd * (b < 3 ? 1 << b : 8);
+      c->vgg_n[b] = 0;
+      for (int j = 0; j < 4; ++j) {
+        const std::string name = p + "vgg." + std::to_string(b + 1) + "." + std::to_string(j);
+        const Tensor* w = find(c, name + ".weight");
+        if (!w) break;
+        MILAN_REQUIRE(w->shape.size() == 4 && w->shape[0] == cout && w->shape[1] == cin &&
+                          w->shape[2] == 3 && w->shape[3] == 3 && find(c, name + ".bias"),
+                      MILAN_ERR_SHAPE,
+                      "vgg.%d.%d: expected a (%d, %d, 3, 3) weight with a bias (block %d has "
+                      "%d x min(2^%d, 8) channels)", b + 1, j, cout, cin, b + 1, wd, b);
+        ConvW& cw = c->vgg[b][j];
+        MILAN_TRY(pack_conv(c, name, "", 1, 1, &cw, s, true));
+        MILAN_REQUIRE(cw.bias != nullptr, MILAN_ERR_SHAPE, "vgg.%d.%d.bias has the wrong size",
+                      b + 1, j);
+        cin = cout;
+        c->vgg_n[b] = j + 1;
+      }
+      MILAN_REQUIRE(c->vgg_n[b] >= 1, MILAN_ERR_SHAPE, "VGG block %d has no conv (vgg.%d.0.weight)",
+                    b + 1, b + 1);
+    }
+    MILAN_TRY(dev_alloc(c, (void**)&c->vgg_w27, sizeof(float) * 27 * (size_t)wd));
+    MILAN_TRY(vgg_pack_first(find(c, p + "vgg.1.0.weight")->dev, wd, c->vgg_w27, s));
+    c->stem = c->vgg[0][0];  // "encoder weights present" marker
   } else {
   if (!find(c, p + "conv1.weight")) return 0;  // decoder-only context
   MILAN_TRY(pack_conv(c, p + "conv1", "", 2, 3, &c->stem, s));
@@ -1345,7 +1396,8 @@ size_t encoder_workspace(const milan_ctx* c, int n_images, int H, int W) {
   Arena a; a.dry = true;
   const int sub = encoder_sub_batch();
   const int n = n_images < sub ? n_images : sub;
-  if (c->d.trunk_kind == MILAN_TRUNK_NONE || c->d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES)
+  if (c->d.trunk_kind == MILAN_TRUNK_NONE || c->d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES ||
+      c->d.trunk_kind == MILAN_TRUNK_VGG)
     return 0;
   if (c->d.trunk_kind == MILAN_TRUNK_ALEXNET) {
     alexnet_workspace_dry(c, n, H, W, a);
@@ -1441,7 +1493,8 @@ int encoder_run_spatial(milan_ctx* c, const void* images, int image_dtype,
                         const void* masks, int mask_dtype, int n, int H, int W,
                         float* out, Arena& ws, hipStream_t s) {
   MILAN_REQUIRE(c->d.trunk_kind != MILAN_TRUNK_ALEXNET &&
-                    c->d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES,
+                    c->d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES &&
+                    c->d.trunk_kind != MILAN_TRUNK_VGG,
                 MILAN_ERR_ARG, "spatial encoding needs a ResNet trunk");
   Arena dry; dry.dry = true;
   EncPlan pl;
@@ -1472,6 +1525,9 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
   MILAN_REQUIRE(c->d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES, MILAN_ERR_ARG,
                 "the Places365 AlexNet trunk has no encoder config: it classifies, ablates and "
                 "taps activations only");
+  MILAN_REQUIRE(c->d.trunk_kind != MILAN_TRUNK_VGG, MILAN_ERR_ARG,
+                "the VGG trunk has no encoder config: it classifies, ablates and taps "
+                "activations only");
   MILAN_REQUIRE(!spatial || c->d.trunk_kind != MILAN_TRUNK_ALEXNET, MILAN_ERR_ARG,
                 "spatial encoding needs a ResNet trunk");
   MILAN_REQUIRE(c->stem.w != nullptr, MILAN_ERR_STATE,

@@ -12,6 +12,11 @@ model zoo (`src/deps/alexnet.py`, `src/deps/resnet152.py`): the first is a netwo
 (grouped convs, an unpadded conv1, an optional LRN, `fc8`), the second the v1.5 bottleneck
 ResNet-152 under Torch7-converted key and layer names.
 
+`VGGClassifier` is torchvision's VGG-11 / 13 / 16 / 19 without batch norm, the VGGs of the
+reference's audit experiment (`experiments/audit.py`) and, after `rekey_vgg16_places`, its
+`vgg16/places365`; it is edited and tapped at the last conv of each block (`LAYERS.VGG11` ..
+`VGG19`).
+
 `ResNetClassifier` is the CNN the reference's experiments dissect and edit
 (`experiments/analyze.py`, `experiments/edit.py`: a torchvision ResNet handed to
 `src/utils/ablations.ImageClassifier`).  It is an `nn.Module` with torchvision's module
@@ -530,3 +535,111 @@ class OldResNet152(ResNetClassifier):
                 raise KeyError(f'layer not found: {name}')
         got = super().activations(images, [self._canonical(name) for name in names])
         return {name: got[self._canonical(name)] for name in names}
+
+
+class VGGClassifier(NativeClassifier):
+    """torchvision's VGG-11 / 13 / 16 / 19 (the variants without batch norm) with a native
+    eval-mode forward: a third of the reference's audit models (`experiments/audit.py`) and,
+    as `vgg16` with 365 classes, its `vgg16/places365`.
+
+    The module tree and the keys are torchvision's: `features`, an `nn.Sequential` of
+    `Conv2d(3x3, padding 1)` / `ReLU(inplace=True)` per conv and one `MaxPool2d(2, 2)` per
+    block; `avgpool = AdaptiveAvgPool2d((7, 7))`; `classifier = Sequential(Linear, ReLU,
+    Dropout, Linear, ReLU, Dropout, Linear)`.  A torchvision checkpoint loads with
+    `load_state_dict` (a Places365 one after `rekey_vgg16_places`).  Channels are `width` x
+    (1, 2, 4, 8, 8), `width` a multiple of 8; 64 and `hidden` 4096 are torchvision's.
+    `precision` as for `ResNetClassifier`.  Edited and tapped at `layers`, the reference's
+    `LAYERS.VGG11` .. `VGG19`: the last conv of each block, e.g. features.2 / 7 / 14 / 21 / 28
+    on vgg16.  A conv's output is followed by an in-place ReLU, so what the pool reads, and
+    what a retain hook sees, is relu(conv + bias) x mask.  The forward takes images of at
+    least 32 x 32; level l of `activations` images of at least 2^l each way.
+    """
+
+    def __init__(self,
+                 config: str = 'vgg16',
+                 num_classes: int = 1000,
+                 width: int = 64,
+                 hidden: int = 4096,
+                 precision: str = 'auto'):
+        super().__init__()
+        if config not in synthetic.VGG_BLOCKS:
+            raise ValueError(f'classifier not supported: {config} (the VGGs are '
+                             f'{sorted(synthetic.VGG_BLOCKS)}, without batch norm)')
+        if precision not in ('auto', 'split_f16', 'f32'):
+            raise ValueError(f'unknown precision: {precision}')
+        if width < 8 or width % 8:
+            raise ValueError(f'width must be a multiple of 8, got {width}')
+        self.config = config
+        self.blocks = synthetic.VGG_BLOCKS[config]
+        self.width = int(width)
+        self.hidden = int(hidden)
+        self.num_classes = int(num_classes)
+        self.precision = precision
+        modules, cin = [], 3
+        for mult, count in zip(synthetic.VGG_CHANNELS, self.blocks):
+            for _ in range(count):
+                modules += [nn.Conv2d(cin, mult * self.width, 3, padding=1),
+                            nn.ReLU(inplace=True)]
+                cin = mult * self.width
+            modules.append(nn.MaxPool2d(2, 2))
+        self.features = nn.Sequential(*modules)
+        self.avgpool = nn.AdaptiveAvgPool2d((7, 7))
+        self.classifier = nn.Sequential(
+            nn.Linear(cin * 49, self.hidden), nn.ReLU(True), nn.Dropout(),
+            nn.Linear(self.hidden, self.hidden), nn.ReLU(True), nn.Dropout(),
+            nn.Linear(self.hidden, self.num_classes))
+        self.layers = hip.vgg_level_names(self.blocks)
+        self._init_native()
+
+    def forward_eager(self, images: torch.Tensor) -> torch.Tensor:
+        """torchvision's `VGG.forward`: the modules in order."""
+        x = self.avgpool(self.features(images))
+        return self.classifier(torch.flatten(x, 1))
+
+    def trunk_keys(self) -> Dict[str, str]:
+        """`features.N` -> the library's `vgg.B.J` (block B = 1..5, conv J within it) for
+        every conv of this config."""
+        return {f'features.{index}': f'vgg.{b + 1}.{j}'
+                for b, indices in enumerate(synthetic.vgg_feature_indices(self.config))
+                for j, index in enumerate(indices)}
+
+    def _make_context(self, device: torch.device) -> hip.Context:
+        sd = {}
+        for old, new in self.trunk_keys().items():
+            module = self.features[int(old.split('.')[1])]
+            sd[f'encoder.encoder.model.{new}.weight'] = module.weight
+            sd[f'encoder.encoder.model.{new}.bias'] = module.bias
+        head = [t for index in (0, 3, 6)
+                for t in (self.classifier[index].weight, self.classifier[index].bias)]
+        return hip.Context(hip.make_dims(sd, 1), sd, device, vgg_head=head)
+
+
+def rekey_vgg16_places(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A state dict of the Places365 VGG-16 checkpoint (`features.conv1_1.weight` ..
+    `features.conv5_3.bias`, `classifier.fc6` / `fc7` / `fc8a`, or `fc8`) under torchvision's
+    key names (`features.0.weight` .. `features.28.bias`, `classifier.0` / `3` / `6`), in the
+    same order.  Keys that already are torchvision's pass through; anything else is a
+    KeyError."""
+    table = {f'conv{b + 1}_{j + 1}': str(index)
+             for b, indices in enumerate(synthetic.vgg_feature_indices('vgg16'))
+             for j, index in enumerate(indices)}
+    convs = set(table.values())
+    linear = {'fc6': '0', 'fc7': '3', 'fc8': '6', 'fc8a': '6'}
+    out = {}
+    for key, value in state_dict.items():
+        parts = key.split('.')
+        if len(parts) != 3 or parts[2] not in ('weight', 'bias'):
+            raise KeyError(f'not a key of the Places365 VGG-16: {key}')
+        group, name, leaf = parts
+        if group == 'features' and name in table:
+            name = table[name]
+        elif group == 'classifier' and name in linear:
+            name = linear[name]
+        elif not ((group == 'features' and name in convs) or
+                  (group == 'classifier' and name in ('0', '3', '6'))):
+            raise KeyError(f'not a key of the Places365 VGG-16: {key}')
+        new = f'{group}.{name}.{leaf}'
+        if new in out:
+            raise KeyError(f'two keys map to {new}')
+        out[new] = value
+    return out

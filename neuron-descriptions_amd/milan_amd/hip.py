@@ -121,8 +121,11 @@ ABI_VERSION = 11  # MILAN_ABI_VERSION this binding was written against
 # milan_dims.trunk_kind and the pyramid width multiplier (F = mult * width)
 TRUNK_BOTTLENECK, TRUNK_BASIC, TRUNK_ALEXNET, TRUNK_NONE = 0, 1, 2, 3
 TRUNK_ALEXNET_PLACES = 4  # the Places365 AlexNet: classify / ablate / activations only
+# torchvision's VGG-11/13/16/19 (no batch norm): classify / ablate / activations only
+TRUNK_VGG = 5
+# (a VGG context cannot encode: nothing reads its multiplier but `make_dims`)
 _FEATURE_MULT = {TRUNK_BOTTLENECK: 61, TRUNK_BASIC: 16, TRUNK_ALEXNET: 18,
-                 TRUNK_ALEXNET_PLACES: 43}
+                 TRUNK_ALEXNET_PLACES: 43, TRUNK_VGG: 23}
 # channels of conv1..conv5 per unit of `trunk_width` (the reference's net has width 32)
 PLACES_ALEXNET_CHANNELS = synthetic.PLACES_ALEXNET_CHANNELS
 
@@ -130,6 +133,10 @@ PLACES_ALEXNET_CHANNELS = synthetic.PLACES_ALEXNET_CHANNELS
 def level_shapes(kind: int, width: int, h: int, w: int):
     """[(C, h, w)] of the tensors of levels 0..4 (`Context.activations`) that a trunk of
     `kind` and `width` makes of an h x w image."""
+    if kind == TRUNK_VGG:
+        # 3x3 / pad 1 convs keep the extent; a 2x2 / 2 pool in front of blocks 2..5 halves it
+        # (floor).  (The library refuses an image too small for a level.)
+        return [(width * m, h >> l, w >> l) for l, m in enumerate(synthetic.VGG_CHANNELS)]
     if kind in (TRUNK_ALEXNET, TRUNK_ALEXNET_PLACES):
         # conv1 11x11/4 pad 2 (Places: pad 0); pool1, pool2 3x3/2 before conv2, conv3; the
         # rest keep.  (The library refuses an image too small for a level: at least 1 then.)
@@ -199,6 +206,9 @@ SIGNATURES = {
     'milan_set_alexnet_head':
         (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P]),
     'milan_set_alexnet_lrn': (_I, [_P, _I, _F, _F]),
+    'milan_set_vgg_head':
+        (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P]),
+    'milan_vgg_trace': (_I, [_P, _P, _P]),
     'milan_lrn': (_I, [_P, ctypes.c_longlong, _I, _I, _I, _F, _F, _P, _P, _P]),
     'milan_linear_packed_bytes': (_SZ, [_I, _I]),
     'milan_linear_pack': (_I, [_P, _I, _I, _P, _P]),
@@ -345,6 +355,7 @@ PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_classify_workspace_bytes', 'milan_classify',
           'milan_classify_sweep', 'milan_activations_workspace_bytes',
           'milan_activations', 'milan_set_alexnet_head', 'milan_set_alexnet_lrn', 'milan_lrn',
+          'milan_set_vgg_head', 'milan_vgg_trace',
           'milan_linear_packed_bytes',
           'milan_linear_pack', 'milan_linear', 'milan_linear_rowwise', 'milan_attention',
           'milan_vit_create', 'milan_vit_destroy', 'milan_vit_set_weight',
@@ -498,13 +509,19 @@ class Context:
 
     def __init__(self, dims: Dims, state_dict: Dict[str, torch.Tensor],
                  device: torch.device, finalize: bool = True,
-                 alexnet_head: Optional[Sequence[torch.Tensor]] = None):
+                 alexnet_head: Optional[Sequence[torch.Tensor]] = None,
+                 vgg_head: Optional[Sequence[torch.Tensor]] = None):
         """`finalize=False`: a context that only carries `dims` (no weights,
         no packed arena) -- what the LM training calls need.  `alexnet_head`: the six
-        tensors of `set_alexnet_head`, installed once the weights are finalized."""
+        tensors of `set_alexnet_head`, installed once the weights are finalized;
+        `vgg_head`: those of `set_vgg_head`."""
         self.lib = load_library()
         self.device = require_device(device)
         self.dims = dims
+        # a VGG's convs per block, as the `vgg.B.J` keys give them (`ablation_levels`)
+        self.vgg_blocks = tuple(
+            sum(f'encoder.encoder.model.vgg.{b}.{j}.weight' in state_dict for j in range(4))
+            for b in range(1, 6))
         self._h = _P()
         with torch.cuda.device(self.device):
             _check(
@@ -551,6 +568,8 @@ class Context:
             self.set_precision(default)
         if alexnet_head is not None:
             self.set_alexnet_head(*alexnet_head)
+        if vgg_head is not None:
+            self.set_vgg_head(*vgg_head)
 
     # -- hipGraph replay of the decode stage ------------------------------------
     def enable_graphs(self, enable: bool = True) -> None:
@@ -964,6 +983,8 @@ class Context:
         """The names of levels 0..4 on this context's trunk."""
         if self.dims.trunk_kind in (TRUNK_ALEXNET, TRUNK_ALEXNET_PLACES):
             return self.ALEXNET_LEVELS
+        if self.dims.trunk_kind == TRUNK_VGG:
+            return vgg_level_names(self.vgg_blocks)
         return self.ABLATION_LEVELS
 
     def set_alexnet_lrn(self, local_size: int = 5, alpha: float = 1e-4,
@@ -980,10 +1001,31 @@ class Context:
         biases (out,)): from then on `set_ablation`, `classify`, `classify_sweep` and
         `activations` accept it, with levels 'conv1'..'conv5'.  The library keeps packed
         copies.  The widths must chain from conv5's channels x 36 (ValueError)."""
-        fn = self._need('milan_set_alexnet_head')
-        tensors = [_dev(t.detach(), self.device, torch.float32)
-                   for t in (fc6_weight, fc6_bias, fc7_weight, fc7_bias, linear8_weight,
-                             linear8_bias)]
+        self._set_head('milan_set_alexnet_head', (fc6_weight, fc6_bias, fc7_weight, fc7_bias,
+                                                  linear8_weight, linear8_bias))
+
+    def set_vgg_head(self, fc0_weight, fc0_bias, fc3_weight, fc3_bias, fc6_weight,
+                     fc6_bias) -> None:
+        """Install torchvision's `classifier.0 / .3 / .6` on a VGG context (weights (out, in),
+        biases (out,)): `classify` and `classify_sweep` need it, `set_ablation` and
+        `activations` do not.  The library keeps packed copies.  The widths must chain from
+        the last block's channels x 49 (ValueError)."""
+        self._set_head('milan_set_vgg_head', (fc0_weight, fc0_bias, fc3_weight, fc3_bias,
+                                              fc6_weight, fc6_bias))
+
+    def vgg_trace(self):
+        """What the walks of the last `classify` / `classify_sweep` / `activations` call
+        launched on a VGG context: {(block 1..5, conv 0..3): (launches, 1 if the conv's last
+        launch multiplied split operands else 0)} for the convs the context has."""
+        fn = self._need('milan_vgg_trace')
+        launches, split = (ctypes.c_int32 * 20)(), (ctypes.c_int32 * 20)()
+        _check(fn(self._h, launches, split))
+        return {(b + 1, j): (int(launches[4 * b + j]), int(split[4 * b + j]))
+                for b, count in enumerate(self.vgg_blocks) for j in range(count)}
+
+    def _set_head(self, entry: str, six) -> None:
+        fn = self._need(entry)
+        tensors = [_dev(t.detach(), self.device, torch.float32) for t in six]
         args = []
         for weight, bias in zip(tensors[0::2], tensors[1::2]):
             if weight.dim() != 2 or tuple(bias.shape) != (weight.shape[0],):
@@ -1017,7 +1059,8 @@ class Context:
     def set_ablation(self, pairs=()) -> None:
         """Install the set of (level, unit) pairs the classify calls zero (level 0..4 or its
         name in `ablation_levels`: 'conv1', 'layer1'..'layer4' on a ResNet, 'conv1'..'conv5'
-        on AlexNet); an empty sequence clears it.  Duplicates and order do
+        on AlexNet, the five `features.N` of the blocks' last convs on a VGG); an empty
+        sequence clears it.  Duplicates and order do
         not matter.  `encode*` / `describe` never read it.  Synchronises the stream."""
         fn = self._need('milan_set_ablation')
         levels, units, count = self._unit_arrays(pairs)
@@ -2312,6 +2355,17 @@ def lrn(x: torch.Tensor, local_size: int, alpha: float, beta: float,
     return y
 
 
+def vgg_level_names(blocks: Sequence[int]) -> Tuple[str, ...]:
+    """torchvision's names of the last conv of each VGG block: `features.N` with a ReLU
+    behind every conv and a pool behind every block ((2, 2, 3, 3, 3) -> features.2 / 7 / 14 /
+    21 / 28, the reference's LAYERS.VGG16)."""
+    names, at = [], 0
+    for count in blocks:
+        names.append(f'features.{at + 2 * (count - 1)}')
+        at += 2 * count + 1
+    return tuple(names)
+
+
 def make_dims(state_dict: Dict[str, torch.Tensor],
               n_vocab_tokens: int,
               blocks: Sequence[int] = (3, 4, 23, 3)) -> Dims:
@@ -2322,6 +2376,8 @@ def make_dims(state_dict: Dict[str, torch.Tensor],
     width = kind = None
     if pre + 'features.0.weight' in sd:  # 'alexnet' config
         kind, width = TRUNK_ALEXNET, sd[pre + 'features.0.weight'].shape[0]
+    elif pre + 'vgg.1.0.weight' in sd:  # a VGG, its `features.N` renamed to `vgg.B.J`
+        kind, width = TRUNK_VGG, sd[pre + 'vgg.1.0.weight'].shape[0]
     elif pre + 'conv5.weight' in sd:  # the Places365 AlexNet (conv1..conv5 by name)
         kind = TRUNK_ALEXNET_PLACES
         if sd[pre + 'conv1.weight'].shape[0] % 3:

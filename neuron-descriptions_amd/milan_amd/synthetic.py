@@ -181,6 +181,49 @@ def places_alexnet_state_dict(seed: int = 0,
     return sd
 
 
+# torchvision's VGGs without batch norm: convs per block, and a block's channels per unit of
+# width (64): 64, 128, 256, 512, 512
+VGG_BLOCKS = {
+    'vgg11': (1, 1, 2, 2, 2),
+    'vgg13': (2, 2, 2, 2, 2),
+    'vgg16': (2, 2, 3, 3, 3),
+    'vgg19': (2, 2, 4, 4, 4),
+}
+VGG_CHANNELS = (1, 2, 4, 8, 8)
+
+
+def vgg_feature_indices(config: str) -> Tuple[Tuple[int, ...], ...]:
+    """Per block, the indices of its convs in torchvision's `features` Sequential (conv, ReLU
+    per conv, one MaxPool2d after each block): vgg16 -> ((0, 2), (5, 7), (10, 12, 14), ...)."""
+    out, at = [], 0
+    for count in VGG_BLOCKS[config]:
+        out.append(tuple(at + 2 * j for j in range(count)))
+        at += 2 * count + 1
+    return tuple(out)
+
+
+def vgg_state_dict(config: str = 'vgg16',
+                   seed: int = 0,
+                   width: int = 64,
+                   hidden: int = 4096,
+                   classes: int = 1000) -> Dict[str, torch.Tensor]:
+    """Synthetic state dict of a torchvision VGG (`features.N`, `classifier.0 / 3 / 6`).
+    Weights are randn * sqrt(2 / fan_in), biases 0.05 * randn: activations keep their scale
+    through the trunk."""
+    g = _gen(seed)
+    sd: Dict[str, torch.Tensor] = {}
+    cin = 3
+    for mult, indices in zip(VGG_CHANNELS, vgg_feature_indices(config)):
+        for index in indices:
+            sd[f'features.{index}.weight'] = _conv(g, mult * width, cin, 3)
+            sd[f'features.{index}.bias'] = 0.05 * torch.randn(mult * width, generator=g)
+            cin = mult * width
+    for index, fan, out in ((0, cin * 49, hidden), (3, hidden, hidden), (6, hidden, classes)):
+        sd[f'classifier.{index}.weight'] = torch.randn(out, fan, generator=g) * (2.0 / fan)**0.5
+        sd[f'classifier.{index}.bias'] = 0.05 * torch.randn(out, generator=g)
+    return sd
+
+
 def _linear(g: torch.Generator, sd: Dict[str, torch.Tensor], name: str,
             out_f: int, in_f: int, scale: float = 1.0) -> None:
     bound = scale / in_f**0.5

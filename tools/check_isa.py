@@ -80,6 +80,16 @@ PINNED = {
     'conv3_p64_kernel': {'mfma': 162, 'lds_dma': 20, 'global_load_x4': 36, 'global_store_x4': 4, 'barriers': 5, 'scratch': 0, 'vmcnt': [0, 5], 'scratch_in_loops': 0, 'hazards': 0},
     'stem_fused_kernelILi7ELi8ELi8ELb0': {'mfma': 84, 'lds_dma': 6, 'global_load_x4': 33, 'global_store_x4': 10, 'barriers': 3, 'scratch': 6, 'vmcnt': [0], 'scratch_in_loops': 3, 'hazards': 0},
     'stem_fused_kernelILi7ELi8ELi8ELb1': {'mfma': 84, 'lds_dma': 0, 'global_load_x4': 33, 'global_store_x4': 10, 'barriers': 5, 'scratch': 8, 'vmcnt': [0], 'scratch_in_loops': 4, 'hazards': 0},
+    # VGG (classify.o): no counted waits of their own (vmcnt is the compiler's: not pinned); what
+    # is pinned is what their byte counts rest on -- an 8-channel piece moves as two 16-byte
+    # operations per pixel, nothing spills
+    'vgg_first_kernelILb0': {'mfma': 0, 'lds_dma': 0, 'global_load_x4': 0, 'global_store_x4': 4, 'barriers': 1, 'scratch': 0, 'vmcnt': None, 'scratch_in_loops': 0, 'hazards': 0},
+    'vgg_first_kernelILb1': {'mfma': 0, 'lds_dma': 0, 'global_load_x4': 0, 'global_store_x4': 4, 'barriers': 1, 'scratch': 0, 'vmcnt': None, 'scratch_in_loops': 0, 'hazards': 0},
+    'maxpool2s2_kernelILb0ELb0': {'mfma': 0, 'lds_dma': 0, 'global_load_x4': 8, 'global_store_x4': 2, 'barriers': 0, 'scratch': 0, 'vmcnt': None, 'scratch_in_loops': 0, 'hazards': 0},
+    'maxpool2s2_kernelILb0ELb1': {'mfma': 0, 'lds_dma': 0, 'global_load_x4': 8, 'global_store_x4': 2, 'barriers': 0, 'scratch': 0, 'vmcnt': None, 'scratch_in_loops': 0, 'hazards': 0},
+    'maxpool2s2_kernelILb1ELb1': {'mfma': 0, 'lds_dma': 0, 'global_load_x4': 8, 'global_store_x4': 2, 'barriers': 0, 'scratch': 0, 'vmcnt': None, 'scratch_in_loops': 0, 'hazards': 0},
+    'vgg_tail_kernelILb0': {'mfma': 0, 'lds_dma': 0, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 0, 'scratch': 0, 'vmcnt': None, 'scratch_in_loops': 0, 'hazards': 0},
+    'vgg_tail_kernelILb1': {'mfma': 0, 'lds_dma': 0, 'global_load_x4': 0, 'global_store_x4': 0, 'barriers': 0, 'scratch': 0, 'vmcnt': None, 'scratch_in_loops': 0, 'hazards': 0},
 }
 
 
@@ -356,7 +366,7 @@ def main():
     args = ap.parse_args()
     build = pathlib.Path(args.build_dir)
     seen, bad, hazard_detail = {}, [], {}
-    for obj in ('chain3.o', 'gemm.o', 'chain.o', 'conv3.o', 'stem.o'):
+    for obj in ('chain3.o', 'gemm.o', 'chain.o', 'conv3.o', 'stem.o', 'classify.o'):
         path = build / obj
         if not path.exists():
             bad.append(f'{path} is missing: build the library first')

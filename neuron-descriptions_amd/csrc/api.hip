@@ -399,7 +399,8 @@ int milan_set_alexnet_head(milan_ctx* c, const float* fc6_weight, const float* f
   const float* w[3] = {fc6_weight, fc7_weight, linear8_weight};
   const float* b[3] = {fc6_bias, fc7_bias, linear8_bias};
   const int out[3] = {fc6_out, fc7_out, linear8_out}, in[3] = {fc6_in, fc7_in, linear8_in};
-  return classify_set_alexnet_head(c, w, b, out, in, (hipStream_t)stream);
+  return classify_set_head(c, *seq_family(MILAN_TRUNK_ALEXNET), w, b, out, in,
+                           (hipStream_t)stream);
 }
 
 int milan_set_vgg_head(milan_ctx* c, const float* fc0_weight, const float* fc0_bias, int fc0_out,
@@ -413,7 +414,7 @@ int milan_set_vgg_head(milan_ctx* c, const float* fc0_weight, const float* fc0_b
   const float* w[3] = {fc0_weight, fc3_weight, fc6_weight};
   const float* b[3] = {fc0_bias, fc3_bias, fc6_bias};
   const int out[3] = {fc0_out, fc3_out, fc6_out}, in[3] = {fc0_in, fc3_in, fc6_in};
-  return classify_set_vgg_head(c, w, b, out, in, (hipStream_t)stream);
+  return classify_set_head(c, *seq_family(MILAN_TRUNK_VGG), w, b, out, in, (hipStream_t)stream);
 }
 
 int milan_vgg_trace(const milan_ctx* c, int32_t* launches, int32_t* split) {

@@ -814,16 +814,19 @@ static bool alex_trunk(const milan_ctx* c) {
 static bool places_trunk(const milan_ctx* c) {
   return c->d.trunk_kind == MILAN_TRUNK_ALEXNET_PLACES;
 }
-// either of them: AlexTrunk walks it
-static bool alexnet_trunk(const milan_ctx* c) { return alex_trunk(c) || places_trunk(c); }
-// VGG: like the Places net it taps and ablates without a head; VggTrunk walks it
+// VGG: like the Places net it taps and ablates without a head
 static bool vgg_trunk(const milan_ctx* c) { return c->d.trunk_kind == MILAN_TRUNK_VGG; }
-static bool classifier_trunk(const milan_ctx* c) {
-  return resnet_trunk(c) || alexnet_trunk(c) || vgg_trunk(c);
+// the sequential nets: SeqTrunk walks them, seq_family has their row
+static bool seq_trunk(const milan_ctx* c) {
+  return alex_trunk(c) || places_trunk(c) || vgg_trunk(c);
 }
+static bool classifier_trunk(const milan_ctx* c) { return resnet_trunk(c) || seq_trunk(c); }
 static const char* level_names(const milan_ctx* c) {
-  if (vgg_trunk(c)) return "the last conv of blocks 1..5";
-  return alexnet_trunk(c) ? "conv1..conv5" : "conv1, layer1..layer4";
+  return seq_trunk(c) ? seq_family(c->d.trunk_kind)->levels : "conv1, layer1..layer4";
+}
+// the width of level l of a sequential net
+static int seq_channels(const milan_ctx* c, int l) {
+  return vgg_trunk(c) ? c->vgg[l][0].cout : c->alex[l].cout;
 }
 static int level_channels(const milan_ctx* c, int level) {
   const int wd = c->d.trunk_width;
@@ -850,22 +853,18 @@ static int init_mask_table(milan_ctx* c, const int* channels, hipStream_t s) {
 // called from milan_finalize_weights after encoder_finalize: keeps fc.weight / fc.bias when the
 // state dict has them (a context without them runs everything but the classify calls)
 int classify_finalize(milan_ctx* c, hipStream_t s) {
-  if (vgg_trunk(c)) {
-    if (c->stem.w == nullptr) return 0;
-    // (vgg_first_kernel keeps 28 x width floats in LDS)
-    MILAN_REQUIRE(c->d.trunk_width <= 512, MILAN_ERR_SHAPE,
-                  "the VGG trunk takes widths up to 512 (got %d)", c->d.trunk_width);
-    int channels[5];
-    for (int l = 0; l < 5; ++l) channels[l] = c->vgg[l][0].cout;
-    return init_mask_table(c, channels, s);
-  }
-  if (places_trunk(c) && c->stem.w != nullptr) {
-    int channels[5];
-    for (int l = 0; l < 5; ++l) channels[l] = c->alex[l].cout;
-    return init_mask_table(c, channels, s);
-  }
-  if (!resnet_trunk(c) || c->stem.w == nullptr) return 0;
+  const SeqFamily* fam = seq_family(c->d.trunk_kind);
+  if ((fam == nullptr && !resnet_trunk(c)) || c->stem.w == nullptr) return 0;
   int channels[5];
+  if (fam != nullptr) {
+    // (torchvision's AlexNet gets its table with its head: until then it only encodes)
+    if (fam->no_head == nullptr) return 0;
+    // (vgg_first_kernel keeps 28 x width floats in LDS)
+    MILAN_REQUIRE(!fam->vgg || c->d.trunk_width <= 512, MILAN_ERR_SHAPE,
+                  "the VGG trunk takes widths up to 512 (got %d)", c->d.trunk_width);
+    for (int l = 0; l < 5; ++l) channels[l] = seq_channels(c, l);
+    return init_mask_table(c, channels, s);
+  }
   for (int l = 0; l < 5; ++l) channels[l] = level_channels(c, l);
   MILAN_TRY(init_mask_table(c, channels, s));
   const std::string p = "encoder.encoder.model.";
@@ -926,7 +925,7 @@ int classify_set_ablation(milan_ctx* c, const int32_t* levels, const int32_t* un
 
 // ---------------------------------------------------------------------------
 // driver: one pass loop, one sweep loop and one workspace dry run, written over
-// a trunk.  A trunk (ResNetTrunk; AlexTrunk, which walks both AlexNets; VggTrunk) is one
+// a trunk.  A trunk (ResNetTrunk; SeqTrunk, which walks the AlexNets and the VGGs) is one
 // pass's plan and walker: it derives from Trunk, fills h / w / lvl_sz and split_tap_scale when it is made, and
 // supplies
 //   carve(a)           its own buffers out of the arena, in its own order
@@ -1134,63 +1133,175 @@ struct ResNetTrunk : Trunk {
   }
 };
 
-// The two AlexNets in eval mode: torchvision's alexnet_seq and the Places365 one
-// (the reference's src/deps/alexnet.py).  Levels 0..4 are conv1..conv5; a level's
-// tensor is relu(conv + bias) * mask, the conv run with the encoder's bias + ReLU epilogue (no
-// mask launch for a level without units).  Every level has a buffer of its own, so the sweep
-// holds a level where it is.  The convs' shapes, paddings and groups are in c->alex (AlexSpec,
-// DESIGN 4.28): the Places net has conv1 without padding and conv2 / conv4 / conv5 grouped
-// (ConvW::groups: one launch each, the group a grid dimension).  Here it differs in an optional
-// LRN after pool1 and pool2 (c->lrn, which only it can set), in what it asks of the image
-// (check_geometry, walk) and in having no adaptive pool in front of fc6 (head).
-// Formats in the split mode: conv l runs on the split kernels when its weights have a split
-// copy (sp[l]), in fp32 otherwise, as level 0 (3 input channels) does in every mode; a level's
-// tensor is in the format its reader takes -- the pools convert fp32 to split on the way, conv3
-// writes fp32 when conv4 is an fp32 level.  torchvision's convs all have a split copy when
-// `split` is on (classify_checks): its levels 1..4 are split at scale 1.  The Places net's
-// grouped convs have one when their per-group input width is a multiple of 32.
-struct AlexTrunk : Trunk {
-  const bool places;  // the Places365 net
-  int hq[3], wq[3];   // pool1, pool2, pool5
-  bool sp[5];         // conv l reads (and multiplies) split operands
-  float *in4, *a[5], *q[2], *qn[2], *flat, *f6, *f7;
+// One step of a sequential net's pass.  A step reads what the step in front of it
+// wrote (the first one of a walk: the walk's `src`).
+struct SeqStep {
+  // RAW: the image -> NHWC4 fp32 for an AlexNet's conv1; VGG_FIRST: the image -> relu(conv1_1 +
+  // bias), vgg_first_kernel; POOL3 / POOL2: the 3x3 / 2 and 2x2 / 2 max-pools; CONV: relu(conv +
+  // bias) on the GEMM tile
+  enum Kind { RAW, VGG_FIRST, POOL3, POOL2, LRN, CONV } kind;
+  const ConvW* cw;           // CONV, VGG_FIRST
+  int hi, wi, ho, wo, C;     // extents of what it reads and writes, channels of what it writes
+  bool in_split, out_split;  // the formats it reads and writes (SeqTrunk::formats)
+  int dst;                   // the buffer it writes (SeqTrunk::buf)
+  int level;                 // -1, or the level whose tensor it writes: mask and emit follow
+  int slot;                  // its slot in milan_vgg_trace, or -1
+};
 
-  AlexTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
-      : Trunk{c, n, H, W, split, s, 1.f}, places(places_trunk(c)) {
-    alex_geometry(c, H, W, h, w, hq, wq);
+// VGG: every pool halves (floor), so level l needs 2^l pixels each way; a walk asks before it
+// launches anything, milan_activations per requested level.  (The AlexNets ask pass by pass and
+// pool by pool: SeqTrunk::check_geometry, walk.)
+static int seq_reach(const milan_ctx* c, int H, int W, int to) {
+  MILAN_REQUIRE(!vgg_trunk(c) || to < 0 || ((H >> to) >= 1 && (W >> to) >= 1), MILAN_ERR_SHAPE,
+                "classify: image %dx%d is too small for VGG level %d (%dx%d at least)", H, W, to,
+                1 << (to < 0 ? 0 : to), 1 << (to < 0 ? 0 : to));
+  return 0;
+}
+
+// The sequential nets in eval mode: torchvision's alexnet_seq (4.23), the
+// Places365 AlexNet (4.27; the reference's src/deps/alexnet.py) and torchvision's VGG-11 / 13 /
+// 16 / 19 without batch norm (4.30), each walked from a step plan that the constructor fills.
+// A level's tensor is relu(conv + bias) * mask, the conv run with the encoder's bias + ReLU
+// epilogue (no mask launch for a level without units).  Every level has a buffer of its own, so
+// the sweep holds a level where it is.
+//   AlexNets: levels 0..4 are conv1..conv5, shapes, paddings and groups in c->alex (AlexSpec,
+//   DESIGN 4.28; a grouped conv is one launch, the group a grid dimension); pool1 and pool2,
+//   each with the Places net's optional LRN behind it (c->lrn), sit in front of conv2 and conv3.
+//   VGG: five blocks of 3x3 / pad 1 convs (c->vgg, as the uploaded keys gave them), a 2x2 / 2
+//   pool in front of blocks 2..5; level l is the last conv of block l + 1.  The convs inside a
+//   block and the pools write two scratch buffers in turn; conv1_1 reads the image itself.
+// What the families differ in besides the plan is their row of SeqFamily (common.h).
+struct SeqTrunk : Trunk {
+  const SeqFamily& fam;
+  SeqStep st[32];
+  int ns = 0;
+  int end[5] = {0, 0, 0, 0, 0};  // one past the step that writes level l
+  size_t bsz[12];                // floats per image of buffer i, in carve order
+  int nbuf = 0;
+  float *buf[12], *flat, *f6, *f7;
+  int th, tw;                    // pool5's extent, which the head's tail kernel reads
+  int hh, ww;                    // (while the plan is made: the extent in flight)
+
+  SeqTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
+      : Trunk{c, n, H, W, split, s, 1.f}, fam(*seq_family(c->d.trunk_kind)), hh(H), ww(W) {
+    if (fam.vgg) plan_vgg(); else plan_alexnet();
+    formats();
+  }
+
+  int buffer(size_t floats) { bsz[nbuf] = floats; return nbuf++; }
+  SeqStep& step(SeqStep::Kind kind, const ConvW* cw, int ho, int wo, int C, int dst,
+                int level = -1, int slot = -1) {
+    st[ns] = SeqStep{kind, cw, hh, ww, ho, wo, C, false, false, dst, level, slot};
+    hh = ho; ww = wo;
+    if (level >= 0) end[level] = ns + 1;
+    return st[ns++];
+  }
+
+  // buffers: in4, a[0..4], then q[0], qn[0], q[1], qn[1] (the LRN's qn with c->lrn alone)
+  void plan_alexnet() {
+    int hq[3], wq[3], a[5], q[2], qn[2];
+    alex_geometry(c, hin, win, h, w, hq, wq);
     // (an image too small for the trunk is refused before anything is used: check_geometry)
     for (int l = 0; l < 5; ++l)
       lvl_sz[l] = (size_t)std::max(h[l], 0) * std::max(w[l], 0) * c->abl_ch[l];
-    sp[0] = false;
-    for (int l = 1; l < 5; ++l) sp[l] = split && c->alex[l].ws != nullptr;
-    // (no pool between conv3, conv4 and conv5: an fp32 level cannot hand on split values)
-    for (int l = 3; l < 5; ++l) sp[l] = sp[l] && sp[l - 1];
-    fmt[1] = sp[1];
-    fmt[2] = sp[3];
-    fmt[3] = sp[4];
-    fmt[4] = sp[4];
+    th = hq[2]; tw = wq[2];
+    const int in4 = buffer((size_t)hin * win * 4);
+    for (int l = 0; l < 5; ++l) a[l] = buffer(lvl_sz[l]);
+    for (int l = 0; l < 2; ++l) {
+      const size_t sz = (size_t)std::max(hq[l], 0) * std::max(wq[l], 0) * c->abl_ch[l];
+      q[l] = buffer(sz);
+      qn[l] = c->lrn.size > 0 ? buffer(sz) : -1;
+    }
+    step(SeqStep::RAW, nullptr, hin, win, 4, in4);
+    for (int l = 0; l < 5; ++l) {
+      if (l == 1 || l == 2) {
+        step(SeqStep::POOL3, nullptr, hq[l - 1], wq[l - 1], c->abl_ch[l - 1], q[l - 1]);
+        if (qn[l - 1] >= 0) step(SeqStep::LRN, nullptr, hh, ww, c->abl_ch[l - 1], qn[l - 1]);
+      }
+      // (h[l] x w[l] is what the launch computes: alex_geometry reads the same ConvW)
+      step(SeqStep::CONV, &c->alex[l], h[l], w[l], c->abl_ch[l], a[l], l);
+    }
+  }
+
+  // buffers: lv[0..4], then the two scratch buffers, each as large as the largest level (a
+  // pool's output is no larger than the level behind it, a conv's inside block b as large)
+  void plan_vgg() {
+    int lv[5], sc[2];
+    h[0] = hin; w[0] = win;
+    for (int l = 1; l < 5; ++l) { h[l] = h[l - 1] / 2; w[l] = w[l - 1] / 2; }
+    for (int l = 0; l < 5; ++l) lvl_sz[l] = (size_t)h[l] * w[l] * c->abl_ch[l];
+    th = h[4] / 2; tw = w[4] / 2;
+    for (int l = 0; l < 5; ++l) lv[l] = buffer(lvl_sz[l]);
+    for (int k = 0; k < 2; ++k) sc[k] = buffer(*std::max_element(lvl_sz, lvl_sz + 5));
+    for (int b = 0; b < 5; ++b) {
+      const int nb = c->vgg_n[b];
+      if (b > 0) step(SeqStep::POOL2, nullptr, h[b], w[b], c->abl_ch[b - 1], sc[0]);
+      for (int j = 0; j < nb; ++j) {
+        // (the level's buffer, or the scratch buffer that the input is not in)
+        const int dst = j == nb - 1 ? lv[b] : (ns > 0 && st[ns - 1].dst == sc[0] ? sc[1] : sc[0]);
+        const int level = j == nb - 1 ? b : -1;
+        if (b > 0 || j > 0) {
+          step(SeqStep::CONV, &c->vgg[b][j], h[b], w[b], c->abl_ch[b], dst, level, 4 * b + j);
+          continue;
+        }
+        // vgg_first_kernel writes the format that the second conv of the net can take, also
+        // across a pool (vgg11: level 0 is then a split tensor and pool1 reads one)
+        const ConvW& second = nb > 1 ? c->vgg[0][1] : c->vgg[1][0];
+        step(SeqStep::VGG_FIRST, &c->vgg[0][0], h[0], w[0], c->abl_ch[0], dst, level, 0)
+            .out_split = split && second.ws != nullptr;
+      }
+    }
+  }
+
+  // The format rule of the split mode, once for every plan.  A conv multiplies split operands
+  // (in_split) when its weights have a split copy and its input can arrive split: a pool
+  // converts fp32 to split on the way, a conv that reads split operands writes either format, a
+  // conv that reads fp32 writes fp32 (conv1 of an AlexNet: 3 input channels).  A step then
+  // writes what its reader takes: a pool and an LRN the format of the next conv, a conv in
+  // front of a conv that conv's (an fp32 conv behind a split one gets fp32, GemmArgs::out_split
+  // = 0), a conv in front of a pool or the head the format it reads itself.  There is no
+  // conversion back to fp32 except that hand-over; walk() asserts that none is needed.  The one
+  // step outside the rule is VGG_FIRST, whose format plan_vgg has set.  Split activations sit
+  // at scale 1.
+  void formats() {
+    bool can = false;   // the tensor in flight can be had in split format
+    for (int k = 0; k < ns; ++k) {
+      SeqStep& t = st[k];
+      if (t.kind == SeqStep::CONV) can = t.in_split = split && t.cw->ws != nullptr && can;
+      else if (t.kind == SeqStep::POOL3 || t.kind == SeqStep::POOL2) can = true;
+      else if (t.kind == SeqStep::VGG_FIRST) can = t.out_split;
+    }
+    bool next = false;  // what the next conv down the plan reads
+    for (int k = ns - 1; k >= 0; --k) {
+      SeqStep& t = st[k];
+      if (t.kind == SeqStep::CONV) {
+        t.out_split = k + 1 < ns && st[k + 1].kind == SeqStep::CONV ? next : t.in_split;
+        next = t.in_split;
+      } else if (t.kind != SeqStep::VGG_FIRST) {
+        t.out_split = next;
+      }
+    }
+    for (int k = 1; k < ns; ++k)
+      if (st[k].kind != SeqStep::CONV) st[k].in_split = st[k - 1].out_split;
+    for (int l = 0; l < 5; ++l) fmt[l] = end[l] > 0 && st[end[l] - 1].out_split;
   }
 
   void carve(Arena& ar) {
     const milan_ctx::AlexHead& hd = c->ahead;
-    in4 = ar.get<float>((size_t)n * hin * win * 4);
-    for (int l = 0; l < 5; ++l) a[l] = ar.get<float>((size_t)n * lvl_sz[l]);
-    for (int l = 0; l < 2; ++l) {
-      const size_t sz = (size_t)n * std::max(hq[l], 0) * std::max(wq[l], 0) * c->abl_ch[l];
-      q[l] = ar.get<float>(sz);
-      qn[l] = c->lrn.size > 0 ? ar.get<float>(sz) : nullptr;
-    }
+    for (int i = 0; i < nbuf; ++i) buf[i] = ar.get<float>((size_t)n * bsz[i]);
     flat = ar.get<float>((size_t)n * hd.in[0]);
     f6 = ar.get<float>((size_t)n * hd.out[0]);
     f7 = ar.get<float>((size_t)n * hd.out[1]);
   }
   void carve_hold(Arena&, size_t) {}
 
-  // torchvision: the smallest image leaves one pixel after pool5 (63 x 63).  Places: conv1 needs
-  // an 11 x 11 image; a pool needs 3 pixels each way, which walk() asks for when it has to cross
-  // one (19 x 19 reaches conv2, 35 x 35 every level); a classify call needs 6 x 6 after pool5
-  // (classify_checks)
+  // torchvision's AlexNet: the smallest image leaves one pixel after pool5 (63 x 63).  Places:
+  // conv1 needs an 11 x 11 image; a pool needs 3 pixels each way, which walk() asks for when it
+  // has to cross one (19 x 19 reaches conv2, 35 x 35 every level); a classify call needs 6 x 6
+  // after pool5 (SeqFamily::tail_lo, classify_checks).  VGG: seq_reach.
   int check_geometry() const {
+    if (fam.vgg) return 0;
+    const bool places = places_trunk(c);
     // (the unpadded conv1: C's division rounds the extent of a smaller image up to 1)
     MILAN_REQUIRE(!places || (hin >= 11 && win >= 11 && h[0] >= 1 && w[0] >= 1), MILAN_ERR_SHAPE,
                   "classify: image %dx%d is too small for the Places365 AlexNet's 11x11 conv1",
@@ -1203,72 +1314,88 @@ struct AlexTrunk : Trunk {
     return 0;
   }
 
-  // ResNetTrunk::walk's contract
+  // ResNetTrunk::walk's contract: the steps between two level boundaries
   int walk(int from, int to, const float* src, const float** out) const {
+    MILAN_TRY(seq_reach(c, hin, win, to));
     const float* x = src;
-    int ho, wo;
-    if (from < 0) {
-      MILAN_TRY(launch_raw_input(src, n, hin, win, false, in4, c->status, s));
-      MILAN_TRY(launch_gemm(encoder_conv_args(c->alex[0], in4, n, hin, win, a[0], EPI_BIAS_RELU,
-                                              nullptr, c->zero, &ho, &wo, false), s));
-      if (c->abl_count[0] > 0) MILAN_TRY(mask(0, a[0], a[0], -1));
-      x = a[0];
-      from = 0;
-      if (tap[0]) MILAN_TRY(emit(0, x));
-    }
-    for (int l = from + 1; l <= to; ++l) {
-      int hh = h[l - 1], ww = w[l - 1];
-      if (l <= 2) {
-        // pool1 / pool2 write the format conv2 / conv3 read, the LRN keeps it
-        const int C = c->abl_ch[l - 1];
-        // (torchvision's net has asked for all three pools in check_geometry)
-        MILAN_REQUIRE(hh >= 3 && ww >= 3, MILAN_ERR_SHAPE,
-                      "classify: image %dx%d is too small for the Places365 AlexNet: pool%d needs "
-                      "3x3 pixels and gets %dx%d (19x19 reaches conv2, 35x35 every level)",
-                      hin, win, l, hh, ww);
-        MILAN_REQUIRE(sp[l] || !fmt[l - 1], MILAN_ERR_STATE,
-                      "internal: alexnet level %d would need a split -> fp32 pool", l);
-        MILAN_TRY(launch_maxpool3s2(x, n, hh, ww, C, hq[l - 1], wq[l - 1], sp[l], fmt[l - 1],
-                                    q[l - 1], c->status, s));
-        x = q[l - 1];
-        hh = hq[l - 1]; ww = wq[l - 1];
-        if (c->lrn.size > 0) {
-          MILAN_TRY(launch_lrn(x, (long long)n * hh * ww, C, sp[l], c->lrn.size, c->lrn.alpha,
-                               c->lrn.beta, qn[l - 1], c->status, s));
-          x = qn[l - 1];
+    bool xs = from >= 0 && fmt[from];   // the format of x
+    int at = from;                      // the level behind x
+    for (int k = from < 0 ? 0 : end[from]; to >= 0 && k < end[to]; ++k) {
+      const SeqStep& t = st[k];
+      float* y = buf[t.dst];
+      const bool conv = t.kind == SeqStep::CONV;
+      MILAN_REQUIRE(t.in_split == xs && (conv ? t.in_split || !t.out_split
+                                              : t.out_split || !t.in_split),
+                    MILAN_ERR_STATE,
+                    "internal: step %d towards level %d would read a tensor of the other format, "
+                    "write split from fp32 operands, or convert split to fp32", k, at + 1);
+      switch (t.kind) {
+        case SeqStep::RAW:
+          MILAN_TRY(launch_raw_input(x, n, t.hi, t.wi, false, y, c->status, s));
+          break;
+        case SeqStep::VGG_FIRST:
+          MILAN_TRY(launch_vgg_first(x, n, t.hi, t.wi, t.C, c->vgg_w27, t.cw->bias, t.out_split,
+                                     y, c->status, s));
+          break;
+        case SeqStep::POOL3:
+          // (torchvision's net has asked for all three pools in check_geometry)
+          MILAN_REQUIRE(t.hi >= 3 && t.wi >= 3, MILAN_ERR_SHAPE,
+                        "classify: image %dx%d is too small for the Places365 AlexNet: pool%d "
+                        "needs 3x3 pixels and gets %dx%d (19x19 reaches conv2, 35x35 every level)",
+                        hin, win, at + 1, t.hi, t.wi);
+          MILAN_TRY(launch_maxpool3s2(x, n, t.hi, t.wi, t.C, t.ho, t.wo, t.out_split, t.in_split,
+                                      y, c->status, s));
+          break;
+        case SeqStep::POOL2:
+          MILAN_TRY(launch_maxpool2s2(x, n, t.hi, t.wi, t.C, t.in_split, t.out_split, y,
+                                      c->status, s));
+          break;
+        case SeqStep::LRN:
+          MILAN_TRY(launch_lrn(x, (long long)n * t.hi * t.wi, t.C, t.in_split, c->lrn.size,
+                               c->lrn.alpha, c->lrn.beta, y, c->status, s));
+          break;
+        case SeqStep::CONV: {
+          int ho, wo;
+          GemmArgs g = encoder_conv_args(*t.cw, x, n, t.hi, t.wi, y, EPI_BIAS_RELU, nullptr,
+                                         c->zero, &ho, &wo, t.in_split, false);
+          if (!t.out_split) g.out_split = 0;   // (a split conv in front of an fp32 one)
+          MILAN_TRY(launch_gemm(g, s));
+          break;
         }
       }
-      // (ho x wo is h[l] x w[l]: alex_geometry reads the same ConvW)
-      GemmArgs g = encoder_conv_args(c->alex[l], x, n, hh, ww, a[l], EPI_BIAS_RELU, nullptr,
-                                     c->zero, &ho, &wo, sp[l], false);
-      if (sp[l] && !fmt[l]) g.out_split = 0;   // the next level is an fp32 one
-      MILAN_REQUIRE(sp[l] || !fmt[l], MILAN_ERR_STATE,
-                    "internal: alexnet level %d is fp32 and would have to write split", l);
-      MILAN_TRY(launch_gemm(g, s));
-      if (c->abl_count[l] > 0) MILAN_TRY(mask(l, a[l], a[l], -1));
-      x = a[l];
-      if (tap[l]) MILAN_TRY(emit(l, x));
+      if (t.slot >= 0) {
+        ++c->vgg_launches[t.slot];
+        c->vgg_split[t.slot] = t.in_split;
+      }
+      x = y; xs = t.out_split;
+      if (t.level < 0) continue;
+      at = t.level;
+      if (c->abl_count[at] > 0) MILAN_TRY(mask(at, y, y, -1));
+      if (tap[at]) MILAN_TRY(emit(at, x));
     }
     *out = x;
     return 0;
   }
 
-  // pool5 + adaptive average pool + flatten in (C, h, w) order, fc6 / fc7 / linear8 (+ argmax)
-  // of the masked level-4 tensor; dropout is the identity in eval mode.  The Places net has no
-  // adaptive pool: with the 6 x 6 pooled pixels it requires, every bin of alex_tail_kernel's
-  // average is one pixel, divided by 1.
+  // pool5 + adaptive average pool + flatten in (C, h, w) order (the family's tail kernel: the two
+  // add up their bins in different orders), fc6 / fc7 / linear8 or classifier.0 / .3 / .6 (+
+  // argmax) of the masked level-4 tensor; dropout is the identity in eval mode.  The Places net
+  // has no adaptive pool: with the 6 x 6 pooled pixels it requires, every bin of
+  // alex_tail_kernel's average is one pixel, divided by 1.
   int head(const float* x4, float* lg, long long* pr) const {
     const milan_ctx::AlexHead& hd = c->ahead;
     const int C = c->abl_ch[4];
-    MILAN_REQUIRE(!places || (hq[2] == 6 && wq[2] == 6 && hd.installed), MILAN_ERR_STATE,
-                  "internal: places head without 6 x 6 features or fc layers");
-    const dim3 grid((36 * C + 255) / 256, n);
-    if (fmt[4])
-      hipLaunchKernelGGL(alex_tail_kernel<true>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
-                         wq[2], 1.f, flat);
+    MILAN_REQUIRE(hd.installed && std::min(th, tw) >= fam.tail_lo &&
+                      std::max(th, tw) <= fam.tail_hi,
+                  MILAN_ERR_STATE,
+                  "internal: head without fc layers or with %d x %d pixels after pool5", th, tw);
+    const dim3 grid((fam.bins * fam.bins * C + 255) / 256, n);
+    const auto vgg_tail = fmt[4] ? vgg_tail_kernel<true> : vgg_tail_kernel<false>;
+    const auto alex_tail = fmt[4] ? alex_tail_kernel<true> : alex_tail_kernel<false>;
+    if (fam.vgg)
+      hipLaunchKernelGGL(vgg_tail, grid, dim3(256), 0, s, x4, h[4], w[4], C, th, tw, flat);
     else
-      hipLaunchKernelGGL(alex_tail_kernel<false>, grid, dim3(256), 0, s, x4, h[4], w[4], C, hq[2],
-                         wq[2], 1.f, flat);
+      hipLaunchKernelGGL(alex_tail, grid, dim3(256), 0, s, x4, h[4], w[4], C, th, tw, 1.f, flat);
     MILAN_CHECK_HIP(hipGetLastError());
     MILAN_TRY(linear_run(flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, f6, s));
     MILAN_TRY(linear_run(f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, f7, s));
@@ -1287,140 +1414,6 @@ struct AlexTrunk : Trunk {
   }
 };
 
-// torchvision's VGG-11 / 13 / 16 / 19 without batch norm in eval mode: five blocks
-// of 3x3 / pad 1 convs (c->vgg, as the uploaded keys gave them), a 2x2 / 2 pool after each.
-// Level l is the output of the last conv of block l + 1 with AlexTrunk's semantics: relu(conv +
-// bias) x mask, the conv run with the encoder's bias + ReLU epilogue.  The five levels have a
-// buffer each (the sweep holds them where they are); the convs inside a block and the pools
-// write two scratch buffers in turn.  walk() runs, for each block it crosses, the pool and then
-// the block's convs; conv1_1 reads the image itself (vgg_first_kernel).
-// Formats in the split mode, conv by conv in network order: conv i multiplies split operands
-// (rd[i]) when its weights have a split copy (cin % 32 == 0) and its input was written in
-// split format -- by the pool in front of it, which converts on the way, by vgg_first_kernel,
-// or by a split conv.  A conv writes the format it reads (of[i] = rd[i]); vgg_first_kernel
-// writes the one the next conv can take.  Channel widths never shrink along a VGG, so a split
-// tensor never has to feed an fp32 conv: walk() asserts that and there is no conversion back.
-// Split activations sit at scale 1, as on the AlexNets.
-struct VggTrunk : Trunk {
-  int nconv = 0;
-  int cb[20], cj[20];       // block and place in its block of conv i (network order)
-  int first[5];             // block b's first conv
-  bool rd[20], of[20];      // conv i reads split operands / writes split format
-  float *lv[5], *sc[2], *flat, *f6, *f7;
-
-  VggTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
-      : Trunk{c, n, H, W, split, s, 1.f} {
-    h[0] = H; w[0] = W;
-    for (int l = 1; l < 5; ++l) { h[l] = h[l - 1] / 2; w[l] = w[l - 1] / 2; }
-    for (int l = 0; l < 5; ++l) lvl_sz[l] = (size_t)h[l] * w[l] * c->abl_ch[l];
-    for (int b = 0; b < 5; ++b) {
-      first[b] = nconv;
-      for (int j = 0; j < c->vgg_n[b]; ++j) { cb[nconv] = b; cj[nconv] = j; ++nconv; }
-    }
-    auto want = [&](int i) { return split && c->vgg[cb[i]][cj[i]].ws != nullptr; };
-    rd[0] = false;
-    of[0] = nconv > 1 && want(1);
-    for (int i = 1; i < nconv; ++i) {
-      rd[i] = want(i) && (cj[i] == 0 || of[i - 1]);
-      of[i] = rd[i];
-    }
-    for (int b = 0; b < 5 && nconv > 0; ++b) fmt[b] = of[first[b] + c->vgg_n[b] - 1];
-  }
-
-  void carve(Arena& ar) {
-    const milan_ctx::AlexHead& hd = c->ahead;
-    for (int l = 0; l < 5; ++l) lv[l] = ar.get<float>((size_t)n * lvl_sz[l]);
-    // (a pool's output is no larger than the level behind it, a conv's inside block b as large)
-    const size_t sc_sz = *std::max_element(lvl_sz, lvl_sz + 5);
-    for (int k = 0; k < 2; ++k) sc[k] = ar.get<float>((size_t)n * sc_sz);
-    flat = ar.get<float>((size_t)n * hd.in[0]);
-    f6 = ar.get<float>((size_t)n * hd.out[0]);
-    f7 = ar.get<float>((size_t)n * hd.out[1]);
-  }
-  void carve_hold(Arena&, size_t) {}
-  // (what a call asks of the image depends on the level it walks to: walk())
-  int check_geometry() const { return 0; }
-
-  void trace(int i, bool split_operands) const {
-    ++c->vgg_launches[cb[i] * 4 + cj[i]];
-    c->vgg_split[cb[i] * 4 + cj[i]] = split_operands;
-  }
-
-  // ResNetTrunk::walk's contract
-  int walk(int from, int to, const float* src, const float** out) const {
-    // every pool halves (floor): level l needs 2^l pixels each way.  Nothing has been launched.
-    MILAN_REQUIRE(to < 0 || (h[to] >= 1 && w[to] >= 1), MILAN_ERR_SHAPE,
-                  "classify: image %dx%d is too small for VGG level %d (%dx%d at least)", hin,
-                  win, to, 1 << (to < 0 ? 0 : to), 1 << (to < 0 ? 0 : to));
-    const float* x = src;
-    bool xs = from >= 0 && fmt[from];   // the format of x
-    for (int b = from + 1; b <= to; ++b) {
-      const int hh = h[b], ww = w[b], i0 = first[b], nb = c->vgg_n[b];
-      int j = 0;
-      if (b == 0) {
-        float* dst = nb == 1 ? lv[0] : sc[0];
-        MILAN_TRY(launch_vgg_first(src, n, hin, win, c->abl_ch[0], c->vgg_w27, c->vgg[0][0].bias,
-                                   of[0], dst, c->status, s));
-        trace(0, false);
-        x = dst; xs = of[0];
-        j = 1;
-      } else {
-        MILAN_REQUIRE(rd[i0] || !xs, MILAN_ERR_STATE,
-                      "internal: vgg block %d is fp32 behind a split level", b + 1);
-        MILAN_TRY(launch_maxpool2s2(x, n, h[b - 1], w[b - 1], c->abl_ch[b - 1], xs, rd[i0], sc[0],
-                                    c->status, s));
-        x = sc[0]; xs = rd[i0];
-      }
-      for (; j < nb; ++j) {
-        const int i = i0 + j;
-        // (the scratch buffer the input is not in)
-        float* dst = j == nb - 1 ? lv[b] : (x == sc[0] ? sc[1] : sc[0]);
-        MILAN_REQUIRE(rd[i] == xs, MILAN_ERR_STATE,
-                      "internal: vgg conv %d.%d would read a tensor of the other format", b + 1, j);
-        int ho, wo;
-        MILAN_TRY(launch_gemm(encoder_conv_args(c->vgg[b][j], x, n, hh, ww, dst, EPI_BIAS_RELU,
-                                                nullptr, c->zero, &ho, &wo, rd[i], false), s));
-        trace(i, rd[i]);
-        x = dst; xs = of[i];
-      }
-      if (c->abl_count[b] > 0) MILAN_TRY(mask(b, lv[b], lv[b], -1));
-      if (tap[b]) MILAN_TRY(emit(b, x));
-    }
-    *out = x;
-    return 0;
-  }
-
-  // pool5 + adaptive average pool + flatten in (C, h, w) order, classifier.0 / .3 / .6 (+ argmax)
-  // of the masked level-4 tensor; dropout is the identity in eval mode
-  int head(const float* x4, float* lg, long long* pr) const {
-    const milan_ctx::AlexHead& hd = c->ahead;
-    const int C = c->abl_ch[4];
-    MILAN_REQUIRE(hd.installed && h[4] >= 2 && w[4] >= 2, MILAN_ERR_STATE,
-                  "internal: vgg head without fc layers or without a pixel after pool5");
-    const dim3 grid((49 * C + 255) / 256, n);
-    if (fmt[4])
-      hipLaunchKernelGGL(vgg_tail_kernel<true>, grid, dim3(256), 0, s, x4, h[4], w[4], C,
-                         h[4] / 2, w[4] / 2, flat);
-    else
-      hipLaunchKernelGGL(vgg_tail_kernel<false>, grid, dim3(256), 0, s, x4, h[4], w[4], C,
-                         h[4] / 2, w[4] / 2, flat);
-    MILAN_CHECK_HIP(hipGetLastError());
-    MILAN_TRY(linear_run(flat, hd.w[0], hd.b[0], n, hd.in[0], hd.out[0], true, f6, s));
-    MILAN_TRY(linear_run(f6, hd.w[1], hd.b[1], n, hd.in[1], hd.out[1], true, f7, s));
-    MILAN_TRY(linear_run(f7, hd.w[2], hd.b[2], n, hd.in[2], hd.out[2], false, lg, s));
-    if (pr) {
-      hipLaunchKernelGGL(row_argmax_kernel, dim3(n), dim3(64), 0, s, lg, hd.out[2], pr);
-      MILAN_CHECK_HIP(hipGetLastError());
-    }
-    return 0;
-  }
-
-  // AlexTrunk::hold_level: every level has a buffer of its own
-  int hold_level(const float* images, int at, int level, const float** held) const {
-    return walk(at, level, at < 0 ? images : *held, held);
-  }
-};
-
 template <class T>
 static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
   Arena a; a.dry = true;
@@ -1432,8 +1425,7 @@ static size_t workspace_dry(const milan_ctx* c, int n_images, int H, int W, int 
 
 size_t classify_workspace(const milan_ctx* c, int n_images, int H, int W, int sweep_units) {
   if (n_images <= 0 || H < 1 || W < 1) return 0;
-  if (vgg_trunk(c)) return workspace_dry<VggTrunk>(c, n_images, H, W, sweep_units);
-  if (alexnet_trunk(c)) return workspace_dry<AlexTrunk>(c, n_images, H, W, sweep_units);
+  if (seq_trunk(c)) return workspace_dry<SeqTrunk>(c, n_images, H, W, sweep_units);
   if (resnet_trunk(c)) return workspace_dry<ResNetTrunk>(c, n_images, H, W, sweep_units);
   return 0;
 }
@@ -1518,51 +1510,26 @@ static int sweep(milan_ctx* c, const float* images, int n, int H, int W, bool sp
   return 0;
 }
 
-static int install_head(milan_ctx* c, const char* what, const float* const* w,
-                        const float* const* b, const int* out, const int* in,
-                        const int* channels, hipStream_t s);
-
-// milan_set_alexnet_head: fc6 / fc7 / linear8 (device fp32, row-major (out, in)) packed into
-// library-owned memory; switches the classify family on for this AlexNet context
-int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
-                              const int* out, const int* in, hipStream_t s) {
-  MILAN_REQUIRE(c->d.trunk_kind == MILAN_TRUNK_ALEXNET || places_trunk(c), MILAN_ERR_ARG,
-                "milan_set_alexnet_head: the context's trunk is not AlexNet");
+// milan_set_alexnet_head (fc6 / fc7 / linear8) and milan_set_vgg_head (classifier.0 / .3 / .6):
+// the three Linear layers (device fp32, row-major (out, in)) packed into library-owned memory.
+// `asked`: a row of the family that the entry point serves.  Switches the classify family on
+// for a torchvision AlexNet context.
+int classify_set_head(milan_ctx* c, const SeqFamily& asked, const float* const* w,
+                      const float* const* b, const int* out, const int* in, hipStream_t s) {
+  const SeqFamily* fam = seq_family(c->d.trunk_kind);
+  const char* what = asked.setter;
+  MILAN_REQUIRE(fam != nullptr && fam->vgg == asked.vgg, MILAN_ERR_ARG,
+                "%s: the context's trunk is not %s", what, asked.trunk);
   MILAN_REQUIRE(c->stem.w != nullptr, MILAN_ERR_STATE, "encoder weights were not uploaded");
-  const int c5 = c->alex[4].cout;
-  MILAN_REQUIRE(out[0] >= 1 && out[1] >= 1 && out[2] >= 1 && in[0] == c5 * 36 &&
+  int channels[5];
+  for (int l = 0; l < 5; ++l) channels[l] = seq_channels(c, l);
+  const int per = fam->bins * fam->bins;
+  MILAN_REQUIRE(out[0] >= 1 && out[1] >= 1 && out[2] >= 1 && in[0] == channels[4] * per &&
                     in[1] == out[0] && in[2] == out[1],
                 MILAN_ERR_SHAPE,
-                "milan_set_alexnet_head: fc6 (%d, %d), fc7 (%d, %d), linear8 (%d, %d) do not "
-                "chain from %d x 36 features",
-                out[0], in[0], out[1], in[1], out[2], in[2], c5);
-  int channels[5];
-  for (int l = 0; l < 5; ++l) channels[l] = c->alex[l].cout;
-  return install_head(c, "milan_set_alexnet_head", w, b, out, in, channels, s);
-}
-
-// milan_set_vgg_head: classifier.0 / .3 / .6 into the same storage
-int classify_set_vgg_head(milan_ctx* c, const float* const* w, const float* const* b,
-                          const int* out, const int* in, hipStream_t s) {
-  MILAN_REQUIRE(vgg_trunk(c), MILAN_ERR_ARG,
-                "milan_set_vgg_head: the context's trunk is not a VGG");
-  MILAN_REQUIRE(c->stem.w != nullptr, MILAN_ERR_STATE, "encoder weights were not uploaded");
-  const int c5 = c->vgg[4][0].cout;
-  MILAN_REQUIRE(out[0] >= 1 && out[1] >= 1 && out[2] >= 1 && in[0] == c5 * 49 &&
-                    in[1] == out[0] && in[2] == out[1],
-                MILAN_ERR_SHAPE,
-                "milan_set_vgg_head: classifier.0 (%d, %d), .3 (%d, %d), .6 (%d, %d) do not "
-                "chain from %d x 49 features",
-                out[0], in[0], out[1], in[1], out[2], in[2], c5);
-  int channels[5];
-  for (int l = 0; l < 5; ++l) channels[l] = c->vgg[l][0].cout;
-  return install_head(c, "milan_set_vgg_head", w, b, out, in, channels, s);
-}
-
-// the three Linear layers packed into library-owned memory (`what`: the calling entry point)
-static int install_head(milan_ctx* c, const char* what, const float* const* w,
-                        const float* const* b, const int* out, const int* in,
-                        const int* channels, hipStream_t s) {
+                "%s: %s (%d, %d), %s (%d, %d), %s (%d, %d) do not chain from %d x %d features",
+                what, fam->fc[0], out[0], in[0], fam->fc[1], out[1], in[1], fam->fc[2], out[2],
+                in[2], channels[4], per);
   milan_ctx::AlexHead& hd = c->ahead;
   for (int i = 0; i < 3; ++i) {
     // (a second call with the same widths reuses the first one's memory)
@@ -1621,33 +1588,26 @@ static int classify_checks(milan_ctx* c, int n, int H, int W, bool* split, bool 
                 "trunk whose head milan_set_alexnet_head has installed");
   MILAN_REQUIRE(c->stem.w != nullptr && c->abl_mask != nullptr, MILAN_ERR_STATE,
                 "encoder weights were not uploaded");
-  MILAN_REQUIRE(!head || !places_trunk(c) || c->ahead.installed, MILAN_ERR_STATE,
-                "this Places365 AlexNet context has no head: milan_set_alexnet_head installs "
-                "fc6 / fc7 / fc8");
-  MILAN_REQUIRE(!head || !vgg_trunk(c) || c->ahead.installed, MILAN_ERR_STATE,
-                "this VGG context has no head: milan_set_vgg_head installs classifier.0 / .3 / "
-                ".6");
-  MILAN_REQUIRE(!head || alexnet_trunk(c) || vgg_trunk(c) || c->fc_w != nullptr, MILAN_ERR_STATE,
+  const SeqFamily* fam = seq_family(c->d.trunk_kind);
+  MILAN_REQUIRE(!head || fam == nullptr || c->ahead.installed, MILAN_ERR_STATE, "%s",
+                fam->no_head);
+  MILAN_REQUIRE(!head || fam != nullptr || c->fc_w != nullptr, MILAN_ERR_STATE,
                 "this context was created without fc.weight: it has no classifier head");
   MILAN_REQUIRE(!c->trunk_f16, MILAN_ERR_ARG,
                 "classification runs in the f32 and split_f16 modes, not in the fast f16 mode");
   MILAN_REQUIRE(n > 0 && H >= 1 && W >= 1, MILAN_ERR_SHAPE,
                 "classify: need n>0 and H,W>=1 (got n=%d H=%d W=%d)", n, H, W);
-  if (places_trunk(c) && head) {
-    // fc6 reads C5 x 6 x 6 features and there is no adaptive pool in front of it
-    int h[5], w[5], hq[3], wq[3];
-    alex_geometry(c, H, W, h, w, hq, wq);
-    MILAN_REQUIRE(h[0] >= 3 && w[0] >= 3 && hq[2] == 6 && wq[2] == 6, MILAN_ERR_SHAPE,
-                  "classify: image %dx%d does not leave 6x6 after pool5 of the Places365 AlexNet "
-                  "(227x227 does; fc6 reads %d features)", H, W, c->ahead.in[0]);
+  if (head && fam != nullptr && fam->head_image != nullptr) {
+    // what pool5 has to leave: the Places net's fc6 reads C5 x 6 x 6 features with no adaptive
+    // pool in front of it, a VGG's adaptive pool needs a pixel (32 x 32: five 2x2 pools)
+    const SeqTrunk t(c, 1, H, W, false, nullptr);
+    MILAN_REQUIRE(t.h[0] >= 3 && t.w[0] >= 3 && std::min(t.th, t.tw) >= fam->tail_lo &&
+                      std::max(t.th, t.tw) <= fam->tail_hi,
+                  MILAN_ERR_SHAPE, fam->head_image, H, W, c->ahead.in[0]);
   }
-  // (VGG: pool5 has to leave a pixel for the adaptive pool)
-  MILAN_REQUIRE(!head || !vgg_trunk(c) || (H >= 32 && W >= 32), MILAN_ERR_SHAPE,
-                "classify: image %dx%d is too small for VGG (32x32 at least: five 2x2 pools)", H,
-                W);
   bool sp = c->precision == MILAN_PRECISION_SPLIT_F16 && c->d.trunk_width % 8 == 0;
   // (Places: conv3 is dense and reads a multiple of 64 channels; the grouped levels decide for
-  // themselves, AlexTrunk::sp)
+  // themselves, SeqTrunk::formats)
   if (places_trunk(c)) sp = sp && c->alex[2].ws != nullptr;
   // (AlexNet: conv1 has 3 input channels and stays fp32, as in alexnet_run_batch)
   for (int l = 1; l < 5 && sp && alex_trunk(c); ++l) sp = c->alex[l].ws != nullptr;
@@ -1663,7 +1623,7 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
   bool split;
   MILAN_TRY(classify_checks(c, n, H, W, &split));
   vgg_trace_reset(c);
-  auto go = vgg_trunk(c) ? run<VggTrunk> : alexnet_trunk(c) ? run<AlexTrunk> : run<ResNetTrunk>;
+  auto go = seq_trunk(c) ? run<SeqTrunk> : run<ResNetTrunk>;
   return go(c, images, n, H, W, split, logits, predictions, nullptr, 4, "classify", ws, s);
 }
 
@@ -1675,8 +1635,7 @@ int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const
   MILAN_TRY(check_units(c, levels, units, count, "milan_classify_sweep"));
   if (count == 0) return 0;
   vgg_trace_reset(c);
-  auto go = vgg_trunk(c) ? sweep<VggTrunk>
-                         : alexnet_trunk(c) ? sweep<AlexTrunk> : sweep<ResNetTrunk>;
+  auto go = seq_trunk(c) ? sweep<SeqTrunk> : sweep<ResNetTrunk>;
   return go(c, images, n, H, W, split, levels, units, count, targets, correct, predictions, ws, s);
 }
 
@@ -1692,11 +1651,8 @@ int activations_run(milan_ctx* c, const float* images, int n, int H, int W, cons
     MILAN_REQUIRE(levels[i] >= 0 && levels[i] <= 4, MILAN_ERR_ARG,
                   "milan_activations: level %d is not one of 0..4 (%s)", levels[i],
                   level_names(c));
-    // (VggTrunk::walk's check, ahead of the one for an output that such a level leaves empty)
-    MILAN_REQUIRE(!vgg_trunk(c) || ((H >> levels[i]) >= 1 && (W >> levels[i]) >= 1),
-                  MILAN_ERR_SHAPE,
-                  "classify: image %dx%d is too small for VGG level %d (%dx%d at least)", H, W,
-                  levels[i], 1 << levels[i], 1 << levels[i]);
+    // (the walk's own question, ahead of the one for an output that such a level leaves empty)
+    MILAN_TRY(seq_reach(c, H, W, levels[i]));
     MILAN_REQUIRE(taps[levels[i]] == nullptr, MILAN_ERR_ARG,
                   "milan_activations: level %d is requested twice", levels[i]);
     MILAN_REQUIRE(outputs[i] != nullptr, MILAN_ERR_ARG,
@@ -1704,13 +1660,12 @@ int activations_run(milan_ctx* c, const float* images, int n, int H, int W, cons
     taps[levels[i]] = outputs[i];
     top = std::max(top, (int)levels[i]);
   }
-  // (the messages about the workspace and the sub-batch have named the call differently on
-  // the two trunks since they were written)
-  const bool alex = alexnet_trunk(c);
   vgg_trace_reset(c);
-  auto go = vgg_trunk(c) ? run<VggTrunk> : alex ? run<AlexTrunk> : run<ResNetTrunk>;
+  auto go = seq_trunk(c) ? run<SeqTrunk> : run<ResNetTrunk>;
+  // (SeqFamily::taps_call: the families' messages about the workspace and the sub-batch name
+  // the call as they did when each was written)
   return go(c, images, n, H, W, split, nullptr, nullptr, taps, top,
-            alex ? "classify" : "activations", ws, s);
+            seq_trunk(c) ? seq_family(c->d.trunk_kind)->taps_call : "activations", ws, s);
 }
 
 }  // namespace milan

@@ -652,7 +652,7 @@ namespace milan {
 // ---- the two AlexNets ------------------------------------------
 // What torchvision's AlexNet (MILAN_TRUNK_ALEXNET) and the Places365 one
 // (MILAN_TRUNK_ALEXNET_PLACES) differ in when encoder_finalize packs conv1..conv5 into
-// milan_ctx::alex; whatever runs them afterwards (alexnet_plan, AlexTrunk) reads alex[l].
+// milan_ctx::alex; whatever runs them afterwards (alexnet_plan, SeqTrunk) reads alex[l].
 struct AlexSpec {
   const char* key[5];  // conv l in the state dict, under the trunk's prefix
   int stride[5], pad[5];
@@ -667,6 +667,48 @@ inline const AlexSpec& alex_spec(int trunk_kind) {
       {{"conv1", "conv2", "conv3", "conv4", "conv5"},
        {4, 1, 1, 1, 1}, {0, 2, 1, 1, 1}, {3, 8, 12, 12, 8}, true, true}};
   return spec[trunk_kind == MILAN_TRUNK_ALEXNET_PLACES];
+}
+
+// ---- the sequential classifier trunks ---------------------------
+// What the nets that classify.hip's SeqTrunk walks differ in outside their step plans: one row
+// per trunk kind.  The message texts are the ones each family had when it was added.
+//   vgg         the convs are milan_ctx::vgg (alex otherwise)
+//   bins        the tail's bins each way: fc reads bins x bins features per channel
+//   tail_lo/hi  pixels each way that pool5 has to leave for the head
+//   levels      the five levels, for messages
+//   setter, trunk, fc   the entry point that installs the head, what it calls the trunk it asks
+//               for, and the three Linear layers
+//   no_head     classify on a context without a head (nullptr: such a context is no classifier)
+//   head_image  (H, W, fc in): an image that the head cannot take (nullptr: the pass refuses it,
+//               SeqTrunk::check_geometry)
+//   taps_call   what milan_activations' workspace and sub-batch messages call it
+struct SeqFamily {
+  bool vgg;
+  int bins, tail_lo, tail_hi;
+  const char *levels, *setter, *trunk, *fc[3], *no_head, *head_image, *taps_call;
+};
+inline const SeqFamily* seq_family(int trunk_kind) {
+  static const SeqFamily alexnet = {
+      false, 6, 1, 1 << 30, "conv1..conv5", "milan_set_alexnet_head", "AlexNet",
+      {"fc6", "fc7", "linear8"}, nullptr, nullptr, "classify"};
+  static const SeqFamily places = {
+      false, 6, 6, 6, "conv1..conv5", "milan_set_alexnet_head", "AlexNet",
+      {"fc6", "fc7", "linear8"},
+      "this Places365 AlexNet context has no head: milan_set_alexnet_head installs fc6 / fc7 / "
+      "fc8",
+      "classify: image %dx%d does not leave 6x6 after pool5 of the Places365 AlexNet (227x227 "
+      "does; fc6 reads %d features)",
+      "classify"};
+  static const SeqFamily vgg = {
+      true, 7, 1, 1 << 30, "the last conv of blocks 1..5", "milan_set_vgg_head", "a VGG",
+      {"classifier.0", ".3", ".6"},
+      "this VGG context has no head: milan_set_vgg_head installs classifier.0 / .3 / .6",
+      "classify: image %dx%d is too small for VGG (32x32 at least: five 2x2 pools)",
+      "activations"};
+  return trunk_kind == MILAN_TRUNK_ALEXNET          ? &alexnet
+         : trunk_kind == MILAN_TRUNK_ALEXNET_PLACES ? &places
+         : trunk_kind == MILAN_TRUNK_VGG            ? &vgg
+                                                    : nullptr;
 }
 
 inline int conv_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
@@ -735,12 +777,11 @@ int classify_run(milan_ctx* c, const float* images, int n, int H, int W, float* 
 int classify_sweep(milan_ctx* c, const float* images, int n, int H, int W, const int32_t* levels,
                    const int32_t* units, int count, const int64_t* targets, int32_t* correct,
                    int64_t* predictions, Arena& ws, hipStream_t s);
-int classify_set_alexnet_head(milan_ctx* c, const float* const* w, const float* const* b,
-                              const int* out, const int* in, hipStream_t s);
+// milan_set_alexnet_head / milan_set_vgg_head: `asked` is a row of the family the entry point
+// serves (fc6 / fc7 / linear8, or classifier.0 / 3 / 6, into the same storage)
+int classify_set_head(milan_ctx* c, const SeqFamily& asked, const float* const* w,
+                      const float* const* b, const int* out, const int* in, hipStream_t s);
 int classify_set_alexnet_lrn(milan_ctx* c, int local_size, float alpha, float beta);
-// milan_set_vgg_head: classify_set_alexnet_head's storage and packing for classifier.0 / 3 / 6
-int classify_set_vgg_head(milan_ctx* c, const float* const* w, const float* const* b,
-                          const int* out, const int* in, hipStream_t s);
 // conv1_1's OIHW weight (cout, 3, 3, 3) -> (27, cout), k = (kh * 3 + kw) * 3 + c (classify.hip)
 int vgg_pack_first(const float* w_oihw, int cout, float* w27, hipStream_t s);
 // across-channel LRN over (pixels, C) with a pixel's channels contiguous, fp32 or split at

@@ -8,6 +8,8 @@
 #include <map>
 
 #include "../../include/milan_hip.h"
+// Epilogue, GemmArgs, shift_group, OutMode -- and the launch plan that reads them
+#include "gemm_plan.h"
 
 // experiments build (make EXPERIMENTS=1): measured-and-rejected kernels and the
 // knobs that force tile configurations; see gemm.hip and DESIGN.md section 5
@@ -41,146 +43,10 @@ void set_error(const char* fmt, ...);
     if (_r != 0) return _r;                                                \
   } while (0)
 
-// ---- implicit-GEMM (conv / linear) -----------------------------------------
-enum Epilogue : int {
-  EPI_BIAS = 0,           // C = acc + bias
-  EPI_BIAS_RELU = 1,      // C = relu(acc + bias)
-  EPI_BIAS_RES_RELU = 2,  // C = relu(acc + bias + aux)
-  EPI_BIAS_TANH = 3,      // C = tanh(acc + bias)
-  EPI_BIAS_SIGMUL = 4,    // C = sigmoid(acc + bias) * aux
-  EPI_BIAS_ADD = 5,       // C = acc + bias + aux
-  EPI_LSTM = 6,           // acc + bias = an LSTM's gate pre-activations, columns
-                          // gate-interleaved per 16 units ([i16 f16 g16 o16] per 64):
-                          // C = h' (ldc), C2 = c' (ldc), aux = c (ldaux), Cs =
-                          // optional split-format copy of h' (ldc); N = 4 H
-  EPI_LSE = 7,            // x = acc + bias is NOT written: per row m and 64-column block cb,
-                          // C[m * ldc + 2 cb] = { max x, sum exp(x - max) } (ldc = 2 ceil(N / 64)),
-                          // and lse_x[m] = x[m][lse_tgt[m * lse_tgt_stride]] -- what a log-softmax
-                          // read at one target column needs (the LM's rerank pass, decoder.hip)
-};
-
-// C[M][N] (row stride ldc) = epi( A (*) W^T + bias ), fp32 MFMA, exact f32.
-// A is an NHWC activation tensor addressed as an implicit im2col matrix:
-//   row m = (img, ho, wo), column kk = (kh, kw, cin) with cin fastest.
-// A plain linear layer is the 1x1 case with H = W = 1 and `a_pix_stride`
-// the row stride of the (possibly strided) input matrix.
-constexpr int MILAN_TAP_CLASSES = 9;  // 3 y-ranges x 3 x-ranges (GemmArgs::tap_cls)
-struct GemmArgs {
-  const float* A;
-  const float* W;     // packed [N][Kp], Kp = round_up(K, 32), zero padded
-  const float* bias;  // [N] or nullptr
-  const float* aux;   // residual / multiplicand, row stride ldaux, or nullptr
-  float* C;
-  int M, N, K, Kp;
-  int ldc, ldaux;
-  // conv geometry
-  int H, Wd, Cin, Ho, Wo, KH, KW, stride, pad;
-  long a_pix_stride;  // floats between consecutive input pixels (>= Cin)
-  long a_img_stride;  // floats between consecutive images
-  int epilogue;
-  const float* zero;  // >= 64 B of zeros (device)
-  int flop_k;         // algorithmic K for FLOP accounting (0 = K)
-  // split-f16 mode (see gemm.hip): A and W hold (hi,lo) f16 pairs
-  int a_split;        // 1: run the 3xf16 MFMA main loop
-  int out_split;      // 1: write C in split format (N % 8 == 0)
-  int aux_split;      // 1: aux is in split format
-  float acc_scale;    // accumulators are multiplied by this (1 / weight scale)
-  int out_mode;       // filled by the launcher (OUT_*)
-  // optional second operand source (split16 kernels only): k >= K1 reads a
-  // 1x1 / stride `stride2` convolution input A2 (H2 x W2d pixels, no padding).
-  // Used to fold a bottleneck's downsample conv into its c3 (K-concatenation).
-  const float* W3;    // 3x3 convs: split weights packed chunk-major
-                      // [N][Cin/16][9 taps][16 slots] (conv3x3_split16_kernel)
-  const float* A2;
-  int K1, H2, W2d, stride2;
-  long a2_pix_stride, a2_img_stride;
-  // anisotropic geometry (general igemm path only): when aniso != 0 the
-  // horizontal stride / padding are stride_w / pad_w instead of stride / pad.
-  // Used by the pixel-pair stem (encoder.hip).
-  int aniso, stride_w, pad_w;
-  int debug;          // MILAN_ABLATE timing experiments (0 in production): 1 no MFMA,
-                      // 2 no DMA (igemm_kernel); 4 epilogue only, 8 main loop only (split16)
-  int tile_hint;      // 0 auto (the kernel follows from the layer's N, K, kernel size);
-                      // experiments: 1 / 2 the round-1 256x128x3 / 128x128x2 kernels, 3 / 4 / 5
-                      // split16 256x256x4 / 256x128x3 / 128x256x3, 6 / 10 N <= 64 on / off the
-                      // 64x64-wave-tile split16 kernel, 8 the LDS-strip 3x3 kernel
-  int stagger;        // experiments build: half of the first-round workgroups of an expand conv
-                      // start this many microseconds late (MILAN_STAGGER)
-  long long* prof;    // experiments build: per-phase cycle sums over all workgroups (16 counters)
-  int chunk_major;    // experiments build, split16 kernels, k x k convs: k runs (16-channel chunk,
-                      // tap) with the taps INNER -- the KH*KW pieces of a pixel are requested in
-                      // consecutive k-tiles and hit L2 -- and W is packed to match (ConvW::ws3)
-  float* C2;          // EPI_LSTM: new cell state
-  float* Cs;          // EPI_LSTM: h' once more in split format, or nullptr
-  unsigned* status;   // device status word (MILAN_STATUS_* bits) or nullptr; filled by the
-                      // launcher from the calling context (set_status_word)
-  int f16;            // fast mode (MILAN_PRECISION_F16): A, W, aux and C hold PLAIN f16 values, 2
-                      // bytes per element.  Every K-side quantity above (Cin, K, Kp, K1, pixel /
-                      // image strides, ldc, ldaux) is then given in 4-byte units, i.e. HALF the
-                      // element count: a row of C f16 channels is addressed exactly like a
-                      // split-format row of C / 2 channels, and the ping-pong kernel multiplies
-                      // "hi . hi + lo . lo" of that pretended row = one f16 MFMA per 16 real k
-  const float* Wt;    // k x k convs, Cin % 32 == 0: the rows of W with k running (32-channel slice, tap,
-                      // channel) instead of (tap, channel) -- ConvW::wst.  The ping-pong kernel then
-                      // asks for the KH * KW shifted copies of a slice in CONSECUTIVE k-tile pairs:
-                      // they hit L2 instead of crossing the fabric once per tap (gemm.hip, TAPI)
-  int tap_inner;      // filled by the launcher: this launch runs in that order
-  const long long* lse_tgt;  // EPI_LSE: target column of row m at lse_tgt[m * lse_tgt_stride]
-  long lse_tgt_stride;
-  float* lse_x;              // EPI_LSE: [M] the target column's x
-  // Row count known only on the DEVICE (round 6; encoder.hip, MILAN_FUSE_SKIP_EMPTY): when
-  // m_live != nullptr the launch is sized for M rows but only the first min(M, *m_live *
-  // m_live_mul) hold work -- the kernel reads the word with a scalar load, workgroups whose
-  // tiles lie beyond it exit, the tile that straddles it masks its rows as for a ragged M.
-  // No host read-back, no hipStreamSynchronize (live_rows() below).
-  const int* m_live;
-  // Row list (gemm.hip, split16_pp32_tile<.., LIST>; encoder.hip, MILAN_FUSE_TAIL_LISTS): when
-  // row_list != nullptr the launch computes only the output rows row_list[0 .. *m_live)
-  // (m_live_mul = 1) -- ascending rows (slot * Ho + ho) * Wo + wo of the DENSE tensors: tile
-  // row r of tile tm is entry 256 * tm + r, its operand rows are read and its output row is
-  // written in place, unlisted rows are not touched.  256 consecutive entries must span at
-  // most 256 slots (the caller's guarantee; row_list_supported() checks the offset range of
-  // that many images).  Same products, same order, same roundings per output value as the
-  // dense launch.
-  const int* row_list;
-  int m_live_mul;
-  // Border-class tiles of a tap-inner launch (gemm.hip, tap_classes(); MILAN_TAP_SKIP).  The
-  // output pixels of an image are grouped by WHICH taps fall inside the input: class c is the
-  // rectangle y0 <= ho < y0 + ny, x0 <= wo < x0 + nx with tap mask (bit kh * KW + kw).  A tile
-  // holds 256 pixels of one class (image-major) and runs only the taps of its mask.  Filled by
-  // the launcher, classes by descending tap count; 0 = linear tile order (all taps).  A caller
-  // sets tap_ncls = -1 to keep a launch on the linear order (test hook).
-  int tap_ncls;
-  int tap_cls[MILAN_TAP_CLASSES][5];  // y0, ny, x0, nx, mask
-  // Grouped convolution: `groups` > 1 runs that many independent products of
-  // the SAME geometry in one launch, the group a grid dimension (blockIdx.y).  Every field
-  // above describes ONE group (N, Cin, K, Kp are per-group; ldc and a_pix_stride the full
-  // rows); group q reads A + q * a_grp, W (Wt) + q * w_grp, bias + q * bias_grp, aux +
-  // q * aux_grp and writes C + q * c_grp (floats).  A grouped kernel shifts its copy of the
-  // arguments at entry (shift_group) and runs unchanged; groups <= 1 is the plain launch.
-  int groups;
-  long a_grp, w_grp, bias_grp, c_grp, aux_grp;
-};
-static_assert(sizeof(GemmArgs) % 4 == 0, "GemmArgs is reloaded word by word");
-
-// group `q` of a grouped launch as a plain launch on offset pointers: what a grouped kernel
-// does to its arguments at entry, and what the per-group baseline (MILAN_GROUP_LAUNCH=0)
-// launches one by one
-__host__ __device__ inline void shift_group(GemmArgs& g, int q) {
-  g.A += (long)q * g.a_grp;
-  g.W += (long)q * g.w_grp;
-  if (g.Wt) g.Wt += (long)q * g.w_grp;
-  if (g.bias) g.bias += (long)q * g.bias_grp;
-  if (g.aux) g.aux += (long)q * g.aux_grp;
-  g.C += (long)q * g.c_grp;
-  g.groups = 1;
-}
-
-enum OutMode : int { OUT_SCALAR = 0, OUT_VEC4 = 1, OUT_SPLIT8 = 2, OUT_F16 = 3 };
-
+// ---- implicit-GEMM (conv / linear): GemmArgs and the plan of a launch are in gemm_plan.h ----
 int launch_gemm(const GemmArgs& g, hipStream_t s);
 // whether launch_gemm() can run `g` on a row list (GemmArgs::row_list) with the bits of the
-// dense launch: the 256-column ping-pong tile, offsets of 256 images within 32 bits
+// dense launch: whether its plan names a pp32l form (gemm_plan.h)
 bool row_list_supported(const GemmArgs& g);
 // Status word of the context whose entry point is running on this thread (api.hip sets it
 // on entry): every kernel that writes split format ORs MILAN_STATUS_SATURATED into it when

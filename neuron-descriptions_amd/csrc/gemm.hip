@@ -2657,21 +2657,6 @@ __global__ __launch_bounds__(2 * (BN / 64) * 64, 2) void conv3x3_split16_kernel(
                        tile_n * BN + wn * 64);
 }
 
-template <int BN>
-static int launch_conv3x3(const GemmArgs& g, hipStream_t s) {
-  constexpr int NT = 2 * (BN / 64) * 64;
-  const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + BN - 1) / BN;
-  size_t lds = sizeof(float) * (size_t)(4 * BN * 16 + 2 * 384 * 16 + 16 + (NT / 64) * 256);
-  const size_t stage_bytes = size_t(NT / 64) * 32 * 68 * sizeof(float);
-  if (lds < stage_bytes) lds = stage_bytes;
-  auto kern = conv3x3_split16_kernel<BN>;
-  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(NT), lds, s, g, tiles_m,
-                     tiles_n);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
 #endif  // MILAN_EXPERIMENTS (LDS-strip 3x3 kernel)
 
 // ---------------------------------------------------------------------------
@@ -2724,45 +2709,6 @@ int launch_f32_to_split(const float* src, long ld_src, float* dst, long ld_dst,
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(f32_to_split_kernel, dim3((int)blocks), dim3(256), 0, s, src,
                      ld_src, dst, ld_dst, rows, K, scale, status_word(), nanrow, stamp);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// launch
-// ---------------------------------------------------------------------------
-template <int BM, int BN, int STAGES, bool CIN32, bool SPLIT>
-static int launch_cfg(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-  constexpr int NT = (BM / 64) * (BN / 64) * 64;
-  size_t lds = size_t(STAGES) * (BM + BN) * 32 * sizeof(float);
-  const size_t stage_bytes = size_t(NT / 64) * 32 * 68 * sizeof(float);
-  if (lds < stage_bytes) lds = stage_bytes;
-  auto kern = igemm_kernel<BM, BN, STAGES, CIN32, SPLIT>;
-  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(NT), lds, s, g,
-                     tiles_m, tiles_n);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// set by the launchers that have a grouped form (GemmArgs::groups > 1): launch_gemm() fails a
-// grouped launch that the dispatch sent anywhere else (it would run group 0 alone)
-static thread_local bool t_group_taken = false;
-
-// the general fp32 kernel with the group as grid.y
-template <int BM, int BN, int STAGES, bool CIN32>
-static int launch_cfg_grouped(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-  constexpr int NT = (BM / 64) * (BN / 64) * 64;
-  size_t lds = size_t(STAGES) * (BM + BN) * 32 * sizeof(float);
-  const size_t stage_bytes = size_t(NT / 64) * 32 * 68 * sizeof(float);
-  if (lds < stage_bytes) lds = stage_bytes;
-  auto kern = igemm_kernel<BM, BN, STAGES, CIN32, false, true>;
-  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-  t_group_taken = true;
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n, g.groups), dim3(NT), lds, s, g, tiles_m,
-                     tiles_n);
   MILAN_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -2951,603 +2897,131 @@ int profile_read_stages(double* table) {
   return 0;
 }
 
-template <int BM, int BN, int STAGES, int SHAPE>
-static int launch_split16_impl(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-  constexpr int NT = (BM / 128) * (BN / 64) * 64;
-  size_t lds = size_t(STAGES) * (BM + BN) * 16 * sizeof(float);
-  const size_t stage_bytes = size_t(NT / 64) * 32 * 68 * sizeof(float);
-  if (lds < stage_bytes) lds = stage_bytes;
-  auto kern = igemm_split16_kernel<BM, BN, STAGES, SHAPE>;
-  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-  int grid = tiles_m * tiles_n;
-#if MILAN_EXPERIMENTS
-  // MILAN_PERSIST=<workgroups>: persistent grid (a multiple of 8)
-  static int persist = -1;
-  if (persist < 0) { const char* e = getenv("MILAN_PERSIST"); persist = e ? atoi(e) : 0; }
-  // (4-wave tiles run two workgroups per CU)
-  const int pgrid = persist / 8 * 8 * (NT == 256 ? 2 : 1);
-  if (persist >= 8 && grid > pgrid) grid = pgrid;
-#endif
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, s, g, tiles_m, tiles_n);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
 
-template <int BM, int BN, int STAGES>
-static int launch_split16_tm2(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-  constexpr int NT = (BM / 64) * (BN / 64) * 64;
-  size_t lds = size_t(STAGES) * (BM + BN) * 16 * sizeof(float);
-  const size_t stage_bytes = size_t(NT / 64) * 32 * 68 * sizeof(float);
-  if (lds < stage_bytes) lds = stage_bytes;
-  if (g.groups > 1) {
-    auto gkern = igemm_split16_tm2_kernel<BM, BN, STAGES, true>;
-    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(gkern), (int)lds));
-    t_group_taken = true;
-    hipLaunchKernelGGL(gkern, dim3(tiles_m * tiles_n, g.groups), dim3(NT), lds, s, g, tiles_m,
-                       tiles_n);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  auto kern = igemm_split16_tm2_kernel<BM, BN, STAGES>;
-  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(NT), lds, s, g, tiles_m,
-                     tiles_n);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// the ping-pong form of the 256 x 256 tile (4-slot ring: 128 KB of LDS)
-// ... staged in k-tile pairs (whole 128-byte lines): A ring 3 x 32 KB + W ring 2 x 32 KB
-// k x k convs whose weights exist in (slice, tap, channel) order run in that order
-// (MILAN_TAP_INNER=0: tap-major, the round-4 bits; A/B timing and traffic)
-static bool tap_inner_wanted(const GemmArgs& g) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("MILAN_TAP_INNER"); on = e ? atoi(e) : 1; }
-  // (Cin in 4-byte units: whole 32-slot slices, which is what slice_major_kernel packed)
-  return on && g.Wt && !g.A2 && g.KH * g.KW > 1 && g.KH * g.KW <= 32 && g.K == g.Kp &&
-         g.Cin % 32 == 0;
-}
-
-// Border classes of a tap-inner launch (GemmArgs::tap_cls) and its grid.  Along one axis the
-// taps k with 0 <= o * stride - pad + k < size form a set per output coordinate o; runs of equal
-// sets are ranges (a few leading coordinates, the middle, a few trailing ones), a class is a
-// (y-range, x-range) rectangle and its tap mask the product of the two sets.  A 3 x 3 kernel
-// gives at most 9.  The launch keeps the linear tile order (tap_ncls = 0, all taps, the grid
-// of tiles_m x tiles_n) when MILAN_TAP_SKIP=0, when the caller asked for it, when the geometry
-// has more classes than the table holds (5 x 5 / pad 2: 25), when some pixel has no tap inside
-// the image at all, or when a class tile -- up to 256 images for a one-pixel class -- would
-// span more input than a 32-bit buffer offset reaches.
-static int tap_classes(GemmArgs& t, int tiles_m, int tiles_n) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("MILAN_TAP_SKIP"); on = e ? atoi(e) : 1; }
-  const bool wanted = on && t.tap_ncls >= 0;
-  t.tap_ncls = 0;
-  const int howo = t.Ho * t.Wo;
-  if (!wanted || howo <= 0 || t.M % howo != 0 || (t.m_live && t.m_live_mul % howo != 0))
-    return tiles_m * tiles_n;
-  struct Run { int o0, n; unsigned set; };
-  auto runs = [](int size, int out, int k, int stride, int pad, Run* r) {
-    int n = 0;
-    for (int o = 0; o < out; ++o) {
-      unsigned set = 0;
-      for (int i = 0; i < k; ++i)
-        if (o * stride - pad + i >= 0 && o * stride - pad + i < size) set |= 1u << i;
-      if (n > 0 && r[n - 1].set == set) { ++r[n - 1].n; continue; }
-      if (n == MILAN_TAP_CLASSES) return MILAN_TAP_CLASSES + 1;
-      r[n++] = Run{o, 1, set};
-    }
-    return n;
+// ---------------------------------------------------------------------------
+// launch: read the knobs once, plan (gemm_plan.h), run the plan
+// ---------------------------------------------------------------------------
+// The knobs of the launch path, from the environment: the only getenv on it.  Defaults and
+// atoi parsing as documented in README / DESIGN 5; the experiments-only ones keep their
+// defaults in the product build.
+static GemmEnv read_gemm_env() {
+  auto num = [](const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
   };
-  Run ry[MILAN_TAP_CLASSES], rx[MILAN_TAP_CLASSES];
-  const int nry = runs(t.H, t.Ho, t.KH, t.stride, t.pad, ry);
-  const int nrx = runs(t.Wd, t.Wo, t.KW, t.stride, t.pad, rx);
-  if (nry * nrx > MILAN_TAP_CLASSES) return tiles_m * tiles_n;
-  int cls[MILAN_TAP_CLASSES][5], n = 0, min_pix = howo;
-  for (int a = 0; a < nry; ++a)
-    for (int b = 0; b < nrx; ++b, ++n) {
-      unsigned mask = 0;
-      for (int kh = 0; kh < t.KH; ++kh)
-        for (int kw = 0; kw < t.KW; ++kw)
-          if ((ry[a].set >> kh & 1u) && (rx[b].set >> kw & 1u)) mask |= 1u << (kh * t.KW + kw);
-      if (mask == 0) return tiles_m * tiles_n;
-      const int c[5] = {ry[a].o0, ry[a].n, rx[b].o0, rx[b].n, (int)mask};
-      // insertion by descending tap count (stable): the long tiles are dispatched first
-      int at = n;
-      while (at > 0 && __builtin_popcount((unsigned)cls[at - 1][4]) < __builtin_popcount(mask)) {
-        memcpy(cls[at], cls[at - 1], sizeof(c));
-        --at;
-      }
-      memcpy(cls[at], c, sizeof(c));
-      if (ry[a].n * rx[b].n < min_pix) min_pix = ry[a].n * rx[b].n;
-    }
-  if ((256L / min_pix + 2) * t.a_img_stride * 4 + 64 >= 0x7fffffffL) return tiles_m * tiles_n;
-  const long imgs = t.M / howo;
-  long grid = 0;
-  for (int c = 0; c < n; ++c)
-    grid += ((imgs * cls[c][1] * cls[c][3] + 255) / 256 * tiles_n + 7) / 8 * 8;
-  if (grid >= 0x7fffffffL) return tiles_m * tiles_n;
-  t.tap_ncls = n;
-  memcpy(t.tap_cls, cls, sizeof(int) * 5 * n);
-  return (int)grid;
-}
-
-// set by the one launcher that has a row-list form: launch_gemm() fails a row-list launch that
-// the dispatch sent anywhere else (it would run densely, in another tile's order)
-static thread_local bool t_row_list_taken = false;
-
-template <int BNW>
-static int launch_split16_pp32(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + BNW - 1) / BNW;
-  const size_t lds = size_t(5) * 256 * 32 * sizeof(float);
-  if (g.row_list != nullptr) {
-    // (launch_gemm checked row_list_supported(): BNW == 256 here)
-    if (BNW != 256) return MILAN_ERR_SHAPE;
-    t_row_list_taken = true;
-    GemmArgs t = g;
-    const bool tapi = tap_inner_wanted(g);
-    if (tapi) { t.W = g.Wt; t.tap_inner = 1; }
-    t.tap_ncls = 0;
-    profile_tag_kernel(tapi ? MILAN_KERNEL_PP32T_256 : MILAN_KERNEL_PP32_256);
-    auto kern = tapi ? igemm_split16_pp32l_kernel<true> : igemm_split16_pp32l_kernel<false>;
-    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, s, t, tiles_m, tiles_n);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  if (g.groups > 1) {
-    // grouped convs: the 128-column tile only (the per-group widths of the Places AlexNet),
-    // one tile per workgroup, the group as grid.y; the k order is the plain launch's
-    MILAN_REQUIRE(BNW == 128, MILAN_ERR_STATE,
-                  "gemm: internal: a grouped launch reached the 256-column tile (N=%d per group)",
-                  g.N);
-    t_group_taken = true;
-    GemmArgs t = g;
-    const bool tapi = tap_inner_wanted(g);
-    int grid = tiles_m * tiles_n;
-    if (tapi) {
-      // (shift_group moves Wt with W: the kernel reads W)
-      t.W = g.Wt;
-      t.Wt = nullptr;
-      t.tap_inner = 1;
-      grid = tap_classes(t, tiles_m, tiles_n);
-    }
-    profile_tag_kernel(MILAN_KERNEL_PP32_128);
-    auto kern = tapi ? igemm_grouped_pp32t_kernel : igemm_grouped_pp32n_kernel;
-    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid, g.groups), dim3(512), lds, s, t, tiles_m, tiles_n);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  if (tap_inner_wanted(g)) {
-    GemmArgs t = g;
-    t.W = g.Wt;
-    t.tap_inner = 1;
-    const int grid = tap_classes(t, tiles_m, tiles_n);
-    profile_tag_kernel(BNW == 256 ? MILAN_KERNEL_PP32T_256 : MILAN_KERNEL_PP32_128);
-    auto kern = igemm_split16_pp32t_kernel<BNW>;
-    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, t, tiles_m, tiles_n);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  int ncus = 0;
-  MILAN_TRY(device_cus8(&ncus));
-  int grid = tiles_m * tiles_n;
-  // MILAN_PP_PERSIST=1: persistent workgroups with the next tile's first pairs prefetched
-  // under the epilogue (=2: only the K <= 512 launches).  Measured slower in every form --
-  // static walk, short-K only, dynamic tile queue (profiles/r4_experiments.txt B, H, K): one
-  // tile per workgroup (hardware dispatch) is the default.
-  static int persist = -1;
-  if (persist < 0) { const char* e = getenv("MILAN_PP_PERSIST"); persist = e ? atoi(e) : 0; }
-  const bool walk = persist && (persist != 2 || g.K <= 512) && grid > ncus;
-  profile_tag_kernel(BNW == 256 ? MILAN_KERNEL_PP32_256 : MILAN_KERNEL_PP32_128);
-  if (BNW == 256 && !walk) {
-    auto kern = igemm_split16_pp32_kernel;
-    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, g, tiles_m, tiles_n);
-  } else {
-    auto kern = igemm_split16_pp32n_kernel<BNW>;
-    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    if (walk) grid = ncus;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, g, tiles_m, tiles_n);
-  }
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-template <int BNW>
-static int launch_f16_pp32(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + BNW - 1) / BNW;
-  const size_t lds = size_t(5) * 256 * 32 * sizeof(float);
-  profile_tag_kernel(MILAN_KERNEL_F16);
-  if (tap_inner_wanted(g)) {
-    GemmArgs t = g;
-    t.W = g.Wt;
-    t.tap_inner = 1;
-    const int grid = tap_classes(t, tiles_m, tiles_n);
-    auto kern = igemm_f16_pp32_kernel<BNW, true>;
-    MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, t, tiles_m, tiles_n);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  }
-  auto kern = igemm_f16_pp32_kernel<BNW, false>;
-  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, s, g, tiles_m, tiles_n);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-static int launch_split16_pp(const GemmArgs& g, hipStream_t s) {
-  const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + 255) / 256;
-  const size_t lds = size_t(4) * (256 + 256) * 16 * sizeof(float);
-  static_assert(size_t(4) * 512 * 16 * sizeof(float) >= size_t(8) * 32 * 68 * sizeof(float),
-                "the epilogue stages through the ring");
-  auto kern = igemm_split16_pp_kernel;
-  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, s, g, tiles_m, tiles_n);
-  MILAN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-// per-launch limits of the ping-pong kernel's 32-bit buffer offsets: a tile's rows span
-// less than 2 GB of the input, the weight panel of a tile less than 2 GB
-static bool pp_eligible(const GemmArgs& g) {
-  if (g.Cin % 16 != 0 || g.aniso) return false;
-  if (g.A2 && (g.K1 % 16 != 0)) return false;
-  const long howo = (long)g.Ho * g.Wo;
-  const long imgs = 256 / (howo > 0 ? howo : 1) + 2;  // images a 256-row tile can touch
-  const long a_span = imgs * g.a_img_stride * 4 + 64;
-  const long a2_span = g.A2 ? imgs * g.a2_img_stride * 4 + 64 : 0;
-  const long w_span = 256L * g.Kp * 4;
-  return a_span < 0x7fffffffL && a2_span < 0x7fffffffL && w_span < 0x7fffffffL;
-}
-
-// MILAN_PP128=0: the round-3 lockstep 256 x 128 kernel instead of the pair-staged tile (A/B timing)
-static bool pp128_on() {
-  static int pp128 = -1;
-  if (pp128 < 0) { const char* e = getenv("MILAN_PP128"); pp128 = e ? atoi(e) : 1; }
-  return pp128 != 0;
-}
-
-template <int BM, int BN, int STAGES>
-static int launch_split16(const GemmArgs& g, hipStream_t s) {
-  if constexpr (BM == 256 && BN == 128 && STAGES == 3) {
-    // MILAN_PP128=0: the round-3 lockstep 256 x 128 kernel (same bits; A/B timing)
-    if (pp128_on() && !g.chunk_major && pp_eligible(g) && g.Cin % 32 == 0 &&
-        (!g.A2 || g.K1 % 32 == 0) && ((long)g.H + g.pad) < 32768 && ((long)g.Wd + g.pad) < 32768)
-      return launch_split16_pp32<128>(g, s);
-  }
-  if constexpr (BM == 256 && BN == 256 && STAGES == 5) {
-    static int pp = -1;  // MILAN_PP=0: the round-3 lockstep kernels (same bits; A/B timing)
-    if (pp < 0) { const char* e = getenv("MILAN_PP"); pp = e ? atoi(e) : 1; }
-    if (pp && !g.chunk_major && pp_eligible(g)) {
-      // pp == 2: the 16-slot form everywhere (A/B timing)
-      if (pp != 2 && g.Cin % 32 == 0 && (!g.A2 || g.K1 % 32 == 0) &&
-          ((long)g.H + g.pad) < 32768 && ((long)g.Wd + g.pad) < 32768)
-        return launch_split16_pp32<256>(g, s);
-      return launch_split16_pp(g, s);
-    }
-  }
+  GemmEnv env;
+  env.pp = num("MILAN_PP", 1);
+  env.pp128 = num("MILAN_PP128", 1);
+  env.pp_persist = num("MILAN_PP_PERSIST", 0);
+  env.tap_inner = num("MILAN_TAP_INNER", 1);
+  env.tap_skip = num("MILAN_TAP_SKIP", 1);
+  env.group_launch = num("MILAN_GROUP_LAUNCH", 1);
+  env.ablate = num("MILAN_ABLATE", 0);
 #if MILAN_EXPERIMENTS
-  static int shape = -1;
-  if (shape < 0) { const char* e = getenv("MILAN_SCHED"); shape = e ? atoi(e) : 0; }
-  if (shape == 1) return launch_split16_impl<BM, BN, STAGES, 1>(g, s);
+  env.tile_hint = num("MILAN_TILE_HINT", 0);
+  // MILAN_TILE_OVERRIDE="N:K:hint,N:K:hint" forces a tile configuration for the layers with
+  // that (N, K)
+  for (const char* e = getenv("MILAN_TILE_OVERRIDE"); e && *e;) {
+    int n = 0, k = 0, h = 0, used = 0;
+    if (sscanf(e, "%d:%d:%d%n", &n, &k, &h, &used) != 3) break;
+    env.tile_override.insert(env.tile_override.end(), {n, k, h});
+    e += used;
+    if (*e == ',') ++e;
+  }
+  env.sched = num("MILAN_SCHED", 0);
+  env.conv3x3 = num("MILAN_CONV3X3", 0) != 0;
+  env.linear_kernel = num("MILAN_LINEAR_KERNEL", 1);
+  env.persist_lin = num("MILAN_PERSIST_LIN", 1);
+  env.persist = num("MILAN_PERSIST", 0);
+  env.stagger = num("MILAN_STAGGER", 0);
+  env.stagger_all = num("MILAN_STAGGER_ALL", 0);
 #endif
+  return env;
+}
+
+// ... once per process, with the CU count of the current device (device_cus8 keeps it per
+// device: a process may drive several)
+static int gemm_env(GemmEnv* out) {
+  static const GemmEnv knobs = read_gemm_env();
+  *out = knobs;
+  return device_cus8(&out->cus);
+}
+
+typedef void (*GemmKernelFn)(GemmArgs, int, int);
+static GemmKernelFn gemm_kernel_fn(int kernel) {
+  switch (kernel) {
+#define MILAN_GK_CASE(id, ...) case id: return __VA_ARGS__;
+#define MILAN_GK_SKIP(id, ...)
 #if MILAN_EXPERIMENTS
-  if (g.chunk_major) return launch_split16_impl<BM, BN, STAGES, 2>(g, s);
-  static int lin = -1;
-  if (lin < 0) { const char* e = getenv("MILAN_LINEAR_KERNEL"); lin = e ? atoi(e) : 1; }
-  if (!lin) return launch_split16_impl<BM, BN, STAGES, 0>(g, s);
-#endif
-  // 1x1 convolutions and Linear layers: the loop variant without tap arithmetic
-  if (g.KH == 1 && g.KW == 1 && g.pad == 0 && g.A2 == nullptr) {
-    if constexpr (BM == 256 && BN == 256 && STAGES == 5) {
-      // more tiles than CUs: persistent workgroups, the next tile's A rows prefetched
-      // under the epilogue (igemm_split16_linp_kernel)
-      int cus = 0;
-      MILAN_TRY(device_cus8(&cus));
-      bool on = true;
-#if MILAN_EXPERIMENTS
-      static int plin = -1;
-      if (plin < 0) { const char* e = getenv("MILAN_PERSIST_LIN"); plin = e ? atoi(e) : 1; }
-      on = plin != 0;
-#endif
-      const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-      if (on && g.Kp / 16 >= STAGES - 1 && tiles_m * tiles_n > cus) {
-        const size_t lds = size_t(STAGES) * (BM + BN) * 16 * sizeof(float);
-        auto kern = igemm_split16_linp_kernel<STAGES>;
-        MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds));
-        hipLaunchKernelGGL(kern, dim3(cus), dim3(512), lds, s, g, tiles_m, tiles_n);
-        MILAN_CHECK_HIP(hipGetLastError());
-        return 0;
-      }
-    }
-    return launch_split16_impl<BM, BN, STAGES, 3>(g, s);
-  }
-  return launch_split16_impl<BM, BN, STAGES, 0>(g, s);
-}
-
-static bool aligned16(const void* p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
-
-#if MILAN_EXPERIMENTS
-static int env_tile_hint() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("MILAN_TILE_HINT");  // experiments only
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
-
-// experiments only: MILAN_TILE_OVERRIDE="N:K:hint,N:K:hint" forces a tile
-// configuration for the layers with that (N, K)
-static int env_tile_override(int N, int K) {
-  static std::vector<int> table;
-  static bool parsed = false;
-  if (!parsed) {
-    parsed = true;
-    const char* e = getenv("MILAN_TILE_OVERRIDE");
-    while (e && *e) {
-      int n = 0, k = 0, h = 0, used = 0;
-      if (sscanf(e, "%d:%d:%d%n", &n, &k, &h, &used) == 3) {
-        table.push_back(n); table.push_back(k); table.push_back(h);
-        e += used;
-        if (*e == ',') ++e;
-      } else {
-        break;
-      }
-    }
-  }
-  for (size_t i = 0; i + 2 < table.size(); i += 3)
-    if (table[i] == N && table[i + 1] == K) return table[i + 2];
-  return 0;
-}
-
-// The LDS-strip 3x3 kernel is OFF by default (MILAN_CONV3X3=1 or tile_hint 8
-// turn it on).  MEASURED in round 2 (profiles/r2_conv3x3_strip_experiment.txt):
-// it cuts the HBM fetch of layer3's 3x3 convs from 6.4 GB to under 1 GB per
-// launch and the A-side DMA instructions by 4x, results pass the same parity
-// tests -- and the layers run 8-13 % SLOWER (l3.x.c2 51.8 vs 46.7 ms per
-// pass): the generic kernel's loop-invariant fragment addresses keep its
-// MFMA / ds_read stream tighter than the per-tap address arithmetic here, and
-// the L2/MALL absorbs the re-reads well enough that the saved traffic was not
-// on the critical path.
-static bool conv3x3_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("MILAN_CONV3X3"); v = e ? atoi(e) != 0 : 0; }
-  return v != 0;
-}
-
+    MILAN_GEMM_KERNELS(MILAN_GK_CASE, MILAN_GK_CASE)
 #else
-static int env_tile_hint() { return 0; }
-static int env_tile_override(int, int) { return 0; }
+    MILAN_GEMM_KERNELS(MILAN_GK_CASE, MILAN_GK_SKIP)
 #endif
+#undef MILAN_GK_CASE
+#undef MILAN_GK_SKIP
+    default: return nullptr;
+  }
+}
 
-// Row-list launches (GemmArgs::row_list) exist for the layers the dense dispatch below gives to
-// the 256-column pair-staged ping-pong tile, in its k order (a k x k conv: tap-inner) -- the
-// conditions of launch_gemm_impl / launch_split16 on that way, spelled once more -- and when
-// 256 + 2 images of either source lie within a 32-bit byte offset and 257 images' pixels count
-// exactly in fp32.
 bool row_list_supported(const GemmArgs& g) {
-  static int pp = -1;
-  if (pp < 0) { const char* e = getenv("MILAN_PP"); pp = e ? atoi(e) : 1; }
-  const long howo = (long)g.Ho * g.Wo;
-  if (g.row_list == nullptr || g.m_live == nullptr || g.m_live_mul != 1) return false;
-  if (!g.a_split || g.f16 || g.chunk_major || g.aniso || g.tile_hint != 0 || env_tile_hint() != 0 ||
-      env_tile_override(g.N, g.K) != 0 || pp != 1)
-    return false;
-#if MILAN_EXPERIMENTS
-  if (conv3x3_enabled() || (getenv("MILAN_SCHED") && atoi(getenv("MILAN_SCHED")))) return false;
-#endif
-  if (g.epilogue == EPI_LSE || g.epilogue == EPI_LSTM || !g.out_split) return false;
-  if (g.N % 256 != 0 || g.Cin % 32 != 0 || g.K != g.Kp || !pp_eligible(g)) return false;
-  if (g.A2 && (g.K1 % 32 != 0 || g.KH != 1 || g.KW != 1)) return false;
-  if (g.KH * g.KW > 1 && !tap_inner_wanted(g)) return false;
-  if ((long)g.H + g.pad >= 32768 || (long)g.Wd + g.pad >= 32768) return false;
-  if (howo <= 0 || g.M % howo != 0 || 257 * howo >= (1L << 24)) return false;
-  if (258 * g.a_img_stride * 4 + 64 >= 0x7fffffffL) return false;
-  if (g.A2 && 258 * g.a2_img_stride * 4 + 64 >= 0x7fffffffL) return false;
-  return true;
+  GemmEnv env;
+  if (g.row_list == nullptr || gemm_env(&env) != 0) return false;
+  const GemmPlan p = plan_gemm(g, env);
+  return p.err == 0 && p.list;
 }
 
-// A launch whose group strides are set is a grouped conv or ONE group of it (shift_group
-// leaves the strides in place): the dispatch gives both the same kernel.
-static bool group_part(const GemmArgs& g) { return g.groups > 1 || g.c_grp != 0; }
-
-// Whether the dispatch below sends `g` (groups > 1) to a kernel with a grouped form: the general
-// fp32 kernel, the 64-column split tile of the k x k convs and the 128-column pair-staged tile.
-// Everything else -- a forced tile, MILAN_PP128=0, the 1x1 convs with N <= 64, a layer beyond the
-// pair-staged tile's 32-bit offsets -- runs as one plain launch per group.
-static bool groups_supported(const GemmArgs& g) {
-  if (g.tile_hint != 0 || env_tile_hint() != 0 || env_tile_override(g.N, g.K) != 0) return false;
-  if (!g.a_split) return true;
-  if (g.f16 || g.A2 || g.chunk_major || g.Cin % 32 != 0) return false;
-#if MILAN_EXPERIMENTS
-  if (conv3x3_enabled() || (getenv("MILAN_SCHED") && atoi(getenv("MILAN_SCHED")))) return false;
-#endif
-  if (g.N <= 64) return g.KH * g.KW > 1;
-  return pp128_on() && pp_eligible(g) && (long)g.H + g.pad < 32768 && (long)g.Wd + g.pad < 32768;
+// one planned launch: the refusal, or the kernel on the arguments the plan filled in
+static int run_plan(const GemmArgs& g, const GemmPlan& p, hipStream_t s) {
+  MILAN_REQUIRE(p.err == 0, p.err, "%s", p.msg);
+  const GemmKernelFn kern = gemm_kernel_fn(p.kernel);
+  MILAN_REQUIRE(kern != nullptr, MILAN_ERR_STATE, "gemm: internal: no kernel %s in this build",
+                gemm_kernel_name(p.kernel));
+  GemmArgs t = g;
+  if (t.status == nullptr) t.status = status_word();
+  t.tile_hint = p.tile_hint;
+  t.debug = p.debug;
+  t.stagger = p.stagger;
+  t.out_mode = p.out_mode;
+  t.acc_scale = p.acc_scale;
+  t.tap_inner = p.tap_inner;
+  t.tap_ncls = p.tap_ncls;
+  if (p.w_from_wt) {
+    t.W = g.Wt;
+    // (a grouped kernel's shift_group moves Wt with W: the kernel reads W)
+    if (p.grid_y > 1) t.Wt = nullptr;
+    memcpy(t.tap_cls, p.tap_cls, sizeof(int) * 5 * p.tap_ncls);
+  }
+  MILAN_TRY(ensure_lds_attr(reinterpret_cast<const void*>(kern), p.lds));
+  hipLaunchKernelGGL(kern, dim3(p.grid_x, p.grid_y), dim3(p.threads), p.lds, s, t, p.tiles_m,
+                     p.tiles_n);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
-static int launch_gemm_impl(GemmArgs g, hipStream_t s) {
-  const bool cin32 = (g.Cin % 32 == 0);
-  if (g.status == nullptr) g.status = status_word();
-  if (g.tile_hint == 0) g.tile_hint = env_tile_hint();
-  if (const int o = env_tile_override(g.N, g.K)) g.tile_hint = o;
-  {
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("MILAN_ABLATE"); dbg = e ? atoi(e) : 0; }
-    g.debug = dbg;  // 1: skip MFMA phase, 2: skip DMA (timing experiments only)
-#if MILAN_EXPERIMENTS
-    static int stg = -1;
-    if (stg < 0) { const char* e = getenv("MILAN_STAGGER"); stg = e ? atoi(e) : 0; }
-    // the expand convs (residual / two-source, epilogue-heavy launches)
-    static int stg_all = -1;
-    if (stg_all < 0) { const char* e = getenv("MILAN_STAGGER_ALL"); stg_all = e ? atoi(e) : 0; }
-    g.stagger = (stg_all || (g.out_split && g.N >= 256 && g.KH == 1 && g.H > 1 && (g.aux || g.A2))) ? stg : 0;
-#endif
-  }
-  // pick the epilogue form
-  if (g.epilogue == EPI_LSE) {
-    MILAN_REQUIRE(!g.out_split && !g.aux_split && !g.f16 && g.aux == nullptr && g.N % 4 == 0 &&
-                      g.ldc == 2 * ((g.N + 63) / 64) && g.C && g.lse_tgt && g.lse_x &&
-                      (g.bias == nullptr || aligned16(g.bias)),
-                  MILAN_ERR_SHAPE, "gemm: bad log-sum-exp epilogue geometry (N=%d ldc=%d)", g.N,
-                  g.ldc);
-    g.out_mode = OUT_VEC4;
-  } else if (g.epilogue == EPI_LSTM) {
-    MILAN_REQUIRE(!g.out_split && !g.aux_split && g.N % 64 == 0 && g.ldc % 8 == 0 &&
-                      g.ldaux % 4 == 0 && g.C && g.C2 && g.aux && aligned16(g.C) &&
-                      aligned16(g.C2) && aligned16(g.aux) &&
-                      (g.Cs == nullptr || aligned16(g.Cs)) &&
-                      (g.bias == nullptr || aligned16(g.bias)),
-                  MILAN_ERR_SHAPE, "gemm: bad LSTM epilogue geometry (N=%d ldc=%d)",
-                  g.N, g.ldc);
-    g.out_mode = OUT_VEC4;
-  } else if (g.f16) {
-    // fast mode: plain f16 operands through the ping-pong tile only (K-side quantities in
-    // 4-byte units, see GemmArgs::f16)
-    MILAN_REQUIRE(g.a_split && !g.out_split && !g.aux_split && g.N % 8 == 0 && g.ldc % 4 == 0 &&
-                      aligned16(g.C) && (g.bias == nullptr || aligned16(g.bias)) &&
-                      (g.aux == nullptr || (g.ldaux % 4 == 0 && aligned16(g.aux))) &&
-                      (g.epilogue == EPI_BIAS || g.epilogue == EPI_BIAS_RELU ||
-                       g.epilogue == EPI_BIAS_RES_RELU) &&
-                      g.Cin % 32 == 0 && (!g.A2 || g.K1 % 32 == 0) && g.N >= 128 &&
-                      !g.chunk_major && ((long)g.H + g.pad) < 32768 && ((long)g.Wd + g.pad) < 32768,
-                  MILAN_ERR_SHAPE, "gemm: unsupported fast-mode (f16) layer N=%d Cin=%d epi=%d",
-                  g.N, g.Cin, g.epilogue);
-    g.out_mode = OUT_F16;
-  } else if (g.out_split || g.aux_split) {
-    MILAN_REQUIRE(g.out_split && g.N % 8 == 0 && g.ldc % 8 == 0 && aligned16(g.C) &&
-                      (g.bias == nullptr || aligned16(g.bias)) &&
-                      (g.aux == nullptr ||
-                       ((g.aux_split || g.epilogue == EPI_BIAS_SIGMUL) &&
-                        g.ldaux % 8 == 0 && aligned16(g.aux))) &&
-                      (g.epilogue == EPI_BIAS || g.epilogue == EPI_BIAS_RELU ||
-                       g.epilogue == EPI_BIAS_RES_RELU ||
-                       g.epilogue == EPI_BIAS_ADD ||
-                       (g.epilogue == EPI_BIAS_SIGMUL && !g.aux_split)),
-                  MILAN_ERR_SHAPE,
-                  "gemm: unsupported split-format epilogue (N=%d ldc=%d epi=%d)",
-                  g.N, g.ldc, g.epilogue);
-    g.out_mode = OUT_SPLIT8;
-  } else {
-    const bool vec_ok = (g.N % 4 == 0) && (g.ldc % 4 == 0) && aligned16(g.C) &&
-                        (g.bias == nullptr || aligned16(g.bias)) &&
-                        (g.aux == nullptr ||
-                         ((g.ldaux % 4 == 0) && aligned16(g.aux)));
-    g.out_mode = vec_ok ? OUT_VEC4 : OUT_SCALAR;
-  }
-  MILAN_REQUIRE(g.A2 == nullptr || (g.a_split && g.N > 64 &&
-                                    g.KH == 1 && g.KW == 1 && g.K1 % 16 == 0 &&
-                                    (g.tile_hint == 0 || g.tile_hint >= 3)),
-                MILAN_ERR_SHAPE, "gemm: two-source A needs the split16 kernels");
-  if (g.a_split) {
-    if (g.acc_scale == 0.f) g.acc_scale = 1.f;
-    if (g.f16) {
-      MILAN_REQUIRE(pp_eligible(g), MILAN_ERR_SHAPE, "gemm: fast-mode layer exceeds the 32-bit "
-                    "buffer offsets of the ping-pong kernel");
-      return g.N % 256 == 0 ? launch_f16_pp32<256>(g, s) : launch_f16_pp32<128>(g, s);
-    }
-    if (!cin32) {
-      // per-lane taps (8-slot groups): only the narrow-N tile is built for it
-      MILAN_REQUIRE(g.Cin % 8 == 0 && g.N <= 64 && !g.A2, MILAN_ERR_SHAPE,
-                    "gemm: split-f16 operands with Cin %% 32 != 0 need "
-                    "Cin %% 8 == 0 and N <= 64 (Cin=%d N=%d)", g.Cin, g.N);
-      return launch_cfg<256, 64, 2, false, true>(g, s);
-    }
-    // (N <= 64 on the split16 pipeline -- 512x64x3 / 256x64x4 tiles -- measured
-    // 10-20 % SLOWER in round 2: these layers are bound by the L2 -> LDS operand
-    // traffic of a 64-column tile, not by the pipeline depth.)
-    // N <= 64: the k x k convs (layer1's 3x3) run on the split16 pipeline with
-    // 64 x 64 wave tiles (256x64 block, 3-deep ring, 2 blocks per CU): round 2,
-    // same-box A/B: l1.x.c2 10.6 -> 9.7 ms per pass.  The 1x1 layers measured
-    // 3-8 % SLOWER on it (and a 128x64 block slower still), so they stay on the
-    // 2-stage kernel; tile_hint 6 / 10 force either.
-    if (g.N <= 64 && g.tile_hint != 10 && !g.A2 &&
-        (g.tile_hint == 6 || (g.tile_hint == 0 && g.KH * g.KW > 1)))
-      return launch_split16_tm2<256, 64, 3>(g, s);
-    if (g.N <= 64) return launch_cfg<256, 64, 2, true, true>(g, s);
-    MILAN_REQUIRE(!g.chunk_major || (MILAN_EXPERIMENTS && g.tile_hint == 0 && !g.A2 && g.Cin % 16 == 0),
-                  MILAN_ERR_SHAPE, "gemm: chunk-major k order: experiments build, split16 kernels");
-#if MILAN_EXPERIMENTS
-    // 3x3 / stride 1 with the chunk-major weight copy: input strip in LDS
-    if (g.W3 && g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad == 1 && !g.A2 &&
-        g.Cin % 16 == 0 && g.a_pix_stride == g.Cin && g.Ho == g.H && g.Wo == g.Wd &&
-        g.a_img_stride == (long)g.H * g.Wd * g.Cin && g.Wd + 1 <= 64 &&
-        (g.tile_hint == 8 || (g.tile_hint == 0 && conv3x3_enabled()))) {
-      if (g.N % 256 == 0) return launch_conv3x3<256>(g, s);
-      if (g.N % 128 == 0) return launch_conv3x3<128>(g, s);
-    }
-#endif
-    // Measured on the 4096-neuron workload (profiles/): the 4-wave 256x128
-    // tile with 16-slot k-tiles, a 3-deep ring and DMA pieces interleaved with
-    // the MFMA groups (2 workgroups per CU) is the fastest split-mode
-    // configuration for every N > 64 layer; the others stay reachable through
-    // tile_hint for experiments.
-    // The kernel is chosen from the LAYER (N, K) only, never from the number
-    // of rows: different tile configurations accumulate in different orders,
-    // and a description must not depend on how many neurons shared its launch
-    // (chunk size, world size).  Short M just leaves tile rows masked.
-#if MILAN_EXPERIMENTS
-    if (g.tile_hint == 3) return launch_split16<256, 256, 4>(g, s);
-    if (g.tile_hint == 7) return launch_split16<256, 256, 5>(g, s);
-    if (g.tile_hint == 4) return launch_split16<256, 128, 3>(g, s);
-    if (g.tile_hint == 5) return launch_split16<128, 256, 3>(g, s);
-    if (g.tile_hint == 1) return launch_cfg<256, 128, 3, true, true>(g, s);
-    if (g.tile_hint == 2) return launch_cfg<128, 128, 2, true, true>(g, s);
-#endif
-    // 256x256 tile, 5-deep ring = all 160 KB of LDS, four k-tiles in flight (round 3,
-    // same-box A/B against the 4-deep ring: +0.5 % end to end, same bits)
-    // (a grouped conv, or one group of it, stays on the 128-column tile at every width: the
-    // tile that has a grouped form, so that both forms of the launch give the same bits)
-    if (group_part(g)) return launch_split16<256, 128, 3>(g, s);
-    if (g.N % 256 == 0) return launch_split16<256, 256, 5>(g, s);
-    {
-      // wide outputs that are not a multiple of 256 (the vocabulary GEMMs, N =
-      // 5004): the 256-column tile when it pads no more than the 128-column one
-      // would (same-box A/B: decode stage -0.5 ms; N = 3904 pads 4.9 % vs 1.6 %
-      // and is slower on it)
-      const int pad256 = (g.N + 255) / 256 * 256 - g.N;
-      const int pad128 = (g.N + 127) / 128 * 128 - g.N;
-      if (g.N > 2048 && pad256 <= pad128)
-        return launch_split16<256, 256, 5>(g, s);
-    }
-    return launch_split16<256, 128, 3>(g, s);
-  }
-  if (g.groups > 1) {
-    // grouped fp32: the tiles of the plain dispatch below, the group as grid.y
-    if (g.N <= 64)
-      return cin32 ? launch_cfg_grouped<256, 64, 2, true>(g, s)
-                   : launch_cfg_grouped<256, 64, 2, false>(g, s);
-    return cin32 ? launch_cfg_grouped<128, 128, 2, true>(g, s)
-                 : launch_cfg_grouped<128, 128, 2, false>(g, s);
-  }
-  if (g.N <= 64) {
-    return cin32 ? launch_cfg<256, 64, 2, true, false>(g, s)
-                 : launch_cfg<256, 64, 2, false, false>(g, s);
-  }
-  // (the 8-wave 3-stage tile measured 4% slower than 128x128x2 in F32 mode,
-  // where one k-tile is 4096 MFMA cycles and latency is already hidden)
-#if MILAN_EXPERIMENTS
-  if (cin32 && g.tile_hint == 1)
-    return launch_cfg<256, 128, 3, true, false>(g, s);
-#endif
-  return cin32 ? launch_cfg<128, 128, 2, true, false>(g, s)
-               : launch_cfg<128, 128, 2, false, false>(g, s);
+// ... between the profiler's event pair while it is on
+static int launch_gemm_checked(const GemmArgs& g, const GemmPlan& p, hipStream_t s) {
+  if (!g_prof.on) return run_plan(g, p, s);
+  ProfRec* e = prof_next();
+  MILAN_REQUIRE(e != nullptr, MILAN_ERR_STATE, "profiler: cannot create events");
+  e->stage = g_prof.stage;
+  e->gemm = true;
+  e->kernel = p.family;
+  e->flops = 2.0 * (double)g.M * (double)g.N * (double)(g.flop_k > 0 ? g.flop_k : g.K);
+  e->bytes = gemm_algorithmic_bytes(g);
+  MILAN_CHECK_HIP(hipEventRecord(e->a, s));
+  const int r = run_plan(g, p, s);
+  MILAN_CHECK_HIP(hipEventRecord(e->b, s));
+  return r;
 }
 
-static int launch_gemm_checked(const GemmArgs& g, hipStream_t s);
 int launch_gemm(const GemmArgs& g, hipStream_t s) {
   MILAN_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, MILAN_ERR_SHAPE,
                 "gemm: empty problem M=%d N=%d K=%d", g.M, g.N, g.K);
-  MILAN_REQUIRE(g.row_list == nullptr || row_list_supported(g), MILAN_ERR_SHAPE,
-                "gemm: no row-list form of this launch (N=%d Cin=%d %dx%d)", g.N, g.Cin, g.KH, g.KW);
+  GemmEnv env;
+  MILAN_TRY(gemm_env(&env));
+  const GemmPlan p = plan_gemm(g, env);
+  // (the one refusal that comes ahead of the argument checks, as it always has)
+  MILAN_REQUIRE(g.row_list == nullptr || p.list, p.err, "%s", p.msg);
   MILAN_REQUIRE(g.Cin % 4 == 0 && g.a_pix_stride % 4 == 0 &&
                     g.a_img_stride % 4 == 0 && g.Kp % 32 == 0 && aligned16(g.A) &&
                     aligned16(g.W),
@@ -3558,55 +3032,17 @@ int launch_gemm(const GemmArgs& g, hipStream_t s) {
     MILAN_REQUIRE(!g.row_list && !g.m_live && !g.A2 && !g.f16 && g.epilogue != EPI_LSE &&
                       g.epilogue != EPI_LSTM && g.groups <= 65535,
                   MILAN_ERR_SHAPE, "gemm: a grouped launch is a plain conv (groups=%d)", g.groups);
-    // MILAN_GROUP_LAUNCH=0: the baseline, one plain launch per group on offset pointers (the
-    // same kernel per group as the grouped launch runs: the dispatch reads per-group sizes)
-    static int one = -1;
-    if (one < 0) { const char* e = getenv("MILAN_GROUP_LAUNCH"); one = e ? atoi(e) : 1; }
-    // ... which is also how a launch without a grouped kernel runs, decided before anything starts
-    if (!one || !groups_supported(g)) {
+    if (p.per_group) {
+      // one plain launch per group on offset pointers, each planned on its own pointers
       for (int q = 0; q < g.groups; ++q) {
         GemmArgs t = g;
         shift_group(t, q);
-        MILAN_TRY(launch_gemm_checked(t, s));
+        MILAN_TRY(launch_gemm_checked(t, plan_gemm(t, env), s));
       }
       return 0;
     }
-    t_group_taken = false;
-    const int r = launch_gemm_checked(g, s);
-    MILAN_REQUIRE(r != 0 || t_group_taken, MILAN_ERR_STATE,
-                  "gemm: a grouped launch was dispatched to a kernel without a grouped form "
-                  "(N=%d Cin=%d %dx%d per group: groups_supported() no longer matches the "
-                  "dispatch)", g.N, g.Cin, g.KH, g.KW);
-    return r;
   }
-  if (g.row_list != nullptr) {
-    // row_list_supported() restates the dispatch below; should the two ever part, the launch
-    // must not run on some other kernel unnoticed
-    t_row_list_taken = false;
-    const int r = launch_gemm_checked(g, s);
-    MILAN_REQUIRE(r != 0 || t_row_list_taken, MILAN_ERR_STATE,
-                  "gemm: a row-list launch was dispatched to a kernel without a list form "
-                  "(row_list_supported() no longer matches the dispatch)");
-    return r;
-  }
-  return launch_gemm_checked(g, s);
-}
-
-static int launch_gemm_checked(const GemmArgs& g, hipStream_t s) {
-  if (!g_prof.on) return launch_gemm_impl(g, s);
-  ProfRec* e = prof_next();
-  MILAN_REQUIRE(e != nullptr, MILAN_ERR_STATE, "profiler: cannot create events");
-  e->stage = g_prof.stage;
-  e->gemm = true;
-  e->kernel = g.a_split ? MILAN_KERNEL_SPLIT_OTHER : MILAN_KERNEL_F32;
-  e->flops = 2.0 * (double)g.M * (double)g.N * (double)(g.flop_k > 0 ? g.flop_k : g.K);
-  e->bytes = gemm_algorithmic_bytes(g);
-  g_prof.open = e;
-  MILAN_CHECK_HIP(hipEventRecord(e->a, s));
-  const int r = launch_gemm_impl(g, s);
-  g_prof.open = nullptr;
-  MILAN_CHECK_HIP(hipEventRecord(e->b, s));
-  return r;
+  return launch_gemm_checked(g, p, s);
 }
 
 }  // namespace milan

@@ -450,9 +450,9 @@ def lm_score(inputs, sd, stop):
 # ---- the dispatch, restated -----------------------------------------------------------
 # csrc/decoder.hip: decoder_finalize / pack_linear / cat_linear (which weights have a
 # split-f16 copy), step_core (the `fused` branch), lin / lstm_layer (the other branch),
-# launch_attend, launch_context, launch_row_select, lm_split_ok.  csrc/gemm.hip:
-# launch_gemm_impl / launch_split16 for a Linear layer (1 x 1, no hint, no environment
-# override, MILAN_PP = MILAN_PP128 = 1).
+# launch_attend, launch_context, launch_row_select, lm_split_ok.  csrc/gemm_plan.h:
+# plan_launch for a Linear layer (1 x 1, no hint, no environment override, MILAN_PP =
+# MILAN_PP128 = 1).
 def fused(d):
     """step_core's `fused` branch under split_f16: every product has a split weight copy
     (K % 32 == 0 for q / gate / vocabulary: H; for the concatenated cell weight: E + F and

@@ -63,8 +63,8 @@ __device__ inline void chain_join8(f32x4 hi, f32x4 lo, float* v) { join8_exact(h
 constexpr int kSRow = 68;        // floats per row of a wave's LDS strip (64 + 4)
 constexpr int kTileFloats = 64 * 64;  // one weight tile: 64 rows x 64 k (16 KB)
 // chain_kernel<.., CONV>: pixels of the 3x3 conv's input region in LDS -- 256 output pixels
-// + (w + 1) before and after, w <= 56, rounded up to whole 4-pixel DMA pieces
-constexpr int kConvMaxW = 56;
+// + (w + 1) before and after, w <= kConvMaxW = 56 (enc_plan.h), rounded up to whole 4-pixel
+// DMA pieces
 constexpr int kConvSlots = (256 + 2 * (kConvMaxW + 1) + 3) / 4 * 4;   // 372
 
 template <int N>
@@ -748,20 +748,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void chain_kernel(ChainArgs g) {
 // of a SIMD multiplied one after the other and the epilogue ran with the pipe idle).  Numbers:
 // DESIGN.md section 4.4, profiles/r3_experiments.txt, profiles/r4_experiments.txt E.
 
-bool chain_conv_supported(int P, int KD, int NR, int h, int w) {
-  return P == 64 && chain_supported(P, KD, NR) && h >= 1 && w >= 1 && w <= kConvMaxW;
-}
-
-bool chain_conv_c1_supported(int P, int KD, int NR, int h, int w) {
-  return chain_conv_supported(P, KD, NR, h, w) && KD == 64 && NR == 64;   // layer1.0
-}
-
-bool chain_supported(int P, int KD, int NR) {
-  if (NR == 2 * P) return KD == 0 && P == 64;  // stage boundary layer1 -> layer2
-  if (NR != P) return false;
-  if (KD == 0) return P == 64 || P == 128 || P == 256;
-  return P == 64 && KD == 64;
-}
+// (what the launches below cover: chain_supported / chain_conv_supported /
+// chain_conv_c1_supported, enc_plan.h)
 
 template <int P, int NW, bool RES_LDS, int KD, bool XACC, bool PROF = false, int NR = P,
           bool CONV = false, bool C1 = false>

@@ -1007,37 +1007,26 @@ static void carve(T& t, int sweep_units, int n_total, Arena& a) {
 // buffers, split at the context's activation scale in the split mode.
 struct ResNetTrunk : Trunk {
   float *in4, *raw, *x0, *x1, *ds, *t1, *t2, *hold = nullptr, *pooled;
+  EncBuffers geo;  // the encoder pass's level extents and buffer sizes (enc_carve)
 
   ResNetTrunk(const milan_ctx* c, int n, int H, int W, bool split, hipStream_t s)
       : Trunk{c, n, H, W, split, s, 1.f / c->act_scale} {
-    h[0] = conv_out(H, 7, 2, 3); w[0] = conv_out(W, 7, 2, 3);
-    for (int l = 1; l < 5; ++l) {
-      h[l] = conv_out(h[l - 1], 3, 2, 1);
-      w[l] = conv_out(w[l - 1], 3, 2, 1);
+    enc_carve(c->d.trunk_kind, c->d.trunk_width, n, H, W, nullptr, &geo);
+    for (int l = 0; l < 5; ++l) {
+      h[l] = geo.lv.h[l]; w[l] = geo.lv.w[l];
+      lvl_sz[l] = (size_t)h[l] * w[l] * level_channels(c, l);
     }
-    for (int l = 0; l < 5; ++l) lvl_sz[l] = (size_t)h[l] * w[l] * level_channels(c, l);
     for (int l = 1; l < 5; ++l) fmt[l] = split;
   }
 
   void carve(Arena& a) {
-    const int wd = c->d.trunk_width;
-    const int exp = c->d.trunk_kind == MILAN_TRUNK_BASIC ? 1 : 4;
-    size_t x_sz = (size_t)h[1] * w[1] * wd, t1_sz = 0, t2_sz = 0;
-    for (int li = 0; li < 4; ++li) {
-      const size_t planes = (size_t)wd << li;
-      const size_t in_px = (size_t)h[li == 0 ? 1 : li] * w[li == 0 ? 1 : li];
-      const size_t out_px = (size_t)h[li + 1] * w[li + 1];
-      x_sz = std::max(x_sz, out_px * planes * exp);
-      t1_sz = std::max(t1_sz, in_px * planes);
-      t2_sz = std::max(t2_sz, out_px * planes);
-    }
     in4 = a.get<float>((size_t)n * hin * (win + 2) * 4);
     raw = a.get<float>((size_t)n * lvl_sz[0]);
-    x0 = a.get<float>((size_t)n * x_sz);
-    x1 = a.get<float>((size_t)n * x_sz);
-    ds = a.get<float>((size_t)n * x_sz);
-    t1 = a.get<float>((size_t)n * t1_sz);
-    t2 = a.get<float>((size_t)n * t2_sz);
+    x0 = a.get<float>((size_t)n * geo.x_sz);
+    x1 = a.get<float>((size_t)n * geo.x_sz);
+    ds = a.get<float>((size_t)n * geo.x_sz);
+    t1 = a.get<float>((size_t)n * geo.t1_sz);
+    t2 = a.get<float>((size_t)n * geo.t2_sz);
     pooled = a.get<float>((size_t)n * level_channels(c, 4));
   }
   void carve_hold(Arena& a, size_t floats) { hold = a.get<float>(floats); }

@@ -8,8 +8,10 @@
 #include <map>
 
 #include "../../include/milan_hip.h"
-// Epilogue, GemmArgs, shift_group, OutMode -- and the launch plan that reads them
-#include "gemm_plan.h"
+// Epilogue, GemmArgs, shift_group, OutMode and the launch plan that reads them (gemm_plan.h);
+// ConvW, Bottleneck, ChainArgs, Arena, the conv argument builders, the fused kernels' shape
+// predicates and the schedule of an encoder pass (enc_plan.h)
+#include "enc_plan.h"
 
 // experiments build (make EXPERIMENTS=1): measured-and-rejected kernels and the
 // knobs that force tile configurations; see gemm.hip and DESIGN.md section 5
@@ -48,6 +50,8 @@ int launch_gemm(const GemmArgs& g, hipStream_t s);
 // whether launch_gemm() can run `g` on a row list (GemmArgs::row_list) with the bits of the
 // dense launch: whether its plan names a pp32l form (gemm_plan.h)
 bool row_list_supported(const GemmArgs& g);
+// the knobs of the launch path, read once per process, with the current device's CU count
+int gemm_env(GemmEnv* out);
 // Status word of the context whose entry point is running on this thread (api.hip sets it
 // on entry): every kernel that writes split format ORs MILAN_STATUS_SATURATED into it when
 // its clamp to +-65504 was hit (split8_* below).  nullptr = nobody is listening.
@@ -95,51 +99,7 @@ int launch_image_classes(const ShareArgs& a, hipStream_t s);
 // stats[0] += n, stats[1] += *live (n when live == nullptr); one thread, nothing read back
 int launch_share_count(long long* stats, int n, const int* live, hipStream_t s);
 
-// ---- fused expand -> reduce chain (chain.hip) --------------------------------
-// One launch = a bottleneck's 1x1 expand conv c3 (+ residual + ReLU) AND the next
-// bottleneck's 1x1 reduce conv c1 (+ ReLU): X = relu(T2 W3^T + b3 + R),
-// T1 = relu(X W1^T + b1); all tensors split-format, dense rows.  P = planes.
-// Optional second expand source (a bottleneck with a stride-1 downsample branch,
-// layer1.0): X = relu([T2 | A2] W3^T + b3) with W3 = [c3 | downsample] along K, no
-// residual (R == nullptr).
-struct ChainArgs {
-  const float* T2;     // [M][P]
-  const float* W3;     // [4P][P] split weights (scaled), K contiguous
-  const float* bias3;  // [4P]
-  const float* R;      // [M][4P] residual
-  float* X;            // [M][4P]
-  const float* W1;     // [NR][4P] split weights (scaled)
-  const float* bias1;  // [NR]
-  float* T1;           // [M][NR]
-  int M, P;
-  const float* A2;     // [M][KD] or nullptr
-  int KD;              // channels of A2 (0 without)
-  float scale3, scale1;  // 1 / weight scale of W3, W1
-  long long* prof;       // timing experiments: per-workgroup phase cycles (8 per WG)
-  int NR;                // output channels of the reduce conv (0 = P; 2 P at a stage boundary)
-  unsigned* status;      // filled by the launcher (status_word())
-  const int* m_live;     // device-side row count, see GemmArgs::m_live (nullptr: M rows)
-  int m_live_mul;
-  // Round 6, the bottleneck's 3x3 conv c2 IN FRONT of the chain (chain_kernel<.., CONV>; planes
-  // 64, stride 1, pad 1): when C2in != nullptr the t2 operand is not read from T2 but computed
-  // in the kernel from c2's input C2in [M][64] (pixels (img, y, x) of ch x cw images, split
-  // format) -- t2 = relu(conv3x3(C2in; W2) * scale2 + bias2) never exists in memory.
-  const float* C2in;
-  const float* W2;       // [64][576] split weights (scaled), k = tap * 64 + channel
-  const float* bias2;    // [64]
-  float scale2;          // 1 / weight scale of W2
-  int ch, cw;            // image height / width of C2in (cw <= 56)
-  // ... and the block's OWN 1x1 reduce conv c1 in front of that (chain_kernel<.., CONV, C1>;
-  // layer1.0, whose input has 64 channels): when W0 != nullptr, C2in is the BLOCK INPUT x
-  // [M][64] and t1 = relu(x W0^T * scale0 + bias0) is computed in place in the LDS copy of
-  // the input region -- neither t1 nor t2 exists in memory (the whole bottleneck in one launch).
-  const float* W0;       // [64][64] split weights (scaled)
-  const float* bias0;    // [64]
-  float scale0;
-};
-bool chain_supported(int P, int KD, int NR = 0);
-bool chain_conv_supported(int P, int KD, int NR, int h, int w);
-bool chain_conv_c1_supported(int P, int KD, int NR, int h, int w);
+// ---- fused expand -> reduce chain (chain.hip): ChainArgs and chain_supported() are in enc_plan.h
 int launch_chain(const ChainArgs& a, hipStream_t s);
 // ---- fused split-f16 stem (stem.hip): conv1 7x7/2 + bn1 + ReLU + maxpool 3x3/2 ----
 struct StemArgs {
@@ -169,7 +129,6 @@ struct StemArgs {
   int W;
   const int* n_live;     // device-side image count (<= n) or nullptr, see GemmArgs::m_live
 };
-bool stem_fused_supported(int cout, int Kp);
 int launch_stem_fused(const StemArgs& a, hipStream_t s);
 // ---- 3x3 / 1 / 1 convolution, 64 -> 64 channels, weights in registers (conv3.hip) ----
 struct Conv3Args {
@@ -186,7 +145,6 @@ struct Conv3Args {
   unsigned* status;      // filled by the launcher (status_word())
   const int* n_live;     // device-side image count (<= n) or nullptr, see GemmArgs::m_live
 };
-bool conv3_p64_supported(int cin, int cout, int kh, int kw, int stride, int pad);
 int launch_conv3_p64(const Conv3Args& a, hipStream_t s);
 bool gemm_profile_active();
 int gemm_profile_read(double* ms, double* flops, long long* launches);
@@ -205,21 +163,6 @@ class StageScope {
   int prev_;
   long idx_;
 };
-
-inline GemmArgs linear_args(const float* A, long lda, const float* W,
-                            const float* bias, float* C, int ldc, int M, int N,
-                            int K, int epi, const float* zero,
-                            const float* aux = nullptr, int ldaux = 0) {
-  GemmArgs g{};
-  g.A = A; g.W = W; g.bias = bias; g.aux = aux; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.Kp = (K + 31) / 32 * 32;
-  g.ldc = ldc; g.ldaux = ldaux;
-  g.H = 1; g.Wd = 1; g.Cin = K; g.Ho = 1; g.Wo = 1; g.KH = 1; g.KW = 1;
-  g.stride = 1; g.pad = 0;
-  g.a_pix_stride = lda; g.a_img_stride = lda;
-  g.epilogue = epi; g.zero = zero;
-  return g;
-}
 
 // torch's LSTM cell, gate order i, f, g, o (one definition for the pointwise
 // kernel and the fused GEMM epilogue, roundings spelled out, so that both give
@@ -241,30 +184,7 @@ __host__ __device__ inline int lstm_interleaved_row(int gate, int u) {
 }
 
 
-// ---- packed weights ----------------------------------------------------------
-struct ConvW {
-  float* w = nullptr;     // [Cout][Kp]
-  float* ws = nullptr;    // same, split-f16 format, scaled by 1/ws_inv
-  float* ws3 = nullptr;   // 3x3 only, experiments build: ws re-ordered chunk-major (gemm.hip)
-  float ws_inv = 1.f;     // exact power of two
-  float* bias = nullptr;  // folded BN shift, [Cout] (nullptr for raw stem)
-  float* bias_s = nullptr;  // bias x activation scale (split-f16 trunk, see milan_ctx::act_scale)
-  float* wf = nullptr;      // fast mode: the hi halves of `ws` as plain f16 rows [Cout][Kp] (2 B each)
-  float* wst = nullptr;     // k x k convs: `ws` with k in (32-channel slice, tap, channel) order (GemmArgs::Wt)
-  float* wft = nullptr;     // ... `wf` in (64-channel slice, tap, channel) order
-  int cout = 0, cin = 0, kh = 0, kw = 0, stride = 1, pad = 0, K = 0, Kp = 0;
-  int cin_real = 0;  // channels before padding to a multiple of 4
-  // grouped conv: cout is the full width; cin, cin_real, K and Kp are those of ONE group (cin =
-  // the weight's second extent, K = kh * kw * cin; an input pixel has cin * groups channels);
-  // w, ws, wst hold the groups' rows back to back ([cout][Kp])
-  int groups = 1;
-};
-struct Bottleneck {
-  ConvW c1, c2, c3, down;
-  ConvW c3d;  // [c3 | downsample] concatenated along K (split mode fusion)
-  bool has_down = false;
-  bool basic = false;  // torchvision BasicBlock: c1 3x3 (stride), c2 3x3, no c3
-};
+// ---- packed weights (ConvW, Bottleneck: enc_plan.h) ---------------------------
 struct LinearW {
   float* w = nullptr;  // [N][Kp]
   float* ws = nullptr; // split-f16 copy (nullptr when K % 32 != 0)
@@ -281,22 +201,6 @@ struct Tensor {
     int64_t n = 1;
     for (auto d : shape) n *= d;
     return n;
-  }
-};
-
-// bump allocator over a caller-provided workspace
-struct Arena {
-  char* base = nullptr;
-  size_t size = 0, off = 0;
-  bool dry = false;  // dry run: only count
-  template <typename T>
-  T* get(size_t n) {
-    size_t bytes = (n * sizeof(T) + 255) & ~size_t(255);
-    size_t o = off;
-    off += bytes;
-    if (dry) return nullptr;
-    if (off > size) return nullptr;
-    return reinterpret_cast<T*>(base + o);
   }
 };
 
@@ -576,8 +480,6 @@ inline const SeqFamily* seq_family(int trunk_kind) {
          : trunk_kind == MILAN_TRUNK_VGG            ? &vgg
                                                     : nullptr;
 }
-
-inline int conv_out(int h, int k, int s, int p) { return (h + 2 * p - k) / s + 1; }
 
 // Extents of conv1..conv5 (h, w) and of pool1, pool2, pool5 (hq, wq: 3 x 3 / 2 without padding,
 // after conv1, conv2 and conv5) of an H x W image, from the packed convs.  C's division

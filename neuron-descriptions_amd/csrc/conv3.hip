@@ -301,10 +301,6 @@ __global__ __launch_bounds__(512, 1) void conv3_p64_kernel(Conv3Args a) {
   report_saturation(a.status, sat);
 }
 
-bool conv3_p64_supported(int cin, int cout, int kh, int kw, int stride, int pad) {
-  return cin == 64 && cout == 64 && kh == 3 && kw == 3 && stride == 1 && pad == 1;
-}
-
 int launch_conv3_p64(const Conv3Args& a0, hipStream_t s) {
   Conv3Args a = a0;
   MILAN_REQUIRE(a.n > 0 && a.h > 0 && a.w > 0 && a.in && a.ws && a.out && a.zero,

@@ -748,13 +748,7 @@ __global__ void bn_relu_maxpool_split_kernel(const float* __restrict__ x, int n,
 // ---------------------------------------------------------------------------
 // src/milan/encoders.py:303-314.  One workgroup per (image, level).  Output:
 // an ORDERED list of (pixel, weight) for the non-zero weights plus its length,
-// so the pooling kernel touches only feature pixels under the mask.
-struct Levels {
-  int h[5], w[5];
-  long off[5];  // offset (entries) of level l inside one image's list
-  long per_image;
-};
-
+// so the pooling kernel touches only feature pixels under the mask.  (Levels: enc_plan.h)
 
 template <typename T>
 __global__ __launch_bounds__(256) void mask_pyramid_kernel(
@@ -1070,7 +1064,7 @@ __global__ void act_absmax_kernel(const float* __restrict__ x, long n,
 // im2col of the needed rows in the (slice, tap, channel) order of the tap-inner kernel -- the
 // same products in the same order, so the pooled features are bitwise those of the dense pass
 // (tests/test_gpu_sparse_tail.py) -- and the row counts stay on the device (GemmArgs::m_live).
-constexpr int kTailMaxP = 1024;   // pixels of the last stage per image (7 x 7 = 49 at 224 x 224)
+// (kTailMaxP, kTailMaxP3 -- pixels of the last two stages per image -- are in enc_plan.h)
 
 // Image sharing: set 0 of trunk slot c is the UNION of its members' level-4 lists, gathered
 // here as a byte map s0[c][p] (zero-filled; every writer stores the same 1).  Dilation
@@ -1158,7 +1152,6 @@ __global__ __launch_bounds__(64) void tail_sets_kernel(
 //   set 1 (W) = V + the downsample's pixels + the listed pixels (s3 != nullptr: their union
 //               over the members of the trunk slot, see tail_union_kernel)
 // is where the last block of this stage is needed.  Ascending, like tail_sets_kernel.
-constexpr int kTailMaxP3 = 4096;  // pixels of that stage per image (14 x 14 = 196 at 224 x 224)
 __global__ __launch_bounds__(64) void tail_sets3_kernel(
     const int* __restrict__ loc, const int* __restrict__ cnt, int k0,
     const int* __restrict__ list_idx, const int* __restrict__ list_n, Levels lv,
@@ -1282,112 +1275,35 @@ __global__ void tail_im2col_kernel(const float4* __restrict__ t1, const int* __r
 }
 
 // ---------------------------------------------------------------------------
-// driver
+// driver: carve (enc_carve), plan (plan_encoder, enc_plan.h), walk the plan
 // ---------------------------------------------------------------------------
-struct EncPlan {
-  Levels lv;
-  int h1, w1, hp, wp;
-  float *in4, *raw, *x0, *x1, *ds, *t1, *t2;
-  size_t x_sz, t1_sz, t2_sz;  // per-image extents of x0/x1/ds, t1, t2 (floats)
-  int *list_idx, *list_n;
-  float* list_w;
-  int* bbox;  // [n][4]: level-0 bounding box of the listed pixels
-  int* poison;  // [n]: 1 = the image holds a non-finite pixel (float inputs only)
-  int *order, *bbox_c, *count;  // images with a non-empty mask (compact_images_kernel)
-  // mask-aware tail of the last stage: per-slot pixel sets [3][n][P4], their counts / offsets
-  // [3][n], the global row lists [3][n * P4] and row counts [3] (device)
-  int *tail_loc, *tail_cnt, *tail_off, *tail_rows, *tail_U;
-  // image sharing (share.hip): per-slot hash / rep / flag / class_of, and the union of the
-  // members' level-4 lists per trunk slot as a byte map [n][P4]
-  void* sh_hash;
-  int *sh_rep, *sh_flag, *class_of;
-  unsigned char* tail_s0;
-  // MILAN_FUSE_TAIL_LISTS: sets V, W of the stage before the last (tail_sets3_kernel), laid
-  // out like the tail_* arrays above with 2 sets of P3 pixels; byte map of the level-3 unions
-  int *tail_loc3, *tail_cnt3, *tail_off3, *tail_rows3, *tail_U3;
-  unsigned char* tail_s3;
-};
-
-static int plan(const milan_ctx* c, int n, int H, int W, Arena& a, EncPlan* pl) {
-  const int wd = c->d.trunk_width;
-  pl->h1 = conv_out(H, 7, 2, 3); pl->w1 = conv_out(W, 7, 2, 3);
-  pl->hp = conv_out(pl->h1, 3, 2, 1); pl->wp = conv_out(pl->w1, 3, 2, 1);
-  Levels& lv = pl->lv;
-  lv.h[0] = pl->h1; lv.w[0] = pl->w1;
-  lv.h[1] = pl->hp; lv.w[1] = pl->wp;
-  for (int l = 2; l < 5; ++l) {
-    lv.h[l] = conv_out(lv.h[l - 1], 3, 2, 1);
-    lv.w[l] = conv_out(lv.w[l - 1], 3, 2, 1);
-  }
-  long off = 0;
-  for (int l = 0; l < 5; ++l) { lv.off[l] = off; off += (long)lv.h[l] * lv.w[l]; }
-  lv.per_image = off;
-  // Per-image extents of the activation buffers: the largest tensor each one
-  // ever holds.  At 224x224 that is always the layer1 tensor, but once an image
-  // is so small that the spatial size bottoms out at 1x1 the channel growth of
-  // the later stages wins.
-  const int exp = c->d.trunk_kind == MILAN_TRUNK_BASIC ? 1 : 4;
-  size_t x_sz = (size_t)pl->hp * pl->wp * wd, t1_sz = 0, t2_sz = 0;
-  for (int li = 0; li < 4; ++li) {
-    const size_t planes = (size_t)wd << li;
-    const size_t in_px = (size_t)lv.h[li == 0 ? 1 : li] * lv.w[li == 0 ? 1 : li];
-    const size_t out_px = (size_t)lv.h[li + 1] * lv.w[li + 1];
-    x_sz = x_sz > out_px * planes * exp ? x_sz : out_px * planes * exp;
-    t1_sz = t1_sz > in_px * planes ? t1_sz : in_px * planes;   // c1 output
-    t2_sz = t2_sz > out_px * planes ? t2_sz : out_px * planes; // c2 output
-  }
-  pl->x_sz = x_sz; pl->t1_sz = t1_sz; pl->t2_sz = t2_sz;
-  pl->in4 = a.get<float>((size_t)n * H * (W + 2) * 4);
-  pl->raw = a.get<float>((size_t)n * pl->h1 * pl->w1 * wd);
-  pl->x0 = a.get<float>((size_t)n * x_sz);
-  pl->x1 = a.get<float>((size_t)n * x_sz);
-  pl->ds = a.get<float>((size_t)n * x_sz);
-  pl->t1 = a.get<float>((size_t)n * t1_sz);
-  pl->t2 = a.get<float>((size_t)n * t2_sz);
-  pl->list_idx = a.get<int>((size_t)n * lv.per_image);
-  pl->list_w = a.get<float>((size_t)n * lv.per_image);
-  pl->list_n = a.get<int>((size_t)n * 5);
-  pl->bbox = a.get<int>((size_t)n * 4);
-  pl->poison = a.get<int>((size_t)n);
-  pl->order = a.get<int>((size_t)n);
-  pl->bbox_c = a.get<int>((size_t)n * 4);
-  pl->count = a.get<int>(4);
-  {
-    const size_t P4 = (size_t)lv.h[4] * lv.w[4];
-    pl->tail_loc = a.get<int>(3 * (size_t)n * P4);
-    pl->tail_rows = a.get<int>(3 * (size_t)n * P4);
-    pl->tail_cnt = a.get<int>(3 * (size_t)n);
-    pl->tail_off = a.get<int>(3 * (size_t)n);
-    pl->tail_U = a.get<int>(4);
-    pl->sh_hash = a.get<unsigned long long>((size_t)n);
-    pl->sh_rep = a.get<int>((size_t)n);
-    pl->sh_flag = a.get<int>((size_t)n);
-    pl->class_of = a.get<int>((size_t)n);
-    pl->tail_s0 = a.get<unsigned char>(((size_t)n * P4 + 3) & ~(size_t)3);
-    const size_t P3 = (size_t)lv.h[3] * lv.w[3];
-    pl->tail_loc3 = a.get<int>(2 * (size_t)n * P3);
-    pl->tail_rows3 = a.get<int>(2 * (size_t)n * P3);
-    pl->tail_cnt3 = a.get<int>(2 * (size_t)n);
-    pl->tail_off3 = a.get<int>(2 * (size_t)n);
-    pl->tail_U3 = a.get<int>(4);
-    pl->tail_s3 = a.get<unsigned char>(((size_t)n * P3 + 3) & ~(size_t)3);
-  }
-  return 0;
+// The knobs of the encoder pass, from the environment: the only getenv on it (README /
+// DESIGN 5).  MILAN_TAPS_INNER exists in the experiments build alone.
+static EncEnv read_enc_env() {
+  auto num = [](const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+  };
+  EncEnv env;
+  env.stem_u8 = num("MILAN_STEM_U8", 1) != 0;
+  env.pool_vec = num("MILAN_POOL_VEC", 1) != 0;
+  // Images per encoder pass: bounds the activation workspace (16 MB/image; 9600 =
+  // 640 neurons x 15 exemplars = 154 GB of the 288).  Smaller sub-batches were
+  // tried for Infinity-Cache locality and lost (tail effects of the smaller GEMM
+  // grids dominate; measured: 240 -15%, 480 -8%, 960 -4% vs 3840).
+  env.enc_sub = num("MILAN_ENC_SUB", 9600);
+  if (env.enc_sub < 1) env.enc_sub = 9600;
+#if MILAN_EXPERIMENTS
+  env.taps_inner = num("MILAN_TAPS_INNER", 0) != 0;
+#endif
+  return env;
 }
-
-// Images per encoder pass: bounds the activation workspace (16 MB/image; 9600 =
-// 640 neurons x 15 exemplars = 154 GB of the 288).  Smaller sub-batches were
-// tried for Infinity-Cache locality and lost (tail effects of the smaller GEMM
-// grids dominate); MILAN_ENC_SUB overrides.
-static int encoder_sub_batch() {
-  static int v = 0;
-  if (v == 0) {
-    const char* e = getenv("MILAN_ENC_SUB");
-    v = e ? atoi(e) : 9600;  // measured: 240 -15%, 480 -8%, 960 -4% vs 3840
-    if (v < 1) v = 9600;
-  }
-  return v;
+// ... once per process
+static const EncEnv& enc_env() {
+  static const EncEnv env = read_enc_env();
+  return env;
 }
+static int encoder_sub_batch() { return enc_env().enc_sub; }
 
 static void alexnet_workspace_dry(const milan_ctx* c, int n, int H, int W,
                                   Arena& a);
@@ -1403,61 +1319,9 @@ size_t encoder_workspace(const milan_ctx* c, int n_images, int H, int W) {
     alexnet_workspace_dry(c, n, H, W, a);
     return a.off;
   }
-  EncPlan pl;
-  plan(c, n, H, W, a, &pl);
+  EncBuffers pl;
+  enc_carve(c->d.trunk_kind, c->d.trunk_width, n, H, W, &a, &pl);
   return a.off;
-}
-
-static GemmArgs conv_args(const ConvW& cw, const float* in, int n, int H, int W,
-                          float* out, int epi, const float* aux,
-                          const float* zero, int* Ho, int* Wo,
-                          bool split = false, bool scaled_bias = true) {
-  GemmArgs g{};
-  *Ho = conv_out(H, cw.kh, cw.stride, cw.pad);
-  *Wo = conv_out(W, cw.kw, cw.stride, cw.pad);
-  g.A = in; g.W = cw.w; g.bias = cw.bias; g.aux = aux; g.C = out;
-  g.M = n * (*Ho) * (*Wo); g.N = cw.cout; g.K = cw.K; g.Kp = cw.Kp;
-  g.ldc = cw.cout; g.ldaux = cw.cout;
-  g.H = H; g.Wd = W; g.Cin = cw.cin; g.Ho = *Ho; g.Wo = *Wo;
-  g.KH = cw.kh; g.KW = cw.kw; g.stride = cw.stride; g.pad = cw.pad;
-  g.a_pix_stride = cw.cin;
-  g.a_img_stride = (long)H * W * cw.cin;
-  g.epilogue = epi; g.zero = zero;
-  g.flop_k = cw.kh * cw.kw * cw.cin_real;
-  if (cw.groups > 1) {
-    // one group's product, the full rows as strides (GemmArgs::groups)
-    const int ng = cw.cout / cw.groups;
-    g.N = ng;
-    g.a_pix_stride = (long)cw.cin * cw.groups;
-    g.a_img_stride = (long)H * W * cw.cin * cw.groups;
-    g.groups = cw.groups;
-    g.a_grp = cw.cin; g.w_grp = (long)ng * cw.Kp;
-    g.bias_grp = ng; g.c_grp = ng; g.aux_grp = ng;
-  }
-  if (split) {
-    g.W = cw.ws; g.a_split = 1; g.out_split = 1; g.aux_split = aux != nullptr;
-    g.acc_scale = cw.ws_inv;
-    g.W3 = cw.ws3;
-    g.Wt = cw.wst;
-    // the ResNet trunks keep split activations in the context's activation scale
-    if (scaled_bias && cw.bias_s) g.bias = cw.bias_s;
-  }
-  return g;
-}
-
-// fast mode (MILAN_PRECISION_F16): the same conv on plain f16 tensors -- every K-side
-// quantity in 4-byte units (GemmArgs::f16), weights = the f16 rows of ConvW::wf
-static GemmArgs conv_args_f16(const ConvW& cw, const float* in, int n, int H, int W,
-                              float* out, int epi, const float* aux, const float* zero,
-                              int* Ho, int* Wo) {
-  GemmArgs g = conv_args(cw, in, n, H, W, out, epi, aux, zero, Ho, Wo, true);
-  g.W = cw.wf; g.W3 = nullptr; g.Wt = cw.wft;
-  g.f16 = 1; g.out_split = 0; g.aux_split = 0;
-  g.Cin = cw.cin / 2; g.K = cw.K / 2; g.Kp = cw.Kp / 2;
-  g.a_pix_stride = cw.cin / 2;
-  g.a_img_stride = (long)H * W * (cw.cin / 2);
-  g.ldc = cw.cout / 2; g.ldaux = cw.cout / 2;
-  return g;
 }
 
 static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
@@ -1468,9 +1332,10 @@ static int alexnet_run_batch(milan_ctx* c, const void* images, int image_dtype,
                              const void* masks, int mask_dtype, int n, int H,
                              int W, float* features, Arena& ws, hipStream_t s);
 
-int encoder_run(milan_ctx* c, const void* images, int image_dtype,
-                const void* masks, int mask_dtype, int n, int H, int W,
-                float* features, Arena& ws, hipStream_t s) {
+// one pass per sub-batch of images; `out` advances by `per_image` floats per image
+static int run_sub_batches(milan_ctx* c, const void* images, int image_dtype, const void* masks,
+                           int mask_dtype, int n, int H, int W, float* out, size_t per_image,
+                           bool spatial, Arena& ws, hipStream_t s) {
   const int sub = encoder_sub_batch();
   const size_t isz = image_dtype == MILAN_DTYPE_U8 ? 1 : 4;
   const size_t msz = mask_dtype == MILAN_DTYPE_U8 ? 1 : 4;
@@ -1479,11 +1344,19 @@ int encoder_run(milan_ctx* c, const void* images, int image_dtype,
     Arena a = ws;  // every pass reuses the same scratch
     const char* im = (const char*)images + (size_t)lo * 3 * H * W * isz;
     const char* mk = masks ? (const char*)masks + (size_t)lo * H * W * msz : nullptr;
+    float* o = out + lo * per_image;
     MILAN_TRY(encoder_run_batch(c, im, image_dtype, mk, mask_dtype, cnt, H, W,
-                                features + (size_t)lo * c->d.feature_size, a, s));
+                                spatial ? nullptr : o, a, s, spatial ? o : nullptr));
     if (a.off > ws.off) ws.off = a.off > ws.size ? ws.size : ws.off;
   }
   return 0;
+}
+
+int encoder_run(milan_ctx* c, const void* images, int image_dtype,
+                const void* masks, int mask_dtype, int n, int H, int W,
+                float* features, Arena& ws, hipStream_t s) {
+  return run_sub_batches(c, images, image_dtype, masks, mask_dtype, n, H, W, features,
+                         (size_t)c->d.feature_size, false, ws, s);
 }
 
 // spatial_out != nullptr: SpatialConvEncoder mode (encoders.py:158-230) -- the
@@ -1496,23 +1369,384 @@ int encoder_run_spatial(milan_ctx* c, const void* images, int image_dtype,
                     c->d.trunk_kind != MILAN_TRUNK_ALEXNET_PLACES &&
                     c->d.trunk_kind != MILAN_TRUNK_VGG,
                 MILAN_ERR_ARG, "spatial encoding needs a ResNet trunk");
-  Arena dry; dry.dry = true;
-  EncPlan pl;
-  plan(c, 1, H, W, dry, &pl);
+  EncBuffers pl;
+  enc_carve(c->d.trunk_kind, c->d.trunk_width, 1, H, W, nullptr, &pl);
   const int C = (c->d.trunk_kind == MILAN_TRUNK_BASIC ? c->d.trunk_width
                                                       : c->d.trunk_width * 4) << 3;
-  const size_t per_image = (size_t)pl.lv.h[4] * pl.lv.w[4] * C;
-  const int sub = encoder_sub_batch();
-  const size_t isz = image_dtype == MILAN_DTYPE_U8 ? 1 : 4;
-  const size_t msz = mask_dtype == MILAN_DTYPE_U8 ? 1 : 4;
-  for (int lo = 0; lo < n; lo += sub) {
-    const int cnt = n - lo < sub ? n - lo : sub;
-    Arena a = ws;
-    const char* im = (const char*)images + (size_t)lo * 3 * H * W * isz;
-    const char* mk = masks ? (const char*)masks + (size_t)lo * H * W * msz : nullptr;
-    MILAN_TRY(encoder_run_batch(c, im, image_dtype, mk, mask_dtype, cnt, H, W,
-                                nullptr, a, s, out + lo * per_image));
-    if (a.off > ws.off) ws.off = a.off > ws.size ? ws.size : ws.off;
+  return run_sub_batches(c, images, image_dtype, masks, mask_dtype, n, H, W, out,
+                         (size_t)pl.lv.h[4] * pl.lv.w[4] * C, true, ws, s);
+}
+
+// One pass: its arguments, its buffers, its schedule, and what the input phase finds out
+// about the batch.  The functions below launch what the schedule names.
+struct EncPass {
+  milan_ctx* c;
+  hipStream_t s;
+  const void* images;
+  int image_dtype;
+  const void* masks;
+  int mask_dtype, n, H, W;
+  float *features, *spatial_out;
+  EncBuffers pl;
+  EncSchedule sc;
+  // float inputs can carry NaN / Inf pixels (uint8 ones cannot): image-level poison flags
+  int* poison;
+  // a compacted pass: batch slot j holds image order[j] (classes: the root image of live class
+  // j, and the pooling of exemplar slot i reads trunk slot class_of[i]); bbox: level-0 boxes
+  const int *order, *class_of, *bbox;
+};
+
+// calibration pass (milan_encoder_absmax): max |x| over every activation tensor of the fp32
+// pass (`word` 1: the word next to it, which bounds the FEATURES -- milan_encoder_absmax folds
+// the raw conv1 output in there, pyramid tap 0, which is no split activation)
+static int track(const EncPass& p, const float* t, long count, int word = 0) {
+  if (p.c->calib == nullptr || p.sc.split || count <= 0) return 0;
+  const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
+  hipLaunchKernelGGL(act_absmax_kernel, dim3(blocks), dim3(256), 0, p.s, t, count,
+                     p.c->calib + word);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+static int run_gemm(const EncPass& p, const GemmArgs& g) {
+  MILAN_TRY(launch_gemm(g, p.s));
+  return track(p, g.C, (long)g.M * g.N);
+}
+
+// everything the schedule depends on, from the context and the call
+static int enc_ask(const milan_ctx* c, const void* images, int image_dtype, const void* masks,
+                   int mask_dtype, int n, int H, int W, bool spatial, EncAsk* a) {
+  a->trunk_kind = c->d.trunk_kind; a->width = c->d.trunk_width; a->feature_size = c->d.feature_size;
+  a->blocks = c->blocks; a->stem = &c->stem; a->stem_pair = &c->stem_pair;
+  a->precision = c->precision; a->trunk_f16 = c->trunk_f16; a->fusion = c->fusion;
+  a->calib = c->calib != nullptr; a->share = c->share_images != 0;
+  for (int ch = 0; ch < 3; ++ch) { a->mean[ch] = c->mean[ch]; a->stdv[ch] = c->stdv[ch]; }
+  a->n = n; a->H = H; a->W = W; a->image_dtype = image_dtype;
+  a->images_aligned4 = (reinterpret_cast<uintptr_t>(images) & 3) == 0;
+  a->masks = masks != nullptr; a->mask_dtype = mask_dtype; a->spatial = spatial;
+  a->zero = c->zero;
+  a->env = enc_env();
+  return gemm_env(&a->genv);
+}
+
+// 1. masks -> per-level normalised sparse weight lists; which images take part; 2. images ->
+// normalised NHWC4 (fp32 stem) or pixel-pair groups (split stem)
+static int run_input(EncPass& p) {
+  milan_ctx* c = p.c;
+  const EncBuffers& pl = p.pl;
+  const int n = p.n, H = p.H, W = p.W;
+  hipStream_t s = p.s;
+  StageScope scope(MILAN_STAGE_ENC_INPUT, s);
+  if (p.spatial_out != nullptr) {
+    // no pooling
+  } else if (p.masks == nullptr || p.mask_dtype == MILAN_DTYPE_U8)
+    hipLaunchKernelGGL(mask_pyramid_kernel<uint8_t>, dim3(n, 5), dim3(256), 0, s,
+                       (const uint8_t*)p.masks, H, W, pl.lv, pl.list_idx,
+                       pl.list_w, pl.list_n, pl.bbox);
+  else
+    hipLaunchKernelGGL(mask_pyramid_kernel<float>, dim3(n, 5), dim3(256), 0, s,
+                       (const float*)p.masks, H, W, pl.lv, pl.list_idx, pl.list_w,
+                       pl.list_n, pl.bbox);
+  MILAN_CHECK_HIP(hipGetLastError());
+
+  // Images with an all-zero mask pool exact zeros at every level: they stay out of the trunk
+  // pass (COMPACT_SKIP_EMPTY).  Batch slot j holds image order[j]; HOW MANY slots hold work
+  // stays on the device (round 6: sc.live, one word written by compact_images_kernel): every
+  // launch below is sized for all n images and reads the count itself (GemmArgs::m_live), so
+  // nothing is read back and the stream is never synchronised -- the header's "all work is
+  // enqueued on `stream`" holds and the whole pass can be captured into a hipGraph.
+  // Image sharing (COMPACT_CLASSES; share.hip): slots of this pass that show the same uint8
+  // image share one trunk slot.  The same mechanism, generalised: slot j of the trunk batch
+  // holds the root image of the j-th live class (order[j]), bbox_c[j] is the union of the
+  // members' boxes and the pooling of exemplar slot i reads trunk slot class_of[i].  masks may
+  // be NULL (every list is full: one class per distinct image).
+  if (p.sc.compact == COMPACT_CLASSES) {
+    ShareArgs sa{};
+    sa.images = (const unsigned char*)p.images; sa.bytes = (long)3 * H * W; sa.n = n;
+    sa.hash_bits = c->share_hash_bits;
+    sa.skip_empty = (c->fusion & MILAN_FUSE_SKIP_EMPTY) != 0;
+    sa.list_n = pl.list_n; sa.bbox = pl.bbox; sa.hash = pl.sh_hash; sa.rep = pl.sh_rep;
+    sa.flag = pl.sh_flag; sa.order = pl.order; sa.bbox_c = pl.bbox_c; sa.count = pl.count;
+    sa.class_of = pl.class_of;
+    MILAN_TRY(launch_image_classes(sa, s));
+    p.class_of = pl.class_of;
+  } else if (p.sc.compact == COMPACT_SKIP_EMPTY) {
+    hipLaunchKernelGGL(compact_images_kernel, dim3(1), dim3(1024), 0, s, pl.list_n, n,
+                       pl.bbox, pl.order, pl.bbox_c, pl.count);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  if (p.sc.compact != COMPACT_NONE) {
+    // rows of the images without work: exact zeros (the pooling writes the others)
+    MILAN_TRY(launch_zero_fill(p.features, sizeof(float) * (size_t)n * c->d.feature_size, s));
+    p.order = pl.order;
+  }
+  // the device-side counters of milan_image_sharing_stats (only while sharing is enabled: the
+  // default pass launches what it always did); a pass that does not share counts slots == images
+  if (c->share_images && c->share_stats != nullptr)
+    MILAN_TRY(launch_share_count(c->share_stats, n, p.class_of ? p.sc.live : nullptr, s));
+  p.bbox = p.order ? pl.bbox_c : pl.bbox;
+
+  // the fused stem reads uint8 images itself (StemArgs::in_u8): no pixel-pair tensor
+  // (MILAN_STEM_U8=0: through preprocess_pairs_kernel, the same bits; A/B timing)
+  if (p.sc.stem_u8) {
+    if (c->stem_lut == nullptr) MILAN_TRY(dev_alloc(c, (void**)&c->stem_lut, sizeof(unsigned) * 772));
+    hipLaunchKernelGGL(stem_lut_kernel, dim3(1), dim3(128), 0, s, c->mean[0], c->mean[1], c->mean[2],
+                       c->stdv[0], c->stdv[1], c->stdv[2], c->stem_lut);
+    MILAN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
+  const bool pair_stem = p.sc.pair_stem;
+  const int G = (W + 2) / 2;  // pixel-pair groups per image row
+  const long np = pair_stem ? (long)n * H * G : (long)n * H * W;
+  const int blocks = (int)((np + 255) / 256 < 8192 ? (np + 255) / 256 : 8192);
+  const float m0 = c->mean[0], m1 = c->mean[1], m2 = c->mean[2];
+  const float s0 = c->stdv[0], s1 = c->stdv[1], s2 = c->stdv[2];
+  const void* mul = p.spatial_out ? p.masks : nullptr;  // spatial mode: x * mask
+  const int mul_u8 = p.mask_dtype == MILAN_DTYPE_U8;
+  int* const poison = p.poison;
+  if (poison) MILAN_TRY(launch_zero_fill(poison, sizeof(int) * (size_t)n, s));
+  if (pair_stem && p.image_dtype == MILAN_DTYPE_U8)
+    hipLaunchKernelGGL(preprocess_pairs_kernel<uint8_t>, dim3(blocks),
+                       dim3(256), 0, s, (const uint8_t*)p.images, np, H, W, G,
+                       m0, m1, m2, s0, s1, s2, pl.in4, mul, mul_u8, nullptr, c->status,
+                       p.order, p.sc.live);
+  else if (pair_stem)
+    hipLaunchKernelGGL(preprocess_pairs_kernel<float>, dim3(blocks), dim3(256),
+                       0, s, (const float*)p.images, np, H, W, G, m0, m1, m2, s0,
+                       s1, s2, pl.in4, mul, mul_u8, poison, c->status);
+  else if (p.image_dtype == MILAN_DTYPE_U8)
+    hipLaunchKernelGGL(preprocess_kernel<uint8_t>, dim3(blocks), dim3(256), 0,
+                       s, (const uint8_t*)p.images, np, H * W, m0, m1, m2, s0, s1,
+                       s2, (float4*)pl.in4, mul, mul_u8, nullptr, nullptr, p.order, p.sc.live);
+  else
+    hipLaunchKernelGGL(preprocess_kernel<float>, dim3(blocks), dim3(256), 0, s,
+                       (const float*)p.images, np, H * W, m0, m1, m2, s0, s1, s2,
+                       (float4*)pl.in4, mul, mul_u8, poison, c->status);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// Pools the level-`level` tensor `tap` of the n trunk slots with the kernel the schedule
+// names.  Image sharing: the grid runs over all exemplar slots, which read n trunk slots.
+static int run_pool(const EncPass& p, const float* tap, int level) {
+  if (p.spatial_out != nullptr) return 0;
+  const EncBuffers& pl = p.pl;
+  const int C = p.sc.pool_C[level], col_off = p.sc.pool_col[level], kind = p.sc.pool[level];
+  const int P = pl.lv.h[level] * pl.lv.w[level], F = p.c->d.feature_size, n = p.n;
+  const bool shared = p.class_of != nullptr;
+  const float inv_scale = kind == POOL_F32 ? 1.f : 1.f / p.c->act_scale;
+  const int ncls = shared ? n : 0;
+  StageScope scope(MILAN_STAGE_ENC_POOL, p.s);
+  if (kind == POOL_SPLIT8) {
+    const int G = C / 8;
+    hipLaunchKernelGGL(shared ? masked_pool_split8_kernel<true> : masked_pool_split8_kernel<false>,
+                       dim3(n, (G + 63) / 64), dim3(256), 0, p.s, tap, P, C, level, pl.lv,
+                       pl.list_idx, pl.list_w, pl.list_n, p.features, F, col_off, 0, inv_scale,
+                       p.poison, p.order, G < 64 ? G : 64, p.sc.live, p.class_of, ncls);
+  } else {
+    const auto kern = kind == POOL_F16     ? (shared ? masked_pool_kernel<2, true> : masked_pool_kernel<2, false>)
+                      : kind == POOL_SPLIT ? (shared ? masked_pool_kernel<1, true> : masked_pool_kernel<1, false>)
+                                           : (shared ? masked_pool_kernel<0, true> : masked_pool_kernel<0, false>);
+    hipLaunchKernelGGL(kern, dim3(n, (C + 63) / 64), dim3(256), 0, p.s, tap, P, C, level, pl.lv,
+                       pl.list_idx, pl.list_w, pl.list_n, p.features, F, col_off, 0, inv_scale,
+                       p.poison, p.order, p.sc.live, p.class_of, ncls);
+  }
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// 3. stem: raw conv1 (tap 0), then bn1+relu+maxpool
+static int run_stem(const EncPass& p) {
+  milan_ctx* c = p.c;
+  const EncBuffers& pl = p.pl;
+  const int n = p.n, wd = c->d.trunk_width;
+  const bool spatial = p.spatial_out != nullptr;
+  hipStream_t s = p.s;
+  if (p.sc.fused_stem) {
+    // conv1 + bn1 + ReLU + maxpool in one persistent launch (stem.hip); the raw
+    // tensor is only materialised where the level-0 pooling will read it
+    StemArgs sa{};
+    sa.in = pl.in4; sa.ws = c->stem_pair.ws; sa.bias = c->stem_pair.bias;
+    if (p.sc.stem_u8) {
+      sa.in = nullptr; sa.in_u8 = (const unsigned char*)p.images; sa.lut = c->stem_lut;
+      sa.order = p.order; sa.W = p.W;
+    }
+    sa.n_live = p.sc.live;
+    sa.acc_scale = c->stem_pair.ws_inv;
+    sa.scale = c->bn1_scale_s; sa.shift = c->bn1_shift_s;  // (activation scale)
+    sa.raw = spatial ? nullptr : pl.raw; sa.y = pl.x0;
+    sa.bbox = spatial ? nullptr : p.bbox;
+    sa.zero = c->zero;
+    sa.n = n; sa.H = p.H; sa.G = (p.W + 2) / 2; sa.h1 = pl.h1; sa.w1 = pl.w1;
+    sa.hp = pl.hp; sa.wp = pl.wp;
+    {
+      StageScope scope(MILAN_STAGE_ENC_STEM, s);
+      MILAN_TRY(launch_stem_fused(sa, s));
+    }
+    return run_pool(p, pl.raw, 0);
+  }
+  const GemmArgs& g = p.sc.stem;
+  {
+    StageScope scope(MILAN_STAGE_ENC_STEM, s);
+    MILAN_TRY(launch_gemm(g, s));
+  }
+  MILAN_TRY(track(p, g.C, (long)g.M * g.N, 1));
+  MILAN_TRY(run_pool(p, pl.raw, 0));
+  {
+    StageScope scope(MILAN_STAGE_ENC_STEM_TAIL, s);
+    const bool split = p.sc.split;
+    const long total = (long)n * pl.hp * pl.wp * (wd / (split ? 8 : 4));
+    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    if (split)
+      hipLaunchKernelGGL(bn_relu_maxpool_split_kernel, dim3(blocks), dim3(256), 0,
+                         s, pl.raw, n, pl.h1, pl.w1, wd, pl.hp, pl.wp,
+                         c->bn1_scale_s, c->bn1_shift_s, pl.x0, c->status, p.sc.live);
+    else
+      hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(blocks), dim3(256), 0, s,
+                         (const float4*)pl.raw, n, pl.h1, pl.w1, wd / 4, pl.hp,
+                         pl.wp, (const float4*)c->bn1_scale,
+                         (const float4*)c->bn1_shift, (float4*)pl.x0, p.sc.live);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  return track(p, pl.x0, (long)n * pl.hp * pl.wp * wd);
+}
+
+// 3b. the row sets of the mask-aware tail (sc.tail; kernels above): sets 0..2 of the last
+// stage from the level-4 pixel lists, and with k0 >= 0 the sets V, W of the stage before
+static int run_tail_sets(const EncPass& p) {
+  const EncBuffers& pl = p.pl;
+  const int n = p.n, P4 = pl.lv.h[4] * pl.lv.w[4], P3 = pl.lv.h[3] * pl.lv.w[3];
+  hipStream_t s = p.s;
+  if (p.sc.tail) {
+    const unsigned char* s0 = nullptr;
+    if (p.class_of != nullptr) {
+      MILAN_TRY(launch_zero_fill(pl.tail_s0, ((size_t)n * P4 + 3) & ~(size_t)3, s));
+      hipLaunchKernelGGL(tail_union_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
+                         p.class_of, P4, pl.tail_s0, 4);
+      s0 = pl.tail_s0;
+    }
+    hipLaunchKernelGGL(tail_sets_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
+                       p.order, p.sc.live, n, pl.tail_loc, pl.tail_cnt, s0, p.sc.lists ? 1 : 0);
+    hipLaunchKernelGGL(tail_scan_kernel, dim3(3), dim3(256), 0, s, pl.tail_cnt, n, pl.tail_off,
+                       pl.tail_U);
+    hipLaunchKernelGGL(tail_fill_kernel, dim3(n, 3), dim3(64), 0, s, pl.tail_loc, pl.tail_cnt,
+                       pl.tail_off, n, P4, pl.tail_rows);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  if (p.sc.k0 >= 0) {
+    const Bottleneck& f = p.c->blocks[3][0];
+    const unsigned char* s3 = nullptr;
+    if (p.class_of != nullptr) {
+      // image sharing: a trunk slot's level-3 pixels are the union of its members' lists
+      MILAN_TRY(launch_zero_fill(pl.tail_s3, ((size_t)n * P3 + 3) & ~(size_t)3, s));
+      hipLaunchKernelGGL(tail_union_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
+                         p.class_of, P3, pl.tail_s3, 3);
+      s3 = pl.tail_s3;
+    }
+    hipLaunchKernelGGL(tail_sets3_kernel, dim3(n), dim3(64), 0, s, pl.tail_loc, pl.tail_cnt, p.sc.k0,
+                       pl.list_idx, pl.list_n, pl.lv, p.order, p.sc.live, n, f.c2.kh, f.c2.kw,
+                       f.c2.stride, f.c2.pad, f.down.stride, s3, pl.tail_loc3, pl.tail_cnt3);
+    hipLaunchKernelGGL(tail_scan_kernel, dim3(2), dim3(256), 0, s, pl.tail_cnt3, n, pl.tail_off3,
+                       pl.tail_U3);
+    hipLaunchKernelGGL(tail_fill_kernel, dim3(n, 2), dim3(64), 0, s, pl.tail_loc3, pl.tail_cnt3,
+                       pl.tail_off3, n, P3, pl.tail_rows3);
+    MILAN_CHECK_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// c1 and c2 of a block, where they are launches of their own
+static int run_front(const EncPass& p, const EncBlock& r) {
+  if (r.c1 == C1_LAUNCH || r.c1 == C1_LIST) MILAN_TRY(run_gemm(p, r.g1));
+  if (r.c2 == C2_CONV3) {
+    // layer1's 3x3: weights in registers, input tile staged once (conv3.hip)
+    const ConvW& c2 = r.b->c2;
+    Conv3Args ca{};
+    ca.in = r.g2.A; ca.ws = c2.ws; ca.bias = c2.bias_s; ca.acc_scale = c2.ws_inv;
+    ca.out = r.g2.C; ca.zero = p.c->zero; ca.n = p.n; ca.h = r.g2.H; ca.w = r.g2.Wd;
+    ca.n_live = p.sc.live;
+    return launch_conv3_p64(ca, p.s);
+  }
+  if (r.c2 != C2_NONE) MILAN_TRY(run_gemm(p, r.g2));
+  return 0;
+}
+
+// TAIL_COPY: one bottleneck on gathered rows -- c1 at set kM, c2 / c3 at set kO; X is dense
+// [n * P4][4P] (valid at least on set kM), Y gets the rows of set kO
+static int run_tail_copy(const EncPass& p, const EncBlock& r) {
+  const EncBuffers& pl = p.pl;
+  const int P4 = pl.lv.h[4] * pl.lv.w[4];
+  const long rows_all = (long)p.n * P4;
+  const int Cin = r.b->c1.cin, P = r.b->c1.cout, Cout = r.b->c3.cout;
+  const int* rowsM = pl.tail_rows + (long)r.kM * p.n * P4;
+  const int* rowsO = pl.tail_rows + (long)r.kO * p.n * P4;
+  const int *UM = pl.tail_U + r.kM, *UO = pl.tail_U + r.kO;
+  hipStream_t s = p.s;
+  auto blocks_for = [](long items) { return (int)((items + 255) / 256 < 8192 ? (items + 255) / 256 : 8192); };
+  hipLaunchKernelGGL(tail_rows_kernel<false>, dim3(blocks_for(rows_all * (Cin / 4))), dim3(256), 0, s,
+                     (const float4*)r.X, rowsM, UM, Cin / 4, (float4*)r.g1.A);
+  MILAN_TRY(launch_gemm(r.g1, s));
+  hipLaunchKernelGGL(tail_rows_kernel<true>, dim3(blocks_for(rows_all * (P / 4))), dim3(256), 0, s,
+                     (const float4*)r.g1.C, rowsM, UM, P / 4, (float4*)r.T1);
+  hipLaunchKernelGGL(tail_im2col_kernel, dim3(blocks_for(rows_all * (9 * P / 4))), dim3(256), 0, s,
+                     (const float4*)r.T1, rowsO, UO, r.h, r.w, P, (float4*)r.g2.A);
+  MILAN_TRY(launch_gemm(r.g2, s));
+  hipLaunchKernelGGL(tail_rows_kernel<false>, dim3(blocks_for(rows_all * (Cin / 4))), dim3(256), 0, s,
+                     (const float4*)r.X, rowsO, UO, Cin / 4, (float4*)r.g3.aux);
+  MILAN_TRY(launch_gemm(r.g3, s));
+  hipLaunchKernelGGL(tail_rows_kernel<true>, dim3(blocks_for(rows_all * (Cout / 4))), dim3(256), 0, s,
+                     (const float4*)r.g3.C, rowsO, UO, Cout / 4, (float4*)r.Y);
+  MILAN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+static int run_block(const EncPass& p, const EncBlock& r) {
+  switch (r.form) {
+    case EF_TAIL_COPY:
+      return run_tail_copy(p, r);
+    case EF_BASIC:
+      MILAN_TRY(run_gemm(p, r.g1));
+      if (r.has_gd) MILAN_TRY(run_gemm(p, r.gd));
+      return run_gemm(p, r.g2);
+    case EF_CHAIN_PLAIN:
+    case EF_CHAIN_DS:
+      MILAN_TRY(run_front(p, r));
+      return launch_chain(r.chain, p.s);
+    case EF_F16:
+    case EF_TAIL_LISTS:
+    case EF_LIST_FIRST:
+    case EF_LIST_LAST3:
+    case EF_TWO_SOURCE:
+    case EF_PLAIN:
+      MILAN_TRY(run_front(p, r));
+      if (r.has_gd) MILAN_TRY(run_gemm(p, r.gd));
+      return run_gemm(p, r.g3);
+  }
+  MILAN_REQUIRE(false, MILAN_ERR_STATE, "internal: block without a form");
+}
+
+// spatial mode: layer4 output, NHWC == the reference's permute(0, 2, 3, 1): (n, h*w, C)
+static int run_spatial_out(const EncPass& p) {
+  const int C = p.sc.pool_C[4], h = p.sc.h_out[3], w = p.sc.w_out[3];
+  const float* x = p.sc.out[3];
+  const long rows = (long)p.n * h * w;
+  hipStream_t s = p.s;
+  if (p.sc.split) {
+    const long total = rows * (C / 8);
+    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    hipLaunchKernelGGL(split_to_f32_kernel, dim3(blocks), dim3(256), 0, s, x,
+                       total, p.spatial_out, 1.f / p.c->act_scale);
+    MILAN_CHECK_HIP(hipGetLastError());
+  } else {
+    MILAN_CHECK_HIP(hipMemcpyAsync(p.spatial_out, x, sizeof(float) * rows * C,
+                                   hipMemcpyDeviceToDevice, s));
+  }
+  if (p.poison) {
+    const long per_image = (long)h * w * C;
+    const long total = (long)p.n * per_image;
+    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(poison_fill_kernel, dim3(blocks), dim3(256), 0, s, p.spatial_out,
+                       per_image, p.n, p.poison);
+    MILAN_CHECK_HIP(hipGetLastError());
   }
   return 0;
 }
@@ -1541,756 +1775,40 @@ static int encoder_run_batch(milan_ctx* c, const void* images, int image_dtype,
     return alexnet_run_batch(c, images, image_dtype, masks, mask_dtype, n, H, W,
                              features, ws, s);
   }
-  EncPlan pl;
-  plan(c, n, H, W, ws, &pl);
+  EncPass p{c, s, images, image_dtype, masks, mask_dtype, n, H, W, features, spatial_out};
+  enc_carve(c->d.trunk_kind, c->d.trunk_width, n, H, W, &ws, &p.pl);
   MILAN_REQUIRE(ws.off <= ws.size, MILAN_ERR_WORKSPACE,
                 "encode: workspace too small (%zu needed, %zu given)", ws.off,
                 ws.size);
-  const int wd = c->d.trunk_width;
-  const int F = c->d.feature_size;
-  // float inputs can carry NaN / Inf pixels (uint8 ones cannot): image-level poison flags
-  int* const poison = image_dtype == MILAN_DTYPE_F32 ? pl.poison : nullptr;
-  // calibration pass (milan_encoder_absmax): max |x| over every activation tensor
-  // (`word` 1: the word next to it, which bounds the FEATURES -- milan_encoder_absmax folds
-  // the raw conv1 output in there, pyramid tap 0, which is no split activation)
-  auto track = [&](const float* t, long count, int word = 0) -> int {
-    if (c->calib == nullptr || count <= 0) return 0;
-    const int blocks = (int)((count + 255) / 256 < 4096 ? (count + 255) / 256 : 4096);
-    hipLaunchKernelGGL(act_absmax_kernel, dim3(blocks), dim3(256), 0, s, t, count,
-                       c->calib + word);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  };
+  EncAsk ask;
+  MILAN_TRY(enc_ask(c, images, image_dtype, masks, mask_dtype, n, H, W, spatial, &ask));
+  p.sc = plan_encoder(ask, p.pl);
+  p.poison = image_dtype == MILAN_DTYPE_F32 ? p.pl.poison : nullptr;
+  p.order = p.class_of = p.bbox = nullptr;
 
-  // 1. masks -> per-level normalised sparse weight lists
-  std::optional<StageScope> stage;  // current profiling region (RAII)
-  stage.emplace(MILAN_STAGE_ENC_INPUT, s);
-  if (spatial) {
-    // no pooling
-  } else if (masks == nullptr || mask_dtype == MILAN_DTYPE_U8)
-    hipLaunchKernelGGL(mask_pyramid_kernel<uint8_t>, dim3(n, 5), dim3(256), 0, s,
-                       (const uint8_t*)masks, H, W, pl.lv, pl.list_idx,
-                       pl.list_w, pl.list_n, pl.bbox);
-  else
-    hipLaunchKernelGGL(mask_pyramid_kernel<float>, dim3(n, 5), dim3(256), 0, s,
-                       (const float*)masks, H, W, pl.lv, pl.list_idx, pl.list_w,
-                       pl.list_n, pl.bbox);
-  MILAN_CHECK_HIP(hipGetLastError());
-
-  // 1b. images with an all-zero mask pool exact zeros at every level: they stay out of the
-  // trunk pass (MILAN_FUSE_SKIP_EMPTY; uint8 images only -- a float image may hold a NaN
-  // pixel, whose image the reference turns into NaN even under a zero mask).  Batch slot j
-  // holds image order[j]; HOW MANY slots hold work stays on the device (round 6: `live`, one
-  // word written by compact_images_kernel): every launch below is sized for all n images
-  // and reads the count itself (GemmArgs::m_live), so nothing is read back and the stream
-  // is never synchronised -- the header's "all work is enqueued on `stream`" holds again
-  // and the whole pass can be captured into a hipGraph.
-  const int n_all = n;
-  const int* order = nullptr;
-  const int* live = nullptr;
-  // 1c. image sharing (milan_set_image_sharing; share.hip): slots of this pass that show the
-  // same uint8 image share one trunk slot.  The same mechanism, generalised: slot j of the
-  // trunk batch holds the root image of the j-th live class (order[j]), bbox_c[j] is the
-  // union of the members' boxes and the pooling of exemplar slot i reads trunk slot
-  // class_of[i].  masks may be NULL (every list is full: one class per distinct image).
-  const int* class_of = nullptr;
-  if (!spatial && image_dtype == MILAN_DTYPE_U8 && c->calib == nullptr && c->share_images) {
-    ShareArgs sa{};
-    sa.images = (const unsigned char*)images; sa.bytes = (long)3 * H * W; sa.n = n_all;
-    sa.hash_bits = c->share_hash_bits;
-    sa.skip_empty = (c->fusion & MILAN_FUSE_SKIP_EMPTY) != 0;
-    sa.list_n = pl.list_n; sa.bbox = pl.bbox; sa.hash = pl.sh_hash; sa.rep = pl.sh_rep;
-    sa.flag = pl.sh_flag; sa.order = pl.order; sa.bbox_c = pl.bbox_c; sa.count = pl.count;
-    sa.class_of = pl.class_of;
-    MILAN_TRY(launch_image_classes(sa, s));
-    MILAN_TRY(launch_zero_fill(features, sizeof(float) * (size_t)n_all * c->d.feature_size, s));
-    order = pl.order;
-    live = pl.count;
-    class_of = pl.class_of;
-  } else if (!spatial && masks != nullptr && image_dtype == MILAN_DTYPE_U8 && c->calib == nullptr &&
-      (c->fusion & MILAN_FUSE_SKIP_EMPTY)) {
-    hipLaunchKernelGGL(compact_images_kernel, dim3(1), dim3(1024), 0, s, pl.list_n, n_all,
-                       pl.bbox, pl.order, pl.bbox_c, pl.count);
-    MILAN_CHECK_HIP(hipGetLastError());
-    // rows of the images without work: exact zeros (the pooling writes the others)
-    MILAN_TRY(launch_zero_fill(features, sizeof(float) * (size_t)n_all * c->d.feature_size, s));
-    order = pl.order;
-    live = pl.count;
-  }
-  // the device-side counters of milan_image_sharing_stats (only while sharing is enabled: the
-  // default pass launches what it always did); a pass that does not share counts slots == images
-  if (c->share_images && c->share_stats != nullptr)
-    MILAN_TRY(launch_share_count(c->share_stats, n_all, class_of ? live : nullptr, s));
-  const int* const bbox = order ? pl.bbox_c : pl.bbox;
-  // every trunk launch carries the device-side image count (rows per image = Ho x Wo)
-  auto launch_live = [&](GemmArgs g) -> int {
-    g.m_live = live;
-    g.m_live_mul = g.Ho * g.Wo;
-    return launch_gemm(g, s);
-  };
-
-  // split-f16 mode needs every bottleneck conv to have a split weight copy
-  bool split = c->precision == MILAN_PRECISION_SPLIT_F16 && wd % 8 == 0;
-  for (int li = 0; li < 4 && split; ++li)
-    for (const Bottleneck& b : c->blocks[li])
-      split = split && b.c1.ws && b.c2.ws && (b.basic || b.c3.ws) &&
-              (!b.has_down || b.down.ws);
-  // fast mode: layer3 / layer4 of a bottleneck trunk on plain f16 (needs every conv's f16 rows)
-  bool fast = split && c->trunk_f16 && !spatial && c->d.trunk_kind == MILAN_TRUNK_BOTTLENECK;
-  for (int li = 2; li < 4 && fast; ++li)
-    for (const Bottleneck& b : c->blocks[li])
-      fast = fast && !b.basic && b.c1.wf && b.c2.wf && (b.has_down ? b.c3d.wf != nullptr : b.c3.wf != nullptr);
-  const bool pair_stem = split && c->stem_pair.ws != nullptr;
-  const int G = (W + 2) / 2;  // pixel-pair groups per image row
-
-  // the fused stem reads uint8 images itself (StemArgs::in_u8): no pixel-pair tensor
-  // (MILAN_STEM_U8=0: through preprocess_pairs_kernel, the same bits; A/B timing)
-  static const bool stem_u8_on = !(getenv("MILAN_STEM_U8") && atoi(getenv("MILAN_STEM_U8")) == 0);
-  float norm_max = 0.f;  // largest normalised pixel magnitude: the table must not saturate
-  for (int ch = 0; ch < 3; ++ch) {
-    const float a0 = fabsf((0.f - c->mean[ch]) / c->stdv[ch]), a1 = fabsf((1.f - c->mean[ch]) / c->stdv[ch]);
-    norm_max = fmaxf(norm_max, fmaxf(a0, a1));
-  }
-  const bool stem_u8 = stem_u8_on && pair_stem && !spatial && image_dtype == MILAN_DTYPE_U8 &&
-                       (c->fusion & MILAN_FUSE_STEM) && norm_max < 60000.f && W % 4 == 0 &&
-                       (reinterpret_cast<uintptr_t>(images) & 3) == 0 &&
-                       stem_fused_supported(c->stem_pair.cout, c->stem_pair.Kp);
-  if (stem_u8) {
-    if (c->stem_lut == nullptr) MILAN_TRY(dev_alloc(c, (void**)&c->stem_lut, sizeof(unsigned) * 772));
-    hipLaunchKernelGGL(stem_lut_kernel, dim3(1), dim3(128), 0, s, c->mean[0], c->mean[1], c->mean[2],
-                       c->stdv[0], c->stdv[1], c->stdv[2], c->stem_lut);
-    MILAN_CHECK_HIP(hipGetLastError());
-  }
-
-  // 2. images -> normalised NHWC4 (fp32 stem) or pixel-pair groups (split stem)
-  if (!stem_u8) {
-    const long np = pair_stem ? (long)n * H * G : (long)n * H * W;
-    const int blocks = (int)((np + 255) / 256 < 8192 ? (np + 255) / 256 : 8192);
-    const float m0 = c->mean[0], m1 = c->mean[1], m2 = c->mean[2];
-    const float s0 = c->stdv[0], s1 = c->stdv[1], s2 = c->stdv[2];
-    const void* mul = spatial ? masks : nullptr;  // spatial mode: x * mask
-    const int mul_u8 = mask_dtype == MILAN_DTYPE_U8;
-    if (poison) MILAN_TRY(launch_zero_fill(poison, sizeof(int) * (size_t)n, s));
-    if (pair_stem && image_dtype == MILAN_DTYPE_U8)
-      hipLaunchKernelGGL(preprocess_pairs_kernel<uint8_t>, dim3(blocks),
-                         dim3(256), 0, s, (const uint8_t*)images, np, H, W, G,
-                         m0, m1, m2, s0, s1, s2, pl.in4, mul, mul_u8, nullptr, c->status,
-                         order, live);
-    else if (pair_stem)
-      hipLaunchKernelGGL(preprocess_pairs_kernel<float>, dim3(blocks), dim3(256),
-                         0, s, (const float*)images, np, H, W, G, m0, m1, m2, s0,
-                         s1, s2, pl.in4, mul, mul_u8, poison, c->status);
-    else if (image_dtype == MILAN_DTYPE_U8)
-      hipLaunchKernelGGL(preprocess_kernel<uint8_t>, dim3(blocks), dim3(256), 0,
-                         s, (const uint8_t*)images, np, H * W, m0, m1, m2, s0, s1,
-                         s2, (float4*)pl.in4, mul, mul_u8, nullptr, nullptr, order, live);
-    else
-      hipLaunchKernelGGL(preprocess_kernel<float>, dim3(blocks), dim3(256), 0, s,
-                         (const float*)images, np, H * W, m0, m1, m2, s0, s1, s2,
-                         (float4*)pl.in4, mul, mul_u8, poison, c->status);
-    MILAN_CHECK_HIP(hipGetLastError());
-  }
-  stage.reset();
-
-  // tap: level-`level` tensor of images img0 .. img0 + cnt - 1
-  auto pool = [&](const float* tap, int level, int C, int col_off, int img0 = 0,
-                  int cnt = -1) -> int {
-    if (spatial) return 0;
-    if (cnt < 0) cnt = n;
-    if (cnt == 0) return 0;
-    StageScope scope(MILAN_STAGE_ENC_POOL, s);
-    const int P = pl.lv.h[level] * pl.lv.w[level];
-    if (class_of != nullptr) {
-      // image sharing: the grid runs over all exemplar slots, `cnt` trunk slots from img0 on
-      if (fast && level >= 3)
-        hipLaunchKernelGGL((masked_pool_kernel<2, true>), dim3(n, (C + 63) / 64), dim3(256), 0, s,
-                           tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
-                           col_off, img0, 1.f / c->act_scale, poison, order, live, class_of, cnt);
-      else if (split && level > 0) {
-        static const bool vec = !(getenv("MILAN_POOL_VEC") && atoi(getenv("MILAN_POOL_VEC")) == 0);
-        const int G = C / 8;
-        if (vec && C % 8 == 0 && (G % 64 == 0 || (G < 64 && 64 % G == 0)) && (col_off % 4) == 0)
-          hipLaunchKernelGGL(masked_pool_split8_kernel<true>, dim3(n, (G + 63) / 64), dim3(256), 0,
-                             s, tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features,
-                             F, col_off, img0, 1.f / c->act_scale, poison, order, G < 64 ? G : 64,
-                             live, class_of, cnt);
-        else
-          hipLaunchKernelGGL((masked_pool_kernel<1, true>), dim3(n, (C + 63) / 64), dim3(256), 0, s,
-                             tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
-                             col_off, img0, 1.f / c->act_scale, poison, order, live, class_of, cnt);
-      } else
-        hipLaunchKernelGGL((masked_pool_kernel<0, true>), dim3(n, (C + 63) / 64), dim3(256), 0, s,
-                           tap, P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
-                           col_off, img0, 1.f, poison, order, live, class_of, cnt);
-      MILAN_CHECK_HIP(hipGetLastError());
-      return 0;
-    }
-    if (fast && level >= 3)
-      hipLaunchKernelGGL(masked_pool_kernel<2>, dim3(cnt, (C + 63) / 64),
-                         dim3(256), 0, s, tap, P, C, level, pl.lv, pl.list_idx,
-                         pl.list_w, pl.list_n, features, F, col_off, img0,
-                         1.f / c->act_scale, poison, order, live);
-    else if (split && level > 0) {
-      // MILAN_POOL_VEC=0: a lane per channel (rounds 1-4; A/B timing)
-      static const bool vec = !(getenv("MILAN_POOL_VEC") && atoi(getenv("MILAN_POOL_VEC")) == 0);
-      const int G = C / 8;
-      if (vec && C % 8 == 0 && (G % 64 == 0 || (G < 64 && 64 % G == 0)) && (col_off % 4) == 0)
-        hipLaunchKernelGGL(masked_pool_split8_kernel<false>, dim3(cnt, (G + 63) / 64), dim3(256), 0, s, tap,
-                           P, C, level, pl.lv, pl.list_idx, pl.list_w, pl.list_n, features, F,
-                           col_off, img0, 1.f / c->act_scale, poison, order, G < 64 ? G : 64, live);
-      else
-        hipLaunchKernelGGL(masked_pool_kernel<1>, dim3(cnt, (C + 63) / 64),
-                           dim3(256), 0, s, tap, P, C, level, pl.lv, pl.list_idx,
-                           pl.list_w, pl.list_n, features, F, col_off, img0,
-                           1.f / c->act_scale, poison, order, live);
-    }
-    else
-      hipLaunchKernelGGL(masked_pool_kernel<0>, dim3(cnt, (C + 63) / 64),
-                         dim3(256), 0, s, tap, P, C, level, pl.lv, pl.list_idx,
-                         pl.list_w, pl.list_n, features, F, col_off, img0, 1.f, poison, order, live);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  };
-
-  // 3. stem: raw conv1 (tap 0), then bn1+relu+maxpool
-  int ho, wo;
-  {
-    GemmArgs g = conv_args(c->stem, pl.in4, n, H, W, pl.raw, EPI_BIAS, nullptr,
-                           c->zero, &ho, &wo);
-    if (pair_stem) {
-      // KH=7 x KW=4 over pixel-pair groups, horizontal stride 1 / pad 1
-      g = conv_args(c->stem_pair, pl.in4, n, H, G, pl.raw, EPI_BIAS, nullptr,
-                    c->zero, &ho, &wo, true);
-      g.Ho = ho = pl.h1; g.Wo = wo = pl.w1;
-      g.M = n * ho * wo;
-      g.aniso = 1; g.stride_w = 1; g.pad_w = 1;
-      g.out_split = 0;  // the raw fp32 output is pyramid tap 0
-      g.flop_k = c->stem.kh * c->stem.kw * c->stem.cin_real;  // 7x7x3 = 147
-    }
-    const bool fused_stem = pair_stem && (c->fusion & MILAN_FUSE_STEM) &&
-                            stem_fused_supported(c->stem_pair.cout, c->stem_pair.Kp);
-    if (fused_stem) {
-      // conv1 + bn1 + ReLU + maxpool in one persistent launch (stem.hip); the raw
-      // tensor is only materialised where the level-0 pooling will read it
-      StemArgs sa{};
-      sa.in = pl.in4; sa.ws = c->stem_pair.ws; sa.bias = c->stem_pair.bias;
-      if (stem_u8) {
-        sa.in = nullptr; sa.in_u8 = (const unsigned char*)images; sa.lut = c->stem_lut;
-        sa.order = order; sa.W = W;
-      }
-      sa.n_live = live;
-      sa.acc_scale = c->stem_pair.ws_inv;
-      sa.scale = c->bn1_scale_s; sa.shift = c->bn1_shift_s;  // (activation scale)
-      sa.raw = spatial ? nullptr : pl.raw; sa.y = pl.x0;
-      sa.bbox = spatial ? nullptr : bbox;
-      sa.zero = c->zero;
-      sa.n = n; sa.H = H; sa.G = G; sa.h1 = pl.h1; sa.w1 = pl.w1;
-      sa.hp = pl.hp; sa.wp = pl.wp;
-      {
-        StageScope scope(MILAN_STAGE_ENC_STEM, s);
-        MILAN_TRY(launch_stem_fused(sa, s));
-      }
-      MILAN_TRY(pool(pl.raw, 0, wd, 0));
-    } else {
-    {
-      StageScope scope(MILAN_STAGE_ENC_STEM, s);
-      MILAN_TRY(launch_live(g));
-    }
-    if (c->calib && !split) MILAN_TRY(track(g.C, (long)g.M * g.N, 1));
-    MILAN_TRY(pool(pl.raw, 0, wd, 0));
-    stage.emplace(MILAN_STAGE_ENC_STEM_TAIL, s);
-    const long total = (long)n * pl.hp * pl.wp * (wd / (split ? 8 : 4));
-    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (split)
-      hipLaunchKernelGGL(bn_relu_maxpool_split_kernel, dim3(blocks), dim3(256), 0,
-                         s, pl.raw, n, pl.h1, pl.w1, wd, pl.hp, pl.wp,
-                         c->bn1_scale_s, c->bn1_shift_s, pl.x0, c->status, live);
-    else
-      hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(blocks), dim3(256), 0, s,
-                         (const float4*)pl.raw, n, pl.h1, pl.w1, wd / 4, pl.hp,
-                         pl.wp, (const float4*)c->bn1_scale,
-                         (const float4*)c->bn1_shift, (float4*)pl.x0, live);
-    MILAN_CHECK_HIP(hipGetLastError());
-    stage.reset();
-    }
-    if (c->calib && !split) {
-      MILAN_TRY(track(pl.x0, (long)n * pl.hp * pl.wp * wd));
-    }
-  }
-
-  // (calibration: every conv output of the fp32 pass is folded into the running maximum)
-  auto gemm_t = [&](const GemmArgs& g) -> int {
-    MILAN_TRY(launch_live(g));
-    if (c->calib && !split) MILAN_TRY(track(g.C, (long)g.M * g.N));
-    return 0;
-  };
-  // 3b. mask-aware tail of the last stage (MILAN_FUSE_SPARSE_TAIL): the row sets the last two
-  // bottlenecks are needed at, from the level-4 pixel lists (kernels above)
-  const int P4 = pl.lv.h[4] * pl.lv.w[4];
-  bool tail = split && !fast && !spatial && masks != nullptr && c->calib == nullptr &&
-              (c->fusion & MILAN_FUSE_SPARSE_TAIL) && c->d.trunk_kind == MILAN_TRUNK_BOTTLENECK &&
-              c->blocks[3].size() >= 2 && P4 >= 1 && P4 <= kTailMaxP;
-  if (tail) {
-    const Bottleneck& lb = c->blocks[3].back();
-    // scratch of a sparse block = the raw conv1 tensor (dead after the level-0 pooling)
-    const size_t need = (size_t)P4 * ((size_t)2 * lb.c1.cin + lb.c3.cout + (size_t)11 * lb.c1.cout);
-    tail = need <= (size_t)pl.h1 * pl.w1 * wd;
-  }
-  // MILAN_FUSE_TAIL_LISTS: the row sets go to the GEMM tile as row lists (GemmArgs::row_list)
-  const bool lists = tail && (c->fusion & MILAN_FUSE_TAIL_LISTS);
-  if (tail) {
-    const unsigned char* s0 = nullptr;
-    if (class_of != nullptr) {
-      MILAN_TRY(launch_zero_fill(pl.tail_s0, ((size_t)n * P4 + 3) & ~(size_t)3, s));
-      hipLaunchKernelGGL(tail_union_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
-                         class_of, P4, pl.tail_s0, 4);
-      s0 = pl.tail_s0;
-    }
-    hipLaunchKernelGGL(tail_sets_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
-                       order, live, n, pl.tail_loc, pl.tail_cnt, s0, lists ? 1 : 0);
-    hipLaunchKernelGGL(tail_scan_kernel, dim3(3), dim3(256), 0, s, pl.tail_cnt, n, pl.tail_off,
-                       pl.tail_U);
-    hipLaunchKernelGGL(tail_fill_kernel, dim3(n, 3), dim3(64), 0, s, pl.tail_loc, pl.tail_cnt,
-                       pl.tail_off, n, P4, pl.tail_rows);
-    MILAN_CHECK_HIP(hipGetLastError());
-  }
-  auto tail_block_ok = [&](const Bottleneck& b) {
-    return !b.basic && !b.has_down && b.c1.ws && b.c2.ws && b.c2.wst && b.c3.ws && b.c1.bias_s &&
-           b.c2.bias_s && b.c3.bias_s && b.c1.kh == 1 && b.c1.kw == 1 && b.c1.stride == 1 &&
-           b.c2.kh == 3 && b.c2.kw == 3 && b.c2.stride == 1 && b.c2.pad == 1 && b.c3.kh == 1 &&
-           b.c3.kw == 1 && b.c3.stride == 1 && b.c1.K == b.c1.Kp && b.c2.K == b.c2.Kp &&
-           b.c3.K == b.c3.Kp && b.c1.cout % 32 == 0 && b.c2.cin == b.c1.cout &&
-           b.c2.cout == b.c1.cout && b.c3.cin == b.c1.cout && b.c3.cout == b.c1.cin &&
-           b.c1.cin % 4 == 0;
-  };
-  // one bottleneck on row sets: c1 at set kM (the 3x3 neighbourhoods of set kO), c2 / c3 at set kO;
-  // X is dense [n * P4][4P] (valid at least on set kM), Y gets the rows of set kO
-  auto tail_block = [&](const Bottleneck& b, const float* X, float* Y, float* T1, int hh,
-                        int ww, int kM, int kO) -> int {
-    const long rows_all = (long)n * P4;
-    const int Cin = b.c1.cin, P = b.c1.cout, Cout = b.c3.cout;
-    float* xg = pl.raw;
-    float* t1c = xg + rows_all * Cin;
-    float* acol = t1c + rows_all * P;
-    float* t2c = acol + rows_all * 9 * P;
-    float* rg = t2c + rows_all * P;
-    float* yc = rg + rows_all * Cin;
-    const int* rowsM = pl.tail_rows + (long)kM * n * P4;
-    const int* rowsO = pl.tail_rows + (long)kO * n * P4;
-    const int* UM = pl.tail_U + kM;
-    const int* UO = pl.tail_U + kO;
-    auto blocks_for = [](long items) { return (int)((items + 255) / 256 < 8192 ? (items + 255) / 256 : 8192); };
-    auto lin = [&](const float* A, int K, const ConvW& cw, const float* W, float* C, int N, int epi,
-                   const float* aux, const int* U) -> int {
-      GemmArgs g = linear_args(A, K, W, cw.bias_s, C, N, (int)rows_all, N, K, epi, c->zero, aux, N);
-      g.a_split = 1; g.out_split = 1; g.aux_split = aux != nullptr;
-      g.acc_scale = cw.ws_inv;
-      g.flop_k = cw.kh * cw.kw * cw.cin_real;
-      g.m_live = U; g.m_live_mul = 1;
-      return launch_gemm(g, s);
-    };
-    hipLaunchKernelGGL(tail_rows_kernel<false>, dim3(blocks_for(rows_all * (Cin / 4))), dim3(256), 0, s,
-                       (const float4*)X, rowsM, UM, Cin / 4, (float4*)xg);
-    MILAN_TRY(lin(xg, Cin, b.c1, b.c1.ws, t1c, P, EPI_BIAS_RELU, nullptr, UM));
-    hipLaunchKernelGGL(tail_rows_kernel<true>, dim3(blocks_for(rows_all * (P / 4))), dim3(256), 0, s,
-                       (const float4*)t1c, rowsM, UM, P / 4, (float4*)T1);
-    hipLaunchKernelGGL(tail_im2col_kernel, dim3(blocks_for(rows_all * (9 * P / 4))), dim3(256), 0, s,
-                       (const float4*)T1, rowsO, UO, hh, ww, P, (float4*)acol);
-    MILAN_TRY(lin(acol, 9 * P, b.c2, b.c2.wst, t2c, P, EPI_BIAS_RELU, nullptr, UO));
-    hipLaunchKernelGGL(tail_rows_kernel<false>, dim3(blocks_for(rows_all * (Cin / 4))), dim3(256), 0, s,
-                       (const float4*)X, rowsO, UO, Cin / 4, (float4*)rg);
-    MILAN_TRY(lin(t2c, P, b.c3, b.c3.ws, yc, Cout, EPI_BIAS_RES_RELU, rg, UO));
-    hipLaunchKernelGGL(tail_rows_kernel<true>, dim3(blocks_for(rows_all * (Cout / 4))), dim3(256), 0, s,
-                       (const float4*)yc, rowsO, UO, Cout / 4, (float4*)Y);
-    MILAN_CHECK_HIP(hipGetLastError());
-    return 0;
-  };
-
-  // ... the same block on row lists (MILAN_FUSE_TAIL_LISTS): the three convs as the dense pass
-  // launches them, each over its set's rows of the DENSE tensors -- no copy, no compact scratch
-  auto on_list = [&](GemmArgs g, const int* rows, const int* U) {
-    g.row_list = rows; g.m_live = U; g.m_live_mul = 1;
-    return g;
-  };
-  auto list_ok = [&](const GemmArgs& g) { return row_list_supported(on_list(g, pl.tail_rows, pl.tail_U)); };
-  auto tail_block_args = [&](const Bottleneck& b, const float* X, float* Y, float* T1, int hh,
-                             int ww, GemmArgs* g1, GemmArgs* g2, GemmArgs* g3) {
-    int h1, w1, h2, w2, h3, w3;
-    *g1 = conv_args(b.c1, X, n, hh, ww, T1, EPI_BIAS_RELU, nullptr, c->zero, &h1, &w1, true);
-    *g2 = conv_args(b.c2, T1, n, h1, w1, pl.t2, EPI_BIAS_RELU, nullptr, c->zero, &h2, &w2, true);
-    *g3 = conv_args(b.c3, pl.t2, n, h2, w2, Y, EPI_BIAS_RES_RELU, X, c->zero, &h3, &w3, true);
-  };
-  auto tail_block_lists_ok = [&](const Bottleneck& b, int hh, int ww) {
-    GemmArgs g1, g2, g3;
-    tail_block_args(b, pl.x0, pl.x1, pl.t1, hh, ww, &g1, &g2, &g3);
-    return lists && list_ok(g1) && list_ok(g2) && list_ok(g3);
-  };
-  auto tail_block_lists = [&](const Bottleneck& b, const float* X, float* Y, float* T1, int hh,
-                              int ww, int kM, int kO) -> int {
-    GemmArgs g1, g2, g3;
-    tail_block_args(b, X, Y, T1, hh, ww, &g1, &g2, &g3);
-    const int* rowsM = pl.tail_rows + (long)kM * n * P4;
-    const int* rowsO = pl.tail_rows + (long)kO * n * P4;
-    MILAN_TRY(launch_gemm(on_list(g1, rowsM, pl.tail_U + kM), s));
-    MILAN_TRY(launch_gemm(on_list(g2, rowsO, pl.tail_U + kO), s));
-    MILAN_TRY(launch_gemm(on_list(g3, rowsO, pl.tail_U + kO), s));
-    return 0;
-  };
-  // c3 and the downsample of a stage's first block as ONE GEMM over [t2 | x(strided)]
-  auto two_source_args = [&](const Bottleneck& b, const float* xin, float* yo, int hh, int ww,
-                             int h2, int w2, int* h3, int* w3) {
-    GemmArgs g3 = conv_args(b.c3d, pl.t2, n, h2, w2, yo, EPI_BIAS_RELU,
-                            nullptr, c->zero, h3, w3, true);
-    g3.Cin = b.c3.cin;              // geometry of source 1 (t2)
-    g3.a_pix_stride = b.c3.cin;
-    g3.a_img_stride = (long)h2 * w2 * b.c3.cin;
-    g3.A2 = xin; g3.K1 = b.c3.K; g3.H2 = hh; g3.W2d = ww;
-    g3.stride2 = b.down.stride;
-    g3.a2_pix_stride = b.down.cin;
-    g3.a2_img_stride = (long)hh * ww * b.down.cin;
-    g3.flop_k = b.c3.K + b.down.K;
-    return g3;
-  };
-  // ... extended downwards: the first block of the last stage feeds nothing but the tail blocks,
-  // which read it at tail set k0 -- its c2 and c3 + downsample run over that set, its c1 over
-  // the pixels V its strided c2 reads there; and the last block of the stage before feeds
-  // nothing but that block and its own stage's pooling: its c2 / c3 run over W
-  // (tail_sets3_kernel).  Decided here, before the stage loop, from the geometry alone.
-  const int h3l = pl.lv.h[3], w3l = pl.lv.w[3], P3 = h3l * w3l;
-  int k0 = -1;
-  bool lists_l3 = false;
-  // (experiments build: MILAN_TAPS_INNER re-orders the 3x3 launches of the stage loop, which
-  // have no list form then -- those blocks keep today's path)
-  bool lists_down = lists;
-#if MILAN_EXPERIMENTS
-  if (getenv("MILAN_TAPS_INNER") && atoi(getenv("MILAN_TAPS_INNER"))) lists_down = false;
-#endif
-  if (lists_down && c->blocks[3].size() >= 2 && c->blocks[3].size() <= 3 && P3 <= kTailMaxP3) {
-    const std::vector<Bottleneck>& b4 = c->blocks[3];
-    const Bottleneck& f = b4[0];
-    bool ok = true;
-    for (size_t bi = 1; bi < b4.size(); ++bi) ok = ok && tail_block_ok(b4[bi]);   // they run on sets
-    ok = ok && !f.basic && f.has_down && f.c3d.ws && f.c3d.cout > 64 && f.c1.kh == 1 && f.c1.kw == 1 &&
-         f.c1.stride == 1 && f.c1.pad == 0 && f.c3.kh == 1 && f.c3.kw == 1 && f.c3.stride == 1 &&
-         f.c3.pad == 0 && f.down.kh == 1 && f.down.kw == 1 && f.down.pad == 0 && f.c2.wst &&
-         f.c1.bias_s && f.c2.bias_s && f.c3d.bias_s &&
-         conv_out(h3l, f.c2.kh, f.c2.stride, f.c2.pad) == pl.lv.h[4] &&
-         conv_out(w3l, f.c2.kw, f.c2.stride, f.c2.pad) == pl.lv.w[4] &&
-         conv_out(h3l, 1, f.down.stride, 0) == pl.lv.h[4] &&
-         conv_out(w3l, 1, f.down.stride, 0) == pl.lv.w[4] &&
-         !(f.down.stride == 1 && (c->fusion & (f.c3.cin >= 256 ? MILAN_FUSE_CHAIN_WIDE : MILAN_FUSE_CHAIN)));
-    if (ok) {
-      int h1, w1, h2, w2, h3, w3;
-      GemmArgs g1 = conv_args(f.c1, pl.x0, n, h3l, w3l, pl.t1, EPI_BIAS_RELU, nullptr, c->zero, &h1, &w1, true);
-      GemmArgs g2 = conv_args(f.c2, pl.t1, n, h1, w1, pl.t2, EPI_BIAS_RELU, nullptr, c->zero, &h2, &w2, true);
-      GemmArgs g3 = two_source_args(f, pl.x0, pl.x1, h3l, w3l, h2, w2, &h3, &w3);
-      ok = list_ok(g1) && list_ok(g2) && list_ok(g3);
-    }
-    if (ok) k0 = (int)b4.size() - 1;
-    const std::vector<Bottleneck>& b3 = c->blocks[2];
-    if (ok && b3.size() >= 2) {
-      const Bottleneck& l = b3.back();
-      bool ok3 = !l.basic && !l.has_down && l.c2.wst && l.c2.bias_s && l.c3.bias_s && l.c2.stride == 1 &&
-                 l.c3.kh == 1 && l.c3.kw == 1 && l.c3.stride == 1 && l.c3.pad == 0 &&
-                 conv_out(h3l, l.c2.kh, 1, l.c2.pad) == h3l && conv_out(w3l, l.c2.kw, 1, l.c2.pad) == w3l;
-      if (ok3) {
-        int h2, w2, h3, w3;
-        GemmArgs g2 = conv_args(l.c2, pl.t1, n, h3l, w3l, pl.t2, EPI_BIAS_RELU, nullptr, c->zero, &h2, &w2, true);
-        GemmArgs g3 = conv_args(l.c3, pl.t2, n, h2, w2, pl.x1, EPI_BIAS_RES_RELU, pl.x0, c->zero, &h3, &w3, true);
-        ok3 = list_ok(g2) && list_ok(g3);
-      }
-      lists_l3 = ok3;
-    }
-  }
-  if (k0 >= 0) {
-    const Bottleneck& f = c->blocks[3][0];
-    const unsigned char* s3 = nullptr;
-    if (class_of != nullptr) {
-      // image sharing: a trunk slot's level-3 pixels are the union of its members' lists
-      MILAN_TRY(launch_zero_fill(pl.tail_s3, ((size_t)n * P3 + 3) & ~(size_t)3, s));
-      hipLaunchKernelGGL(tail_union_kernel, dim3(n), dim3(64), 0, s, pl.list_idx, pl.list_n, pl.lv,
-                         class_of, P3, pl.tail_s3, 3);
-      s3 = pl.tail_s3;
-    }
-    hipLaunchKernelGGL(tail_sets3_kernel, dim3(n), dim3(64), 0, s, pl.tail_loc, pl.tail_cnt, k0,
-                       pl.list_idx, pl.list_n, pl.lv, order, live, n, f.c2.kh, f.c2.kw, f.c2.stride,
-                       f.c2.pad, f.down.stride, s3, pl.tail_loc3, pl.tail_cnt3);
-    hipLaunchKernelGGL(tail_scan_kernel, dim3(2), dim3(256), 0, s, pl.tail_cnt3, n, pl.tail_off3,
-                       pl.tail_U3);
-    hipLaunchKernelGGL(tail_fill_kernel, dim3(n, 2), dim3(64), 0, s, pl.tail_loc3, pl.tail_cnt3,
-                       pl.tail_off3, n, P3, pl.tail_rows3);
-    MILAN_CHECK_HIP(hipGetLastError());
-  }
-  const int* rowsV = pl.tail_rows3;
-  const int* rowsW = pl.tail_rows3 + (long)n * P3;
-
-  // 4. bottleneck stages; tap after each stage
-  float *x = pl.x0, *y = pl.x1;
-  int h = pl.hp, w = pl.wp, col = wd;
-  // t1_ready: pl.t1 already holds this block's c1 output -- the previous block's
-  // expand conv and this block's reduce conv ran as one launch (chain.hip); survives
-  // the stage boundary (the last block of layer1 chains into layer2.0's conv1)
-  bool t1_ready = false;
-  // c1 output of the current block.  A chain launch with the 3x3 conv in front (MILAN_FUSE_BNECK)
-  // reads it WITH its neighbours' pixels while writing the next block's, so those launches
-  // alternate between two buffers; pl.ds is free for that in split mode (every downsample
-  // conv is folded into its c3, and the fast mode borrows it from layer3 on only)
-  float *t1buf = pl.t1, *t1alt = pl.ds;
+  MILAN_TRY(run_input(p));
+  MILAN_TRY(run_stem(p));
+  MILAN_TRY(run_tail_sets(p));
+  // 4. the stages; tap after each stage
   for (int li = 0; li < 4; ++li) {
-    stage.emplace(MILAN_STAGE_ENC_LAYER1 + li, s);
-    const std::vector<Bottleneck>& blocks = c->blocks[li];
-    if (fast && li == 2) {
-      // the residual stream leaves the split format: f16(hi + lo) into the spare buffer
-      const long groups = (long)n * h * w * ((wd * 4) << 1) / 8;   // layer2's output channels
-      const int nb = (int)((groups + 255) / 256 < 16384 ? (groups + 255) / 256 : 16384);
-      hipLaunchKernelGGL(split_to_f16_kernel, dim3(nb), dim3(256), 0, s, x, groups, pl.ds, live,
-                         groups / n);
-      MILAN_CHECK_HIP(hipGetLastError());
-      y = x; x = pl.ds;
+    {
+      StageScope scope(MILAN_STAGE_ENC_LAYER1 + li, s);
+      if (p.sc.fast && li == 2) {
+        // the residual stream leaves the split format: f16(hi + lo) into the spare buffer
+        const long groups = p.sc.f16_groups;
+        const int nb = (int)((groups + 255) / 256 < 16384 ? (groups + 255) / 256 : 16384);
+        hipLaunchKernelGGL(split_to_f16_kernel, dim3(nb), dim3(256), 0, s, p.sc.f16_src, groups,
+                           p.pl.ds, p.sc.live, groups / n);
+        MILAN_CHECK_HIP(hipGetLastError());
+      }
+      for (int k = p.sc.first[li]; k < p.sc.first[li + 1]; ++k)
+        MILAN_TRY(run_block(p, p.sc.blocks[k]));
     }
-    for (size_t bi = 0; bi < blocks.size(); ++bi) {
-      const Bottleneck& b = blocks[bi];
-      int h1, w1, h2, w2, h3, w3;
-      if (fast && li >= 2) {
-        GemmArgs g1 = conv_args_f16(b.c1, x, n, h, w, pl.t1, EPI_BIAS_RELU, nullptr, c->zero, &h1, &w1);
-        MILAN_TRY(launch_live(g1));
-        GemmArgs g2 = conv_args_f16(b.c2, pl.t1, n, h1, w1, pl.t2, EPI_BIAS_RELU, nullptr, c->zero, &h2, &w2);
-        MILAN_TRY(launch_live(g2));
-        if (b.has_down) {
-          // c3 and the downsample as ONE GEMM over [t2 | x(strided)]
-          GemmArgs g3 = conv_args_f16(b.c3d, pl.t2, n, h2, w2, y, EPI_BIAS_RELU, nullptr, c->zero, &h3, &w3);
-          g3.Cin = b.c3.cin / 2;
-          g3.a_pix_stride = b.c3.cin / 2;
-          g3.a_img_stride = (long)h2 * w2 * (b.c3.cin / 2);
-          g3.A2 = x; g3.K1 = b.c3.K / 2; g3.H2 = h; g3.W2d = w;
-          g3.stride2 = b.down.stride;
-          g3.a2_pix_stride = b.down.cin / 2;
-          g3.a2_img_stride = (long)h * w * (b.down.cin / 2);
-          g3.flop_k = b.c3.K + b.down.K;
-          MILAN_TRY(launch_live(g3));
-        } else {
-          GemmArgs g3 = conv_args_f16(b.c3, pl.t2, n, h2, w2, y, EPI_BIAS_RES_RELU, x, c->zero, &h3, &w3);
-          MILAN_TRY(launch_live(g3));
-        }
-        float* tmp = x; x = y; y = tmp;
-        h = h3; w = w3;
-        continue;
-      }
-      if (tail && li == 3 && bi >= 1 && bi + 2 >= blocks.size() && tail_block_ok(b) &&
-          (bi + 1 == blocks.size() || tail_block_ok(blocks.back())) &&
-          h == pl.lv.h[4] && w == pl.lv.w[4]) {
-        // the last block is needed at the listed pixels (set 0) and its c1 at set 1; the block
-        // before it at set 1 and its c1 at set 2
-        const int kO = bi + 1 == blocks.size() ? 0 : 1;
-        if (tail_block_lists_ok(b, h, w)) MILAN_TRY(tail_block_lists(b, x, y, t1buf, h, w, kO + 1, kO));
-        else MILAN_TRY(tail_block(b, x, y, t1buf, h, w, kO + 1, kO));
-        float* tmp = x; x = y; y = tmp;
-        continue;
-      }
-      if (b.basic) {
-        // BasicBlock (resnet18/34): relu(bn2(conv2(relu(bn1(conv1(x))))) + id)
-        GemmArgs g1 = conv_args(b.c1, x, n, h, w, pl.t1, EPI_BIAS_RELU, nullptr,
-                                c->zero, &h1, &w1, split);
-        MILAN_TRY(gemm_t(g1));
-        const float* identity = x;
-        if (b.has_down) {
-          int hd, wdn;
-          GemmArgs gd = conv_args(b.down, x, n, h, w, pl.ds, EPI_BIAS, nullptr,
-                                  c->zero, &hd, &wdn, split);
-          MILAN_TRY(gemm_t(gd));
-          identity = pl.ds;
-        }
-        GemmArgs g2 = conv_args(b.c2, pl.t1, n, h1, w1, y, EPI_BIAS_RES_RELU,
-                                identity, c->zero, &h3, &w3, split);
-        MILAN_TRY(gemm_t(g2));
-        float* tmp = x; x = y; y = tmp;
-        h = h3; w = w3;
-        continue;
-      }
-      GemmArgs g1 = conv_args(b.c1, x, n, h, w, t1buf, EPI_BIAS_RELU, nullptr,
-                              c->zero, &h1, &w1, split);
-      // (MILAN_FUSE_BNECK, layer1.0: c1 may run inside the block's chain launch -- decided below,
-      // once the launch's shape is known)
-      const bool c1_pending = !t1_ready;
-      t1_ready = false;
-      GemmArgs g2 = conv_args(b.c2, t1buf, n, h1, w1, pl.t2, EPI_BIAS_RELU,
-                              nullptr, c->zero, &h2, &w2, split);
-#if MILAN_EXPERIMENTS
-      {
-        // MILAN_TAPS_INNER=1: 3x3 convs of layer2..4 with the nine taps of a 16-channel
-        // chunk in consecutive k-tiles (each pixel crosses the fabric once, not once per
-        // tap; NOT the same bits; measured: no gain, profiles/r3_experiments.txt L)
-        static const bool taps_inner = getenv("MILAN_TAPS_INNER") && atoi(getenv("MILAN_TAPS_INNER"));
-        if (split && taps_inner && b.c2.ws3 && b.c2.cin >= 128 && b.c2.cout > 64) {
-          g2.W = b.c2.ws3;
-          g2.chunk_major = 1;
-          g2.W3 = nullptr;  // not the LDS-strip kernel
-        }
-      }
-#endif
-      // the next block: in this stage, or the first one of the next stage (its conv1
-      // is a 1x1 / stride 1 over this stage's output; the stride sits on its conv2)
-      const bool last_of_stage = bi + 1 == blocks.size();
-      const Bottleneck* nbp = !last_of_stage ? &blocks[bi + 1]
-                              : (li + 1 < 4 && !c->blocks[li + 1].empty())
-                                    ? &c->blocks[li + 1][0] : nullptr;
-      // chain launch of this block (expand conv + the next block's reduce conv): shapes
-      bool chain_plain = false, chain_ds = false;
-      int chain_P = 0, chain_NR = 0;
-      if (split && nbp != nullptr && !(fast && last_of_stage && li + 1 >= 2) && !b.basic &&
-          (c->fusion & (b.c3.cin >= 256 ? MILAN_FUSE_CHAIN_WIDE : MILAN_FUSE_CHAIN))) {
-        const Bottleneck& nb = *nbp;
-        chain_P = b.c3.cin;
-        chain_NR = last_of_stage ? 2 * chain_P : chain_P;
-        const bool shapes = !nb.basic && nb.has_down == last_of_stage && nb.c1.ws &&
-                            b.c3.ws && b.c3.kh == 1 && b.c3.kw == 1 && b.c3.stride == 1 &&
-                            b.c3.K == b.c3.Kp && b.c3.cout == 4 * chain_P &&
-                            nb.c1.kh == 1 && nb.c1.kw == 1 && nb.c1.stride == 1 &&
-                            nb.c1.cin == 4 * chain_P && nb.c1.cout == chain_NR &&
-                            nb.c1.K == nb.c1.Kp && b.c3.bias && nb.c1.bias;
-        h2 = conv_out(h1, b.c2.kh, b.c2.stride, b.c2.pad);
-        w2 = conv_out(w1, b.c2.kw, b.c2.stride, b.c2.pad);
-        chain_plain = shapes && !b.has_down && chain_supported(chain_P, 0, chain_NR);
-        chain_ds = shapes && b.has_down && b.c3d.ws && b.down.kh == 1 &&
-                   b.down.kw == 1 && b.down.stride == 1 && h2 == h &&
-                   w2 == w && chain_supported(chain_P, b.down.cin, chain_NR);
-      }
-      // round 6 (MILAN_FUSE_BNECK): layer1's 3x3 conv runs in front of that chain launch --
-      // t2 never exists in memory (chain.hip, chain_kernel<.., CONV>)
-      const bool conv_front =
-          (chain_plain || chain_ds) && (c->fusion & MILAN_FUSE_BNECK) && b.c2.K == b.c2.Kp &&
-          b.c2.bias_s && conv3_p64_supported(b.c2.cin, b.c2.cout, b.c2.kh, b.c2.kw, b.c2.stride,
-                                             b.c2.pad) &&
-          chain_conv_supported(chain_P, chain_ds ? b.down.cin : 0, chain_NR, h1, w1);
-      // ... and for the stage's first block (64-channel input, no t1 yet) the block's own c1
-      // as well: the whole bottleneck in one launch (chain_kernel<.., CONV, C1>)
-      const bool c1_front =
-          conv_front && c1_pending && chain_ds && b.c1.ws && b.c1.bias_s && b.c1.kh == 1 &&
-          b.c1.kw == 1 && b.c1.stride == 1 && b.c1.cin == 64 && b.c1.cout == 64 &&
-          b.c1.K == b.c1.Kp && h1 == h && w1 == w &&
-          chain_conv_c1_supported(chain_P, b.down.cin, chain_NR, h1, w1);
-      if (k0 >= 0 && li == 3 && bi == 0 && !chain_plain && !chain_ds && h == h3l && w == w3l) {
-        // MILAN_FUSE_TAIL_LISTS: c1 at V, c2 and c3 + downsample at tail set k0
-        const int* rows0 = pl.tail_rows + (long)k0 * n * P4;
-        if (c1_pending) MILAN_TRY(launch_gemm(on_list(g1, rowsV, pl.tail_U3), s));
-        MILAN_TRY(launch_gemm(on_list(g2, rows0, pl.tail_U + k0), s));
-        GemmArgs g3 = two_source_args(b, x, y, h, w, h2, w2, &h3, &w3);
-        MILAN_TRY(launch_gemm(on_list(g3, rows0, pl.tail_U + k0), s));
-        float* tmp = x; x = y; y = tmp;
-        h = h3; w = w3;
-        continue;
-      }
-      if (lists_l3 && k0 >= 0 && li == 2 && last_of_stage && !chain_plain && !chain_ds &&
-          h == h3l && w == w3l) {
-        // ... the last block of the stage before: c1 as ever (dense), c2 and c3 at W
-        if (c1_pending) MILAN_TRY(gemm_t(g1));
-        MILAN_TRY(launch_gemm(on_list(g2, rowsW, pl.tail_U3 + 1), s));
-        GemmArgs g3 = conv_args(b.c3, pl.t2, n, h2, w2, y, EPI_BIAS_RES_RELU, x, c->zero, &h3, &w3, split);
-        MILAN_TRY(launch_gemm(on_list(g3, rowsW, pl.tail_U3 + 1), s));
-        float* tmp = x; x = y; y = tmp;
-        h = h3; w = w3;
-        continue;
-      }
-      if (c1_pending && !c1_front) MILAN_TRY(gemm_t(g1));
-      if (conv_front) {
-        // (nothing to launch here)
-      } else if (split && (c->fusion & MILAN_FUSE_CONV3) && b.c2.K == b.c2.Kp &&
-          conv3_p64_supported(b.c2.cin, b.c2.cout, b.c2.kh, b.c2.kw, b.c2.stride,
-                              b.c2.pad)) {
-        // layer1's 3x3: weights in registers, input tile staged once (conv3.hip)
-        Conv3Args ca{};
-        ca.in = t1buf; ca.ws = b.c2.ws; ca.bias = b.c2.bias_s; ca.acc_scale = b.c2.ws_inv;
-        ca.out = pl.t2; ca.zero = c->zero; ca.n = n; ca.h = h1; ca.w = w1;
-        ca.n_live = live;
-        MILAN_TRY(launch_conv3_p64(ca, s));
-      } else {
-        MILAN_TRY(gemm_t(g2));
-      }
-      const float* identity = x;
-      // Expand conv of this block + reduce conv of the next one in ONE launch: the
-      // 4P-channel block output is written once and not read back by the next c1.
-      if (chain_plain || chain_ds) {
-        const Bottleneck& nb = *nbp;
-        ChainArgs ca{};
-        ca.T2 = pl.t2; ca.X = y; ca.W1 = nb.c1.ws; ca.bias1 = nb.c1.bias_s;
-        ca.T1 = t1buf; ca.M = n * h2 * w2; ca.P = chain_P; ca.scale1 = nb.c1.ws_inv;
-        ca.NR = chain_NR;
-        ca.m_live = live; ca.m_live_mul = h2 * w2;
-        if (conv_front) {
-          // c2's input is this block's t1; the next block's t1 goes to the OTHER buffer
-          // (workgroups read their neighbours' input pixels while those write their output)
-          ca.C2in = t1buf; ca.W2 = b.c2.ws; ca.bias2 = b.c2.bias_s; ca.scale2 = b.c2.ws_inv;
-          ca.ch = h1; ca.cw = w1;
-          ca.T2 = nullptr; ca.T1 = t1alt;
-          if (c1_front) {   // the region is the block INPUT; t1 is made in LDS
-            ca.C2in = x; ca.W0 = b.c1.ws; ca.bias0 = b.c1.bias_s; ca.scale0 = b.c1.ws_inv;
-          }
-        }
-        if (chain_plain) {
-          ca.W3 = b.c3.ws; ca.bias3 = b.c3.bias_s; ca.R = x; ca.scale3 = b.c3.ws_inv;
-        } else {
-          ca.W3 = b.c3d.ws; ca.bias3 = b.c3d.bias_s; ca.A2 = x; ca.KD = b.down.cin;
-          ca.scale3 = b.c3d.ws_inv;
-        }
-        MILAN_TRY(launch_chain(ca, s));
-        if (conv_front) { float* tt = t1buf; t1buf = t1alt; t1alt = tt; }
-        t1_ready = true;
-        float* tmp = x; x = y; y = tmp;
-        h = h2; w = w2;
-        continue;
-      }
-      if (b.has_down && split && b.c3d.ws && b.c3d.cout > 64) {
-        // c3 and the downsample as ONE GEMM over [t2 | x(strided)]
-        int h3, w3;
-        GemmArgs g3 = two_source_args(b, x, y, h, w, h2, w2, &h3, &w3);
-        MILAN_TRY(gemm_t(g3));
-        float* tmp = x; x = y; y = tmp;
-        h = h3; w = w3;
-        continue;
-      }
-      if (b.has_down) {
-        int hd, wdn;
-        GemmArgs gd = conv_args(b.down, x, n, h, w, pl.ds, EPI_BIAS, nullptr,
-                                c->zero, &hd, &wdn, split);
-        MILAN_TRY(gemm_t(gd));
-        identity = pl.ds;
-      }
-      GemmArgs g3 = conv_args(b.c3, pl.t2, n, h2, w2, y, EPI_BIAS_RES_RELU,
-                              identity, c->zero, &h3, &w3, split);
-      MILAN_TRY(gemm_t(g3));
-      float* tmp = x; x = y; y = tmp;
-      h = h3; w = w3;
-    }
-    stage.reset();
-    const int C = (c->d.trunk_kind == MILAN_TRUNK_BASIC ? wd : wd * 4) << li;
-    MILAN_REQUIRE(h == pl.lv.h[li + 1] && w == pl.lv.w[li + 1], MILAN_ERR_SHAPE,
-                  "internal: stage %d geometry mismatch", li + 1);
-    MILAN_TRY(pool(x, li + 1, C, col));
-    col += C;
+    MILAN_REQUIRE(p.sc.h_out[li] == p.pl.lv.h[li + 1] && p.sc.w_out[li] == p.pl.lv.w[li + 1],
+                  MILAN_ERR_SHAPE, "internal: stage %d geometry mismatch", li + 1);
+    MILAN_TRY(run_pool(p, p.sc.out[li], li + 1));
   }
-  if (spatial) {
-    // layer4 output, NHWC == the reference's permute(0, 2, 3, 1): (n, h*w, C)
-    const int C = (c->d.trunk_kind == MILAN_TRUNK_BASIC ? wd : wd * 4) << 3;
-    const long rows = (long)n * h * w;
-    if (split) {
-      const long total = rows * (C / 8);
-      const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-      hipLaunchKernelGGL(split_to_f32_kernel, dim3(blocks), dim3(256), 0, s, x,
-                         total, spatial_out, 1.f / c->act_scale);
-      MILAN_CHECK_HIP(hipGetLastError());
-    } else {
-      MILAN_CHECK_HIP(hipMemcpyAsync(spatial_out, x, sizeof(float) * rows * C,
-                                     hipMemcpyDeviceToDevice, s));
-    }
-    if (poison) {
-      const long per_image = (long)h * w * C;
-      const long total = (long)n * per_image;
-      const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-      hipLaunchKernelGGL(poison_fill_kernel, dim3(blocks), dim3(256), 0, s, spatial_out,
-                         per_image, n, poison);
-      MILAN_CHECK_HIP(hipGetLastError());
-    }
-  }
+  if (spatial) MILAN_TRY(run_spatial_out(p));
   return 0;
 }
 
@@ -2327,18 +1845,7 @@ int launch_raw_input(const float* images, int n, int H, int W, bool pairs, float
 // conv1 7x7/2 as encoder_run_batch's unfused stem launches it: raw fp32 output (n, h1, w1, width)
 GemmArgs encoder_stem_args(const milan_ctx* c, const float* in4, int n, int H, int W, float* raw,
                            bool pair_stem) {
-  int ho, wo;
-  GemmArgs g = conv_args(c->stem, in4, n, H, W, raw, EPI_BIAS, nullptr, c->zero, &ho, &wo);
-  if (pair_stem) {
-    const int G = (W + 2) / 2;
-    g = conv_args(c->stem_pair, in4, n, H, G, raw, EPI_BIAS, nullptr, c->zero, &ho, &wo, true);
-    g.Ho = conv_out(H, 7, 2, 3); g.Wo = conv_out(W, 7, 2, 3);
-    g.M = n * g.Ho * g.Wo;
-    g.aniso = 1; g.stride_w = 1; g.pad_w = 1;
-    g.out_split = 0;
-    g.flop_k = c->stem.kh * c->stem.kw * c->stem.cin_real;
-  }
-  return g;
+  return stem_args(c->stem, c->stem_pair, c->zero, in4, n, H, W, raw, pair_stem);
 }
 
 // bn1 + ReLU + maxpool 3x3/2 of the raw conv1 tensor -> fp32 or split format (activation scale)

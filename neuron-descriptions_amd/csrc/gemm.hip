@@ -2941,7 +2941,7 @@ static GemmEnv read_gemm_env() {
 
 // ... once per process, with the CU count of the current device (device_cus8 keeps it per
 // device: a process may drive several)
-static int gemm_env(GemmEnv* out) {
+int gemm_env(GemmEnv* out) {
   static const GemmEnv knobs = read_gemm_env();
   *out = knobs;
   return device_cus8(&out->cus);

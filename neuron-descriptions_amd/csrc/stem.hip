@@ -385,8 +385,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void stem_fused_kernel(St
   report_saturation(a.status, sat);
 }
 
-bool stem_fused_supported(int cout, int Kp) { return cout == 64 && Kp == 224; }
-
 template <int PR, int PC, int NW, bool U8>
 static int launch_stem_cfg(StemArgs a, int cus, hipStream_t s) {
   using T = StemTile<PR, PC, NW>;

@@ -827,6 +827,45 @@ int milan_conv2d_nhwc(const float* x, int n, int h, int w, int cin,
                       const float* residual, float* y, int precision,
                       milan_stream stream);
 
+/* Building block exposed for kernel-level tests: ONE launch of the implicit GEMM with every
+ * argument of its launcher in the caller's hand (milan_conv2d_nhwc reaches fp32 output, dense
+ * rows and three epilogues only).  The caller owns the device buffers A, A2, aux and C -- in
+ * the format the flags announce: split format [hi x8 | lo x8] per 8 channels where a_split /
+ * aux_split / out_split say so, fp32 otherwise -- with their strides, so an operand may sit in
+ * a channel slice of a wider row; and the int32 word m_live, the int32 row_list and the uint32
+ * status word (set as a context's is for the launch; NULL = nobody listens).
+ * The entry point owns the weights: `weight` is fp32 [groups][N][K] in the GEMM's k order
+ * ((tap, channel) of A, then the channels of A2), from which it makes what a trunk makes with
+ * the library's own packers: rows padded to Kp = round_up(K, 32), the groups' rows back to back
+ * (that is the weights' group stride), with a_split their split copy at a power-of-two scale
+ * undone by the accumulator scale, and for a k x k conv of whole 32-channel slices the
+ * (slice, tap, channel) copy unless no_wt is set.  bias: fp32 [groups][N] or NULL.
+ * Every other field is the launcher's argument of the same name; K1 = 0 without A2;
+ * tap_ncls = -1 keeps a tap-inner launch on the linear tile order; groups <= 1 = none.
+ * Nothing is decided here: the plan of the launch (which kernel, which refusal) is the
+ * library's.  f16 != 0 and the LSTM / log-sum-exp epilogues (epilogue > 5) are MILAN_ERR_ARG.
+ * Allocates temporaries and synchronises: not for the hot path. */
+typedef struct milan_gemm_probe_args {
+  const void* A;
+  const void* A2;
+  const void* aux;
+  void* C;
+  const float* weight;
+  const float* bias;
+  const int32_t* m_live;
+  const int32_t* row_list;
+  uint32_t* status;
+  int64_t a_pix_stride, a_img_stride, a2_pix_stride, a2_img_stride;
+  int64_t a_grp, bias_grp, c_grp, aux_grp;
+  int32_t M, N, K, ldc, ldaux;
+  int32_t H, Wd, Cin, Ho, Wo, KH, KW, stride, pad;
+  int32_t aniso, stride_w, pad_w;
+  int32_t epilogue, a_split, out_split, aux_split, f16;
+  int32_t K1, H2, W2d, stride2;
+  int32_t m_live_mul, groups, tap_ncls, no_wt;
+} milan_gemm_probe_args;
+int milan_gemm_probe(const milan_gemm_probe_args* args, milan_stream stream);
+
 /* ---- LanguageModel training (src/milan/lms.py:134-265) --------------------
  * Loss, forward and backward of Embedding -> nn.LSTM(dropout) -> Linear ->
  * LogSoftmax -> NLLLoss(ignore_index = pad_index) over a padded batch.

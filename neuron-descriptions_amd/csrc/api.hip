@@ -725,6 +725,79 @@ int milan_conv2d_nhwc(const float* x, int n, int h, int w, int cin,
   return r;
 }
 
+int milan_gemm_probe(const milan_gemm_probe_args* d, milan_stream stream) {
+  MILAN_REQUIRE(d && d->A && d->weight && d->C, MILAN_ERR_ARG, "gemm_probe: null argument");
+  MILAN_REQUIRE(!d->f16 && d->epilogue >= EPI_BIAS && d->epilogue <= EPI_BIAS_ADD, MILAN_ERR_ARG,
+                "gemm_probe: fast mode and the LSTM / log-sum-exp epilogues are not probed "
+                "(f16=%d epilogue=%d)", d->f16, d->epilogue);
+  MILAN_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->groups >= 0 && d->groups <= 65535,
+                MILAN_ERR_ARG, "gemm_probe: M=%d N=%d K=%d groups=%d", d->M, d->N, d->K, d->groups);
+  set_status_word(nullptr);  // (weight packing is not a saturation event of the launch)
+  hipStream_t s = (hipStream_t)stream;
+  const int groups = d->groups > 1 ? d->groups : 1, taps = d->KH * d->KW;
+  const int Kp = (d->K + 31) / 32 * 32;
+  const long rows = (long)groups * d->N;
+  const size_t wbytes = sizeof(float) * (size_t)rows * Kp;
+  float *wp = nullptr, *zero = nullptr, *wsp = nullptr, *wst = nullptr;
+  MILAN_CHECK_HIP(hipMalloc((void**)&wp, wbytes));
+  int r = (int)hipMalloc((void**)&zero, 256);
+  if (r == 0) r = (int)hipMemsetAsync(zero, 0, 256, s);
+  // rows of K floats -> rows of Kp, zero padded
+  if (r == 0) r = (int)hipMemsetAsync(wp, 0, wbytes, s);
+  if (r == 0)
+    r = (int)hipMemcpy2DAsync(wp, sizeof(float) * Kp, d->weight, sizeof(float) * d->K,
+                              sizeof(float) * d->K, rows, hipMemcpyDeviceToDevice, s);
+  if (r != 0) set_error("gemm_probe: %s", hipGetErrorString((hipError_t)r));
+  GemmArgs g{};
+  g.A = static_cast<const float*>(d->A); g.W = wp; g.bias = d->bias;
+  g.aux = static_cast<const float*>(d->aux); g.C = static_cast<float*>(d->C);
+  g.M = d->M; g.N = d->N; g.K = d->K; g.Kp = Kp; g.ldc = d->ldc; g.ldaux = d->ldaux;
+  g.H = d->H; g.Wd = d->Wd; g.Cin = d->Cin; g.Ho = d->Ho; g.Wo = d->Wo; g.KH = d->KH; g.KW = d->KW;
+  g.stride = d->stride; g.pad = d->pad;
+  g.a_pix_stride = d->a_pix_stride; g.a_img_stride = d->a_img_stride;
+  g.epilogue = d->epilogue; g.zero = zero;
+  g.a_split = d->a_split; g.out_split = d->out_split; g.aux_split = d->aux_split;
+  g.A2 = static_cast<const float*>(d->A2); g.K1 = d->K1; g.H2 = d->H2; g.W2d = d->W2d;
+  g.stride2 = d->stride2; g.a2_pix_stride = d->a2_pix_stride; g.a2_img_stride = d->a2_img_stride;
+  g.aniso = d->aniso; g.stride_w = d->stride_w; g.pad_w = d->pad_w;
+  g.m_live = d->m_live; g.row_list = d->row_list; g.m_live_mul = d->m_live_mul;
+  g.tap_ncls = d->tap_ncls;
+  g.groups = d->groups;
+  g.a_grp = d->a_grp; g.w_grp = (long)d->N * Kp; g.bias_grp = d->bias_grp; g.c_grp = d->c_grp;
+  g.aux_grp = d->aux_grp;
+  if (r == 0 && d->a_split) {
+    // what pack_conv (encoder.hip) makes of a conv's packed rows
+    r = (int)hipMalloc((void**)&wsp, wbytes);
+    if (r != 0) set_error("gemm_probe: out of memory");
+    if (r == 0)
+      r = split_weight_into(wp, (int)rows, Kp, wsp, &g.acc_scale,
+                            reinterpret_cast<unsigned int*>(zero) + 32, s);
+    g.W = wsp;
+    if (r == 0 && !d->no_wt && taps > 1 && taps <= 32 && d->K == Kp && d->Cin % 32 == 0) {
+      r = (int)hipMalloc((void**)&wst, wbytes);
+      if (r != 0) set_error("gemm_probe: out of memory");
+      if (r == 0) r = make_slice_major(wsp, (int)rows, taps, d->Cin, 4, 2, wst, s);
+      g.Wt = wst;
+    }
+  }
+  if (r == 0) {
+    set_status_word(d->status);
+    r = launch_gemm(g, s);
+  }
+  hipError_t e = hipStreamSynchronize(s);
+  // (the word is the caller's memory: a later ctx-less call must not report into it)
+  set_status_word(nullptr);
+  (void)hipFree(wp);
+  if (zero) (void)hipFree(zero);
+  if (wsp) (void)hipFree(wsp);
+  if (wst) (void)hipFree(wst);
+  if (r == 0 && e != hipSuccess) {
+    set_error("gemm_probe: %s", hipGetErrorString(e));
+    r = (int)e;
+  }
+  return r;
+}
+
 int milan_set_fusion(milan_ctx* c, int flags) {
   MILAN_REQUIRE(c, MILAN_ERR_ARG, "null ctx");
   MILAN_REQUIRE((flags & ~(MILAN_FUSE_CHAIN | MILAN_FUSE_CHAIN_WIDE | MILAN_FUSE_STEM | MILAN_FUSE_CONV3 |

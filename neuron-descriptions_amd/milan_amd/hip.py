@@ -324,6 +324,7 @@ SIGNATURES = {
     'milan_conv2d_nhwc':
         (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I,
               _P]),
+    'milan_gemm_probe': (_I, [_P, _P]),
     'milan_attention': (_I, [_P, _P, _I, _I, _I, _I, _P]),
     'milan_vit_create': (_I, [ctypes.POINTER(_P), _I,
                               ctypes.POINTER(VitDims)]),
@@ -362,7 +363,7 @@ PROBED = ('milan_lm_grad_workspace_bytes', 'milan_lm_forward_train',
           'milan_vit_finalize_weights', 'milan_vit_workspace_bytes', 'milan_vit_run',
           'milan_sagan_attention', 'milan_gan_create', 'milan_gan_destroy',
           'milan_gan_set_weight', 'milan_gan_finalize_weights', 'milan_gan_taps',
-          'milan_gan_workspace_bytes', 'milan_gan_run')
+          'milan_gan_workspace_bytes', 'milan_gan_run', 'milan_gemm_probe')
 
 _lib = None
 
@@ -2195,6 +2196,47 @@ def conv2d_nhwc(x: torch.Tensor,
                                   y.data_ptr(), _CONV_PRECISIONS[precision],
                                   _stream(device)))
     return y
+
+
+class GemmProbeArgs(ctypes.Structure):
+    """`milan_gemm_probe_args` (include/milan_hip.h)."""
+    POINTERS = ('A', 'A2', 'aux', 'C', 'weight', 'bias', 'm_live', 'row_list', 'status')
+    _fields_ = ([(name, ctypes.c_void_p) for name in POINTERS] +
+                [(name, ctypes.c_int64) for name in (
+                    'a_pix_stride', 'a_img_stride', 'a2_pix_stride', 'a2_img_stride',
+                    'a_grp', 'bias_grp', 'c_grp', 'aux_grp')] +
+                [(name, ctypes.c_int32) for name in (
+                    'M', 'N', 'K', 'ldc', 'ldaux',
+                    'H', 'Wd', 'Cin', 'Ho', 'Wo', 'KH', 'KW', 'stride', 'pad',
+                    'aniso', 'stride_w', 'pad_w',
+                    'epilogue', 'a_split', 'out_split', 'aux_split', 'f16',
+                    'K1', 'H2', 'W2d', 'stride2',
+                    'm_live_mul', 'groups', 'tap_ncls', 'no_wt')])
+
+
+def gemm_probe(device=None, **fields) -> None:
+    """Test hook: one launch of the implicit GEMM with every launcher argument given
+    (milan_gemm_probe).  `fields` are the members of `milan_gemm_probe_args`; a pointer is a
+    GPU tensor, a device address (an int: a tensor's data_ptr() plus a byte offset, to place an
+    operand inside a wider buffer) or None.  The buffers, their formats and their sizes are the
+    caller's; nothing is allocated or checked here.  Synchronises.  A launch the library's plan
+    refuses raises ValueError with the plan's text."""
+    fn = _need_export('milan_gemm_probe')
+    args = GemmProbeArgs()
+    known = {name for name, _ in GemmProbeArgs._fields_}
+    for name, value in fields.items():
+        if name not in known:
+            raise TypeError(f'gemm_probe: no field {name!r} in milan_gemm_probe_args')
+        if name in GemmProbeArgs.POINTERS:
+            if isinstance(value, torch.Tensor):
+                device = device if device is not None else value.device
+                value = value.data_ptr()
+            setattr(args, name, value)
+        else:
+            setattr(args, name, int(value))
+    device = require_device(device if device is not None else 'cuda')
+    with torch.cuda.device(device):
+        _check(fn(ctypes.byref(args), _stream(device)))
 
 
 def beam_merge(cand_v: torch.Tensor,

@@ -31,6 +31,7 @@ from torch.utils import data
 import actref
 import placesref
 from featclass import FEATURE_CLASS
+from splitfmt import from_split, to_split
 from milan_amd import classifiers, exemplars, hip, synthetic
 from oracle import exemplars_oracle as E
 
@@ -154,23 +155,6 @@ def test_full_width_once(precision):
 
 
 # ---- 2. the LRN kernel alone --------------------------------------------------------------------
-def to_split(x):
-    """(P, C) float32 -> the split-f16 groups at scale 1 as a float32 tensor of the same shape:
-    per 8 channels [hi x8 | lo x8]; and the value they hold, float64."""
-    p, c = x.shape
-    hi = x.half()
-    lo = (x - hi.float()).half()
-    packed = torch.stack([hi.view(p, c // 8, 8), lo.view(p, c // 8, 8)], dim=2)
-    held = hi.double() + lo.double()
-    return packed.contiguous().view(torch.float32).view(p, c), held
-
-
-def from_split(y):
-    p, c = y.shape
-    halves = y.contiguous().view(torch.float16).view(p, c // 8, 2, 8)
-    return (halves[:, :, 0].double() + halves[:, :, 1].double()).reshape(p, c)
-
-
 @pytest.mark.parametrize('split', (False, True))
 @pytest.mark.parametrize('beta', (0.75, 0.5))
 @pytest.mark.parametrize('local_size', (5, 3))

@@ -2,10 +2,14 @@
 //
 //   g++ -std=c++17 -O1 tools/gemm_plan_dump.cpp -o gemm_plan_dump
 //   gemm_plan_dump N Cin KH KW stride pad H W images f32|split|f16 [option ...]
+//   gemm_plan_dump kernels     the product build's kernel forms (MILAN_GEMM_KERNELS), one
+//                              "id=name" line each (id: the GemmKernel enumerator's value)
 //
 // N and Cin are per group.  Options (name=value):
 //   out_split= Wt= row_list= groups= tile_hint= tap_ncls= M= ldc= ldaux=
 //   A2=<channels of the second source>   epilogue=bias|relu|res_relu|tanh|sigmul|add|lstm|lse
+//   stride2=   aux_split=   (default: a split launch's residual is split, SIGMUL's fp32)
+//   m_live=1 m_live_mul=   a row count on the device   aniso=1 stride_w= pad_w=
 //   shift_group=<q>   plan group q of the grouped conv as the per-group baseline launches it
 //   cus= experiments=   and every knob of the launch path, MILAN_PP=0 and the like
 // One "key=value" line per field of the plan; a refusal prints err= and msg= instead.
@@ -26,6 +30,14 @@ static int usage(const char* why) {
 }
 
 int main(int argc, char** argv) {
+  if (argc == 2 && strcmp(argv[1], "kernels") == 0) {
+#define MILAN_GK_PRINT(id, ...) printf("%d=%s\n", (int)id, #__VA_ARGS__);
+#define MILAN_GK_SKIP(id, ...)
+    MILAN_GEMM_KERNELS(MILAN_GK_PRINT, MILAN_GK_SKIP)
+#undef MILAN_GK_PRINT
+#undef MILAN_GK_SKIP
+    return 0;
+  }
   if (argc < 11) return usage("too few arguments");
   int v[9];
   for (int i = 0; i < 9; ++i) v[i] = atoi(argv[1 + i]);
@@ -43,8 +55,8 @@ int main(int argc, char** argv) {
   g.f16 = prec == "f16";
   g.out_split = prec == "split";
   g.epilogue = EPI_BIAS;
-  int a2 = 0, shift = -1, M = -1, ldc = -1, ldaux = -1;
-  bool wt = false, list = false;
+  int a2 = 0, shift = -1, M = -1, ldc = -1, ldaux = -1, stride2 = 1, aux_split = -1;
+  bool wt = false, list = false, live = false;
   for (int i = 11; i < argc; ++i) {
     const char* eq = strchr(argv[i], '=');
     if (!eq) return usage("options are name=value");
@@ -61,6 +73,13 @@ int main(int argc, char** argv) {
     else if (name == "ldc") ldc = n;
     else if (name == "ldaux") ldaux = n;
     else if (name == "shift_group") shift = n;
+    else if (name == "stride2") stride2 = n;
+    else if (name == "aux_split") aux_split = n;
+    else if (name == "m_live") live = n != 0;
+    else if (name == "m_live_mul") g.m_live_mul = n;
+    else if (name == "aniso") g.aniso = n;
+    else if (name == "stride_w") g.stride_w = n;
+    else if (name == "pad_w") g.pad_w = n;
     else if (name == "cus") env.cus = n;
     else if (name == "experiments") env.experiments = n != 0;
     else if (name == "epilogue") {
@@ -94,7 +113,8 @@ int main(int argc, char** argv) {
   }
   const int groups = g.groups > 1 ? g.groups : 1;
   g.Ho = (g.H + 2 * g.pad - g.KH) / g.stride + 1;
-  g.Wo = (g.Wd + 2 * g.pad - g.KW) / g.stride + 1;
+  g.Wo = g.aniso ? (g.Wd + 2 * g.pad_w - g.KW) / g.stride_w + 1
+               : (g.Wd + 2 * g.pad - g.KW) / g.stride + 1;
   g.M = M > 0 ? M : images * g.Ho * g.Wo;
   g.K1 = g.KH * g.KW * g.Cin;
   g.K = g.K1 + a2;
@@ -110,7 +130,7 @@ int main(int argc, char** argv) {
   if (wt) g.Wt = base + (5 << 20);
   if (a2 > 0) {
     g.A2 = base + (6 << 20);
-    g.H2 = g.Ho; g.W2d = g.Wo; g.stride2 = 1;
+    g.H2 = (g.Ho - 1) * stride2 + 1; g.W2d = (g.Wo - 1) * stride2 + 1; g.stride2 = stride2;
     g.a2_pix_stride = a2;
     g.a2_img_stride = (long)g.H2 * g.W2d * a2;
   } else {
@@ -120,6 +140,7 @@ int main(int argc, char** argv) {
     g.aux = base + (7 << 20);
     g.aux_split = g.out_split && g.epilogue != EPI_BIAS_SIGMUL;
     g.ldaux = g.ldc;
+    if (aux_split >= 0) g.aux_split = aux_split;
   }
   if (g.epilogue == EPI_LSTM) {
     g.aux = base + (7 << 20);
@@ -138,6 +159,10 @@ int main(int argc, char** argv) {
     g.row_list = reinterpret_cast<const int*>(base + (11 << 20));
     g.m_live = reinterpret_cast<const int*>(base + (12 << 20));
     g.m_live_mul = 1;
+  }
+  if (live) {
+    g.m_live = reinterpret_cast<const int*>(base + (12 << 20));
+    if (g.m_live_mul == 0) g.m_live_mul = 1;
   }
   if (groups > 1) {
     g.a_grp = g.Cin; g.w_grp = (long)g.N * g.Kp; g.bias_grp = g.N; g.c_grp = g.N; g.aux_grp = g.N;
